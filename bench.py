@@ -2,6 +2,7 @@
 """bench.py -- throughput of the I2R-Net inference hot path on MI355X (BASELINE.json metric).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME] [--precision P] [--pipeline] [--ragged-stream] [--scaling strong]
+                  [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
@@ -22,7 +23,7 @@ are issued on a side stream under the next forward (dist.PostStep).  The line's 
 --scaling strong (default weak): the total job is FIXED -- 64 images with 1-6 persons -- and cut into contiguous image shards balanced by
 crop count (dist.shard_bounds); the ranks' crop counts differ, the line carries them and the imbalance (`shards`).
 
-One JSON line is printed by rank 0:
+One JSON line is printed by rank 0, and stdout holds nothing else (library output goes to stderr):
   value        crops/s of the whole job (all ranks), from the max-over-ranks wall time of exactly K steps
   roofline     the kernel with the LARGEST share of the step (over all kernels), measured IN SITU: the forward of the timed region is re-run
                with a HIP stop event bound to every dispatch and a start marker in front of it, on the launch's own stream
@@ -45,6 +46,9 @@ One JSON line is printed by rank 0:
   cpu_baseline the CPU oracle (oracle/i2r_cpu.py, a port of the reference forward) timed on this host, rank 0, N = 1 only
 --pipeline times the validate() step around the forward as one unit: uint8 image -> affine crops + bbox masks -> flip-test forward
 -> key-point decode, all on the device (lib/core/function.py:124-200); see make_pipeline().
+--dump-outputs DIR writes what the last timed step computed (heat maps; --pipeline: key points and their maxima; N > 1: also the gathered
+payload) as DIR/<name>.npy, float32, 64 MB at most; the line's `dump_outputs` lists the arrays.  Inputs and weights are seeded, so
+the same arguments give the same inputs in every run.
 --ragged-stream times what validate() really feeds the model (lib/core/function.py:124-140): a stream of batches whose crop count
 changes with every batch (16 images of 1-6 persons); see ragged_stream().
 """
@@ -984,6 +988,32 @@ def collective_overhead(dev, cname="hrt_192_p4_b4", rounds=5, steps=20):
             dist.destroy_process_group()
 
 
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all arrays together
+
+
+def dump_outputs(arrays, out_dir, limit=DUMP_LIMIT_BYTES):
+    """{name: tensor} -> out_dir/<name>.npy in float32 (float64 stays float64).  Every array gets an equal share of `limit`; one that is
+    larger keeps a fixed sample of its leading-axis rows (rng seed 0, sorted, the same for the same shape).  -> {name: summary}"""
+    os.makedirs(out_dir, exist_ok=True)
+    share = limit // max(1, len(arrays))
+    report = {}
+    for name, t in sorted(arrays.items()):
+        a = t.detach().cpu()
+        a = (a.double() if a.dtype == torch.float64 else a.float()).numpy()
+        entry = {"shape": list(a.shape), "dtype": str(a.dtype)}
+        if a.nbytes > share and a.ndim and a.shape[0] > 1:
+            keep = max(1, share // (a.nbytes // a.shape[0]))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))
+            a = a[rows]
+            entry["sampled_rows"] = [int(r) for r in rows]
+        a = np.ascontiguousarray(a)
+        if a.nbytes > share:
+            raise SystemExit("--dump-outputs: %s is %d bytes even as one row (limit %d)" % (name, a.nbytes, share))
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        report[name] = entry
+    return report
+
+
 # ------------------------------------------------------------------------------------------------------------------------------
 def self_launch(argv, n):
     """`python bench.py --gpus N` without a launcher: start the N ranks (one process per GPU) under torch.distributed.run on the
@@ -1030,6 +1060,11 @@ def parse_args(argv=None):
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-parity", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, rank 0 writes what the LAST timed step computed -- the arrays a caller of the timed path "
+                         "receives -- as DIR/<name>.npy (float32 / float64, %d MB in all at most: a larger array is cut to a fixed, seeded "
+                         "sample of its rows); the inputs are seeded, so two builds run with the same arguments compare output for output"
+                         % (DUMP_LIMIT_BYTES >> 20))
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help=argparse.SUPPRESS)
     ap.add_argument("--selftest-stub", action="store_true",
                     help=argparse.SUPPRESS)  # tests/test_bench_launcher.py: the launcher / shard / gather / timing path on CPU with gloo; the model step is a constant tensor and the line says so
@@ -1045,6 +1080,12 @@ def main(argv=None):
         raise SystemExit("--scaling strong times the bare forward over the fixed image list (no --pipeline / --ragged-stream)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(argv, args.gpus))
+    # stdout carries the result line and nothing else: what the libraries print on the way (RCCL writes its version banner to the C
+    # stdout when a communicator is created, at a point of the output that depends on buffering) goes to stderr; the line is written
+    # to the saved descriptor at the end
+    sys.stdout.flush()
+    result_out = os.fdopen(os.dup(1), "w")
+    os.dup2(2, 1)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -1120,6 +1161,7 @@ def main(argv=None):
 
     from i2r_amd import caller
     pending = [None]
+    last = {}  # the arrays the latest step handed its caller (--dump-outputs)
     pipe = make_pipeline(net, cfg, length, H_, W_, dev, seed=rank) if (args.pipeline and not stub and not args.ragged_stream) else None
     stub_y = torch.full((sum(length), J, H_ // 4, W_ // 4), float(rank), dtype=torch.float32) if stub else None
 
@@ -1129,21 +1171,32 @@ def main(argv=None):
             h = None
             if stub:
                 y = stub_y
+                last.clear()
+                last["heatmaps"] = y
                 if coll:
                     h = (i2r_dist.gather_keypoints(y[:, :, :1, 0].expand(-1, -1, 2), y[:, :, :1, 0], counts, async_op=True)
                          if gather == "keypoints" else i2r_dist.gather_heatmaps_async(y, counts))
             elif pipe is not None:
                 preds, maxv = pipe()
                 y = torch.cat([preds, maxv], 2)
+                last.clear()
+                last.update(preds=preds, maxvals=maxv)
                 if coll:
                     h = i2r_dist.gather_heatmaps_async(y, counts)
             else:
-                ys = []
+                ys, outs = [], []
                 for xb, mb, ln in batches:
                     yb = net(xb, mb, ln)
                     ys.append(yb["multi"] if isinstance(yb, dict) else yb)
+                    outs.append(yb)
                 # (strong scaling: a rank's forwards of one step are gathered together -- ranks run different numbers of forwards)
                 y = ys[0] if len(ys) == 1 else (torch.cat(ys, 0) if ys else torch.zeros(0, J, H_ // 4, W_ // 4, device=dev))
+                last.clear()
+                last["heatmaps"] = y
+                if outs and isinstance(outs[0], dict):  # (the two-stage models also hand back their first stage's heat maps)
+                    for k in outs[0]:
+                        if k != "multi":
+                            last["heatmaps_" + k] = outs[0][k] if len(outs) == 1 else torch.cat([o[k] for o in outs], 0)
                 if coll:  # decode (key points: [S, J, 3], 168 B/crop instead of 172 KB/crop) + all-gather on a side stream, under the next forward
                     post[gather](y)
                     return y
@@ -1161,10 +1214,12 @@ def main(argv=None):
 
     def drain():
         if pending[0] is not None:
-            pending[0].wait()
+            last["gathered"] = pending[0].wait()
             pending[0] = None
         for ps in post.values():
-            ps.result()
+            g = ps.result()
+            if g is not None:
+                last["gathered"] = g
 
     def sync():
         if not stub:
@@ -1196,6 +1251,7 @@ def main(argv=None):
 
     dt, y = timed(make_step(args.gather), args.steps, args.warmup)
     assert torch.isfinite(y).all()
+    dumped = dump_outputs(last, args.dump_outputs) if (args.dump_outputs and rank == 0) else None
     alt = None
     if coll and pipe is None:
         other = "keypoints" if args.gather == "heatmaps" else "heatmaps"
@@ -1233,6 +1289,8 @@ def main(argv=None):
                          "gather_rows_padded_to": max(counts)}
     if alt is not None:
         out["gather_alt"] = alt
+    if dumped is not None:
+        out["dump_outputs"] = {"dir": args.dump_outputs, "step": "the last of the %d timed steps" % args.steps, "arrays": dumped}
     if stub:
         out["data"] = "SELFTEST STUB: no model ran (launcher / sharding / all-gather / timing path only)"
         out["value"], out["model_tflops_algorithmic"] = 0.0, 0.0
@@ -1280,7 +1338,8 @@ def main(argv=None):
         if not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(cfg, sd, H_, W_, first)
     if rank == 0:
-        print(json.dumps(out), flush=True)
+        result_out.write(json.dumps(out) + "\n")
+    result_out.close()
     if coll:
         dist.barrier()
         dist.destroy_process_group()

@@ -177,7 +177,7 @@ def default_config():
 CONFIG_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "configs")
 
 # short names for the shipped workload configs (BASELINE.json configs 1-5) and for the rest of the reference's experiments/*.yaml;
-# REFERENCE_YAML maps each name to the reference file it mirrors (checked by tests/test_host.py in the build container)
+# REFERENCE_YAML maps each name to the reference file it mirrors (checked by tests/test_host.py against tests/golden/reference_yaml.json)
 REFERENCE_YAML = {
     "w48_pure_en6": "crowdpose/interformer_crowdpose_w48_pure_en6", "tph_192_p6_b4": "crowdpose/interformer_crowdpose_tph_192_p6_b4",
     "hrt_192_p4_b4": "crowdpose/interformer_crowdpose_hrt_192_p4_b4", "coco_hrt_288_p2_b4": "coco/interformer_coco_hrt_288_p2_b4",

@@ -3,8 +3,8 @@
 flip test:  lib/core/function.py:142-162 + lib/utils/transforms.py:16-30 (flip_back).
 decode:     lib/core/inference.py:20-112 + lib/utils/transforms.py:50-101.
 
-Pinning: get_max_preds and taylor are checked against the reference's own numpy functions imported here
-(tests/test_post_oracle.py, skipped without /root/reference).  The blur step calls cv2.GaussianBlur in the reference and
+Pinning: get_max_preds and taylor are checked against stored outputs of the reference's own numpy functions
+(tests/test_post_oracle.py, tests/golden/post_reference.npz made by oracle/make_golden_refdata.py).  The blur step calls cv2.GaussianBlur in the reference and
 cv2 is not installable here -> that step restates OpenCV's published algorithm (separable filter with
 getGaussianKernel(ksize, sigma<=0): sigma = 0.3*((ksize-1)*0.5-1)+0.8, coefficients exp(-(i-c)^2/(2 sigma^2)) normalised to 1)
 and is *parity unpinned*; the inverse affine is the closed form of cv2.getAffineTransform for rot = 0.

@@ -107,3 +107,45 @@ def test_gpus2_strong_scaling_gloo_stub():
     assert sh["forwards_per_rank_step"] == [-(-(b[r + 1] - b[r]) // 16) for r in range(2)]  # batches of <= 16 images (31 / 33 images: 2 / 3)
     assert out["config"]["crops_per_gpu_step"] == sh["crops_per_rank"][0]
     assert "STUB" in out["data"] and out["value"] == 0.0
+
+
+def test_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: the arrays the last timed step handed its caller, as DIR/<name>.npy in float32; the line says what was written
+    and `steps` / `ms_per_step` are those of the timed region.  Two runs with the same arguments write the same arrays."""
+    import numpy as np
+    lines = []
+    for d in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--backend", "gloo",
+                            "--selftest-stub", "--dump-outputs", str(tmp_path / d)], cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+        (line,) = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        lines.append(json.loads(line))
+    out = lines[0]
+    assert out["steps"] == 3 and out["ms_per_step"] > 0
+    arrays = out["dump_outputs"]["arrays"]
+    assert sorted(arrays) == ["gathered", "heatmaps"]
+    hm = np.load(str(tmp_path / "a" / "heatmaps.npy"))
+    assert hm.dtype == np.float32 and list(hm.shape) == arrays["heatmaps"]["shape"] == [32, 14, 64, 48] and (hm == 0).all()  # rank 0's shard
+    kp = np.load(str(tmp_path / "a" / "gathered.npy"))
+    assert kp.shape == (64, 14, 3) and (kp[:32] == 0).all() and (kp[32:] == 1).all()  # both ranks' key points
+    for name in arrays:
+        assert np.array_equal(np.load(str(tmp_path / "a" / (name + ".npy"))), np.load(str(tmp_path / "b" / (name + ".npy"))))
+
+
+def test_dump_outputs_samples_rows_within_the_limit(tmp_path):
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    big = torch.arange(100 * 10, dtype=torch.float16).reshape(100, 10)
+    small = torch.arange(6, dtype=torch.float64)
+    rep = bench.dump_outputs({"big": big, "small": small}, str(tmp_path / "a"), limit=2 * 400)
+    rep2 = bench.dump_outputs({"big": big, "small": small}, str(tmp_path / "b"), limit=2 * 400)
+    assert rep == rep2 and "sampled_rows" not in rep["small"]
+    rows = rep["big"]["sampled_rows"]
+    assert len(rows) == 10 and rows == sorted(rows) and rep["big"]["shape"] == [100, 10]  # 400 bytes / 40 bytes per float32 row
+    a = np.load(str(tmp_path / "a" / "big.npy"))
+    assert a.dtype == np.float32 and np.array_equal(a, big.float().numpy()[rows])
+    s = np.load(str(tmp_path / "a" / "small.npy"))
+    assert s.dtype == np.float64 and np.array_equal(s, small.numpy())
+    assert sum(os.path.getsize(str(f)) for f in (tmp_path / "a").iterdir()) < 2 * 400 + 2 * 128  # (+ the .npy headers)

@@ -16,6 +16,22 @@ from i2r_amd import arch, cabi, config, models, synth
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def _reference_yaml(tmp_path):
+    """the reference's experiments/*.yaml, written back from tests/golden/reference_yaml.json (oracle/make_golden_refdata.py):
+    {relative path without .yaml -> yaml file under tmp_path}"""
+    import json
+    import yaml
+    with open(os.path.join(ROOT, "tests", "golden", "reference_yaml.json")) as f:
+        docs = json.load(f)
+    out = {}
+    for rel, doc in docs.items():
+        path = tmp_path / "experiments" / (rel + ".yaml")
+        path.parent.mkdir(parents=True, exist_ok=True)
+        path.write_text(yaml.safe_dump(doc, sort_keys=False))
+        out[rel] = str(path)
+    return out
+
+
 def test_config_defaults_merge_and_freeze(tmp_path):
     cfg = config.load_config("w48_pure_en6")
     assert cfg.MODEL.NAME == "interformer_pureMulti" and cfg["MODEL"]["EXTRA"]["STAGE3"]["NUM_CHANNELS"] == [48, 96, 192]
@@ -35,14 +51,14 @@ def test_config_defaults_merge_and_freeze(tmp_path):
     assert c3.MODEL.EXTRA.ANY.NEW == 1 and c3.GPUS == (0, 1)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/experiments"), reason="reference tree only in the build container")
-def test_reference_yaml_files_load_unchanged():
-    files = glob.glob("/root/reference/experiments/*/*.yaml")
+def test_reference_yaml_files_load_unchanged(tmp_path):
+    ref = _reference_yaml(tmp_path)
+    files = glob.glob(str(tmp_path / "experiments" / "*" / "*.yaml"))
     assert len(files) == 10
     for f in files:
         cfg = config.load_config(f)
         assert cfg.MODEL.NAME in ("interformer", "interformer_pureMulti", "interformer_2stage")
-    a = config.load_config("/root/reference/experiments/crowdpose/interformer_crowdpose_w48_pure_en6.yaml")
+    a = config.load_config(ref["crowdpose/interformer_crowdpose_w48_pure_en6"])
     b = config.load_config("w48_pure_en6")
     for k in b.MODEL:
         if k != "EXTRA":
@@ -187,13 +203,14 @@ int main(void){ printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu 
     assert sizes == mine
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/experiments"), reason="reference tree only in the build container")
-def test_named_configs_equal_reference_yaml():
+def test_named_configs_equal_reference_yaml(tmp_path):
     """every shipped configs/*.yaml carries its reference yaml's MODEL section (checkpoint paths aside) and the TEST keys of validate()"""
     assert len(config.REFERENCE_YAML) == 10
+    ref = _reference_yaml(tmp_path)
+    assert sorted(ref) == sorted(config.REFERENCE_YAML.values())
     for name, rel in config.REFERENCE_YAML.items():
         a = config.load_config(name)
-        b = config.load_config("/root/reference/experiments/%s.yaml" % rel)
+        b = config.load_config(ref[rel])
         for k in b.MODEL:
             if k == "EXTRA":
                 for e in b.MODEL.EXTRA:
@@ -205,7 +222,7 @@ def test_named_configs_equal_reference_yaml():
 
 
 @pytest.mark.parametrize("name", sorted(config.REFERENCE_YAML))
-def test_every_shipped_yaml_builds(name):
+def test_every_shipped_yaml_builds(name, tmp_path):
     """all ten experiments/*.yaml of the reference: the engine accepts the configuration (engine.validate_config is what
     Engine.__init__ runs first), the parameter tree is built by the factory and every weight the packer will ask for exists"""
     from i2r_amd import engine
@@ -213,10 +230,9 @@ def test_every_shipped_yaml_builds(name):
     engine.validate_config(cfg)
     net = eval("models." + cfg.MODEL.NAME + ".get_pose_net")(cfg, is_train=False)
     sd = net.state_dict()
-    if os.path.isdir("/root/reference/experiments"):
-        ref = config.load_config("/root/reference/experiments/%s.yaml" % config.REFERENCE_YAML[name])
-        engine.validate_config(ref)
-        assert [k for k, _, _ in arch.param_spec(ref)] == list(sd)
+    ref = config.load_config(_reference_yaml(tmp_path)[config.REFERENCE_YAML[name]])
+    engine.validate_config(ref)
+    assert [k for k, _, _ in arch.param_spec(ref)] == list(sd)
     M = cfg.MODEL
     if M.USE_MULTI_POS:
         p = "position_embedding" if M.NAME == "interformer_pureMulti" else "multi_position_embedding"

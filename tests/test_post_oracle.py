@@ -1,16 +1,13 @@
-"""CPU: the post-forward oracle (oracle/post_cpu.py) against the reference's own numpy functions where they are
-importable (get_max_preds, taylor, flip_back); cv2 is absent, so GaussianBlur is checked against an independent scipy filter."""
+"""CPU: the post-forward oracle (oracle/post_cpu.py) against stored outputs of the reference's own numpy functions (get_max_preds,
+taylor, flip_back: tests/golden/post_reference.npz); cv2 is absent, so GaussianBlur is checked against an independent scipy filter."""
 import os
-import sys
-import types
 
 import numpy as np
-import pytest
 
 import post_cpu
 from i2r_amd import caller, synth
 
-REF = "/root/reference/lib"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def _hm(S=3, J=4, h=32, w=24, seed=5):
@@ -18,28 +15,23 @@ def _hm(S=3, J=4, h=32, w=24, seed=5):
     return u ** 6  # peaky
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree only in the build container")
 def test_argmax_taylor_flip_back_match_reference_functions():
-    if "cv2" not in sys.modules:
-        sys.modules["cv2"] = types.ModuleType("cv2")  # imported at module top only; never called by the functions used here
-    sys.path.insert(0, REF)
-    try:
-        from core import inference as ref_inf
-        from utils import transforms as ref_tr
-    finally:
-        sys.path.remove(REF)
+    """against the outputs of the reference's own functions on the same heat maps (oracle/make_golden_refdata.py)"""
+    g = np.load(os.path.join(GOLDEN, "post_reference.npz"))
     hm = _hm()
-    p0, m0 = ref_inf.get_max_preds(hm)
+    assert np.array_equal(hm, g["hm"])  # (the seeded input the fixture was made from)
+    p0, m0 = g["preds"], g["maxvals"]
     p1, m1 = post_cpu.get_max_preds(hm)
     assert np.array_equal(p0, p1) and np.array_equal(m0, m1)
     lg = np.log(np.maximum(hm, 1e-10))
     for s in range(hm.shape[0]):
         for j in range(hm.shape[1]):
-            a = ref_inf.taylor(lg[s, j], p0[s, j].copy())
+            a = g["taylor"][s, j]
             b = post_cpu.taylor(lg[s, j], p0[s, j].copy())
             assert np.allclose(a, b, atol=1e-5)
     pairs = caller.FLIP_PAIRS["crowdpose"][:2]
-    assert np.array_equal(ref_tr.flip_back(hm.copy(), pairs), post_cpu.flip_back(hm.copy(), pairs))
+    assert np.array_equal(g["flip_pairs"], np.asarray(pairs))
+    assert np.array_equal(g["flip_back"], post_cpu.flip_back(hm.copy(), pairs))
 
 
 def test_blur_matches_independent_separable_filter():
