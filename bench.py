@@ -2,7 +2,7 @@
 """bench.py -- throughput of the I2R-Net inference hot path on MI355X (BASELINE.json metric).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME] [--precision P] [--pipeline] [--ragged-stream] [--scaling strong]
-                  [--dump-outputs DIR]
+                  [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
@@ -18,13 +18,19 @@ Every rank runs its own batch of the workload's shape (weak scaling, images are 
 all-gathered over RCCL each step: the key points decoded on the device, [S, J, 3] (168 B per crop: what validate() keeps of a batch;
 --gather heatmaps gathers the predicted heat maps, the payload BASELINE.json's north_star names, 172 KB per crop).  Decode and gather
 are issued on a side stream under the next forward (dist.PostStep).  The line's `value` is timed with the --gather payload;
-`gather_alt` is the same K steps re-timed with the other payload.
+`gather_alt` (--full) is the same K steps re-timed with the other payload.
 
 --scaling strong (default weak): the total job is FIXED -- 64 images with 1-6 persons -- and cut into contiguous image shards balanced by
 crop count (dist.shard_bounds); the ranks' crop counts differ, the line carries them and the imbalance (`shards`).
 
-One JSON line is printed by rank 0, and stdout holds nothing else (library output goes to stderr):
+One JSON line is printed by rank 0, and stdout holds nothing else (library output goes to stderr).  A plain run sets up, warms up,
+times the K steps, writes --dump-outputs and prints the line: the headline (metric, value, unit, higher_is_better, dtype, ms_per_step),
+the run's shape (config, shards) and `lanes`.  Everything else the benchmark measures or checks runs only with --full, after the timed
+region (the --no-* options leave single legs of it out):
   value        crops/s of the whole job (all ranks), from the max-over-ranks wall time of exactly K steps
+  lanes        what the engine's stream probe found (candidate streams, alone / together spin times, roles), whether the device-side
+               lane synchronisation is in use and that none of its waits timed out
+--full adds:
   roofline     the kernel with the LARGEST share of the step (over all kernels), measured IN SITU: the forward of the timed region is re-run
                with a HIP stop event bound to every dispatch and a start marker in front of it, on the launch's own stream
                (i2r_run_program_timed) -- avg_launch_us = mean kernel duration with lanes / sibling programs in flight, busy_ms_per_step =
@@ -35,8 +41,6 @@ One JSON line is printed by rank 0, and stdout holds nothing else (library outpu
                markers slow the forward (forward_ms_with_timing_events), so frac is a LOWER bound; `standalone` = the same launches alone
                on one stream; `concurrent_programs` = the part-batch programs fork -> join between two events (unperturbed);
                `kernels` = the same figures for the five largest kernels; attention_blocks = the encoder kernels
-  lanes        what the engine's stream probe found (candidate streams, alone / together spin times, roles), whether the device-side
-               lane synchronisation is in use and that none of its waits timed out
   collective_overhead  (default line) BASELINE configs[3] timed alternately as the plain step and as the data-parallel step (device decode +
                RCCL all-gather through a one-rank group, on a side stream under the next forward) in this process
   other_workloads  (default single-GPU line only) BASELINE configs[2..4] at their own batch shapes and dtypes, the ragged stream and the
@@ -1045,13 +1049,17 @@ def parse_args(argv=None):
     ap.add_argument("--gather", default="keypoints", choices=["keypoints", "heatmaps"],
                     help="N > 1: payload of the per-step all-gather whose timing is `value`: the key points decoded on the device [S,J,3] "
                          "(168 B per crop: what validate() keeps of a batch, lib/core/function.py:190-200) or the heat maps [S,J,h,w] "
-                         "(172 KB per crop, the payload north_star names); the other payload is re-timed and reported as gather_alt")
+                         "(172 KB per crop, the payload north_star names); with --full the other payload is re-timed and reported as gather_alt")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak (default): every rank runs a batch of the workload's shape.  strong: a FIXED ragged list of 64 images with 1-6 persons "
                          "each (rng seed 0) is cut into contiguous shards balanced by crop count (dist.shard_bounds); a step = one pass over the whole "
                          "list, each rank running its images in batches of <= 16 (TEST.BATCH_SIZE_PER_GPU) and one padded all-gather of its uneven crop count")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure and check everything beyond the headline: roofline, parity, cpu_baseline, "
+                         "gather_alt, and on the default single-GPU line other_workloads and collective_overhead (the --no-* options "
+                         "leave single legs out); without it the run times the steps and prints the headline only")
     ap.add_argument("--no-other-workloads", action="store_true",
-                    help="default single-GPU run only: skip the short runs of BASELINE configs[2..4], the ragged stream and the pipeline that are "
+                    help="--full, default single-GPU run only: skip the short runs of BASELINE configs[2..4], the ragged stream and the pipeline that are "
                          "embedded in the line as other_workloads")
     ap.add_argument("--world1-collective", action="store_true",
                     help="--gpus 1 only: create a ONE-rank process group and run the per-step all-gather, the barriers and the max-over-ranks "
@@ -1253,7 +1261,7 @@ def main(argv=None):
     assert torch.isfinite(y).all()
     dumped = dump_outputs(last, args.dump_outputs) if (args.dump_outputs and rank == 0) else None
     alt = None
-    if coll and pipe is None:
+    if args.full and coll and pipe is None:
         other = "keypoints" if args.gather == "heatmaps" else "heatmaps"
         dt2, _ = timed(make_step(other), args.steps, min(args.warmup, 3))
         alt = {"payload": other, "ms_per_step": round(dt2 / args.steps * 1e3, 4), "value": round(sum(length_all) * args.steps / dt2, 2)}
@@ -1297,7 +1305,7 @@ def main(argv=None):
         out["gathered_ok"] = True
     if rank == 0 and not stub:
         eng = net.engine()
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             def fwd1():
                 if pipe is not None:
                     return pipe()
@@ -1308,7 +1316,7 @@ def main(argv=None):
                 out["roofline"]["model_tflops_executed"] = round(out["roofline"].pop("_executed_gflop_per_step") * args.steps / dt / 1e3, 2)
             out["roofline"].pop("_executed_gflop_per_step", None)
             out["roofline"]["kernel_time_overlap"] = round(out["roofline"]["kernel_time_sum_ms_per_step"] / (dt / args.steps * 1e3), 3)
-        if not args.no_parity and not args.pipeline:
+        if args.full and not args.no_parity and not args.pipeline:
             y1 = net(x, m, first)
             y1 = y1["multi"] if isinstance(y1, dict) else y1
             out["parity"] = oracle_parity(cfg, sd, x, m, first, y1, precision)
@@ -1319,9 +1327,9 @@ def main(argv=None):
             out["ragged_stream"] = ragged_stream(net, cfg, dev, H_, W_, 64, flip_pairs=pairs)
         default_line = (world == 1 and args.config == "w48_pure_en6" and not args.pipeline and not args.ragged_stream and not strong
                         and args.precision in (None, "fp32"))
-        if default_line and not args.no_other_workloads:
-            # the driver only runs `bench.py --gpus 1`: BASELINE configs[2..4] at their own batch shapes / dtypes, the ragged stream and
-            # the pipeline are measured in the same process right after the headline's timed region, 10-30 steps each
+        if args.full and default_line and not args.no_other_workloads:
+            # BASELINE configs[2..4] at their own batch shapes / dtypes, the ragged stream and the pipeline are measured in the same
+            # process right after the headline's timed region, 10-30 steps each
             t_other = time.perf_counter()
             out["other_workloads"] = other_workloads(net, cfg, dev)
             out["other_workloads"]["wall_s"] = round(time.perf_counter() - t_other, 1)
@@ -1330,12 +1338,12 @@ def main(argv=None):
         # a device-side wait that saw nothing for 50 ms gives up and raises a flag instead of hanging the GPU: none may have (the step's results
         # would not be ordered); checked here, behind the timed region's synchronize
         out["lanes"]["device_side_waits_timed_out"] = any(P.sync_timed_out() for v in eng.programs.values() for P in v[:1])
-        if default_line and not args.no_other_workloads and not coll:
+        if args.full and default_line and not args.no_other_workloads and not coll:
             try:
                 out["collective_overhead"] = collective_overhead(dev)
             except Exception as e:  # (an RCCL group that cannot be created here must not cost the driver its bench line)
                 out["collective_overhead"] = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(cfg, sd, H_, W_, first)
     if rank == 0:
         result_out.write(json.dumps(out) + "\n")

@@ -20,7 +20,7 @@ def _env():
 
 def test_gpus2_self_launch_gloo_stub():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--backend", "gloo",
-                        "--selftest-stub", "--config", "hrt_192_p4_b4"], cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=600)
+                        "--selftest-stub", "--config", "hrt_192_p4_b4", "--full"], cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout  # ONE line, from rank 0 only
@@ -31,12 +31,25 @@ def test_gpus2_self_launch_gloo_stub():
     assert "STUB" in out["data"] and out["value"] == 0.0  # a stub run can never be mistaken for a measurement
 
 
+def test_plain_run_times_the_headline_only():
+    """Without --full the run times its steps and prints the headline: no second timed pass with the other payload (gather_alt)."""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--backend", "gloo",
+                        "--selftest-stub"], cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+    (line,) = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    out = json.loads(line)
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and "dp2" in out["config"]["parallelism"]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype"):
+        assert k in out, k
+    assert "gather_alt" not in out
+
+
 def test_gpus1_world1_collective_strong_gloo_stub():
     """--world1-collective: the N = 1 step with the collective in place (a ONE-rank process group: gather, barriers, max-over-ranks
     reduction) -- here on gloo with the stub step; tests/test_dist_gpu.py runs the real model over RCCL.  Strong scaling: the line
     carries `shards` (all 64 images on the one rank, 4 forwards of uneven crop counts per step, gathered together)."""
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--backend", "gloo",
-                        "--selftest-stub", "--world1-collective", "--scaling", "strong"], cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=600)
+                        "--selftest-stub", "--world1-collective", "--scaling", "strong", "--full"], cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     (line,) = [l for l in p.stdout.splitlines() if l.startswith("{")]
     out = json.loads(line)

@@ -82,14 +82,16 @@ def test_post_step_on_side_stream_equals_direct_gather(nccl_world1):
         assert torch.equal(got_kp.view_as(kp), kp) and torch.equal(got_hm.view_as(y), y)
 
 
-def _bench(*args, timeout=900):
-    """bench.py as the driver runs it (a process of its own), -> its one JSON line"""
+def _bench(*args, timeout=900, full=True):
+    """bench.py as the driver runs it (a process of its own), -> its one JSON line.  full: --full without the roofline, CPU baseline and
+    other workloads (parity and gather_alt stay); else the plain run"""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT") and not k.startswith("I2R_")}
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--no-cpu-baseline", "--no-roofline", "--no-other-workloads"] + list(args),
+    opts = ["--full", "--no-cpu-baseline", "--no-roofline", "--no-other-workloads"] if full else []
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + opts + list(args),
                        cwd=root, env=env, capture_output=True, text=True, timeout=timeout)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     (line,) = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -118,3 +120,14 @@ def test_bench_config4_with_collective_matches_plain_line():
     assert "dp1" in coll["config"]["parallelism"] and coll["config"]["crops_per_gpu_step"] == 16
     assert plain["value"] > 0 and coll["value"] > 0
     print("collective/plain throughput at N=1 (recorded, not asserted): %.1f / %.1f = %.3f" % (coll["value"], plain["value"], coll["value"] / plain["value"]))
+
+
+def test_bench_plain_line_is_the_headline():
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: the headline of the timed steps and the lane map, none of the legs that
+    --full runs after the timed region"""
+    out = _bench("--gpus", "1", "--steps", "3", "--warmup", "2", full=False)
+    assert out["steps"] == 3 and out["warmup"] == 2 and out["ms_per_step"] > 0 and out["value"] > 1000
+    assert out["unit"] == "images/sec" and out["higher_is_better"] is True and out["dtype"] == "f32" and out["n_gpus"] == 1
+    assert not out["lanes"]["device_side_waits_timed_out"]
+    for k in ("roofline", "parity", "cpu_baseline", "other_workloads", "collective_overhead", "gather_alt"):
+        assert k not in out, k

@@ -18,7 +18,7 @@ steps = sys.argv[4] if len(sys.argv) > 4 else "30"
 def bench(*extra):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT") and not k.startswith("I2R_")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", cname, "--gpus", "1", "--steps", steps, "--warmup", "10",
-                        "--no-cpu-baseline", "--no-roofline", "--no-parity", "--no-other-workloads"] + list(extra),
+                        "--full", "--no-cpu-baseline", "--no-roofline", "--no-parity", "--no-other-workloads"] + list(extra),
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     (line,) = [l for l in p.stdout.splitlines() if l.startswith("{")]
