@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define I2R_ABI_VERSION 14
+#define I2R_ABI_VERSION 15
 
 /* The library is built with -fvisibility=hidden: the entry points declared in this header (marked I2R_API) are its ONLY exported
  * symbols (tests/test_host.py holds the header, the dynamic symbol table and cabi.EXPORTS equal). */
@@ -91,7 +91,7 @@ typedef struct i2r_conv_desc {
                                       rep = out_step = 1, no in2; `w` then holds the TRANSFORMED weights U = G g G^T in the k4 layout with the 16
                                       Winograd positions (row-major 4x4) in place of the taps: float w[16][cin/4][cout_pad][4].  tile_w selects the
                                       fragment shape (16 Winograd tiles = 64 output pixels): 16, 8 or 4 pixels wide (0 = choose); mt = fragments per
-                                      workgroup (1 or 2, 0 = 1; 2 only for cout_pad / 16 a multiple of 3).  2.25x fewer matrix-pipe operations than algo 0 for the same sum. */
+                                      workgroup (0 or 1: one).  2.25x fewer matrix-pipe operations than algo 0 for the same sum. */
 } i2r_conv_desc;
 
 I2R_API int i2r_conv(const i2r_conv_desc* d, void* stream);
@@ -106,36 +106,6 @@ I2R_API int i2r_conv(const i2r_conv_desc* d, void* stream);
  * (sum over members of n_img * ceil(conv_h/tile_h) * ceil(conv_w/tile_w) * cout_blocks). */
 I2R_API int i2r_conv_grouped(const i2r_conv_desc* const* descs, int32_t n, const int32_t* block_map, int32_t map_len,
                      void* stream);
-
-/* i2r_conv_chain (EXPERIMENTAL: correct and tested, but measured slower than one i2r_conv_grouped per layer on MI355X at 32 crops;
- * the host side keeps it behind I2R_CONV_CHAIN=1) -- n_layers DEPENDENT stride-1 convolutions (layer l of member g reads layer l-1's output of member g) for up to
- * I2R_MAX_GROUP independent members in ONE persistent launch: the 8 convs of the 4 BasicBlocks of every branch of a
- * HighResolutionModule (interformer_pureMulti.py:392-397).  Instead of a chip-wide barrier per layer, a tile starts as soon as the
- * 3x3 tile neighbourhood of the previous layer has finished (completion counters in `flags`), which removes the per-launch
- * fill / drain and round quantisation.  descs: host array [n_layers * n_members], layer-major; every layer of a member must resolve
- * to the same tiling.  Workspaces are the caller's:
- *   i2r_conv_chain_pack(a, host_buf, bytes)  validates, fills the outputs below and (host_buf != NULL) writes the kernel-side
- *       descriptors into host_buf (a->kdesc_bytes bytes) for the caller to copy to the device (a->kdesc);
- *   items / item_ofs: eight work queues, one per XCD -- the persistent workgroups with (index % 8) == x pop
- *       items[item_ofs[x] .. item_ofs[x+1]) in order; each item = (layer << 26) | (member << 24) | workgroup index within the member
- *       (numbered as i2r_conv_grouped numbers them: cout block fastest, then tile x, tile y, image); every queue must be sorted
- *       by layer and hold ALL items of its images (producers and consumers then share one L2); n_blocks <= a->capacity;
- *   flags: n_flags + 17 int32 (zeroed by i2r_conv_chain itself; word [n_flags] afterwards: 0 ok, 1 = a dependency wait timed out,
- *       2 = workgroups of one residue class (index % 8) ran on different XCDs, i.e. the same-L2 assumption of the schedule is void). */
-typedef struct i2r_conv_chain_args {
-    const i2r_conv_desc* const* descs;
-    int32_t n_layers, n_members;
-    const void* kdesc;
-    const int32_t* item_ofs;
-    const int32_t* items;
-    int32_t* flags;
-    int32_t n_blocks;
-    /* outputs of i2r_conv_chain_pack */
-    int32_t n_flags, kdesc_bytes, capacity, nt, mt, cap, pf, lds_bytes;
-    int32_t tiles[I2R_MAX_GROUP][4];  /* per member: tiles_y, tiles_x, cout blocks, workgroups per layer */
-} i2r_conv_chain_args;
-I2R_API int i2r_conv_chain_pack(i2r_conv_chain_args* a, void* host_buf, int64_t host_bytes);
-I2R_API int i2r_conv_chain(const i2r_conv_chain_args* a, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * i2r_stem_conv -- first 3x3 stride-2 pad-1 conv of a tower (cin = 1..4) + folded BN + ReLU, reading the
@@ -483,27 +453,26 @@ typedef struct i2r_scramble_args { const float* o; float* out; const int32_t* pe
  * Program runner: replay a pre-built list of launches from one C call (no per-op host overhead, and
  * capturable into a hipGraph by the caller).  Streams: ops carry a lane id 0..3; lane 0 is `stream`,
  * other lanes are forked/joined with events by I2R_OP_FORK / I2R_OP_JOIN (op.lane = mask of the lanes 1..3 involved).
- * I2R_OP_XSYNC (op.lane = mask of lanes, bit 0 = lane 0): every lane of the mask continues only after everything issued so far on
- * every OTHER lane of the mask (one event per lane, all-to-all waits) -- the barrier between the branch blocks and the fuse
- * layers of an HRFormer module when branch i and fuse output i both live on lane i, so that no lane idles behind lane 0.
  * I2R_OP_RECORD / I2R_OP_WAIT (round 6; op.lane = lane | slot << 8, slot 0..7): RECORD puts event 8 + slot on the lane's stream behind
  * everything issued on it so far; WAIT makes the lane's stream wait for the LAST record of that slot (nothing if it was recorded on the
  * same stream).  Point-to-point, so a lane waits only for what its next launch reads, in the order the producers finish: on MI355X
  * a cross-stream wait costs the waiter ~10 us after the producer ends and the all-to-all form ~20 us for three lanes
- * (tools/probe/xstream_latency*.hip) -- the HRFormer fuse layers now start the terms of the early lanes under the last lane's blocks.
+ * (tools/probe/xstream_latency*.hip) -- the HRFormer fuse layers start the terms of the early lanes under the last lane's blocks.
  * A program with these ops needs an `events` array of 16 entries; RECORD's op.lane also carries the consumer lanes (mask << 16).
  * DEVICE-SIDE FORM: behind an I2R_OP_LANE_FLAGS op (op.args = device int32[64], zeroed once by the caller; NULL = stay with events)
  * FORK / JOIN / RECORD / WAIT become one-wave kernels -- the producer's stream sets flags behind its work, the consumer's stream spins
  * on its flag, clears it and ends (~6 us instead of ~20 us per cross-lane hop).  The caller hands the buffer over ONLY when every lane
  * stream is its own hardware queue (a spinning kernel in front of the kernel that signals it would never end; engine.lane_streams
  * probes this) and never replays two programs that share a buffer at the same time; a wait gives up after 50 ms and sets entry 63 of
- * the buffer instead of hanging the GPU.  XSYNC keeps the event form.
+ * the buffer instead of hanging the GPU.
+ * Op kinds 14 and 18 are reserved (retired: a persistent conv-chain launch and an all-to-all lane barrier); a program holding them is
+ * rejected.
  * ------------------------------------------------------------------------------------------------ */
 enum {
     I2R_OP_CONV = 1, I2R_OP_STEM = 2, I2R_OP_MAXPOOL = 3, I2R_OP_HEAD = 4,
     I2R_OP_ENC_KV = 5, I2R_OP_ENC_LAYER = 6, I2R_OP_FORK = 7, I2R_OP_JOIN = 8, I2R_OP_CONV_GROUP = 9,
-    I2R_OP_LAYERNORM = 10, I2R_OP_WINATTN = 11, I2R_OP_DWCONV = 12, I2R_OP_UPSAMPLE = 13, I2R_OP_CONV_CHAIN = 14,
-    I2R_OP_PE_RES_STEM = 15, I2R_OP_HRT_ATTN = 16, I2R_OP_HRT_MLP = 17, I2R_OP_XSYNC = 18, I2R_OP_FUSE_UP = 19,
+    I2R_OP_LAYERNORM = 10, I2R_OP_WINATTN = 11, I2R_OP_DWCONV = 12, I2R_OP_UPSAMPLE = 13, /* 14: reserved */
+    I2R_OP_PE_RES_STEM = 15, I2R_OP_HRT_ATTN = 16, I2R_OP_HRT_MLP = 17, /* 18: reserved */ I2R_OP_FUSE_UP = 19,
     I2R_OP_CONV1X1_PAIR = 20, I2R_OP_CONV1X1_LP = 21, I2R_OP_MH_ATTN = 22, I2R_OP_PE_CAT_VEC = 23, I2R_OP_ROWS_GATHER = 24, I2R_OP_VIEW_SCRAMBLE = 25,
     I2R_OP_RECORD = 26, I2R_OP_WAIT = 27, I2R_OP_LANE_FLAGS = 28
 };
@@ -584,7 +553,7 @@ typedef struct i2r_op {
  * RECORD / WAIT ops) created by the caller with hipEventDisableTiming.  Both may be NULL when every op uses lane 0. */
 I2R_API int i2r_run_program(const i2r_op* ops, int32_t n_ops, void* const* streams, void* const* events);
 /* The same replay with every LAUNCH timed through caller-owned events (hipEventCreate with timing enabled; entries of sync ops -- FORK /
- * JOIN / XSYNC -- are ignored): the launch of op i goes out through hipExtLaunchKernelGGL with t1[i] BOUND to the dispatch (its completion
+ * JOIN / RECORD / WAIT / LANE_FLAGS -- are ignored): the launch of op i goes out through hipExtLaunchKernelGGL with t1[i] BOUND to the dispatch (its completion
  * signal carries the kernel's end time; no extra packet, the replay is not slowed down) and, where t0[i] is non-NULL, t0[i] as a marker in
  * front of it (~5 us of stream time).  hipEventElapsedTime(t0[i], t1[i]) is the kernel's own duration IN SITU -- with the program's other
  * lanes and any sibling program in flight; for a launch without a start marker the start is the completion of whatever it waited for (its

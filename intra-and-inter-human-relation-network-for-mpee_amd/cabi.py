@@ -14,15 +14,15 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libi2r_hip.so")
 
 MAX_TAPS = 9
-ABI_VERSION = 14  # I2R_ABI_VERSION of include/i2r_hip.h
+ABI_VERSION = 15  # I2R_ABI_VERSION of include/i2r_hip.h
 OP_CONV, OP_STEM, OP_MAXPOOL, OP_HEAD, OP_ENC_KV, OP_ENC_LAYER, OP_FORK, OP_JOIN, OP_CONV_GROUP = 1, 2, 3, 4, 5, 6, 7, 8, 9
 MAX_GROUP = 4
 OP_LAYERNORM, OP_WINATTN, OP_DWCONV, OP_UPSAMPLE = 10, 11, 12, 13
-OP_CONV_CHAIN = 14
+OP_CONV_CHAIN = 14  # retired (reserved in the header): never emitted
 OP_PE_RES_STEM = 15
 OP_HRT_ATTN = 16
 OP_HRT_MLP = 17
-OP_XSYNC = 18
+OP_XSYNC = 18  # retired (reserved in the header): never emitted
 OP_FUSE_UP = 19
 OP_CONV1X1_PAIR = 20
 OP_CONV1X1_LP = 21
@@ -31,7 +31,7 @@ OP_PE_CAT_VEC = 23
 OP_ROWS_GATHER, OP_VIEW_SCRAMBLE = 24, 25
 OP_RECORD, OP_WAIT = 26, 27  # point-to-point: lane field = lane | slot << 8 (| consumer lanes << 16 for RECORD)
 OP_LANE_FLAGS = 28          # args = device int32[64] flag buffer: the sync ops behind it run as device-side signal / wait kernels
-SYNC_OPS = (OP_FORK, OP_JOIN, OP_XSYNC, OP_RECORD, OP_WAIT, OP_LANE_FLAGS)  # ops that launch nothing (FORK / JOIN / XSYNC: `lane` is a lane mask)
+SYNC_OPS = (OP_FORK, OP_JOIN, OP_XSYNC, OP_RECORD, OP_WAIT, OP_LANE_FLAGS)  # ops that launch nothing (FORK / JOIN: `lane` is a lane mask)
 
 _fp = C.c_void_p  # device pointers travel as integers
 _i32 = C.c_int32
@@ -159,13 +159,6 @@ class ConvGroupArgs(C.Structure):
     _fields_ = [("d", C.POINTER(ConvDesc) * MAX_GROUP), ("block_map", _fp), ("n", _i32), ("map_len", _i32)]
 
 
-class ConvChainArgs(C.Structure):
-    _fields_ = [("descs", C.POINTER(C.POINTER(ConvDesc))), ("n_layers", _i32), ("n_members", _i32),
-                ("kdesc", _fp), ("item_ofs", _fp), ("items", _fp), ("flags", _fp), ("n_blocks", _i32),
-                ("n_flags", _i32), ("kdesc_bytes", _i32), ("capacity", _i32), ("nt", _i32), ("mt", _i32), ("cap", _i32), ("pf", _i32),
-                ("lds_bytes", _i32), ("tiles", (_i32 * 4) * MAX_GROUP)]
-
-
 class ImageRef(C.Structure):   # i2r_image_ref (24 bytes)
     _fields_ = [("img", C.c_void_p), ("ih", _i32), ("iw", _i32), ("row_bytes", _i32), ("reserved", _i32)]
 
@@ -180,7 +173,7 @@ class Op(C.Structure):
 
 # every symbol include/i2r_hip.h declares (tests/test_host.py::test_cabi_library_exports_every_declared_symbol checks the built library exports them all)
 EXPORTS = ("i2r_conv", "i2r_conv_grouped", "i2r_conv_kernel_name", "i2r_stem_conv", "i2r_pe_res_stem", "i2r_maxpool3x3s2", "i2r_head", "i2r_layernorm", "i2r_window_attn", "i2r_hrt_attn_block", "i2r_hrt_mlp_block", "i2r_dwconv3x3",
-           "i2r_upsample_bilinear_add", "i2r_upsample_bilinear_add_multi", "i2r_fuse_up_add", "i2r_conv1x1_pair", "i2r_conv1x1_lp", "i2r_flip_merge", "i2r_decode", "i2r_crop_affine", "i2r_box_mask", "i2r_crop_affine_cv2", "i2r_box_mask_cv2", "i2r_person_inputs_cv2", "i2r_conv_chain_pack", "i2r_conv_chain", "i2r_encoder_kv", "i2r_encoder_layer", "i2r_mh_attention", "i2r_pe_cat_vec", "i2r_rows_gather", "i2r_view_scramble",
+           "i2r_upsample_bilinear_add", "i2r_upsample_bilinear_add_multi", "i2r_fuse_up_add", "i2r_conv1x1_pair", "i2r_conv1x1_lp", "i2r_flip_merge", "i2r_decode", "i2r_crop_affine", "i2r_box_mask", "i2r_crop_affine_cv2", "i2r_box_mask_cv2", "i2r_person_inputs_cv2", "i2r_encoder_kv", "i2r_encoder_layer", "i2r_mh_attention", "i2r_pe_cat_vec", "i2r_rows_gather", "i2r_view_scramble",
            "i2r_run_program", "i2r_run_program_timed", "i2r_abi_version", "i2r_last_error", "i2r_device_check")
 
 _LIB = None
@@ -199,8 +192,6 @@ def load_library(path=LIB_PATH):
     L = C.CDLL(path)
     L.i2r_conv.argtypes = [C.POINTER(ConvDesc), C.c_void_p]
     L.i2r_conv_grouped.argtypes = [C.POINTER(C.POINTER(ConvDesc)), _i32, _fp, _i32, C.c_void_p]
-    L.i2r_conv_chain_pack.argtypes = [C.POINTER(ConvChainArgs), C.c_void_p, C.c_int64]
-    L.i2r_conv_chain.argtypes = [C.POINTER(ConvChainArgs), C.c_void_p]
     L.i2r_conv_kernel_name.argtypes = [C.POINTER(C.POINTER(ConvDesc)), _i32, C.c_char_p, _i32]
     L.i2r_stem_conv.argtypes = [_fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.c_void_p]
     L.i2r_pe_res_stem.argtypes = [_fp, _fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.c_void_p]

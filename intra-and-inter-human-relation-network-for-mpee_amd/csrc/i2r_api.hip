@@ -80,30 +80,6 @@ static int run_program(const i2r_op* ops, int32_t n_ops, void* const* streams, v
             flags = streams ? (int*)op.args : nullptr;
             continue;
         }
-        if (op.kind == I2R_OP_XSYNC) {  // all-to-all among the lanes of the mask: one event per lane, every other lane waits for it
-            if (!streams) continue;  // single-stream replay: program order already is the order
-            bool distinct = false;
-            for (int l = 1; l < 4; ++l)
-                if ((op.lane & (1 << l)) && streams[l] != streams[0]) distinct = true;
-            if (!distinct) continue;
-            I2R_CHECK_ARG(events, "i2r_run_program: xsync needs events");
-            hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-            for (int l = 0; l < 4 && rc == I2R_OK; ++l)
-                if (op.lane & (1 << l)) {
-                    ev[l] = (hipEvent_t)events[next_event++ & 7];
-                    if (hipEventRecord(ev[l], (hipStream_t)streams[l]) != hipSuccess) rc = I2R_E_LAUNCH;
-                }
-            for (int d = 0; d < 4 && rc == I2R_OK; ++d)
-                if (op.lane & (1 << d))
-                    for (int l = 0; l < 4 && rc == I2R_OK; ++l)
-                        if (l != d && ev[l] && streams[l] != streams[d])
-                            if (hipStreamWaitEvent((hipStream_t)streams[d], ev[l], 0) != hipSuccess) rc = I2R_E_LAUNCH;
-            if (rc != I2R_OK) {
-                i2r_set_error("i2r_run_program: xsync failed at op %d", i);
-                return rc;
-            }
-            continue;
-        }
         if (op.kind == I2R_OP_RECORD || op.kind == I2R_OP_WAIT) {  // point-to-point: lane = op.lane & 3, event 8 + slot
             if (!streams) continue;
             const int l = op.lane & 3, slot = (op.lane >> 8) & 7, consumers = (op.lane >> 16) & 15;
@@ -206,9 +182,6 @@ static int run_program(const i2r_op* ops, int32_t n_ops, void* const* streams, v
                 rc = i2r_layernorm(a->in, a->w, a->b, a->out, a->npix, a->c, a->cs, a->eps, a->out_dt, st);
                 break;
             }
-            case I2R_OP_CONV_CHAIN:
-                rc = i2r_conv_chain((const i2r_conv_chain_args*)op.args, st);
-                break;
             case I2R_OP_WINATTN: {
                 const i2r_winattn_args* a = (const i2r_winattn_args*)op.args;
                 rc = i2r_window_attn(a->qkv, a->bias, a->out, a->n_img, a->h, a->w_, a->c, a->cs, a->heads, st);

@@ -314,7 +314,6 @@ __global__ __launch_bounds__(256, (MT == 1 ? (NT == 3 ? 4 : 3) : 2)) void conv_w
 
 void* i2r_pick_conv_wino(int nt, int mt) {
     conv_fn fn = nullptr;
-    if (mt == 2 && nt == 3) fn = conv_wino_f32<2, 3>;
     if (mt == 1 && nt == 3) fn = conv_wino_f32<1, 3>;
     if (mt == 1 && nt == 4) fn = conv_wino_f32<1, 4>;
     return reinterpret_cast<void*>(fn);

@@ -111,39 +111,23 @@ def wino_fragment(conv_h, conv_w):
     return best[1], best[2]
 
 
-def _tune(name, default):
-    """A/B switches of tools/ (kernel variants, fusion on/off): read from the environment ONLY when I2R_TUNING=1 is set, so a product
-    run (bench.py refuses any I2R_* variable, tests never set them) cannot pick up a stray one.  16-bit note: LP1X1_MAX_PIX selects
-    the 1x1 kernel by the batch's pixel count, so a crop's 16-bit heat map is tolerance-stable, not bit-stable, across batch sizes
-    (fp32 results do not depend on the batch)."""
-    return os.environ.get(name, default) if os.environ.get("I2R_TUNING") == "1" else default
-
-
-_WINO_TABLE = _tune("I2R_WINO_TABLE", "0") == "1"  # LPT dispatch table for Winograd launches (default: members heaviest first)
-_WINO_MT = int(_tune("I2R_WINO_MT", "0"))  # fragments per Winograd workgroup
-LP1X1 = _tune("I2R_LP1X1", "1") != "0"  # 16-bit modes: single 1x1 convs over few pixels on i2r_conv1x1_lp
-LP1X1_MAX_PIX = int(_tune("I2R_LP1X1_MAX_PIX", "65536"))  # beyond that the implicit-GEMM kernel has enough workgroups to hide its staging
-_LP1X1_MT = int(_tune("I2R_LP1X1_MT", "0"))
+LP1X1 = True  # 16-bit modes: single 1x1 convs over few pixels on i2r_conv1x1_lp
+# ... up to this many pixels per batch: beyond that the implicit-GEMM kernel has enough workgroups to hide its staging.  The kernel is
+# chosen by the batch's pixel count, so a crop's 16-bit heat map is tolerance-stable, not bit-stable, across batch sizes (fp32 results do
+# not depend on the batch).
+LP1X1_MAX_PIX = 65536
 # branch widths whose transformer-block halves run as the fused 16-bit kernels (i2r_hrt_attn_block / i2r_hrt_mlp_block)
-_HRT_FUSED_ATTN = tuple(int(v) for v in _tune("I2R_HRT_FUSED_ATTN", "78,156,312").split(",") if v)
-_HRT_ATTN_VARIANT = int(_tune("I2R_HRT_ATTN_VARIANT", "0"))  # i2r_hrt_attn_block: 0 the library's choice, 1 wave per token tile, 2 wave per head
-_HRT_FUSED_MLP = tuple(int(v) for v in _tune("I2R_HRT_FUSED_MLP", "78,156,312").split(",") if v)
-_ENC_LP4 = _tune("I2R_ENC_LP4", "1") != "0"  # 16-bit encoder, long groups: four waves per workgroup share the K / V stream through LDS
-_HRT_MLP_VARIANT = int(_tune("I2R_HRT_MLP_VARIANT", "0"))  # i2r_hrt_mlp_block: 0 the table below, 1 fc2 accumulated per wave, 2 fc2 by output-block ownership
+_HRT_FUSED_ATTN = (78, 156, 312)
+_HRT_FUSED_MLP = (78, 156, 312)
 _MLP_VARIANT = {78: 1, 156: 2, 312: 2}  # measured (tools/time_hrt_mlp.py, host_rate.py): C = 156 29.0 -> 22.0 us, config 5 forward 4.19 -> 3.87 ms
-PAIR1X1 = _tune("I2R_PAIR1X1", "1") != "0"  # layer1's conv3 + next conv1 as one i2r_conv1x1_pair launch (fp32)
-_PAIR_MT = int(_tune("I2R_PAIR_MT", "0"))  # 16-pixel tiles per wave of that kernel
-WINOGRAD = _tune("I2R_WINOGRAD", "1") != "0"  # fp32 3x3 stride-1 convs on the Winograd F(2x2, 3x3) kernels
-_S2_MT = int(_tune("I2R_S2_MT", "1"))  # pixel fragments per wave of the stride-2 convs of the direct kernels (A/B: 0 = cost model's choice)
-_FUSE_PRE = int(_tune("I2R_FUSE_PRE", "1"))  # A/B: 0 = the fuse layers' down paths run entirely on the output's lane, after the xsync
+PAIR1X1 = True  # layer1's conv3 + next conv1 as one i2r_conv1x1_pair launch (fp32)
+WINOGRAD = True  # fp32 3x3 stride-1 convs on the Winograd F(2x2, 3x3) kernels
 # fork / join / record / wait as device-side signal / wait kernels (csrc/i2r_api.hip) when the lanes are independent queues.  A wait kernel
 # spins until ANOTHER kernel signals it: under a tool that lets one kernel run at a time (rocprofv3 counter collection serialises dispatches)
 # it could only time out, so the event form is used whenever a profiler library is attached to the process.
 PROFILER_ATTACHED = bool(os.environ.get("ROCP_TOOL_LIBRARIES") or os.environ.get("ROCPROFILER_LIBRARY_CTOR") or os.environ.get("HSA_TOOLS_LIB")
                          or any(t in os.environ.get("LD_PRELOAD", "") for t in ("rocprof", "roctracer", "rocprofiler")))  # rocprofv3 / rocprofv2 / rocprof / preloaded tools
-DEVICE_SYNC = _tune("I2R_DEVICE_SYNC", "1") != "0" and (not PROFILER_ATTACHED or _tune("I2R_DEVICE_SYNC_UNDER_PROFILER", "0") == "1")
-_FUSE_P2P = int(_tune("I2R_FUSE_P2P", "1"))  # A/B: 0 = one all-to-all xsync between a module's blocks and its fuse layers (rounds 3-5)
-_LANE_CAP = int(_tune("I2R_LANE_CAP", "4"))  # HRFormer-B: branches i >= cap - 1 share stream lane cap - 1 (A/B: fewer, longer lanes)
+DEVICE_SYNC = not PROFILER_ATTACHED
 
 
 class PackedConv:
@@ -723,7 +707,7 @@ class Program:
 
     def release_deferred(self, *acts):
         """buffers that SEVERAL lanes of the current fork region read (the branch outputs under the fuse layers): reusable only after
-        the next xsync / join has ordered every lane behind those reads"""
+        every lane is ordered behind those reads -- behind the next round of records and waits (all_waited) or the join"""
         for a in acts:
             if self.in_fork:
                 self.pending.append(a.t)
@@ -801,8 +785,6 @@ class Program:
             fw, fh = wino_fragment(conv_h, conv_w)
             d.algo, d.w = 1, pc.w_wino.data_ptr()
             mt = 1  # one fragment per item: 114 registers = 4 waves per SIMD (measured faster than two fragments at 2 waves per SIMD)
-            if _WINO_MT and nt == 3:  # (A/B; <2, 4> is not instantiated)
-                mt = _WINO_MT
             d.tile_h, d.tile_w, d.mt, d.wn, d.ck = fh, fw, mt, 1, 0
             n_frag = x.n * -(-conv_h // fh) * -(-conv_w // fw)
             geo = ("wino", -(-n_frag // mt) * (nfrag // nt))
@@ -814,7 +796,7 @@ class Program:
             # stride-2 convs stage four input pixels per output pixel: one fragment per wave and three or more workgroups per CU
             # hide that staging (tools/sweep_conv.py at 16 crops: 64->64 s2 82 -> 43 us, 256->96 s2 77 -> 67 us); the cost model's
             # rounds-of-256-workgroups term was fitted on stride-1 shapes
-            th, tw, mt = choose_tile(conv_h, conv_w, 4 // wn, pc.stride, max_d, x.n, n_cblk, force_mt=_S2_MT if pc.stride == 2 else 0)
+            th, tw, mt = choose_tile(conv_h, conv_w, 4 // wn, pc.stride, max_d, x.n, n_cblk, force_mt=1 if pc.stride == 2 else 0)
             d.tile_h, d.tile_w, d.mt, d.wn, d.ck = th, tw, mt, wn, 0
             geo = (conv_h, conv_w, 4 // wn, pc.stride, max_d, x.n, n_cblk)
             key = nt
@@ -831,8 +813,8 @@ class Program:
         """common mt + per-member tiles of a grouped launch (cost model: workgroups of all members share the chip)"""
         best = None
         # (all members: with 1x1 members in the group -- the fuse layers' second launch -- forcing it measured -0.7 % on the fp32 tower, +1.5 % on the bf16 one)
-        s2 = _S2_MT and all(geo[3] == 2 for _, geo, _ in group)
-        for mt in ((_S2_MT,) if s2 else (2, 3, 4, 1)):
+        s2 = all(geo[3] == 2 for _, geo, _ in group)
+        for mt in ((1,) if s2 else (2, 3, 4, 1)):
             try:
                 tiles = [choose_tile(*geo, force_mt=mt, want_cost=True) for _, geo, _ in group]
             except AssertionError:
@@ -850,74 +832,6 @@ class Program:
                 best = (cost, mt, tiles)
         _, mt, tiles = best
         return mt, tiles
-
-    def conv_chain(self, layers, lane=0):
-        """layers: list of groups (as collected by conv(group=...)), layer l of member g reading layer l-1's output of member g.
-        EXPERIMENTAL, off by default (I2R_CONV_CHAIN=1 enables): ONE persistent chain launch (i2r_conv_chain: tile-level dataflow
-        between the layers) instead of one grouped launch per layer.  Measured on MI355X at 32 crops: bit-identical results, but
-        7.9 ms/step against 7.2 ms with per-layer launches -- the per-item cache invalidation that makes the
-        producer's data visible costs more than the layer barriers it removes.  Returns True if the chain launch was used."""
-        G = len(layers[0])
-        ok = (G <= cabi.MAX_GROUP and all(len(g) == G for g in layers) and len({m[2] for g in layers for m in g}) == 1
-              and not any(m[0].algo for g in layers for m in g))
-        if not ok or _tune("I2R_CONV_CHAIN", "0") != "1":
-            for g in layers:
-                self.flush_group(g, lane)
-            return False
-        mt, tiles = self._group_tiles(layers[0])
-        order = sorted(range(G), key=lambda i: -(layers[0][i][0].cin * layers[0][i][0].ntaps))
-        L = len(layers)
-        ptrs = (C.POINTER(cabi.ConvDesc) * (L * G))()
-        for l, g in enumerate(layers):
-            for slot, i in enumerate(order):
-                d = g[i][0]
-                d.tile_h, d.tile_w, d.mt = tiles[i][1], tiles[i][2], mt
-                ptrs[l * G + slot] = C.pointer(d)
-                self.keep.append(d)
-        a = cabi.ConvChainArgs()
-        a.descs, a.n_layers, a.n_members = ptrs, L, G
-        lib = cabi.lib()
-        if lib.i2r_conv_chain_pack(C.byref(a), None, 0) != 0 or a.capacity < 8:
-            if _tune("I2R_CONV_CHAIN_VERBOSE", ""):
-                print("conv_chain fallback:", lib.i2r_last_error(), "capacity", a.capacity)
-            for g in layers:  # (no chain kernel for this blocking)
-                self.flush_group(g, lane)
-            return False
-        host = (C.c_char * a.kdesc_bytes)()
-        cabi.check(lib.i2r_conv_chain_pack(C.byref(a), host, a.kdesc_bytes), "i2r_conv_chain_pack")
-        kdesc = torch.frombuffer(host, dtype=torch.uint8).clone().to(self.device)
-        # ---- schedule: one work queue per XCD (workgroup index % 8) holding all items of its images, layer by layer, heaviest first
-        n_blocks = a.capacity // 8 * 8
-        n_img = layers[0][order[0]][1][5]
-        queues = []
-        for x in range(8):
-            q = []
-            imgs = [i for i in range(n_img) if i % 8 == x]
-            for l in range(L):
-                items = []
-                for slot in range(G):
-                    ty, tx, ncb, _ = [int(v) for v in a.tiles[slot]]
-                    cost = layers[0][order[slot]][0].cin * layers[0][order[slot]][0].ntaps
-                    for img in imgs:
-                        for t in range(ty * tx):
-                            for cb in range(ncb):
-                                items.append((-cost, (l << 26) | (slot << 24) | ((img * ty * tx + t) * ncb + cb)))
-                items.sort()
-                q += [code for _, code in items]
-            queues.append(q)
-        ofs = [0]
-        for q in queues:
-            ofs.append(ofs[-1] + len(q))
-        item_ofs = torch.tensor(ofs, dtype=torch.int32, device=self.device)
-        items = torch.tensor([c for q in queues for c in q], dtype=torch.int32, device=self.device)
-        flags = torch.zeros(a.n_flags + 17, dtype=torch.int32, device=self.device)
-        a.kdesc, a.item_ofs, a.items, a.flags, a.n_blocks = kdesc.data_ptr(), item_ofs.data_ptr(), items.data_ptr(), flags.data_ptr(), n_blocks
-        self.keep += [ptrs, kdesc, item_ofs, items, flags, host]
-        self.chain_flags = getattr(self, "chain_flags", []) + [(flags, a.n_flags)]
-        self.ops.append((cabi.OP_CONV_CHAIN, lane, a))
-        for g in layers:
-            del g[:]
-        return True
 
     def flush_group(self, group, lane=0):
         """Emit the convs collected in `group` as ONE grouped launch (same NT required; a common mt is chosen by the
@@ -953,7 +867,7 @@ class Program:
                 counts.append(-(-conv_h // d.tile_h) * -(-conv_w // d.tile_w) * n_img * n_cblk)
             works.append(d.cin * d.ntaps)
         a.n = len(group)
-        if (wino and _WINO_TABLE) or (not wino and len(set(works)) > 1):  # dispatch order: heaviest items first, balanced over the CUs
+        if not wino and len(set(works)) > 1:  # dispatch order: heaviest items first, balanced over the CUs
             bm = lpt_block_table(self.device, counts, works)
             self.keep.append(bm)
             a.block_map, a.map_len = bm.data_ptr(), bm.numel()
@@ -1082,10 +996,10 @@ class Program:
         return out
 
     def hrt_attn(self, x, ab, eps=1e-6, lane=0, variant=None):
-        """fused x + out_proj(window_attn(qkv(LN1 x))) (16-bit modes, i2r_hrt_attn_block); variant: None = the library's choice"""
+        """fused x + out_proj(window_attn(qkv(LN1 x))) (16-bit modes, i2r_hrt_attn_block); variant: None / 0 = the library's choice,
+        1 wave per token tile, 2 wave per head"""
         assert x.dt == 0 and x.c == ab["c"] and x.cs == ab["cs"]
-        variant = _HRT_ATTN_VARIANT if variant is None else variant
-        if variant == 0 or (variant == 1 and ab["c"] not in (78, 156)):
+        if not variant or (variant == 1 and ab["c"] not in (78, 156)):
             variant = 2  # measured (tools/time_hrt_attn.py, 16 crops bf16): wave per head 20.4 / 19.3 us against 25.6 / 30.2 us (C = 78 / 156)
         out = self.alloc(x.n, x.h, x.w, x.c)
         self.keep.append(ab)
@@ -1095,10 +1009,10 @@ class Program:
         return out
 
     def hrt_mlp(self, x, mb, eps=1e-6, lane=0, variant=None):
-        """fused x + mlp(LN2 x) (16-bit modes, i2r_hrt_mlp_block); variant: None = the measured choice per width"""
+        """fused x + mlp(LN2 x) (16-bit modes, i2r_hrt_mlp_block); variant: None / 0 = the measured choice per width (_MLP_VARIANT),
+        1 fc2 accumulated per wave, 2 fc2 by output-block ownership"""
         assert x.dt == 0 and x.c == mb["c"] and x.cs == mb["cs"]
-        variant = _HRT_MLP_VARIANT if variant is None else variant
-        if variant == 0 or (variant == 1 and mb["c"] > 156):
+        if not variant or (variant == 1 and mb["c"] > 156):
             variant = _MLP_VARIANT[mb["c"]]
         out = self.alloc(x.n, x.h, x.w, x.c)
         self.keep.append(mb)
@@ -1149,7 +1063,7 @@ class Program:
         self.keep.append(pc)
         a = cabi.Conv1x1LpArgs(x.ptr, pc.w_lp1.data_ptr(), pc.bias.data_ptr(), res1.ptr if res1 is not None else None,
                                res_post.ptr if res_post is not None else None, out.ptr, x.n * x.h * x.w, pc.cin_pad, pc.cout_pad, x.cs, out.cs,
-                               (int(relu) if act is None else act), pc.dtype, int(x.dt != 0), int(out.dt != 0), _LP1X1_MT,
+                               (int(relu) if act is None else act), pc.dtype, int(x.dt != 0), int(out.dt != 0), 0,
                                res2.ptr if res2 is not None else None)
         self.ops.append((cabi.OP_CONV1X1_LP, lane, a))
         return out
@@ -1164,7 +1078,7 @@ class Program:
         a = cabi.Conv1x1PairArgs(x.ptr, pa.w_frag.data_ptr(), pa.bias.data_ptr(), res.ptr if res is not None else None, y.ptr,
                                  pb.w_frag.data_ptr() if pb is not None else None, pb.bias.data_ptr() if pb is not None else None,
                                  z.ptr if z is not None else None, x.n * x.h * x.w, pa.cin, pa.cout, pb.cout if pb is not None else 0,
-                                 x.cs, y.cs, z.cs if z is not None else 0, 1, 1, _PAIR_MT)
+                                 x.cs, y.cs, z.cs if z is not None else 0, 1, 1, 0)
         self.ops.append((cabi.OP_CONV1X1_PAIR, lane, a))
         return y, z
 
@@ -1323,7 +1237,7 @@ class Program:
         grouping["goff"][:len(offs)].copy_(torch.tensor(offs, dtype=torch.int32).pin_memory(), non_blocking=True)
         for d, dt in grouping["descs"]:
             d.n_grp, d.n_qtiles32, d.n_qtiles16, d.n_qtiles64 = len(offs) - 1, nq, nq16, nq64
-            d.n_qtiles192 = nq192 if _ENC_LP4 else 0
+            d.n_qtiles192 = nq192  # (16-bit encoder, long groups: four waves per workgroup share the K / V stream through LDS)
             d.dtype = dt  # (both kernel families take any group offsets: K / V blocks are numbered group by group)
         for a in grouping.get("mh", ()):
             a.n_grp, a.n_qtiles16, a.n_qtiles32, a.n_qtiles64 = len(offs) - 1, nq16, nq, nq64
@@ -1344,16 +1258,9 @@ class Program:
             self.pool.setdefault(numel, []).extend(lst)
         self.lane_pool = {}
 
-    def xsync(self, mask):
-        """inside a fork region: every lane of `mask` (bit 0 = lane 0) continues after everything issued so far on the other lanes of
-        the mask.  It must name every lane the region uses: whatever any lane released before it is then reusable by all of them."""
-        assert self.in_fork
-        self.ops.append((cabi.OP_XSYNC, mask, None))
-        self._flush_lane_pools()
-
     # Point-to-point synchronisation inside a fork region (round 6).  `records(lanes)`: every lane puts an event behind what it has issued so
     # far; `wait(lane, slot)`: that lane's stream waits for one of them -- emitted right before the first launch that reads the other
-    # lane's data, so a lane starts the terms of the lanes that are done while the last one is still busy (an all-to-all xsync costs
+    # lane's data, so a lane starts the terms of the lanes that are done while the last one is still busy (an all-to-all barrier costs
     # every lane ~20 us after the LAST lane ends, tools/probe/xstream_latency2.hip).  Buffers: what the lanes had released when they
     # recorded becomes reusable by every lane at `all_waited()` -- the point of the launch list behind which every lane has waited for
     # every record; what is released after the records waits for the next round.  tests/test_lanes.py replays the happens-before relation.
@@ -1433,11 +1340,11 @@ class Program:
 
     # In-situ per-launch timing (bench.py `roofline`): while `Program.timing_log` is a list, every run() of every program
     # goes through i2r_run_program_timed and appends (program, t0 events, t1 events, the four lanes' stream handles); the forward itself --
-    # streams, lanes, sibling part-batch programs, fork / join / xsync -- is exactly the product's.  Every launch gets a STOP event bound
+    # streams, lanes, sibling part-batch programs, fork / join / record / wait -- is exactly the product's.  Every launch gets a STOP event bound
     # to its dispatch and (timing_markers) a START marker in front of it: elapsed(start, stop) is the kernel's own duration, whatever the
     # host or the other lanes do; the marker costs its stream ~5 us per launch (tools/probe/event_timing.hip), so the timed forward is
     # 10-20 % slower than the real one.  Without markers (only the first launch on each stream of a program has one) a launch's start is
-    # the completion of what it waited for -- its predecessor on the stream, or the lanes a fork / join / xsync named -- which
+    # the completion of what it waited for -- its predecessor on the stream, or the lanes a fork / join / wait named -- which
     # bench.in_situ_timing reconstructs from the stop events; measured on MI355X that form counts every moment a stream waits for the
     # HOST as kernel time (w48: 52.4 us per Winograd launch against 46.9 with markers) and still slows the forward by 12 %.
     # The caller synchronises, then reads the events (before the next timed run of the same program re-binds them).
@@ -1476,7 +1383,7 @@ class Program:
 
     def _own_events(self):
         if not hasattr(self, "_events"):
-            self._events = [torch.cuda.Event(enable_timing=False) for _ in range(16)]  # 0..7: fork / join / xsync (rotating), 8..15: record slots
+            self._events = [torch.cuda.Event(enable_timing=False) for _ in range(16)]  # 0..7: fork / join (rotating), 8..15: record slots
             for e in self._events:
                 e.record()  # forces creation of the underlying hipEvent_t
         return self._events
@@ -1524,29 +1431,17 @@ class HRNetW48:
         goes out in one launch, and the fuse sums are evaluated level by level (one launch per dependency depth)."""
         nb = mod["nb"]
         xs = list(xs)
-        nblk = max(len(b) for b in mod["blocks"])
-        uniform = all(len(b) == nblk for b in mod["blocks"])  # every branch has the same depth -> one persistent chain launch
-        layers = []
-        for k in range(nblk):
+        for k in range(max(len(b) for b in mod["blocks"])):
             grp, ts = [], {}
             for i in range(nb):
                 if k < len(mod["blocks"][i]):
                     ts[i] = P.conv(xs[i], mod["blocks"][i][k][0], relu=True, group=grp)
-            if uniform:
-                layers.append(grp)
-                grp = []
-            else:
-                P.flush_group(grp)
+            P.flush_group(grp)
             for i, t in ts.items():
                 y = P.conv(t, mod["blocks"][i][k][1], relu=True, res1=xs[i], group=grp)
                 P.release(t, xs[i])
                 xs[i] = y
-            if uniform:
-                layers.append(grp)
-            else:
-                P.flush_group(grp)
-        if uniform and layers:
-            P.conv_chain(layers)
+            P.flush_group(grp)
         # fuse (interformer_pureMulti.py:392-410): y_i = ReLU(sum_j f_ij(x_j)), f_ii = identity, summed left to right.
         #  * down-sampling terms (j < i, chains of stride-2 convs) are evaluated level by level, one grouped launch per level: every
         #    chain advances one conv per level while, per output, at most one term whose source is ready is ACCUMULATED into y_i
@@ -1725,9 +1620,9 @@ class HRFormerB:
     @classmethod
     def _emit_module(cls, P, mod, xs, lanes):
         """One HighResolutionTransformerModule.  With `lanes` the caller has forked lanes 0..nb-1 for the whole STAGE: branch i and fuse
-        output i both run on lane i, so the only synchronisation of a module is one all-to-all xsync between its branch blocks and
-        its fuse layers (every output reads every branch, hrformer.py:1716-1731) -- the next module's blocks of branch i read what
-        lane i itself has just written."""
+        output i both run on lane i, so the only synchronisation of a module is one round of point-to-point records and waits between
+        its branch blocks and its fuse layers (every output reads every branch, hrformer.py:1716-1731) -- the next module's blocks of
+        branch i read what lane i itself has just written."""
         nb = mod["nb"]
         xs = list(xs)
         # The branches of a module are independent until the fuse layers (hrformer.py:1708-1715) and the low-resolution ones are far
@@ -1736,57 +1631,51 @@ class HRFormerB:
         for k in range(max(len(b) for b in mod["blocks"])):
             for i in range(nb):
                 if k < len(mod["blocks"][i]):
-                    xs[i] = cls._emit_block(P, mod["blocks"][i][k], xs[i], lane=min(i, _LANE_CAP - 1) if lanes else 0)
+                    xs[i] = cls._emit_block(P, mod["blocks"][i][k], xs[i], lane=i if lanes else 0)
         # Down paths of the fuse layers (output i > source j: hops of dw 3x3 s2 + 1x1 conv, hrformer.py:1656-1700) read only branch j
         # until their last 1x1 conv, which adds the running sum of output i.  Everything before that conv runs on lane j BEFORE the
-        # all-to-all xsync: the high-resolution lanes finish their blocks early (fused kernels) while the low-resolution lanes, with
+        # records: the high-resolution lanes finish their blocks early (fused kernels) while the low-resolution lanes, with
         # eight small launches per block, are the longest of every region (tools/op_list.py) -- and would otherwise also run the
         # down paths' dw convs over the big maps.
         pre, pre_y = {}, {}
-        if lanes and _FUSE_PRE:
+        if lanes:
             for i in range(mod["n_out"]):
-                for j in range(min(i, nb)):
-                    lj = min(j, _LANE_CAP - 1)
-                    P.lane_ctx = lj
+                for j in range(i):
+                    P.lane_ctx = j
                     cur = xs[j]
                     hops = mod["fuse"][(i, j)]
                     for k, (dw, pc) in enumerate(hops):
-                        d = P.dwconv(cur, dw, 2, act=0, lane=lj)
+                        d = P.dwconv(cur, dw, 2, act=0, lane=j)
                         if cur is not xs[j]:
                             P.release(cur)
                         if k < len(hops) - 1:
-                            cur = P.conv(d, pc, relu=True, lane=lj)
+                            cur = P.conv(d, pc, relu=True, lane=j)
                             P.release(d)
                     pre[(i, j)] = d
-                    if _FUSE_P2P and j == 0 and i >= 2 and i < nb:
+                    if j == 0 and i >= 2:
                         # the FIRST term of output i >= 2 adds nothing (y = fuse[i][0](x_0), hrformer.py:1718): its last 1x1 conv runs here
                         # too, on the source lane -- the low-resolution lane i, the last to finish its blocks, then has one launch less
                         # between its blocks and the next module's
                         y0 = P.alloc(xs[i].n, xs[i].h, xs[i].w, xs[i].c)
-                        P.conv(d, hops[-1][1], relu=False, out=y0, lane=lj)
+                        P.conv(d, hops[-1][1], relu=False, out=y0, lane=j)
                         P.release(d)
                         pre_y[i] = y0
-        # Round 6: point-to-point waits instead of one all-to-all xsync.  Every lane records behind its blocks (and the down-path
-        # prologues); a fuse lane waits for lane j right before its first launch that reads lane j's data.  The low-resolution lane is
-        # the last to finish its blocks, and the terms that do not read it -- the 1x1 convs over the other branches, the last convs of the
-        # down paths -- now run under it instead of ~20 us after it (I2R_FUSE_P2P=0: the all-to-all form).
-        p2p = lanes and _FUSE_P2P
+        # Point-to-point waits (round 6): every lane records behind its blocks (and the down-path prologues); a fuse lane waits for lane j
+        # right before its first launch that reads lane j's data.  The low-resolution lane is the last to finish its blocks, and the terms
+        # that do not read it -- the 1x1 convs over the other branches, the last convs of the down paths -- run under it instead of ~20 us
+        # after it (an all-to-all barrier, rounds 3-5).
         slots, waited = {}, {}
-        if p2p:
-            region = sorted({min(i, _LANE_CAP - 1) for i in range(nb)})
-            slots = P.records(region)
-            waited = {l: {l} for l in region}
-        elif lanes:
-            P.xsync((1 << nb) - 1)
+        if lanes:
+            slots = P.records(range(nb))
+            waited = {l: {l} for l in range(nb)}
 
         def need(ln, j):  # lane ln is about to read what branch j's lane wrote before the records
-            lj = min(j, _LANE_CAP - 1)
-            if p2p and lj not in waited[ln]:
-                P.wait(ln, slots[lj])
-                waited[ln].add(lj)
+            if lanes and j not in waited[ln]:
+                P.wait(ln, slots[j])
+                waited[ln].add(j)
         outs = []
         for i in range(mod["n_out"]):
-            ln = min(i, _LANE_CAP - 1) if lanes else 0
+            ln = i if lanes else 0
             P.lane_ctx = ln
             # y = ((t_0 + t_1) + ...) then ReLU (hrformer.py:1716-1731); identity terms ride as residual inputs
             acc, y, j = None, None, 0
@@ -1817,7 +1706,7 @@ class HRFormerB:
                     hops = mod["fuse"][(i, j)]
                     need(ln, j)
                     for k, (dw, pc) in enumerate(hops):
-                        if (i, j) in pre:  # (everything up to the last dw conv ran on lane j before the xsync)
+                        if (i, j) in pre:  # (everything up to the last dw conv ran on lane j before the records)
                             if k < len(hops) - 1:
                                 continue
                             d = pre[(i, j)]
@@ -1838,13 +1727,13 @@ class HRFormerB:
                             P.release(d)
                 acc, j = y, jn
             outs.append(y)
-        if p2p:  # every lane behind every record before anything released ahead of the records changes hands
+        if lanes:  # every lane behind every record before anything released ahead of the records changes hands
             for ln in waited:
                 for lj in waited:
                     if lj not in waited[ln]:
                         P.wait(ln, slots[lj])
             P.all_waited()
-        P.release_deferred(*xs)  # (read by every fuse lane: reusable after the next xsync / round of waits / the stage's join)
+        P.release_deferred(*xs)  # (read by every fuse lane: reusable after the next round of waits / the stage's join)
         return outs
 
     def emit(self, P, n, h, w, n_src=None):
@@ -1866,7 +1755,7 @@ class HRFormerB:
                     P.release(ys[i])
             # one fork region per stage: lanes 1..nb-1 start behind the transition convs (lane 0) and are joined after the last module
             nb = st["mods"][0]["nb"]
-            lanes = 1 < nb <= 4 and _tune("I2R_BRANCH_LANES", "1") != "0"
+            lanes = 1 < nb <= 4
             mask = ((1 << nb) - 1) & ~1
             if lanes:
                 P.fork(mask)
@@ -1974,8 +1863,6 @@ def lane_streams(device, n):
             cur = torch.cuda.current_stream(device)
             _LANE_CALLER.setdefault(key, cur.cuda_stream)
             spare = _LANE_SPARE.setdefault(key, [])
-            for _ in range(int(_tune("I2R_STREAM_SKIP", "0"))):  # (A/B: shift the creation order)
-                spare.append(torch.cuda.Stream(device=device))
             tries = 0
             while len(lst) < n and tries < 12:
                 tries += 1
@@ -2500,7 +2387,7 @@ class Engine:
     # Not for the four-lane HRFormer-B programs (twice the launches of kernels whose time barely depends on the batch: 5.2 vs 3.8 ms).
     SPLIT_MIN_CROPS = 24
     SPLIT_MIN_PART = 8   # crops of the smallest part: a [23, 1] batch would double the launches for nothing to overlap with
-    SPLIT_PARTS = int(_tune("I2R_SPLIT_PARTS", "2"))
+    SPLIT_PARTS = 2
 
     def _split_bounds(self, length, H=None, W=None):
         """image index cuts [0, b1, ..., n] of the concurrent part-batches, or None (one program): every part needs >= SPLIT_MIN_PART
@@ -2508,9 +2395,7 @@ class Engine:
         tower's total stride; any other size takes the one-program path, which handles it)"""
         from .dist import shard_bounds
         parts = min(self.SPLIT_PARTS, len(length))
-        if _tune("I2R_SPLIT_BATCH", "1") == "0" or parts < 2 or sum(length) < self.SPLIT_MIN_CROPS:
-            return None
-        if not isinstance(getattr(self, "tower", None), HRNetW48) and _tune("I2R_SPLIT_BATCH", "1") != "2":  # (2: A/B, any tower)
+        if parts < 2 or sum(length) < self.SPLIT_MIN_CROPS or not isinstance(getattr(self, "tower", None), HRNetW48):
             return None
         if H is not None and (H % 16 or W % 16):
             return None

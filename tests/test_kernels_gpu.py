@@ -1,5 +1,4 @@
 """-m gpu: each HIP entry point of include/i2r_hip.h against the plain fp32 torch CPU op it replaces."""
-import os
 import pytest
 import torch
 import torch.nn.functional as F
@@ -539,54 +538,6 @@ def test_hrnet_fuse_module_matches_torch(nb):
         assert got.shape == refs[i].shape
         err = (got - refs[i]).abs().max().item()
         assert err < 1e-5 * max(1.0, refs[i].abs().max().item()), "fuse output %d: max-abs %.3e" % (i, err)
-
-
-def _chain_case(use_chain, n_img=9):
-    """two BasicBlocks (4 dependent 3x3 convs, residuals) on two branches, the way HRNetW48._emit_module emits them"""
-    os.environ["I2R_TUNING"], os.environ["I2R_CONV_CHAIN"] = "1", ("1" if use_chain else "0")  # (engine._tune: switches need I2R_TUNING=1)
-    saved_wino, engine.WINOGRAD = engine.WINOGRAD, False  # (the experimental chain launch drives the direct kernel)
-    try:
-        P = engine.Program(torch.device(DEV))
-        pk_sd, xs = {}, []
-        shapes = [(48, 32, 24), (96, 16, 12)]
-        for i, (c, h, w) in enumerate(shapes):
-            for l in range(4):
-                pk_sd["m%d.l%d.weight" % (i, l)] = _rand((c, c, 3, 3), "chw%d%d" % (i, l), (6.0 / (c * 9)) ** 0.5)
-            xs.append(to_act(P, _rand((n_img, c, h, w), "chx%d" % i)))
-        pk = engine.Packer(pk_sd, torch.device(DEV))
-        layers, cur = [], list(xs)
-        for blk in range(2):
-            g1, ts = [], []
-            for i in range(2):
-                ts.append(P.conv(cur[i], pk.conv("m%d.l%d" % (i, 2 * blk), None), relu=True, group=g1))
-            layers.append(g1)
-            g2 = []
-            for i in range(2):
-                y = P.conv(ts[i], pk.conv("m%d.l%d" % (i, 2 * blk + 1), None), relu=True, res1=cur[i], group=g2)
-                P.release(ts[i])
-                if blk > 0:
-                    P.release(cur[i])
-                cur[i] = y
-            layers.append(g2)
-        used = P.conv_chain(layers)
-        run(P)
-        run(P)  # replay: completion counters are re-zeroed by the launch
-        errs = [int(f[n].item()) for f, n in getattr(P, "chain_flags", [])]
-        return used, [from_act(t) for t in cur], errs
-    finally:
-        os.environ.pop("I2R_CONV_CHAIN", None)
-        os.environ.pop("I2R_TUNING", None)
-        engine.WINOGRAD = saved_wino
-
-
-def test_conv_chain_matches_per_layer_launches():
-    """the persistent dataflow launch computes exactly what the per-layer grouped launches compute (same kernels, same tiles)"""
-    used, ys, errs = _chain_case(True)
-    assert used and errs == [0], "chain launch not used / dependency wait timed out: %r %r" % (used, errs)
-    used0, ys0, _ = _chain_case(False)
-    assert not used0
-    for a, b in zip(ys, ys0):
-        assert torch.equal(a, b)
 
 
 @pytest.mark.parametrize("h,w,flip", [(256, 192, False), (64, 48, True), (38, 30, False)])

@@ -1,7 +1,7 @@
-"""CPU: memory safety of the stream-lane schedule of a launch program (engine.Program fork / join / xsync + the arena's buffer reuse).
+"""CPU: memory safety of the stream-lane schedule of a launch program (engine.Program fork / join / record / wait + the arena's buffer reuse).
 The HRFormer tower's program is built on the host (nothing is launched) and replayed symbolically: every op reads / writes byte ranges
 of arena buffers on its lane; two accesses to overlapping ranges of which at least one is a write must be ordered by the happens-before
-relation the fork / join / xsync ops create (vector clocks per lane).  A race here would not necessarily show up in a parity test."""
+relation the fork / join / record / wait ops create (vector clocks per lane).  A race here would not necessarily show up in a parity test."""
 import ctypes as C
 
 import pytest
@@ -93,12 +93,6 @@ def check_program(program):
             continue
         if kind == cabi.OP_WAIT:    # the waiting lane sees everything the slot's last record saw
             clock[lane & 3] = [max(a, b) for a, b in zip(clock[lane & 3], slot_clock[(lane >> 8) & 7])]
-            continue
-        if kind == cabi.OP_XSYNC:  # all-to-all among the lanes of the mask
-            ls = [l for l in range(4) if lane & (1 << l)]
-            m = [max(clock[l][i] for l in ls) for i in range(4)]
-            for l in ls:
-                clock[l] = list(m)
             continue
         clock[lane][lane] += 1
         snap = list(clock[lane])

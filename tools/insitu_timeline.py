@@ -48,18 +48,14 @@ for rep in range(3):
                     ready[sk] = mx(ready.get(sk), slot_t.get(slot))
                 rows.append((None, pi, -1, ("RECORD" if kind == cabi.OP_RECORD else "WAIT") + " lane %d slot %d" % (lane & 3, slot), None, None, i))
                 continue
-            if kind in cabi.SYNC_OPS:
+            if kind in (cabi.OP_FORK, cabi.OP_JOIN):
                 ls = [lanes[l] for l in range(4) if lane & (1 << l)]
                 if kind == cabi.OP_FORK:
                     for l in ls:
                         ready[l] = mx(ready.get(l), ready.get(lanes[0]))
-                elif kind == cabi.OP_JOIN:
-                    ready[lanes[0]] = mx(ready.get(lanes[0]), *[ready.get(l) for l in ls])
                 else:
-                    mm = mx(*[ready.get(l) for l in ls])
-                    for l in ls:
-                        ready[l] = mm
-                rows.append((None, pi, -1, {cabi.OP_FORK: "FORK", cabi.OP_JOIN: "JOIN"}.get(kind, "XSYNC") + " %x" % lane, None, None, i))
+                    ready[lanes[0]] = mx(ready.get(lanes[0]), *[ready.get(l) for l in ls])
+                rows.append((None, pi, -1, ("FORK" if kind == cabi.OP_FORK else "JOIN") + " %x" % lane, None, None, i))
                 continue
             end = e0.elapsed_time(t1[i]) * 1e3
             start = e0.elapsed_time(t0[i]) * 1e3 if t0[i] is not None else ready.get(lanes[lane])
