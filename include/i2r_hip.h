@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define I2R_ABI_VERSION 15
+#define I2R_ABI_VERSION 16
 
 /* The library is built with -fvisibility=hidden: the entry points declared in this header (marked I2R_API) are its ONLY exported
  * symbols (tests/test_host.py holds the header, the dynamic symbol table and cabi.EXPORTS equal). */
@@ -433,6 +433,22 @@ typedef struct i2r_mh_attn_args {
 } i2r_mh_attn_args;
 I2R_API int i2r_mh_attention(const i2r_mh_attn_args* a, void* stream);
 
+/* Attention maps: the need_weights output of nn.MultiheadAttention -- attn_output_weights averaged over the heads, [batch, L, L]
+ * (torch/nn/functional.py multi_head_attention_forward; read by the reference's visualize.py:128-268,270-420 through forward hooks on
+ * <stack>.layers[i].self_attn, discarded by validate()).  Per group g (= one batch entry of the reference, L_g tokens):
+ *   out[out_off[g] + i * L_g + j] = (1 / heads) sum_h softmax_j(q_h[i] . k_h[j])      i, j < L_g, row-major [L_g, L_g]
+ *   qk, grp_off, heads, hp, k_off, qk_cs: exactly as i2r_mh_attention reads them (q already scaled by head_dim^-0.5, pad dims 0)
+ *   out_off  device int64 [n_grp]: float offset of group g's block (sum L_g^2 exceeds 2^31 floats for large TransPose-H batches)
+ *   ws       device workspace of ws_stride floats per token row (rows up to grp_off[n_grp]); ws_stride >= 2 * heads * ceil(max L_g / 128)
+ *   n_tiles  = sum over the n_grp groups of ceil(L_g / 16) * ceil(L_g / 128): one wave per (16-query tile, 128-key block)
+ * Only the first n_grp groups are computed; nothing outside their blocks is written.  Two launches (row statistics per key block, then
+ * the normalised probabilities), fp32 matrix pipe, exp2-based softmax with fp32 statistics, heads summed in a fixed order: deterministic. */
+typedef struct i2r_attn_weights_args {
+    const float* qk; float* out; const int32_t* grp_off; const int64_t* out_off; float* ws;
+    int32_t n_grp, heads, hp, k_off, qk_cs, n_tiles, ws_stride;
+} i2r_attn_weights_args;
+I2R_API int i2r_attn_weights(const i2r_attn_weights_args* a, void* stream);
+
 /* MODEL.ATTENTION_TYPE != 'default' (MODEL.NAME interformer: attention.py:991-1031,1046-1062) -- the inter-human "encoder" is ONE
  * GeneralTransformerBlock: a multi-head attention (q / k / v / out projections with bias, MHA_ :494-835; the relative position bias is
  * gathered but its addition is commented out, :780-786) over the (person, y, x) tokens of an image INCLUDING the padded persons' rows
@@ -474,7 +490,7 @@ enum {
     I2R_OP_LAYERNORM = 10, I2R_OP_WINATTN = 11, I2R_OP_DWCONV = 12, I2R_OP_UPSAMPLE = 13, /* 14: reserved */
     I2R_OP_PE_RES_STEM = 15, I2R_OP_HRT_ATTN = 16, I2R_OP_HRT_MLP = 17, /* 18: reserved */ I2R_OP_FUSE_UP = 19,
     I2R_OP_CONV1X1_PAIR = 20, I2R_OP_CONV1X1_LP = 21, I2R_OP_MH_ATTN = 22, I2R_OP_PE_CAT_VEC = 23, I2R_OP_ROWS_GATHER = 24, I2R_OP_VIEW_SCRAMBLE = 25,
-    I2R_OP_RECORD = 26, I2R_OP_WAIT = 27, I2R_OP_LANE_FLAGS = 28
+    I2R_OP_RECORD = 26, I2R_OP_WAIT = 27, I2R_OP_LANE_FLAGS = 28, I2R_OP_ATTN_WEIGHTS = 29
 };
 
 typedef struct i2r_stem_args {

@@ -172,6 +172,151 @@ __global__ __launch_bounds__(256) void view_scramble_k(const float* __restrict__
     out[i] = v;
 }
 
+// ---- attention maps: the need_weights output of nn.MultiheadAttention (head-averaged softmax(q k^T)) --------------------------------
+// Work item = (group, 16-query tile, block of kAwKeys keys), one wave each, four independent waves per workgroup.  Both passes walk the
+// heads in order 0..heads-1 and the block's key tiles of 16, with the S^T = K Q^T fragment form of enc_mh_attn_k (lane (g, li) holds
+// S^T[key 4g + r][query li], r < 4), fp32 matrix pipe, no LDS:
+//   pass 1 (aw_stats_k)  per head: the running max m and the sum of exp2(s - m) of every query row over the block's keys -> ws
+//   pass 2 (aw_probs_k)  per head: combine the row's block statistics into (M, 1 / L), recompute s, p = exp2(s - M) / L, add into the
+//                        block's accumulators (fixed head order, no atomics); then one 16-byte store per lane and key tile: 4
+//                        consecutive keys of one query row (4-float pieces when the row length and the group's offset are multiples of
+//                        4, element stores otherwise -- no piece ever straddles a row end or touches a byte outside the block)
+// ws: per query row (token index) ws_stride floats = (m, l) per (key block, head).
+constexpr int kAwKeys = 128, kAwTiles = kAwKeys / 16;
+
+struct AwK {
+    const float* qk;
+    float* out;
+    const int* grp_off;
+    const long long* out_off;
+    float2* ws;
+    int n_grp, heads, hp, k_off, qk_cs, n_tiles, ws_stride;
+};
+
+// the work item of wave `item`: group gi (rows [g0, g1)), query rows [q0, q0 + 16), keys [k0, k0 + kAwKeys); false past the last one
+__device__ __forceinline__ bool aw_item(const AwK& p, int item, int& gi, int& g0, int& g1, int& q0, int& kb, int& nkb) {
+    for (gi = 0; gi < p.n_grp; ++gi) {
+        g0 = p.grp_off[gi];
+        g1 = p.grp_off[gi + 1];
+        const int len = g1 - g0;
+        if (len <= 0) continue;
+        nkb = (len + kAwKeys - 1) / kAwKeys;
+        const int nt = (len + 15) / 16 * nkb;
+        if (item < nt) {
+            q0 = g0 + item / nkb * 16;
+            kb = item - item / nkb * nkb;
+            return 2 * p.heads * nkb <= p.ws_stride;  // (a workspace row too short for this group: compute nothing rather than overrun it)
+        }
+        item -= nt;
+    }
+    return false;
+}
+
+template <int HB>
+__device__ __forceinline__ void aw_load_q(const AwK& p, int qrow, int head, int g, f32x4 (&q)[HB]) {
+    const float* qp = p.qk + (size_t)qrow * p.qk_cs + head * p.hp + 4 * g;
+#pragma unroll
+    for (int u = 0; u < HB; ++u) q[u] = *reinterpret_cast<const f32x4*>(qp + 16 * u) * kLog2e;
+}
+
+template <int HB>
+__device__ __forceinline__ f32x4 aw_scores(const AwK& p, int krow, int head, int g, const f32x4 (&q)[HB]) {
+    const float* kp = p.qk + (size_t)krow * p.qk_cs + p.k_off + head * p.hp + 4 * g;
+    f32x4 kk[HB];
+#pragma unroll
+    for (int u = 0; u < HB; ++u) kk[u] = *reinterpret_cast<const f32x4*>(kp + 16 * u);
+    f32x4 s = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int u = 0; u < HB; ++u)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) s = mfma16(kk[u][c], q[u][c], s);
+    return s;
+}
+
+template <int HB>
+__global__ __launch_bounds__(256) void aw_stats_k(const AwK p) {
+    const int lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4;
+    int gi, g0, g1, q0, kb, nkb;
+    if (!aw_item(p, blockIdx.x * 4 + (threadIdx.x >> 6), gi, g0, g1, q0, kb, nkb)) return;
+    const int qrow = min(q0 + li, g1 - 1), k_beg = g0 + kb * kAwKeys, k_end = min(k_beg + kAwKeys, g1);
+    for (int head = 0; head < p.heads; ++head) {
+        f32x4 q[HB];
+        aw_load_q<HB>(p, qrow, head, g, q);
+        float m = -INFINITY, l = 0.f;
+        for (int k0 = k_beg; k0 < k_end; k0 += 16) {
+            f32x4 s = aw_scores<HB>(p, min(k0 + li, g1 - 1), head, g, q);
+            float mx = -INFINITY;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                if (k0 + 4 * g + r >= k_end) s[r] = -INFINITY;
+                mx = fmaxf(mx, s[r]);
+            }
+            mx = fmaxf(mx, __shfl_xor(mx, 16));
+            mx = fmaxf(mx, __shfl_xor(mx, 32));
+            const float m_new = fmaxf(m, mx);  // (finite: key k0 of every tile exists)
+            float ps = 0.f;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) ps += __builtin_amdgcn_exp2f(s[r] - m_new);
+            l = l * __builtin_amdgcn_exp2f(m - m_new) + ps;
+            m = m_new;
+        }
+        l += __shfl_xor(l, 16);
+        l += __shfl_xor(l, 32);
+        if (g == 0 && q0 + li < g1) p.ws[(size_t)(q0 + li) * (p.ws_stride / 2) + kb * p.heads + head] = make_float2(m, l);
+    }
+}
+
+template <int HB>
+__global__ __launch_bounds__(256) void aw_probs_k(const AwK p) {
+    const int lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4;
+    int gi, g0, g1, q0, kb, nkb;
+    if (!aw_item(p, blockIdx.x * 4 + (threadIdx.x >> 6), gi, g0, g1, q0, kb, nkb)) return;
+    const int qrow = min(q0 + li, g1 - 1), k_beg = g0 + kb * kAwKeys, k_end = min(k_beg + kAwKeys, g1);
+    const int n_kt = (k_end - k_beg + 15) / 16;
+    const float2* st = p.ws + (size_t)qrow * (p.ws_stride / 2);
+    f32x4 acc[kAwTiles];
+#pragma unroll
+    for (int t = 0; t < kAwTiles; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int head = 0; head < p.heads; ++head) {
+        float mm = -INFINITY;
+        for (int b = 0; b < nkb; ++b) mm = fmaxf(mm, st[b * p.heads + head].x);
+        float ll = 0.f;
+        for (int b = 0; b < nkb; ++b) {
+            const float2 e = st[b * p.heads + head];
+            ll += e.y * __builtin_amdgcn_exp2f(e.x - mm);
+        }
+        const float inv = 1.f / ll;
+        f32x4 q[HB];
+        aw_load_q<HB>(p, qrow, head, g, q);
+#pragma unroll
+        for (int t = 0; t < kAwTiles; ++t) {
+            if (t < n_kt) {
+                const f32x4 s = aw_scores<HB>(p, min(k_beg + 16 * t + li, g1 - 1), head, g, q);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) acc[t][r] += __builtin_amdgcn_exp2f(s[r] - mm) * inv;
+            }
+        }
+    }
+    if (q0 + li >= g1) return;
+    const float rh = 1.f / (float)p.heads;
+    const long long len = g1 - g0;
+    float* row = p.out + p.out_off[gi] + (long long)(q0 + li - g0) * len;
+    const bool whole = (len & 3) == 0 && (p.out_off[gi] & 3) == 0 && (reinterpret_cast<uintptr_t>(p.out) & 15) == 0;
+#pragma unroll
+    for (int t = 0; t < kAwTiles; ++t) {
+        const int k = k_beg + 16 * t + 4 * g - g0;  // first of the lane's 4 keys, relative to the group
+        if (t >= n_kt || k >= len) continue;
+        const f32x4 v = acc[t] * rh;
+        if (whole) {
+            *reinterpret_cast<f32x4*>(row + k) = v;
+        } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (k + r < len) row[k + r] = v[r];
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int i2r_rows_gather(const float* src, float* out, const int32_t* map, int32_t n_out, int32_t floats_per_crop, void* stream) {
@@ -229,5 +374,29 @@ extern "C" int i2r_mh_attention(const i2r_mh_attn_args* a, void* stream) {
     const int wpb = a->heads >= 4 ? 4 : a->heads;  // waves (= heads) per workgroup
     i2r_launch(fn, dim3((unsigned)n_tiles, (unsigned)((a->heads + wpb - 1) / wpb)), dim3(64 * wpb), 0, (hipStream_t)stream, k);
     I2R_CHECK_LAUNCH("i2r_mh_attention");
+    return I2R_OK;
+}
+
+extern "C" int i2r_attn_weights(const i2r_attn_weights_args* a, void* stream) {
+    I2R_CHECK_ARG(a && a->qk && a->out && a->grp_off && a->out_off && a->ws, "i2r_attn_weights: null pointer");
+    I2R_CHECK_ARG(a->heads > 0 && a->hp > 0 && a->hp % 16 == 0 && a->hp <= 256, "i2r_attn_weights: heads=%d hp=%d (hp: multiple of 16, <= 256)", a->heads, a->hp);
+    const int hs = a->heads * a->hp;
+    I2R_CHECK_ARG(a->k_off >= hs && a->k_off % 4 == 0 && a->qk_cs >= a->k_off + hs && a->qk_cs % 4 == 0,
+                  "i2r_attn_weights: row stride qk=%d (k at %d) for %d heads x %d", a->qk_cs, a->k_off, a->heads, a->hp);
+    I2R_CHECK_ARG(a->n_grp > 0 && a->n_tiles > 0 && a->ws_stride >= 2 * a->heads && a->ws_stride % 2 == 0,
+                  "i2r_attn_weights: n_grp=%d n_tiles=%d ws_stride=%d", a->n_grp, a->n_tiles, a->ws_stride);
+    I2R_CHECK_ARG(reinterpret_cast<uintptr_t>(a->qk) % 16 == 0 && reinterpret_cast<uintptr_t>(a->ws) % 8 == 0, "i2r_attn_weights: alignment");
+    AwK k{a->qk, a->out, a->grp_off, reinterpret_cast<const long long*>(a->out_off), reinterpret_cast<float2*>(a->ws), a->n_grp, a->heads, a->hp,
+          a->k_off, a->qk_cs, a->n_tiles, a->ws_stride};
+    typedef void (*fn_t)(const AwK);
+#define I2R_AW_TABLE(K) {K<1>, K<2>, K<3>, K<4>, K<5>, K<6>, K<7>, K<8>, K<9>, K<10>, K<11>, K<12>, K<13>, K<14>, K<15>, K<16>}
+    static const fn_t stats[16] = I2R_AW_TABLE(aw_stats_k);
+    static const fn_t probs[16] = I2R_AW_TABLE(aw_probs_k);
+#undef I2R_AW_TABLE
+    const dim3 grid((unsigned)((a->n_tiles + 3) / 4));
+    i2r_launch(stats[a->hp / 16 - 1], grid, dim3(256), 0, (hipStream_t)stream, k);
+    I2R_CHECK_LAUNCH("i2r_attn_weights (statistics)");
+    i2r_launch(probs[a->hp / 16 - 1], grid, dim3(256), 0, (hipStream_t)stream, k);
+    I2R_CHECK_LAUNCH("i2r_attn_weights (probabilities)");
     return I2R_OK;
 }

@@ -679,6 +679,7 @@ class Program:
         self.groupings = []  # (grouping, tokens per crop) of encoders whose groups follow `length` (set_groups)
         self.enc_stacks = []
         self.split_counters = []  # hand-off counters of the encoder stacks (zero between launches; re-zeroed when a run fails)
+        self.captures = []   # encoder stacks whose attention maps this program computes (_capture_begin)
         self.store_dt = 0    # storage type the conv TOWER keeps its maps in (set by the engine in the 16-bit modes: 1 bf16, 2 f16)
         self.in_fork = False
         self.nbytes = 0
@@ -1105,15 +1106,19 @@ class Program:
             self.release(tmp)
         return a
 
-    def encoder(self, x, layers, grp_off_host, pos=None, pos_period=0, lane=0, regroupable=False, pre_norm=False, pos_table=None):
+    def encoder(self, x, layers, grp_off_host, pos=None, pos_period=0, lane=0, regroupable=False, pre_norm=False, pos_table=None, capture=None):
         """x: Act viewed as tokens [n*h*w, cs]; grp_off_host: python list of token offsets per group.
         regroupable: the grouping (persons per image) may be changed later with set_groups() without rebuilding the program:
-        the offset table gets capacity for one group per crop."""
+        the offset table gets capacity for one group per crop.
+        capture: dict(stack=state-dict prefix, layers={i: fp32 Packer.encoder_layer_mh pack of layer i}) -- the attention maps of those
+        layers are computed too (i2r_attn_weights, emitted before the layer's input is released); see set_capture."""
         assert x.dt == 0, "the encoder kernels read fp32 token rows"
         if layers and layers[0].get("mh"):
             return self.encoder_mh(x, layers, grp_off_host, pos=pos, pos_period=pos_period, lane=lane, regroupable=regroupable, pre_norm=pre_norm,
-                                   pos_table=pos_table)
+                                   pos_table=pos_table, capture=capture)
         assert not pre_norm, "the fused layer kernels are post-norm"
+        cap = self._capture_begin(capture, x)
+        pos_act = self._pos_rows(x, pos, pos_period, pos_table) if cap is not None else None
         n_tok = x.n * x.h * x.w
         cs = x.cs
         n_pad = (n_tok + 63) // 64 * 64 + 64
@@ -1138,6 +1143,11 @@ class Program:
         descs = []
         for i, L in enumerate(layers):
             assert L["cs"] == cs
+            if cap is not None and i in capture["layers"]:  # q|k of the fused layer's input, projected again in fp32 (the fused kernels keep it on chip)
+                mh = capture["layers"][i]
+                qk = self.conv(cur, mh["qk"], in2=pos_act, lane=lane)
+                self._capture_layer(cap, i, qk, mh, goff, lane)
+                self.release(qk)
             out = self.alloc(x.n, x.h, x.w, x.c)
             d = cabi.EncoderDesc()
             d.src, d.pos = cur.ptr, (pos if pos else None)
@@ -1162,34 +1172,32 @@ class Program:
             cur = out
         grouping = dict(descs=descs, goff=goff, current=None)
         self.set_groups(grouping, grp_off_host)
+        if cap is not None:
+            cap["grouping"] = grouping
         self.enc_stacks.append(grouping)  # every encoder stack of the program (bench.py: algorithmic FLOPs of the attention blocks)
         if regroupable:
             self.groupings.append((grouping, x.h * x.w))
         return cur
 
-    def encoder_mh(self, x, layers, grp_off_host, pos=None, pos_period=0, lane=0, regroupable=False, pre_norm=False, pos_table=None):
+    def encoder_mh(self, x, layers, grp_off_host, pos=None, pos_period=0, lane=0, regroupable=False, pre_norm=False, pos_table=None, capture=None):
         """The general encoder stack (Packer.encoder_layer_mh): per layer, post-norm (forward_post, attention.py:61-82)
             q|k = (src + pos) Wqk ; v = src Wv ; a = mh_attention ; x = LN1(src + a Wo) ; out = LN2(x + W2 relu(W1 x))
         or pre-norm (forward_pre, attention.py:84-103: q and k from LN1(src) + pos, the VALUE from src itself)
             q|k = (LN1(src) + pos) Wqk ; v = src Wv ; x = src + a Wo ; out = x + W2 relu(W1 LN2(x)).
-        pos: device address of per-token rows laid out like x, or of a [pos_period, cs] table (TransPose-H), or 0."""
-        pos_act = None
-        if pos:
-            if pos_period:  # the conv kernel adds a second INPUT of the same geometry: the table repeated per crop, built once
-                assert x.h * x.w == pos_period and pos_table is not None and pos_table.data_ptr() == pos and tuple(pos_table.shape) == (pos_period, x.cs)
-                rep = pos_table.unsqueeze(0).expand(x.n, pos_period, x.cs).contiguous()
-                self.keep.append(rep)
-                self.nbytes += rep.numel() * 4
-                pos = rep.data_ptr()
-            pos_act = _RawAct(pos, x)
+        pos: device address of per-token rows laid out like x, or of a [pos_period, cs] table (TransPose-H), or 0.
+        capture: as for encoder(); the maps are read from each captured layer's own q|k activation."""
+        pos_act = self._pos_rows(x, pos, pos_period, pos_table)
         goff = torch.zeros(x.n + 1, dtype=torch.int32, device=self.device)
         self.keep += [goff, layers]
         self.nbytes += goff.numel() * 4
+        cap = self._capture_begin(capture, x)
         cur, mh_args = x, []
-        for L in layers:
+        for i, L in enumerate(layers):
             assert L["cs"] == x.cs
             qk_in = self.layernorm(cur, L["ln1"], eps=1e-5, lane=lane) if pre_norm else cur
             qk = self.conv(qk_in, L["qk"], in2=pos_act, lane=lane)
+            if cap is not None and i in capture["layers"]:
+                self._capture_layer(cap, i, qk, L, goff, lane)
             v = self.conv(cur, L["v"], lane=lane)
             if pre_norm:
                 self.release(qk_in)
@@ -1218,10 +1226,75 @@ class Program:
                 self.release(y)
         grouping = dict(descs=[], mh=mh_args, goff=goff, current=None)
         self.set_groups(grouping, grp_off_host)
+        if cap is not None:
+            cap["grouping"] = grouping
         self.enc_stacks.append(grouping)
         if regroupable:
             self.groupings.append((grouping, x.h * x.w))
         return cur
+
+    def _pos_rows(self, x, pos, pos_period, pos_table):
+        """the position embedding as a second conv input laid out like x (None without one): per-token rows as they are, a [pos_period, cs]
+        table (TransPose-H) repeated per crop once at build time"""
+        if not pos:
+            return None
+        if pos_period:
+            assert x.h * x.w == pos_period and pos_table is not None and pos_table.data_ptr() == pos and tuple(pos_table.shape) == (pos_period, x.cs)
+            rep = pos_table.unsqueeze(0).expand(x.n, pos_period, x.cs).contiguous()
+            self.keep.append(rep)
+            self.nbytes += rep.numel() * 4
+            pos = rep.data_ptr()
+        return _RawAct(pos, x)
+
+    # ---- attention maps (capture programs) ----
+    # A capture program computes, next to its usual outputs, the head-averaged attention maps of the requested encoder layers
+    # (i2r_attn_weights) into ONE per-call buffer.  The launch list is fixed at build time; set_capture() patches the per-call part --
+    # output pointer, workspace, group count, tile count -- and uploads the group offsets of the blocks, like set_groups() does.
+    def _capture_begin(self, capture, x):
+        if not capture:
+            return None
+        cap = dict(stack=capture["stack"], x=x, ops=[], out_off=torch.zeros(x.n, dtype=torch.int64, device=self.device))
+        self.keep.append(cap["out_off"])
+        self.captures.append(cap)
+        return cap
+
+    def _capture_layer(self, cap, i, qk, L, goff, lane):
+        assert qk.dt == 0 and qk.cs >= 2 * L["hs"]
+        a = cabi.AttnWeightsArgs(qk.ptr, 0, goff.data_ptr(), cap["out_off"].data_ptr(), 0, 0, L["heads"], L["hp"], L["hs"], qk.cs, 0, 0)
+        self.keep.append(L)
+        self.ops.append((cabi.CAPTURE_OP_ATTN_WEIGHTS, lane, a))
+        cap["ops"].append((i, a))
+
+    AW_KEYS = 128  # key block of i2r_attn_weights (csrc/i2r_encoder_mh.hip kAwKeys)
+
+    def set_capture(self, glens):
+        """glens: per capture (program order) the token count of every group to compute (the real images / crops of this call, a prefix of
+        the stack's groups).  -> (buffer, {(stack, layer): [L_g x L_g views]}, {stack: input Act})."""
+        sizes, need_ws, rows = [], 2, 0
+        for cap, lens in zip(self.captures, glens):
+            assert len(lens) >= 1 and list(lens) == [cap["grouping"]["current"][g + 1] - cap["grouping"]["current"][g] for g in range(len(lens))]
+            heads = max(a.heads for _, a in cap["ops"]) if cap["ops"] else 1
+            need_ws = max(need_ws, 2 * heads * -(-max(lens) // self.AW_KEYS))
+            rows = max(rows, sum(lens))
+            offs = [0]
+            for n in lens:
+                offs.append(offs[-1] + n * n)
+            sizes.append(offs)
+        per_layer = [-(-offs[-1] // 4) * 4 for offs in sizes]  # (layer blocks start on 16-byte boundaries)
+        total = sum(n * len(cap["ops"]) for n, cap in zip(per_layer, self.captures))
+        buf = torch.empty(max(total, 1), dtype=torch.float32, device=self.device)
+        ws = torch.empty(rows * need_ws, dtype=torch.float32, device=self.device)
+        self._capture_ws = ws  # (kept until the next call: the launches read it asynchronously; torch's allocator orders reuse by stream)
+        maps, base = {}, 0
+        for cap, lens, offs, n_layer in zip(self.captures, glens, sizes, per_layer):
+            cap["out_off"][:len(lens)].copy_(torch.tensor(offs[:-1], dtype=torch.int64).pin_memory(), non_blocking=True)
+            tiles = sum(-(-n // 16) * -(-n // self.AW_KEYS) for n in lens)
+            for i, a in cap["ops"]:
+                a.out, a.ws = buf.data_ptr() + 4 * base, ws.data_ptr()
+                a.n_grp, a.n_tiles, a.ws_stride = len(lens), tiles, need_ws
+                maps[(cap["stack"], i)] = [buf[base + o:base + o + n * n].view(n, n) for o, n in zip(offs, lens)]
+                base += n_layer
+        return buf, maps, {cap["stack"]: cap["x"] for cap in self.captures}
 
     def set_groups(self, grouping, grp_off_host):
         """(Re)define the token groups of an encoder stack: uploads the offset table and patches the per-layer descriptors."""
@@ -2022,12 +2095,51 @@ class Engine:
             self._pk32 = self._pk if self._pk.dtype == 0 else Packer(self._pk.sd, self.device, "fp32")
         return self._pk32.encoder_layer_mh(p, d, dff, heads)
 
+    def capture_stacks(self):
+        """encoder stacks whose attention maps forward(..., capture=) / forward_single(..., capture=) can return: state-dict prefix ->
+        number of layers (the window-type block and the HRFormer stage are not encoder stacks)"""
+        out = {}
+        if getattr(self, "single_layers", None):
+            out[self.single_stack] = len(self.single_layers)
+        if getattr(self, "layers", None):
+            out["global_encoder" if self.name == "interformer_pureMulti" else "multi_global_encoder"] = len(self.layers)
+        return out
+
+    def _capture_spec(self, capture, stack, layers, d=None):
+        """the Program.encoder capture argument for one stack: {layer i: a pack with fp32 q|k projection weights} -- the layer's own pack
+        on the general path, else an fp32 Packer.encoder_layer_mh pack of the fused layer, built on first use"""
+        want = sorted(i for st, i in capture if st == stack)
+        if not want:
+            return None
+        cache = self.__dict__.setdefault("_capture_packs", {})
+        packs = {}
+        for i in want:
+            L = layers[i]
+            if not L.get("mh"):
+                if (stack, i) not in cache:
+                    if getattr(self, "_pk32", None) is None:
+                        self._pk32 = self._pk if self._pk.dtype == 0 else Packer(self._pk.sd, self.device, "fp32")
+                    M = self.cfg["MODEL"]
+                    cache[(stack, i)] = self._pk32.encoder_layer_mh("%s.layers.%d" % (stack, i), L["d"] if d is None else d, M["DIM_FEEDFORWARD"], M["N_HEAD"])
+                L = cache[(stack, i)]
+            packs[i] = L
+        return dict(stack=stack, layers=packs)
+
+    def _check_capture(self, capture):
+        stacks = self.capture_stacks()
+        capture = frozenset((str(st), int(i)) for st, i in capture)
+        for st, i in capture:
+            if st not in stacks or not 0 <= i < stacks[st]:
+                raise ValueError("capture (%r, %d): this model's encoder stacks are %s" % (st, i, stacks))
+        return capture
+
     def _pack_single(self, pk, sf, p):
         """first (intra-human) stage under key prefix p: transpose_h.TransPoseH (:418-480) or hrformer.HRFormer (:2470-2476)"""
         M = self.cfg["MODEL"]
         d, dff = M["DIM_MODEL"], M["DIM_FEEDFORWARD"]
         if sf == "transpose_h":
             self.tower = HRNetW48(pk, p, M["EXTRA"])
+            self.single_stack = p + "global_encoder"
             self.res_layer = M["HRNET_RES_LAYER"]
             self.reduce = pk.conv(p + "reduce")
             w, h = M["IMAGE_SIZE"]
@@ -2039,7 +2151,7 @@ class Engine:
             self.tower = HRFormerB(pk, p)
             self.single_head = pk.head(p + "keypoint_head.final_layer")
 
-    def _emit_single(self, P, S, H, W, n_src):
+    def _emit_single(self, P, S, H, W, n_src, capture=()):
         """-> (first-stage feature Act [S, H/4, W/4, d], stem args): tower (+ reduce + per-crop encoder for TransPose-H, :649-655)"""
         xs, stem_args = self.tower.emit(P, S, H, W, n_src=n_src)
         if self.singleformer == "hrformer":
@@ -2048,9 +2160,11 @@ class Engine:
         P.release(*xs)
         tok = f.h * f.w
         assert tok == self.single_tokens, "input size does not match MODEL.IMAGE_SIZE (pos_embedding rows)"
+        cap = self._capture_spec(capture, self.single_stack, self.single_layers) if capture else None
         g = P.encoder(f, self.single_layers, [i * tok for i in range(S + 1)],
-                      pos=self.single_pos.data_ptr() if self.single_pos is not None else 0, pos_period=tok, pos_table=self.single_pos)
-        P.release(f)
+                      pos=self.single_pos.data_ptr() if self.single_pos is not None else 0, pos_period=tok, pos_table=self.single_pos, capture=cap)
+        if cap is None:  # (a capture program returns the stack's input: the reduce output)
+            P.release(f)
         return g, stem_args
 
     def _pack_pos(self, pk, p, mode):
@@ -2150,12 +2264,13 @@ class Engine:
             b = c
         return b, pe_args
 
-    def _build(self, S, H, W, length, flip=False, part=None):
+    def _build(self, S, H, W, length, flip=False, part=None, capture=()):
         """flip: the flip test of validate() (lib/core/function.py:142-162) batched into the same forward -- crops S..2S-1 are
         the mirrored copies (mirroring happens inside the stem kernels), every image appears twice as a token group.
         part (models whose first stage is the bare HRNet tower): "tower" = the per-crop tower + reduce only -> (P, patch, features Act);
         "tail" = everything behind it (position branch, inter-human encoder, deconvs, head) reading a feature buffer that tower
-        programs fill (patch["feat"]) -- the two halves of a part-batch forward (_forward_split)."""
+        programs fill (patch["feat"]) -- the two halves of a part-batch forward (_forward_split).
+        capture: frozenset of (stack, layer) whose attention maps the program computes too (Program.set_capture)."""
         M = self.cfg["MODEL"]
         P = Program(self.device, multi_lane=self.multi_lane)
         P.store_dt = self.store_dt
@@ -2186,7 +2301,7 @@ class Engine:
                 P.finalize()
                 return P, patch, f
         else:
-            g, patch["x"] = self._emit_single(P, S, H, W, n_src)
+            g, patch["x"] = self._emit_single(P, S, H, W, n_src, capture)
             single_feat = g
             if self.return_dict:
                 patch["single"] = P.head(g, self.single_head)
@@ -2216,7 +2331,9 @@ class Engine:
         offs = [0]
         for n in length:
             offs.append(offs[-1] + n * tok)
-        e = P.encoder(f, self.layers, offs, pos=pos_ptr, regroupable=True, pre_norm=self.pre_norm)
+        stack = "global_encoder" if self.name == "interformer_pureMulti" else "multi_global_encoder"
+        cap = self._capture_spec(capture, stack, self.layers, d=f.c) if capture else None
+        e = P.encoder(f, self.layers, offs, pos=pos_ptr, regroupable=True, pre_norm=self.pre_norm, capture=cap)
         if cat is not None:  # self.fc: Conv2d(DIM_MODEL + MULTI_POS_EMBEDDING_DIM, DIM_MODEL, 1) with bias (interformer.py:157-158,302-303)
             t = P.conv(e, self.cat_fc, out_dt=0)
             P.release(e)
@@ -2310,18 +2427,20 @@ class Engine:
             # (NHWC arena buffer -> the reference's NCHW tensor: a torch view + copy, boundary plumbing only)
             return f.t.view(S, f.h, f.w, f.cs)[..., :f.c].permute(0, 3, 1, 2).contiguous()
 
-    def forward_single(self, x):
+    def forward_single(self, x, capture=None):
         """Stand-alone first stage, as the reference's InterFormer calls it (interformer.py:288): transpose_h.TransPoseH.forward
-        (:649-655) / hrformer.HRFormer.forward (:2477-2480): x [S,3,H,W] -> (features [S,d,H/4,W/4], heatmaps [S,J,H/4,W/4])."""
+        (:649-655) / hrformer.HRFormer.forward (:2477-2480): x [S,3,H,W] -> (features [S,d,H/4,W/4], heatmaps [S,J,H/4,W/4]).
+        capture: see forward(); then -> ((features, heatmaps), maps)."""
         assert self.name in ("transpose_h", "hrformer") and x.dim() == 4 and x.shape[1] == 3 and x.dtype == torch.float32
         S, _, H, W = x.shape
         x = x.to(self.device).contiguous()
-        key = (S, H, W, "single")
+        capture = self._check_capture(capture) if capture else frozenset()
+        key = (S, H, W, "single") + (("capture", capture) if capture else ())
         with torch.cuda.device(self.device):
             def build():
                 P = Program(self.device)
                 P.store_dt = self.store_dt
-                g, px = self._emit_single(P, S, H, W, S)
+                g, px = self._emit_single(P, S, H, W, S, capture)
                 hd = P.head(g, self.single_head)
                 P.finalize()
                 return (P, px, g, hd)
@@ -2330,10 +2449,22 @@ class Engine:
             J = self.cfg["MODEL"]["NUM_JOINTS"]
             hm = torch.empty(S, J, g.h, g.w, dtype=torch.float32, device=self.device)
             hd.out = hm.data_ptr()
+            if capture:
+                _, maps, inputs = P.set_capture([[g.h * g.w] * S])
             P.run(self.side_streams if P.uses_lanes else None)
             # (NHWC arena buffer -> the reference's NCHW feature tensor: a torch view + copy, boundary plumbing only)
             feat = g.t.view(S, g.h, g.w, g.cs)[..., :g.c].permute(0, 3, 1, 2).contiguous()
+            if capture:
+                return (feat, hm), self._capture_result(maps, inputs, S)
         return feat, hm
+
+    @staticmethod
+    def _capture_result(maps, inputs, S):
+        """maps + per captured stack its input features [S, c, h, w] (NCHW copies: the `reduce` output for the stacks fed by one)"""
+        out = dict(maps)
+        for st, a in inputs.items():
+            out[(st, "input")] = a.view()[:S, :, :, :a.c].permute(0, 3, 1, 2).contiguous()
+        return out
 
     @staticmethod
     def capacity(S):
@@ -2353,15 +2484,24 @@ class Engine:
     MAX_PROGRAMS = 48
     MAX_PROGRAM_BYTES = 32 << 30
 
-    def forward(self, x, pos_mask, length, flip_joint_map=None):
+    def forward(self, x, pos_mask, length, flip_joint_map=None, capture=None):
         """flip_joint_map (device int32 [J], see caller.joint_map): run the flip test in the same forward and return the merged
-        'multi' heatmaps (the reference merges only outputs['multi'], function.py:137-162)."""
+        'multi' heatmaps (the reference merges only outputs['multi'], function.py:137-162).
+        capture: a set of (stack, layer) -- stack a state-dict prefix of capture_stacks() -- whose attention maps to return as well:
+        -> (output, maps), maps[(stack, layer)] = per batch entry of that stack (image: inter-human, crop: intra-human) the [L, L] fp32
+        head-averaged softmax(q k^T) (views into one buffer per call), maps[(stack, "input")] = the stack's input features [S, c, h, w].
+        A capture forward is one program (no part-batches), built once per capture set; the default programs are not touched."""
         M = self.cfg["MODEL"]
         assert x.dim() == 4 and x.shape[1] == 3 and x.dtype == torch.float32
         S, _, H, W = x.shape
         assert S == sum(length), "sum(length)=%d != number of crops %d" % (sum(length), S)
         assert all(n >= 1 for n in length), "every image needs at least one person"
         self._sine_n = max(length)  # (MULTI_POS_EMBEDDING sine: the canvas is max(length) persons wide, for every part of this batch)
+        if capture:
+            capture = self._check_capture(capture)
+            assert flip_joint_map is None and not self.window_attn, "attention maps: no flip test, no window-type block"
+            with torch.cuda.device(self.device):
+                return self._forward_part(x, pos_mask, list(length), None, S, H, W, capture=capture)
         if self.window_attn and flip_joint_map is not None:
             # the window type mixes the rows of ALL images of a call (attention.py:1025-1029): the mirrored batch must be a call of its
             # own, as in validate() (function.py:142-162), not extra token groups of this one
@@ -2549,7 +2689,7 @@ class Engine:
             return merged
         return out[:S]
 
-    def _forward_part(self, x, pos_mask, length, flip_joint_map, S, H, W, slot=0):
+    def _forward_part(self, x, pos_mask, length, flip_joint_map, S, H, W, slot=0, capture=frozenset()):
         M = self.cfg["MODEL"]
         x = x.to(self.device).contiguous()
         flip = flip_joint_map is not None
@@ -2559,7 +2699,9 @@ class Engine:
         key = (cap, H, W, flip) if slot == 0 else (cap, H, W, flip, slot)  # (a Program owns its arena: the concurrent half needs its own)
         if self.window_attn:  # the padded person layout IS the program: no capacity slots, one program per `length`
             cap, key = S, (S, H, W, flip, "window", tuple(length))
-        P, patch = self._program(key, lambda: self._build(cap, H, W, list(length) + [1] * (cap - S), flip))
+        if capture:
+            key = key + ("capture", capture)
+        P, patch = self._program(key, lambda: self._build(cap, H, W, list(length) + [1] * (cap - S), flip, capture=capture))
         self.last_concurrent = []
         self.last_programs = [P]  # the program(s) of the most recent forward (bench.py's per-launch timing pass replays them; _forward merges the parts')
         glen = list(length) + [1] * (cap - S)
@@ -2591,6 +2733,12 @@ class Engine:
         if "single" in patch:
             single = torch.empty_like(out)
             patch["single"].out = single.data_ptr()
+        if capture:  # the real images / crops of this call: the capacity slots behind them cost nothing
+            glens = []
+            for c in P.captures:
+                tok = c["x"].h * c["x"].w
+                glens.append([tok] * S if c["stack"] == getattr(self, "single_stack", None) else [n * tok for n in length])
+            _, maps, inputs = P.set_capture(glens)
         P.run(self.side_streams if P.uses_lanes else None)
         if flip:
             merged = torch.empty(S, J, H // 4, W // 4, dtype=torch.float32, device=self.device)
@@ -2598,6 +2746,7 @@ class Engine:
             cabi.check(cabi.lib().i2r_flip_merge(out.data_ptr(), out[cap:].data_ptr(), flip_joint_map.data_ptr(), merged.data_ptr(),
                                                  S, J, H // 4, W // 4, st), "i2r_flip_merge")
             return merged
-        if self.name != "interformer_pureMulti" and self.return_dict:
-            return {"single": single[:S], "multi": out[:S]}
-        return out[:S]
+        res = {"single": single[:S], "multi": out[:S]} if self.name != "interformer_pureMulti" and self.return_dict else out[:S]
+        if capture:
+            return res, self._capture_result(maps, inputs, S)
+        return res

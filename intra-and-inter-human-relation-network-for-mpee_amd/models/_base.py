@@ -11,6 +11,37 @@ import torch.nn as nn
 from .. import arch, synth
 
 
+# Encoder stacks whose attention maps the forward hooks can capture (state-dict prefix of the stack -> the `reduce` conv that feeds it, or
+# None): the reference's visualize.py:128-268,270-420 registers hooks on <stack>.layers[i].self_attn (nn.MultiheadAttention, output[1] =
+# the head-averaged weights) and on reduce.  Their `layers` containers are nn.ModuleLists, so layers[i] / len(layers) work as there.
+ATTN_STACKS = {"global_encoder": "reduce", "multi_global_encoder": None, "singleformer.global_encoder": "singleformer.reduce"}
+
+
+def pad_attention_maps(maps):
+    """per batch entry [L_b, L_b] maps -> the reference's [batch, L, L] layout, L = max L_b: block [b, :L_b, :L_b] = maps[b], zeros
+    elsewhere.  Columns L_b.. are exactly what the reference's key_padding_mask gives; rows L_b.. would be the attention of the
+    zero-feature padded persons, which this port never builds."""
+    L = max(m.shape[0] for m in maps)
+    out = maps[0].new_zeros(len(maps), L, L)
+    for b, m in enumerate(maps):
+        out[b, :m.shape[0], :m.shape[1]] = m
+    return out
+
+
+def unpad_attention_maps(weights, lens):
+    """inverse of pad_attention_maps: [batch, L, L] + per-entry lengths -> list of [L_b, L_b] views"""
+    return [weights[b, :n, :n] for b, n in enumerate(lens)]
+
+
+def _call_forward_hooks(module, output):
+    """the module's forward hooks, called as a forward of it would (inputs: none -- the fused forward has no per-module call)"""
+    for hid, hook in list(module._forward_hooks.items()):
+        if hid in getattr(module, "_forward_hooks_with_kwargs", {}):
+            hook(module, (), {}, output)
+        else:
+            hook(module, (), output)
+
+
 def sine_position_embedding(h, w, d_model, temperature=10000.0, scale=2 * math.pi):
     """Fixed 2-D sine table [h*w, 1, d] the reference constructors store as a frozen parameter
     (interformer_pureMulti.py:516-541, transpose_h.py:502-527): cumsum coordinates normalised to (0, 2pi],
@@ -43,9 +74,10 @@ class I2RModule(nn.Module):
         for key, shape, dtype in spec:
             parts = key.split(".")
             mod = self
-            for p in parts[:-1]:
+            for j, p in enumerate(parts[:-1]):
                 if p not in mod._modules:
-                    mod.add_module(p, nn.Module())
+                    stack_layers = p == "layers" and ".".join(parts[:j]) in ATTN_STACKS
+                    mod.add_module(p, nn.ModuleList() if stack_layers else nn.Module())
                 mod = mod._modules[p]
             leaf = parts[-1]
             val = torch.from_numpy(synth.make_tensor(key, shape, dtype, seed=1234))
@@ -54,6 +86,15 @@ class I2RModule(nn.Module):
             else:
                 mod.register_parameter(leaf, nn.Parameter(val, requires_grad=False))
         self._init_sine_tables()
+        # hook sites, listed once: the per-forward check is a look at these modules' hook dicts
+        self._attn_sites, self._reduce_sites = [], []
+        mods = dict(self.named_modules())
+        for stack, red in ATTN_STACKS.items():
+            layers = mods.get(stack + ".layers")
+            if isinstance(layers, nn.ModuleList):
+                self._attn_sites += [(stack, i, layers[i].self_attn) for i in range(len(layers)) if "self_attn" in layers[i]._modules]
+                if red is not None and red in mods:
+                    self._reduce_sites.append((stack, mods[red]))
 
     def _init_sine_tables(self):
         M = self.cfg["MODEL"]
@@ -146,9 +187,29 @@ class I2RModule(nn.Module):
         with torch.no_grad():
             return eng.forward(x, pos_mask, [int(n) for n in length], flip_joint_map=jm)
 
+    def _hooked(self):
+        """(stack, layer, self_attn module) of every layer with forward hooks on its self_attn (usually none)"""
+        return [site for site in self._attn_sites if site[2]._forward_hooks]
+
+    def _serve_hooks(self, hooked, maps, length=None):
+        """call the hooks of the captured stacks' reduce modules (features [S, d, h, w]) and self_attn modules ((None, weights [batch, L, L]))"""
+        stacks = {st for st, _, _ in hooked}
+        for st, m in self._reduce_sites:
+            if st in stacks and m._forward_hooks:
+                _call_forward_hooks(m, maps[(st, "input")])
+        for st, i, m in hooked:
+            _call_forward_hooks(m, (None, pad_attention_maps(maps[(st, i)])))
+
     def forward(self, x, pos_mask, length):
-        """model(input, pos_mask, length) -- reference lib/core/function.py:135."""
+        """model(input, pos_mask, length) -- reference lib/core/function.py:135.  With forward hooks on <stack>.layers[i].self_attn the
+        same forward also computes those layers' attention maps and serves them to the hooks (visualize.py); without, the default path."""
         if torch.is_tensor(length):
             length = length.tolist()
+        length = [int(n) for n in length]
+        hooked = self._hooked()
         with torch.no_grad():
-            return self.engine().forward(x, pos_mask, [int(n) for n in length])
+            if not hooked:
+                return self.engine().forward(x, pos_mask, length)
+            out, maps = self.engine().forward(x, pos_mask, length, capture={(st, i) for st, i, _ in hooked})
+            self._serve_hooks(hooked, maps, length)
+            return out

@@ -22,8 +22,13 @@ class TransPoseH(I2RModule):
 
     def forward(self, x):
         """x [S, 3, H, W] -> (features, heatmaps)  (transpose_h.py:649-655)"""
+        hooked = self._hooked()
         with torch.no_grad():
-            return self.engine().forward_single(x)
+            if not hooked:
+                return self.engine().forward_single(x)
+            out, maps = self.engine().forward_single(x, capture={(st, i) for st, i, _ in hooked})
+            self._serve_hooks(hooked, maps)
+            return out
 
 
 def get_pose_net(cfg, is_train, pretrained_path="", is_end2end=False, **kwargs):
