@@ -1367,3 +1367,54 @@ def test_record_wait_ops_order_two_lanes(device_sync):
         assert not P1.sync_timed_out()
     finally:
         engine.DEVICE_SYNC = saved
+
+
+# ---------------------------------------------------------------------------------------------------------
+# every instantiation of the implicit-GEMM conv family, through the raw C-ABI (tests/_conv_cases.py)
+# ---------------------------------------------------------------------------------------------------------
+import _conv_cases as cc  # noqa: E402
+
+
+@pytest.mark.parametrize("case", cc.CASES, ids=lambda c: c.id)
+def test_conv_every_instantiation_matches_float64(case):
+    """i2r_conv called directly with a descriptor that resolves to ONE named instantiation conv_igemm_f32 / conv_igemm_lp<MT, NT, CAP, PF>
+    (the engine's cost model picks only a few of the 144 for the small shapes of the other tests), against the header formula of
+    i2r_conv_desc in float64 (cc.reference).  Tolerances are the ones this file already uses: fp32 2e-5 * max(1, max |ref|)
+    (test_conv_winograd_matches_torch_and_direct), 16-bit operands 5e-4 absolute against the sum of the rounded operands
+    (test_conv_low_precision), 16-bit output one ulp relative + 5e-4 (test_conv_16bit_activation_storage).  The output sits between guard
+    rows in a buffer full of 7.0: pixels the descriptor does not own, the guard rows and the channels past cout_pad keep the 7.0, channels
+    cout .. cout_pad - 1 are exactly zero."""
+    import ctypes as C
+    from i2r_amd import cabi
+    dev = torch.device(DEV)
+    t = cc.make_tensors(case)
+    d, out, keep = cc.launch_args(case, t, dev)
+    rc, name, err = cc.resolve([d])
+    assert rc == 0 and name == case.name, (name, err)
+    cabi.check(cabi.lib().i2r_conv(C.byref(d), torch.cuda.current_stream(dev).cuda_stream), "i2r_conv")
+    torch.cuda.synchronize()
+    cc.check_output(case, t, out.cpu())
+
+
+@pytest.mark.parametrize("group", cc.GROUP_CASES, ids=lambda g: g.id)
+def test_conv_grouped_forced_variants_match_float64(group):
+    """i2r_conv_grouped with 2..4 members that alone would run different staging variants: resolve() forces the most general one on all of
+    them (PF 1 + PF 2 -> PF 2; narrow + wide CAP -> the wide kernel running a member with 4 channel groups per chunk; any PF 0 -> all
+    PF 0), with and without a dispatch table (engine.lpt_block_order, a reversed and an interleaved order).  Every member has its own
+    guarded output and is checked like a single launch."""
+    import ctypes as C
+    from i2r_amd import cabi
+    dev = torch.device(DEV)
+    ts = [cc.make_tensors(m) for m in group.members]
+    args = [cc.launch_args(m, t, dev) for m, t in zip(group.members, ts)]
+    descs = [a[0] for a in args]
+    rc, name, err = cc.resolve(descs)
+    assert rc == 0 and name == group.name, (name, err)
+    bm = group.block_map()
+    bmd = torch.tensor(bm, dtype=torch.int32, device=dev) if bm is not None else None
+    arr = (C.POINTER(cabi.ConvDesc) * len(descs))(*[C.pointer(d) for d in descs])
+    cabi.check(cabi.lib().i2r_conv_grouped(arr, len(descs), bmd.data_ptr() if bm is not None else None, len(bm) if bm is not None else 0,
+                                           torch.cuda.current_stream(dev).cuda_stream), "i2r_conv_grouped")
+    torch.cuda.synchronize()
+    for m, t, a in zip(group.members, ts, args):
+        cc.check_output(m, t, a[1].cpu())
