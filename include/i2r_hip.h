@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define I2R_ABI_VERSION 16
+#define I2R_ABI_VERSION 17
 
 /* The library is built with -fvisibility=hidden: the entry points declared in this header (marked I2R_API) are its ONLY exported
  * symbols (tests/test_host.py holds the header, the dynamic symbol table and cabi.EXPORTS equal). */
@@ -171,6 +171,36 @@ I2R_API int i2r_flip_merge(const float* y, const float* y_flipped, const int32_t
  * heatmaps [n, joints, h, w]; center, scale [n, 2] (unused when transform_back == 0); preds [n, joints, 2]; maxvals [n, joints]. */
 I2R_API int i2r_decode(const float* heatmaps, const float* center, const float* scale, float* preds, float* maxvals, int32_t n,
                int32_t joints, int32_t h, int32_t w, int32_t blur_kernel, int32_t transform_back, void* stream);
+
+/* i2r_pose_nms -- what every dataset class of the reference does with the decoded key points before it writes a result: the per-person
+ * rescoring (lib/dataset/coco.py:384-396, same block in crowdpose.py / ochuman.py / coco_ochuman.py) and the per-image OKS-NMS or
+ * soft-OKS-NMS (lib/nms/nms.py:75-181).  One workgroup per image.
+ *   rescoring  score = mean of maxvals[j] over the joints with maxvals[j] > in_vis_thre (0 if none) * box_score; fp32, joints added in
+ *              ascending order, one division, one multiplication: bit-identical to the reference's float32 value
+ *   OKS        e_j = (dx^2 + dy^2) / (2 sigma_j)^2 / ((area_g + area_d) / 2 + spacing(1)) / 2, oks = mean_j exp(-e_j); dx^2 + dy^2 in fp32
+ *              (the reference's key points are float32), the rest in fp64.  use_oks_vis != 0: only the joints of the CANDIDATE d with
+ *              maxvals > oks_vis_thre count (nms.py:95 evaluates to that mask alone); no such joint: oks = 0.  The dataset classes
+ *              never pass that threshold: use_oks_vis = 0 is the reference's evaluate()
+ *   hard form  descending score; keep the head, drop every remaining person with oks(head, person) > oks_thre, repeat (max_dets unused)
+ *   soft form  (soft = 1) take the head, multiply every remaining score by exp(-oks^2 / oks_thre), re-sort, stop after max_dets (20 in
+ *              the reference; <= 0: no limit).  The decayed scores stay inside the kernel: `score` is the rescored value
+ *   equal scores: the person with the lower crop index first (the reference's order is that of an unstable sort: undefined)
+ * Inputs (device): preds [n_crops, joints, 2] and maxvals [n_crops, joints] as i2r_decode writes them; area [n_crops], or, when area is
+ * null, scale [n_crops, 2] with area = (scale_x * 200) * (scale_y * 200) in fp32 (lib/core/function.py:220); box_score [n_crops];
+ * img_off int32 [n_img + 1]: crop offset of every image (prefix sums of `length`, img_off[n_img] <= n_crops); sigmas [joints].
+ * max_persons: HOST-side upper bound of the persons of one image (sizes the LDS; 1..1024, more is I2R_E_ARG and nothing is launched).
+ * Outputs (device, per crop / per image, fixed size): score [n_crops] fp32; rank int32 [n_crops]: position in the reference's `keep`
+ * list of the crop's image, -1 = suppressed or cut by max_dets; n_keep int32 [n_img].  An image whose offsets do not describe the
+ * batch (negative count, beyond n_crops, more than max_persons persons) gets n_keep = -1 and nothing else written.  Crops outside
+ * [img_off[0], img_off[n_img]) are not written.  n_crops == 0 or n_img == 0 returns I2R_OK at once.  1 <= joints <= 32. */
+typedef struct i2r_pose_nms_args {
+    const float* preds; const float* maxvals; const float* scale; const float* area; const float* box_score;
+    const int32_t* img_off; const float* sigmas;
+    float* score; int32_t* rank; int32_t* n_keep;
+    double in_vis_thre, oks_thre, oks_vis_thre;
+    int32_t n_crops, n_img, joints, max_persons, soft, max_dets, use_oks_vis, reserved;
+} i2r_pose_nms_args;
+I2R_API int i2r_pose_nms(const i2r_pose_nms_args* a, void* stream);
 
 /* ---- input side (reference lib/dataset/JointsDataset.py:296-333) ------------------------
  * i2r_crop_affine -- cv2.warpAffine(image, trans, IMAGE_SIZE, INTER_LINEAR) + ToTensor + Normalize for the n persons of ONE

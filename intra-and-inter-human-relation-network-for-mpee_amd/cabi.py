@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libi2r_hip.so")
 
 MAX_TAPS = 9
-ABI_VERSION = 16  # I2R_ABI_VERSION of include/i2r_hip.h
+ABI_VERSION = 17  # I2R_ABI_VERSION of include/i2r_hip.h
 OP_CONV, OP_STEM, OP_MAXPOOL, OP_HEAD, OP_ENC_KV, OP_ENC_LAYER, OP_FORK, OP_JOIN, OP_CONV_GROUP = 1, 2, 3, 4, 5, 6, 7, 8, 9
 MAX_GROUP = 4
 OP_LAYERNORM, OP_WINATTN, OP_DWCONV, OP_UPSAMPLE = 10, 11, 12, 13
@@ -167,6 +167,14 @@ class ConvGroupArgs(C.Structure):
     _fields_ = [("d", C.POINTER(ConvDesc) * MAX_GROUP), ("block_map", _fp), ("n", _i32), ("map_len", _i32)]
 
 
+class PoseNmsArgs(C.Structure):   # i2r_pose_nms_args
+    _fields_ = [("preds", _fp), ("maxvals", _fp), ("scale", _fp), ("area", _fp), ("box_score", _fp), ("img_off", _fp), ("sigmas", _fp),
+                ("score", _fp), ("rank", _fp), ("n_keep", _fp),
+                ("in_vis_thre", C.c_double), ("oks_thre", C.c_double), ("oks_vis_thre", C.c_double),
+                ("n_crops", _i32), ("n_img", _i32), ("joints", _i32), ("max_persons", _i32), ("soft", _i32), ("max_dets", _i32),
+                ("use_oks_vis", _i32), ("reserved", _i32)]
+
+
 class ImageRef(C.Structure):   # i2r_image_ref (24 bytes)
     _fields_ = [("img", C.c_void_p), ("ih", _i32), ("iw", _i32), ("row_bytes", _i32), ("reserved", _i32)]
 
@@ -181,7 +189,7 @@ class Op(C.Structure):
 
 # every symbol include/i2r_hip.h declares (tests/test_host.py::test_cabi_library_exports_every_declared_symbol checks the built library exports them all)
 EXPORTS = ("i2r_conv", "i2r_conv_grouped", "i2r_conv_kernel_name", "i2r_stem_conv", "i2r_pe_res_stem", "i2r_maxpool3x3s2", "i2r_head", "i2r_layernorm", "i2r_window_attn", "i2r_hrt_attn_block", "i2r_hrt_mlp_block", "i2r_dwconv3x3",
-           "i2r_upsample_bilinear_add", "i2r_upsample_bilinear_add_multi", "i2r_fuse_up_add", "i2r_conv1x1_pair", "i2r_conv1x1_lp", "i2r_flip_merge", "i2r_decode", "i2r_crop_affine", "i2r_box_mask", "i2r_crop_affine_cv2", "i2r_box_mask_cv2", "i2r_person_inputs_cv2", "i2r_encoder_kv", "i2r_encoder_layer", "i2r_mh_attention", "i2r_attn_weights", "i2r_pe_cat_vec", "i2r_rows_gather", "i2r_view_scramble",
+           "i2r_upsample_bilinear_add", "i2r_upsample_bilinear_add_multi", "i2r_fuse_up_add", "i2r_conv1x1_pair", "i2r_conv1x1_lp", "i2r_flip_merge", "i2r_decode", "i2r_pose_nms", "i2r_crop_affine", "i2r_box_mask", "i2r_crop_affine_cv2", "i2r_box_mask_cv2", "i2r_person_inputs_cv2", "i2r_encoder_kv", "i2r_encoder_layer", "i2r_mh_attention", "i2r_attn_weights", "i2r_pe_cat_vec", "i2r_rows_gather", "i2r_view_scramble",
            "i2r_run_program", "i2r_run_program_timed", "i2r_abi_version", "i2r_last_error", "i2r_device_check")
 
 _LIB = None
@@ -205,6 +213,7 @@ def load_library(path=LIB_PATH):
     L.i2r_pe_res_stem.argtypes = [_fp, _fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.c_void_p]
     L.i2r_flip_merge.argtypes = [_fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, C.c_void_p]
     L.i2r_decode.argtypes = [_fp, _fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, C.c_void_p]
+    L.i2r_pose_nms.argtypes = [C.POINTER(PoseNmsArgs), C.c_void_p]
     L.i2r_crop_affine.argtypes = [_fp, _i32, _i32, _i32, _i32, _fp, _fp, _fp, _fp, _i32, _i32, _i32, C.c_void_p]
     L.i2r_box_mask.argtypes = [_fp, _i32, _i32, _fp, _i32, _i32, _i32, C.c_void_p]
     L.i2r_crop_affine_cv2.argtypes = [_fp, _i32, _i32, _i32, _i32, _fp, _fp, _fp, _fp, _i32, _i32, _i32, C.c_void_p]

@@ -101,10 +101,30 @@ def gather_keypoints(preds, maxvals, counts, group=None, async_op=False):
     return gather_heatmaps(kp, counts, group)
 
 
+def gather_poses(preds, maxvals, nms, counts, group=None, async_op=False):
+    """The per-step collective when rescoring + OKS-NMS run on the device too (caller.rescore_nms -> nms.score [S_r], nms.rank [S_r]):
+    rows [sum(counts), J * 3 + 2] in global crop order = key points (x, y, score per joint), rescored value, rank as a float (-1 =
+    suppressed; ranks stay below 2^24, so the float holds them exactly) through the same padded all-gather.  Images are never split
+    across ranks (shard_bounds), so the NMS is rank-local and the ranks need no correction.  unpack_poses() splits the rows again."""
+    S, J = preds.shape[0], preds.shape[1]
+    rows = torch.cat([torch.cat([preds, maxvals.reshape(S, J, 1)], dim=2).reshape(S, J * 3), nms.score.reshape(S, 1).to(preds.dtype),
+                      nms.rank.reshape(S, 1).to(preds.dtype)], dim=1).contiguous()
+    if async_op:
+        return gather_heatmaps_async(rows, counts, group)
+    return gather_heatmaps(rows, counts, group)
+
+
+def unpack_poses(rows):
+    """rows [S, J * 3 + 2] of gather_poses -> (key points [S, J, 3], score [S] fp32, rank [S] int32)"""
+    S, J = rows.shape[0], (rows.shape[1] - 2) // 3
+    return rows[:, :J * 3].reshape(S, J, 3), rows[:, J * 3], rows[:, J * 3 + 1].to(torch.int32)
+
+
 class PostStep:
     """What follows the forward inside a data-parallel step -- device decode + the all-gather -- issued on a side stream so that it runs
     under the NEXT forward instead of between two forwards: the caller's stream only records one event; the side stream waits for it,
-    decodes (`decode(y) -> (preds, maxvals)`, or None for the heat-map payload), starts the asynchronous all-gather and, one step later,
+    decodes (`decode(y) -> (preds, maxvals)`, or `(preds, maxvals, nms)` with nms = caller.rescore_nms(...) for the gather_poses payload,
+    or None for the heat-map payload), starts the asynchronous all-gather and, one step later,
     waits for it.  `result()` joins the caller's stream with the last gather and returns its tensor (the host-visible end of a run).
     The forward's output stays alive for the side stream through record_stream."""
 
@@ -135,8 +155,12 @@ class PostStep:
         with torch.cuda.stream(self.stream):
             self.stream.wait_event(self.ready)
             if self.decode is not None:
-                preds, maxv = self.decode(y)
-                h = gather_keypoints(preds, maxv, self.counts, self.group, async_op=True)
+                dec = self.decode(y)
+                if len(dec) == 3:   # (preds, maxvals, nms): rescoring + OKS-NMS ran on this stream too
+                    h = gather_poses(dec[0], dec[1], dec[2], self.counts, self.group, async_op=True)
+                else:
+                    preds, maxv = dec
+                    h = gather_keypoints(preds, maxv, self.counts, self.group, async_op=True)
             else:
                 h = gather_heatmaps_async(y, self.counts, self.group)
             if self.pending is not None:
