@@ -26,6 +26,8 @@
 extern "C" {
 #endif
 
+/* Bumped when an existing entry point, struct layout or op code changes.  Entry points that are only ADDED (i2r_joint_targets,
+ * i2r_val_metrics) do not bump it: a binding built against the older header keeps working with the newer library. */
 #define I2R_ABI_VERSION 17
 
 /* The library is built with -fvisibility=hidden: the entry points declared in this header (marked I2R_API) are its ONLY exported
@@ -201,6 +203,64 @@ typedef struct i2r_pose_nms_args {
     int32_t n_crops, n_img, joints, max_persons, soft, max_dets, use_oks_vis, reserved;
 } i2r_pose_nms_args;
 I2R_API int i2r_pose_nms(const i2r_pose_nms_args* a, void* stream);
+
+/* ---- the two numbers validate() logs per batch: loss and PCK accuracy (lib/core/function.py:167-174) ------------------------------
+ * i2r_joint_targets -- JointsDataset.generate_target + adjust_target_weight (lib/dataset/JointsDataset.py:394-450), target_type
+ * 'gaussian', for every (crop, joint).  One workgroup per map.
+ *   weight     target_weight = joints_vis; tmp_size = 3 * sigma, ul = int(mu - tmp_size), br = int(mu + tmp_size + 1) with int()
+ *              truncating toward zero (so br < 0 means mu + tmp_size + 1 <= -1); weight -> 0 when ul_x >= w or ul_y >= h or br_x < 0 or
+ *              br_y < 0
+ *   map        exp(-((x - mu_x)^2 + (y - mu_y)^2) / (2 sigma^2)) over the WHOLE map (this reference has no 13 x 13 window), drawn only
+ *              when the adjusted weight is > 0.5; otherwise the map is zero while a non-zero weight still reaches the loss.  The
+ *              argument is evaluated in fp64 as the reference does (no contraction), rounded to fp32, one expf: within 2.5e-7 of the reference's value
+ *   joints_weight (optional, LOSS.USE_DIFFERENT_JOINTS_WEIGHT) multiplies the weight AFTER that decision, in fp32
+ * Inputs (device): joints_hm float64 [n_crops, joints, 2], (x, y) in heat-map pixels -- float64 because the reference's joints_3d is
+ * (an fp32 mu of 50 px is off by 4e-6 px, which alone moves map values by 6e-7); joints_vis fp32 [n_crops, joints] (column 0 of the
+ * reference's array); joints_weight fp32 [joints] or null.  sigma > 0 (MODEL.SIGMA).
+ * Outputs (device): target_weight fp32 [n_crops, joints]; target fp32 [n_crops, joints, h, w], or null: only the weights are written.
+ * n_crops == 0 returns I2R_OK without a launch.  joints < 1, h < 1, w < 1, n_crops * joints or h * w beyond 2^31 - 1: I2R_E_ARG. */
+typedef struct i2r_joint_targets_args {
+    const double* joints_hm; const float* joints_vis; const float* joints_weight;
+    float* target_weight; float* target;
+    double sigma;
+    int32_t n_crops, joints, h, w;
+} i2r_joint_targets_args;
+I2R_API int i2r_joint_targets(const i2r_joint_targets_args* a, void* stream);
+
+/* i2r_val_metrics -- JointsMSELoss.forward (lib/core/loss.py:15-41) + accuracy (lib/core/evaluate.py:16-71, get_max_preds
+ * lib/core/inference.py:20-48) in one pass over the prediction `output` fp32 [n_crops, joints, h, w].  Two launches: one workgroup per
+ * map, then one workgroup that adds the per-map partials up in a fixed order (no floating-point atomics: two runs give the same bits).
+ * The target comes in ONE of two forms (both or neither: I2R_E_ARG):
+ *   tensor    target fp32 [n_crops, joints, h, w] + target_weight fp32 [n_crops, joints] (may be null when use_target_weight == 0)
+ *   analytic  joints_hm, joints_vis, joints_weight, sigma as i2r_joint_targets takes them (target and target_weight null): every target
+ *             value is evaluated in the kernel, never stored or read
+ * Per map:
+ *   sum of (p * w - t * w)^2, every one of the four fp32 operations rounded on its own as torch does them, accumulated in fp64;
+ *             use_target_weight == 0: (p - t)^2
+ *   arg-max   first flat index of the maximum of p, and of t; coordinates (idx % w, floor(idx / w)), both 0 when the maximum is not > 0
+ * Results (device, all required but meter):
+ *   sse float64 [joints] raw sums; loss float64 [1] = sum_j 0.5 * sse[j] / (n_crops * h * w) / joints
+ *   hits, valid int32 [joints]; acc float64 [joints + 1]; avg_acc float64 [1]; cnt int32 [1] -- accuracy / calc_dists / dist_acc:
+ *             a (crop, joint) counts only when the TARGET's arg-max has x > 1 and y > 1; norm = [h, w] / 10 meets (x, y) in that order
+ *             (x is divided by h / 10); dist = sqrt((px / n0 - tx / n0)^2 + (py / n1 - ty / n1)^2) in fp64, divided THEN subtracted; a hit
+ *             is dist < 0.5; acc[j + 1] = hits[j] / valid[j], or -1 when no crop counts, which keeps the joint out of avg_acc (the mean
+ *             of the others) and cnt; acc[0] = avg_acc (0 when cnt == 0)
+ *   pred fp32 [n_crops, joints, 2]: the arg-max coordinates of the prediction (accuracy's fourth return value)
+ *   meter (optional) float64 [4], caller-owned and caller-zeroed: += loss * n_crops, n_crops, avg_acc * cnt, cnt in stream order -- the
+ *             sums and counts of validate()'s two AverageMeters
+ * sse, hits and valid are raw so that shards of a data-parallel step can be combined exactly.
+ * ws: workspace of 16 * n_crops * joints bytes, 8-byte aligned, contents irrelevant before and after.
+ * n_crops == 0 returns I2R_OK without a launch and writes nothing.  joints < 1, h < 1, w < 1, counts beyond 2^31 - 1: I2R_E_ARG. */
+typedef struct i2r_val_metrics_args {
+    const float* output;
+    const float* target; const float* target_weight;                                  /* tensor form */
+    const double* joints_hm; const float* joints_vis; const float* joints_weight;     /* analytic form */
+    void* ws;
+    double* loss; double* acc; double* avg_acc; int32_t* cnt; float* pred; double* sse; int32_t* hits; int32_t* valid; double* meter;
+    double sigma;
+    int32_t n_crops, joints, h, w, use_target_weight, reserved;
+} i2r_val_metrics_args;
+I2R_API int i2r_val_metrics(const i2r_val_metrics_args* a, void* stream);
 
 /* ---- input side (reference lib/dataset/JointsDataset.py:296-333) ------------------------
  * i2r_crop_affine -- cv2.warpAffine(image, trans, IMAGE_SIZE, INTER_LINEAR) + ToTensor + Normalize for the n persons of ONE

@@ -9,9 +9,18 @@ per-person rescoring and per-image OKS-NMS / soft-OKS-NMS, one device kernel, no
 
     nms   = rescore_nms_cfg(cfg, preds, maxvals, scale, box_score, length)         # coco.py:384-412
     rows  = results(preds, maxvals, nms, length, image_ids, center, scale)         # the one copy to the host
+
+and of the two numbers validate() logs per batch (function.py:167-174: JointsMSELoss, lib/core/loss.py:15-41, and the PCK accuracy,
+lib/core/evaluate.py:41-71), from the joint positions alone -- the target heat maps are never stored, nothing is copied to the host:
+
+    meter = ValMeter(device)                                                       # the two AverageMeters, once per epoch
+    jhm   = heatmap_joints(joints, center, scale, cfg.MODEL.HEATMAP_SIZE)          # JointsDataset.py:295-320 (host, float64)
+    m     = val_metrics_cfg(cfg, out, joints_hm=jhm, joints_vis=vis, meter=meter)  # function.py:167-174; m.pred = accuracy's pred
+    valid_loss, valid_acc = meter.result()                                         # end of the epoch: the one copy to the host
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from . import cabi
@@ -160,3 +169,146 @@ def results(preds, maxvals, nms, length, image_ids, center, scale):
         out.append(rows)
         o += n
     return out
+
+
+# LOSS.USE_DIFFERENT_JOINTS_WEIGHT tables of the dataset classes (reference lib/dataset/coco.py:106-112, crowdpose.py:104-110,
+# ochuman.py:101-107), keyed like FLIP_PAIRS
+JOINTS_WEIGHT = {
+    "coco": (1., 1., 1., 1., 1., 1., 1., 1.2, 1.2, 1.5, 1.5, 1., 1., 1.2, 1.2, 1.5, 1.5),
+    "crowdpose": (1., 1., 1.2, 1.2, 1.5, 1.5, 1., 1., 1.2, 1.2, 1.5, 1.5, 1., 1.),
+    "ochuman": (1., 1., 1., 1., 1., 1., 1., 1.2, 1.2, 1.5, 1.5, 1., 1., 1.2, 1.2, 1.5, 1.5),
+}
+
+
+def heatmap_joints(joints, center, scale, heatmap_size):
+    """Image-space joints -> heat-map coordinates, the reference's joints_heatmap (JointsDataset.py:295-320 at rot 0): host, float64.
+    joints [S, J, 2 or 3] (x, y first), center / scale [S, 2], heatmap_size (w, h) -> float64 numpy [S, J, 2].  cv2-unpinned like the
+    rest of the input side: the transform is input.affine_transforms, not cv2.getAffineTransform."""
+    from . import input as i2r_input
+    j = np.asarray(joints, dtype=np.float64)
+    S = j.shape[0]
+    t = i2r_input.affine_transforms(center, scale, heatmap_size)                    # [S, 2, 3]
+    pt = np.concatenate([j[:, :, :2], np.ones((S, j.shape[1], 1))], 2)              # affine_transform: t . (x, y, 1)
+    return np.matmul(t[:, None], pt[..., None])[..., 0]
+
+
+def _dev(t, dtype, dev, shape):
+    t = torch.as_tensor(t, dtype=dtype).to(dev, non_blocking=True).contiguous()
+    assert tuple(t.shape) == shape, (tuple(t.shape), shape)
+    return t
+
+
+def _joint_inputs(joints_hm, joints_vis, joints_weight, dev):
+    hm = torch.as_tensor(joints_hm)
+    assert hm.dtype == torch.float64 and hm.dim() == 3 and hm.shape[2] == 2, "joints_hm: float64 [S, J, 2] (heatmap_joints)"
+    S, J = hm.shape[0], hm.shape[1]
+    hm = hm.to(dev, non_blocking=True).contiguous()
+    vis = torch.as_tensor(joints_vis, dtype=torch.float32)
+    if vis.dim() == 3:                     # the reference's [S, J, 3] array: column 0
+        vis = vis[:, :, 0]
+    vis = _dev(vis, torch.float32, dev, (S, J))
+    jw = _dev(joints_weight, torch.float32, dev, (J,)) if joints_weight is not None else None
+    return hm, vis, jw
+
+
+def joint_targets(joints_hm, joints_vis, heatmap_size, sigma=2, joints_weight=None, want_target=True, device=None):
+    """generate_target (JointsDataset.py:394-450) for every crop on the device.  joints_hm float64 [S, J, 2] (heatmap_joints), joints_vis
+    [S, J] (or the reference's [S, J, 3]), heatmap_size (w, h) -> (target [S, J, h, w] fp32 | None, target_weight [S, J] fp32)."""
+    dev = torch.device(device) if device is not None else (joints_hm.device if torch.is_tensor(joints_hm) and joints_hm.is_cuda
+                                                          else torch.device("cuda", torch.cuda.current_device()))
+    hm, vis, jw = _joint_inputs(joints_hm, joints_vis, joints_weight, dev)
+    S, J = hm.shape[0], hm.shape[1]
+    w, h = int(heatmap_size[0]), int(heatmap_size[1])
+    tw = torch.empty(S, J, dtype=torch.float32, device=dev)
+    target = torch.empty(S, J, h, w, dtype=torch.float32, device=dev) if want_target else None
+    if S == 0:
+        return target, tw
+    a = cabi.JointTargetsArgs(joints_hm=hm.data_ptr(), joints_vis=vis.data_ptr(), joints_weight=jw.data_ptr() if jw is not None else None,
+                              target_weight=tw.data_ptr(), target=target.data_ptr() if want_target else None, sigma=float(sigma),
+                              n_crops=S, joints=J, h=h, w=w)
+    with torch.cuda.device(dev):
+        cabi.check(cabi.lib().i2r_joint_targets(ctypes.byref(a), torch.cuda.current_stream(dev).cuda_stream), "i2r_joint_targets")
+    return target, tw
+
+
+class ValMetrics:
+    """What i2r_val_metrics writes, device tensors: loss [1], acc [J + 1], avg_acc [1] float64; cnt [1] int32; pred [S, J, 2] fp32
+    (accuracy's fourth return value); sse [J] float64, hits [J], valid [J] int32 (raw sums: shards can be combined exactly)."""
+    __slots__ = ("loss", "acc", "avg_acc", "cnt", "pred", "sse", "hits", "valid")
+
+
+class ValMeter:
+    """validate()'s two AverageMeters (losses, acc; function.py:168-174) as four doubles on the device: sum of loss * S, sum of S, sum of
+    avg_acc * cnt, sum of cnt.  val_metrics(..., meter=) adds to it in stream order; result() is the one copy to the host."""
+
+    def __init__(self, device):
+        self.buf = torch.zeros(4, dtype=torch.float64, device=device)
+
+    def reset(self):
+        self.buf.zero_()
+
+    def result(self):
+        """-> (losses.avg, acc.avg); a meter that saw no sample / no counted joint gives 0 for it, as AverageMeter does"""
+        ls, ln, as_, an = self.buf.cpu().tolist()
+        return (ls / ln if ln != 0 else 0.0), (as_ / an if an != 0 else 0.0)
+
+
+def val_metrics(output, target=None, target_weight=None, *, joints_hm=None, joints_vis=None, sigma=2, joints_weight=None,
+                use_target_weight=True, meter=None):
+    """JointsMSELoss + accuracy of one batch (function.py:167-172) on the current stream, without a host synchronisation.
+    output [S, J, h, w] fp32 cuda, plus ONE target form: the data loader's tensors (target [S, J, h, w], target_weight [S, J] or
+    [S, J, 1]), or the joints themselves (joints_hm float64 [S, J, 2], joints_vis, sigma, joints_weight as joint_targets takes them): the
+    target is then evaluated inside the kernel.  meter: a ValMeter to update.  -> ValMetrics."""
+    assert output.is_cuda and output.dtype == torch.float32 and output.dim() == 4
+    if (target is None) == (joints_hm is None):
+        raise cabi.I2RError("val_metrics: give either target (+ target_weight) or joints_hm (+ joints_vis)")
+    out = output.contiguous()
+    S, J, h, w = out.shape
+    dev = out.device
+    r = ValMetrics()
+    f64 = torch.zeros(J + 1 + 1 + 1 + J, dtype=torch.float64, device=dev)    # (a batch without crops launches nothing: all 0)
+    i32 = torch.zeros(1 + 2 * J, dtype=torch.int32, device=dev)
+    r.acc, r.avg_acc, r.loss, r.sse = f64[:J + 1], f64[J + 1:J + 2], f64[J + 2:J + 3], f64[J + 3:]
+    r.cnt, r.hits, r.valid = i32[:1], i32[1:1 + J], i32[1 + J:]
+    r.pred = torch.empty(S, J, 2, dtype=torch.float32, device=dev)
+    ws = torch.empty(2 * S * J, dtype=torch.float64, device=dev)              # 16 bytes per map
+    a = cabi.ValMetricsArgs(output=out.data_ptr(), ws=ws.data_ptr(), loss=r.loss.data_ptr(), acc=r.acc.data_ptr(), avg_acc=r.avg_acc.data_ptr(),
+                            cnt=r.cnt.data_ptr(), pred=r.pred.data_ptr(), sse=r.sse.data_ptr(), hits=r.hits.data_ptr(), valid=r.valid.data_ptr(),
+                            meter=meter.buf.data_ptr() if meter is not None else None, sigma=float(sigma), n_crops=S, joints=J, h=h, w=w,
+                            use_target_weight=int(bool(use_target_weight)))
+    if target is not None:
+        assert target.is_cuda and target.dtype == torch.float32 and tuple(target.shape) == (S, J, h, w), tuple(target.shape)
+        keep = [target.contiguous()]
+        a.target = keep[0].data_ptr()
+        if target_weight is not None:
+            keep.append(_dev(torch.as_tensor(target_weight).reshape(S, J), torch.float32, dev, (S, J)))
+            a.target_weight = keep[1].data_ptr()
+        elif use_target_weight:
+            raise cabi.I2RError("val_metrics: use_target_weight without target_weight")
+    else:
+        keep = _joint_inputs(joints_hm, joints_vis, joints_weight, dev)
+        assert tuple(keep[0].shape) == (S, J, 2), (tuple(keep[0].shape), (S, J))
+        a.joints_hm, a.joints_vis = keep[0].data_ptr(), keep[1].data_ptr()
+        a.joints_weight = keep[2].data_ptr() if keep[2] is not None else None
+    if meter is not None:
+        assert meter.buf.device == dev
+    if S == 0:  # (a data-parallel rank without images: nothing is launched, the results stay 0, the meter untouched)
+        return r
+    with torch.cuda.device(dev):
+        cabi.check(cabi.lib().i2r_val_metrics(ctypes.byref(a), torch.cuda.current_stream(dev).cuda_stream), "i2r_val_metrics")
+    return r
+
+
+def val_metrics_cfg(cfg, output, target=None, target_weight=None, **kw):
+    """val_metrics with what the reference's criterion and dataset class read from a config: LOSS.USE_TARGET_WEIGHT,
+    LOSS.USE_DIFFERENT_JOINTS_WEIGHT (the JOINTS_WEIGHT table of DATASET.DATASET), MODEL.SIGMA, MODEL.HEATMAP_SIZE.
+    LOSS.USE_OHKM raises: the reference's JointsOHKMMSELoss.forward takes no `length` and cannot run under validate() either."""
+    if cfg.LOSS.USE_OHKM:
+        raise cabi.I2RError("val_metrics_cfg: LOSS.USE_OHKM -- the reference's OHKM loss does not run under validate(); not provided")
+    w, h = int(cfg.MODEL.HEATMAP_SIZE[0]), int(cfg.MODEL.HEATMAP_SIZE[1])
+    assert tuple(output.shape[1:]) == (cfg.MODEL.NUM_JOINTS, h, w), (tuple(output.shape), cfg.MODEL.NUM_JOINTS, h, w)
+    if target is None and cfg.LOSS.USE_DIFFERENT_JOINTS_WEIGHT and "joints_weight" not in kw:
+        if cfg.DATASET.DATASET not in JOINTS_WEIGHT:
+            raise cabi.I2RError("val_metrics_cfg: no joints_weight table for dataset %r -- pass joints_weight" % cfg.DATASET.DATASET)
+        kw["joints_weight"] = JOINTS_WEIGHT[cfg.DATASET.DATASET]
+    return val_metrics(output, target, target_weight, sigma=cfg.MODEL.SIGMA, use_target_weight=cfg.LOSS.USE_TARGET_WEIGHT, **kw)
