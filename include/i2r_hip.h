@@ -94,6 +94,12 @@ typedef struct i2r_conv_desc {
                                       Winograd positions (row-major 4x4) in place of the taps: float w[16][cin/4][cout_pad][4].  tile_w selects the
                                       fragment shape (16 Winograd tiles = 64 output pixels): 16, 8 or 4 pixels wide (0 = choose); mt = fragments per
                                       workgroup (0 or 1: one).  2.25x fewer matrix-pipe operations than algo 0 for the same sum. */
+    int32_t t1_shift, t2_shift;    /* fused input (below): log2 of the up-sampling factors of t1 / t2, 1 or 2 */
+    const float* t1;               /* algo 1 only, optional "fused input": the conv's input is  ReLU((in + up(t1)) + up(t2))  instead of `in` --  */
+    const float* t2;               /*   the closing pass of an HRNet fuse layer (i2r_fuse_up_add, same summation order) folded into the staging. */
+    float* y;                      /*   t1 / t2 (optional): [n_img, in_h >> shift, in_w >> shift, in_cs], nearest-neighbour up-sampled; the map is
+                                        also written to y (required with t1; laid out like `in`, in_cs == cin) for the consumers after this conv.
+                                        y must not alias in, t1, t2, out or a residual.  All null = none. */
 } i2r_conv_desc;
 
 I2R_API int i2r_conv(const i2r_conv_desc* d, void* stream);

@@ -50,6 +50,7 @@ class ConvDesc(C.Structure):
         ("out_step", _i32), ("out_off_y", _i32), ("out_off_x", _i32), ("rep", _i32), ("relu", _i32),
         ("tile_h", _i32), ("tile_w", _i32), ("ck", _i32), ("wn", _i32), ("mt", _i32), ("dtype", _i32),
         ("in_f16", _i32), ("out_f16", _i32), ("algo", _i32),
+        ("t1_shift", _i32), ("t2_shift", _i32), ("t1", _fp), ("t2", _fp), ("y", _fp),
     ]
 
 

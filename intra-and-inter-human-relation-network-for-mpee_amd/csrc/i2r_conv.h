@@ -46,6 +46,12 @@ struct ConvK {
     int algo, w_fwlog, w_pitch, w_half, w_nfrag, w_rcp;  // w_rcp = ceil(65536 / pw): patch row of a pixel index without a division
     int w_band;                                          // fragment groups per XCD band (launches without a dispatch table, i2r_conv_wino.hip)
     unsigned w_m_cblk, w_m_img, w_m_tx;                  // ceil(2^32 / d) for d = n_cblk, fragments per crop, fragments per row (item decode)
+    // fused input of a Winograd member (i2r_conv_desc.t1 / t2 / y): the conv reads ReLU((in + up(f_t1)) + up(f_t2)) and writes it to f_y
+    const float* f_t1;
+    const float* f_t2;
+    float* f_y;
+    int f_sh1, f_sh2;             // log2 of the terms' up-sampling factors
+    unsigned f_bytes1, f_bytes2;  // byte sizes of the terms' maps
 };
 
 // n / d through m = ceil(2^32 / d): exact while n * (m * d - 2^32) < 2^32, i.e. for every n < 2^32 / d (prepare() checks the ranges);
@@ -288,5 +294,5 @@ typedef void (*conv_fn)(const ConvGroupK);
 void* i2r_pick_conv_bf16(int nt, int mt, int cap, int pf);
 void* i2r_pick_conv_f16(int nt, int mt, int cap, int pf);
 // Winograd F(2x2, 3x3) fp32 kernels (i2r_conv_wino.hip): MT fragments x NT channel fragments per workgroup; LDS bytes of a workgroup
-void* i2r_pick_conv_wino(int nt, int mt);
+void* i2r_pick_conv_wino(int nt, int mt, int fin);
 size_t i2r_conv_wino_lds(int nt, int mt, int plane);

@@ -321,6 +321,7 @@ static void copy_desc(const i2r_conv_desc* d, ConvK& k) {
     k.w_m_cblk = k.w_m_img = k.w_m_tx = 0; k.in_bytes = k.w_bytes = k.out_bytes = 0;
     k.m_cblk = k.m_tx = k.m_ty = k.m_pw = k.m_tw = 0; k.wn_log = 0; k.npass = 0;
     k.dbg = 0;
+    k.f_t1 = d->t1; k.f_t2 = d->t2; k.f_y = d->y; k.f_sh1 = d->t1_shift; k.f_sh2 = d->t2 ? d->t2_shift : 0; k.f_bytes1 = k.f_bytes2 = 0;
 }
 
 // Winograd F(2x2, 3x3) launch geometry (i2r_conv_wino.hip): fragment shape, patch layout in LDS, workgroup count
@@ -336,6 +337,18 @@ static int prepare_wino(const i2r_conv_desc* d, int force_mt, ConvK& k, int* nt_
                       (long long)16 * d->cin * d->cout_pad < (1ll << 29),
                   "i2r_conv: algo 1 addresses its tensors through buffer descriptors of < 2 GiB");
     I2R_CHECK_ARG(d->conv_h == d->in_h && d->conv_w == d->in_w && d->out_h == d->conv_h && d->out_w == d->conv_w, "i2r_conv: algo 1 geometry");
+    if (d->t1) {  // fused input: ReLU((in + up(t1)) + up(t2)) staged in place of `in` and written to y
+        I2R_CHECK_ARG(d->y != nullptr, "i2r_conv: a fused input (t1) needs y");
+        I2R_CHECK_ARG(d->in_cs == d->cin, "i2r_conv: fused input: y is complete only when the conv reads every channel (cin=%d in_cs=%d)", d->cin, d->in_cs);
+        for (int t = 0; t < (d->t2 ? 2 : 1); ++t) {
+            const int sh = t ? d->t2_shift : d->t1_shift;
+            I2R_CHECK_ARG((sh == 1 || sh == 2) && d->in_h % (1 << sh) == 0 && d->in_w % (1 << sh) == 0,
+                          "i2r_conv: fused input: t%d_shift %d must be 1 or 2 and the %dx%d map divisible by the scale", t + 1, sh, d->in_h, d->in_w);
+        }
+        const void* others[] = {d->in, d->t1, d->t2, d->out, d->res1, d->res2, d->res_post};
+        for (const void* o : others) I2R_CHECK_ARG((const void*)d->y != o, "i2r_conv: fused input: y aliases another tensor of the launch");
+        I2R_CHECK_ARG(d->t1 != (const float*)d->out && d->t2 != (const float*)d->out, "i2r_conv: out aliases a fused-input term");
+    }
     const int nfrag = d->cout_pad / 16;
     const int nt = nfrag % 3 == 0 ? 3 : (nfrag % 4 == 0 ? 4 : 0);
     I2R_CHECK_ARG(nt != 0, "i2r_conv: algo 1 needs cout_pad=%d to be a multiple of 48 or 64", d->cout_pad);
@@ -367,6 +380,8 @@ static int prepare_wino(const i2r_conv_desc* d, int force_mt, ConvK& k, int* nt_
     k.in_bytes = (unsigned)((long long)d->n_img * d->in_h * d->in_w * d->in_cs * 4);
     k.w_bytes = (unsigned)((long long)16 * d->cin * d->cout_pad * 4);
     k.out_bytes = (unsigned)((long long)d->n_img * d->out_h * d->out_w * d->out_cs * 4);
+    if (d->t1) k.f_bytes1 = (unsigned)((long long)d->n_img * (d->in_h >> d->t1_shift) * (d->in_w >> d->t1_shift) * d->in_cs * 4);
+    if (d->t2) k.f_bytes2 = (unsigned)((long long)d->n_img * (d->in_h >> d->t2_shift) * (d->in_w >> d->t2_shift) * d->in_cs * 4);
     // item decode without integer divisions: n / d = mulhi(n, ceil(2^32 / d)) is exact for n < 2^20 and d < 2^11
     auto magic = [](int d) { return d == 1 ? 0u : (unsigned)(((1ull << 32) + d - 1) / d); };
     k.w_m_cblk = magic(k.n_cblk); k.w_m_img = magic(k.tiles_y * k.tiles_x); k.w_m_tx = magic(k.tiles_x);
@@ -407,6 +422,7 @@ static int prepare(const i2r_conv_desc* d, int force_mt, int force_cap, int forc
                   "i2r_conv: destination grid exceeds out tensor");
     I2R_CHECK_ARG(d->in2 != (const float*)d->out && d->in != (const float*)d->out, "i2r_conv: out aliases in");
     I2R_CHECK_ARG(d->algo == 0 || d->algo == 1, "i2r_conv: algo %d", d->algo);
+    I2R_CHECK_ARG(d->t1 ? d->algo == 1 : (!d->t2 && !d->y), "i2r_conv: a fused input (t1, t2, y) needs algo 1 and starts with t1");
     if (d->algo == 1) return prepare_wino(d, force_mt, k, nt_out, mt_out, cap_out, pf_out, lds_out, nblk_out);
 
     int max_dy = 0, max_dx = 0;
@@ -599,6 +615,13 @@ static int resolve(const i2r_conv_desc* const* descs, int32_t n, ConvGroupK& grp
     return I2R_OK;
 }
 
+// a grouped Winograd launch takes the fused-input form of the kernel only when a member needs it
+static bool any_fused_input(const i2r_conv_desc* const* descs, int32_t n) {
+    for (int i = 0; i < n; ++i)
+        if (descs[i]->t1) return true;
+    return false;
+}
+
 extern "C" int i2r_conv_grouped(const i2r_conv_desc* const* descs, int32_t n, const int32_t* block_map,
                                 int32_t map_len, void* stream) {
     ConvGroupK grp;
@@ -609,7 +632,7 @@ extern "C" int i2r_conv_grouped(const i2r_conv_desc* const* descs, int32_t n, co
     if (rc) return rc;
     grp.blk_map = block_map;
     I2R_CHECK_ARG(block_map == nullptr || map_len == (int32_t)total, "i2r_conv_grouped: block_map has %d entries, grid has %lld", map_len, total);
-    conv_fn fn = descs[0]->algo == 1 ? reinterpret_cast<conv_fn>(i2r_pick_conv_wino(nt0, mt0))
+    conv_fn fn = descs[0]->algo == 1 ? reinterpret_cast<conv_fn>(i2r_pick_conv_wino(nt0, mt0, any_fused_input(descs, n)))
                  : descs[0]->dtype == 0 ? pick_kernel(nt0, mt0, cap0, pf0)
                                       : reinterpret_cast<conv_fn>(descs[0]->dtype == 1 ? i2r_pick_conv_bf16(nt0, mt0, cap0, pf0) : i2r_pick_conv_f16(nt0, mt0, cap0, pf0));
     I2R_CHECK_ARG(fn != nullptr, "i2r_conv: no kernel for nt=%d mt=%d cap=%d pf=%d dtype=%d", nt0, mt0, cap0, pf0, descs[0]->dtype);
@@ -632,7 +655,7 @@ extern "C" int i2r_conv_kernel_name(const i2r_conv_desc* const* descs, int32_t n
     if (rc) return rc;
     I2R_CHECK_ARG(buf && buflen > 0, "i2r_conv_kernel_name: buffer");
     if (descs[0]->algo == 1)
-        snprintf(buf, (size_t)buflen, "conv_wino_f32<%d, %d>", mt0, nt0);
+        snprintf(buf, (size_t)buflen, "conv_wino_%sf32<%d, %d>", any_fused_input(descs, n) ? "fin_" : "", mt0, nt0);
     else if (descs[0]->dtype)
         snprintf(buf, (size_t)buflen, "conv_igemm_lp<%d, %d, %d, %d>/%s", mt0, nt0, cap0, pf0, descs[0]->dtype == 1 ? "bf16" : "f16");
     else

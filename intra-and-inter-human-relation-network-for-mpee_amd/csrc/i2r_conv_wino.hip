@@ -38,8 +38,13 @@ namespace {
 
 constexpr int kWinoPatchMax = 108;  // patch pixels of a fragment: 6 x 18 (FW = 8 or 2), 10 x 10 (FW = 4)
 
-template <int MT, int NT>
-__global__ __launch_bounds__(256, (MT == 1 ? (NT == 3 ? 4 : 3) : 2)) void conv_wino_f32(const ConvGroupK grp) {
+// FIN: the "fused input" form.  A member with f_t1 set takes  ReLU((in + up(t1)) + up(t2))  as its input -- the closing pass of an
+// HRNet fuse layer (fuse_up_add_k, same summation order) folded into the staging -- and writes that map to f_y on the way (the
+// block's second conv reads it as its residual): the non-halo pixels of the fragment patches are disjoint and cover the map, and
+// all cin channels pass through the staging, so the items of channel block 0 store every value exactly once.  f_y must not alias
+// `in`: the halo reads of neighbouring items are not ordered against those stores.  A member without f_t1 runs as in the plain form.
+template <int MT, int NT, bool FIN>
+__device__ __forceinline__ void conv_wino_body(const ConvGroupK& grp) {
     extern __shared__ __attribute__((aligned(16))) f32x4 lds[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wi = __builtin_amdgcn_readfirstlane(tid >> 6);  // Winograd row of this wave
@@ -111,6 +116,14 @@ __global__ __launch_bounds__(256, (MT == 1 ? (NT == 3 ? 4 : 3) : 2)) void conv_w
     const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w), 0, p.w_bytes, 0x00020000);
     unsigned goff[NIT];  // byte offset of (pixel, channel group) in `in`, kOOB (out of range: reads zeros) outside the image
     int lslot[NIT];      // LDS slot, -1 = no item
+    // fused input: the same piece of the up-sampled terms sits at (iy >> s, ix >> s) of their (in_h >> s) x (in_w >> s) maps.  A lane
+    // outside the image has all three offsets at kOOB and stages ReLU(0 + 0 + 0) = 0: the zero padding needs no select.  The value
+    // goes to f_y from the lanes holding an interior (non-halo) pixel (own) in the items of channel block 0: at `goff`, f_y being laid out like `in`
+    const bool fin = FIN && p.f_t1 != nullptr, fin2 = fin && p.f_t2 != nullptr;  // (uniform)
+    const __amdgpu_buffer_rsrc_t rs_t1 = make_rsrc(fin ? p.f_t1 : nullptr, p.f_bytes1), rs_t2 = make_rsrc(fin2 ? p.f_t2 : nullptr, p.f_bytes2),
+                                 rs_y = make_rsrc(fin ? p.f_y : nullptr, p.in_bytes);
+    unsigned goff1[FIN ? NIT : 1], goff2[FIN ? NIT : 1];
+    bool own[FIN ? NIT : 1];
 #pragma unroll
     for (int k = 0; k < NIT; ++k) {
         const int it = tid + k * 256;
@@ -122,6 +135,7 @@ __global__ __launch_bounds__(256, (MT == 1 ? (NT == 3 ? 4 : 3) : 2)) void conv_w
         const int row = (pp * p.w_rcp) >> 16, col = pp - row * PC;
         goff[k] = kOOB;
         lslot[k] = -1;
+        if constexpr (FIN) { goff1[k] = goff2[k] = kOOB; own[k] = false; }
         if (f < MT) {
             int img = f_img[0], oy = f_oy[0], ox = f_ox[0];
             bool ok = f_ok[0];
@@ -130,7 +144,15 @@ __global__ __launch_bounds__(256, (MT == 1 ? (NT == 3 ? 4 : 3) : 2)) void conv_w
                 if (f == m) { img = f_img[m]; oy = f_oy[m]; ox = f_ox[m]; ok = f_ok[m]; }
             const int iy = oy - 1 + row, ix = ox - 1 + col;
             lslot[k] = (f * 4 + cg) * plane + row * pitch + (col & 1) * half + (col >> 1);
-            if (ok && iy >= 0 && iy < p.in_h && ix >= 0 && ix < p.in_w) goff[k] = (unsigned)(((img * p.in_h + iy) * p.in_w + ix) * p.in_cs + cg * 4) * 4u;
+            if (ok && iy >= 0 && iy < p.in_h && ix >= 0 && ix < p.in_w) {
+                goff[k] = (unsigned)(((img * p.in_h + iy) * p.in_w + ix) * p.in_cs + cg * 4) * 4u;
+                if constexpr (FIN) {
+                    const int s1 = p.f_sh1, s2 = p.f_sh2;
+                    goff1[k] = (unsigned)(((img * (p.in_h >> s1) + (iy >> s1)) * (p.in_w >> s1) + (ix >> s1)) * p.in_cs + cg * 4) * 4u;
+                    goff2[k] = (unsigned)(((img * (p.in_h >> s2) + (iy >> s2)) * (p.in_w >> s2) + (ix >> s2)) * p.in_cs + cg * 4) * 4u;
+                    own[k] = row >= 1 && row < p.ph - 1 && col >= 1 && col < PC - 1;
+                }
+            }
         }
     }
     f32x4 v[NIT];
@@ -140,7 +162,39 @@ __global__ __launch_bounds__(256, (MT == 1 ? (NT == 3 ? 4 : 3) : 2)) void conv_w
             v[k] = (I2R_DBG(p) & 2) ? (f32x4){0.f, 0.f, 0.f, 0.f}
                                     : __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_in, goff[k], c0 * 4, 0));
     };
-    auto stage_store = [&](f32x4* buf) {
+    // fused input: the first term is fetched with the base piece; the second one takes over its registers half a pass later
+    // (stage_mid), after the first has been added -- one extra staging register set instead of two
+    f32x4 vt[FIN ? NIT : 1];
+    auto stage_load_t1 = [&](int c0) {
+        if constexpr (FIN) {
+            if (fin) {
+#pragma unroll
+                for (int k = 0; k < NIT; ++k) vt[k] = buf_ld16(rs_t1, goff1[k], c0 * 4);
+            }
+        }
+    };
+    auto stage_mid = [&](int c0) {
+        if constexpr (FIN) {
+            if (fin2) {
+#pragma unroll
+                for (int k = 0; k < NIT; ++k) {
+                    v[k] += vt[k];
+                    vt[k] = buf_ld16(rs_t2, goff2[k], c0 * 4);
+                }
+            }
+        }
+    };
+    auto stage_store = [&](f32x4* buf, int c0) {
+        if constexpr (FIN) {
+            if (fin) {
+#pragma unroll
+                for (int k = 0; k < NIT; ++k) {
+                    v[k] += vt[k];
+                    v[k][0] = fmaxf(v[k][0], 0.f); v[k][1] = fmaxf(v[k][1], 0.f); v[k][2] = fmaxf(v[k][2], 0.f); v[k][3] = fmaxf(v[k][3], 0.f);
+                    if (cb == 0) buf_st16(rs_y, own[k] ? goff[k] : kOOB, c0 * 4, v[k]);  // (uniform)
+                }
+            }
+        }
 #pragma unroll
         for (int k = 0; k < NIT; ++k)
             if (lslot[k] >= 0) buf[lslot[k]] = v[k];
@@ -201,22 +255,36 @@ __global__ __launch_bounds__(256, (MT == 1 ? (NT == 3 ? 4 : 3) : 2)) void conv_w
         f32x4* cur = lds + (pass_ & 1) * bufsz;                                                  \
         f32x4* nxt = lds + ((pass_ + 1) & 1) * bufsz;                                            \
         const bool more = pass_ + 1 < npass;                                                     \
-        if (more) stage_load((pass_ + 1) * 16);                                                  \
+        if (more) { stage_load((pass_ + 1) * 16); stage_load_t1((pass_ + 1) * 16); }             \
         load_a(cur, a);                                                                          \
         wp += inc_j; fetch_b(b1);                                                                \
         WINO_MMA(0, b0, FIRST)                                                                   \
         wp += inc_j; fetch_b(b0);                                                                \
         WINO_MMA(1, b1, FIRST)                                                                   \
+        if (more) stage_mid((pass_ + 1) * 16);                                                   \
         wp += inc_j; fetch_b(b1);                                                                \
         WINO_MMA(2, b0, FIRST)                                                                   \
         if (more) { wp += inc_wrap; fetch_b(b0); }                                               \
         WINO_MMA(3, b1, FIRST)                                                                   \
-        if (more) stage_store(nxt);                                                              \
+        if (more) stage_store(nxt, (pass_ + 1) * 16);                                            \
         if (!(I2R_DBG(p) & 64)) __syncthreads();                                                 \
     }
     stage_load(0);
+    stage_load_t1(0);
+    if constexpr (FIN) {  // first chunk: the accumulators do not exist yet, so both terms are in flight with the base piece (one latency)
+        if (fin2) {
+            f32x4 vu[NIT];
+#pragma unroll
+            for (int k = 0; k < NIT; ++k) vu[k] = buf_ld16(rs_t2, goff2[k], 0);
+#pragma unroll
+            for (int k = 0; k < NIT; ++k) {
+                v[k] += vt[k];
+                vt[k] = vu[k];
+            }
+        }
+    }
     fetch_b(b0);
-    stage_store(lds);
+    stage_store(lds, 0);
     __syncthreads();
     if (stamp) ts1 = __builtin_amdgcn_s_memtime();
     WINO_PASS(0, true)
@@ -310,12 +378,23 @@ __global__ __launch_bounds__(256, (MT == 1 ? (NT == 3 ? 4 : 3) : 2)) void conv_w
     }
 }
 
+template <int MT, int NT>
+__global__ __launch_bounds__(256, (MT == 1 ? (NT == 3 ? 4 : 3) : 2)) void conv_wino_f32(const ConvGroupK grp) {
+    conv_wino_body<MT, NT, false>(grp);
+}
+
+// the fused-input form (a grouped launch takes it when a member has f_t1)
+template <int MT, int NT>
+__global__ __launch_bounds__(256, (MT == 1 ? (NT == 3 ? 4 : 3) : 2)) void conv_wino_fin_f32(const ConvGroupK grp) {
+    conv_wino_body<MT, NT, true>(grp);
+}
+
 }  // namespace
 
-void* i2r_pick_conv_wino(int nt, int mt) {
+void* i2r_pick_conv_wino(int nt, int mt, int fin) {
     conv_fn fn = nullptr;
-    if (mt == 1 && nt == 3) fn = conv_wino_f32<1, 3>;
-    if (mt == 1 && nt == 4) fn = conv_wino_f32<1, 4>;
+    if (mt == 1 && nt == 3) fn = fin ? conv_wino_fin_f32<1, 3> : conv_wino_f32<1, 3>;
+    if (mt == 1 && nt == 4) fn = fin ? conv_wino_fin_f32<1, 4> : conv_wino_f32<1, 4>;
     return reinterpret_cast<void*>(fn);
 }
 

@@ -121,6 +121,8 @@ _HRT_FUSED_ATTN = (78, 156, 312)
 _HRT_FUSED_MLP = (78, 156, 312)
 _MLP_VARIANT = {78: 1, 156: 2, 312: 2}  # measured (tools/time_hrt_mlp.py, host_rate.py): C = 156 29.0 -> 22.0 us, config 5 forward 4.19 -> 3.87 ms
 PAIR1X1 = True  # layer1's conv3 + next conv1 as one i2r_conv1x1_pair launch (fp32)
+FUSE_IN = True  # the closing pass of an HRNet fuse layer rides in the staging of the next module's first Winograd conv (fp32)
+PRUNE_FUSE = True  # the last HRNet module computes only the fuse outputs its caller reads (HRNetW48.emit(need=...))
 WINOGRAD = True  # fp32 3x3 stride-1 convs on the Winograd F(2x2, 3x3) kernels
 # fork / join / record / wait as device-side signal / wait kernels (csrc/i2r_api.hip) when the lanes are independent queues.  A wait kernel
 # spins until ANOTHER kernel signals it: under a tool that lets one kernel run at a time (rocprofv3 counter collection serialises dispatches)
@@ -701,6 +703,8 @@ class Program:
 
     def release(self, *acts):
         for a in acts:
+            if a is None:  # (a tower output nobody asked for: HRNetW48.emit(need=...))
+                continue
             if self.in_fork:
                 self.lane_pool.setdefault((self.lane_ctx, a.t.numel()), []).append(a.t)
             else:
@@ -734,12 +738,14 @@ class Program:
         return out, a
 
     def conv(self, x, pc, relu=False, res1=None, res2=None, res_post=None, in2=None, up=1, out=None, out_step=1,
-             out_off=(0, 0), out_hw=None, lane=0, group=None, act=None, out_dt=None):
+             out_off=(0, 0), out_hw=None, lane=0, group=None, act=None, out_dt=None, fuse_in=None):
         """out_dt: storage type of a newly allocated output (default: the input's, so a 16-bit tower stays 16-bit; pass 0 where the
-        consumer is an fp32 kernel: encoder, max-pool, head, ...)"""
+        consumer is an fp32 kernel: encoder, max-pool, head, ...)
+        fuse_in = (terms, y): the conv's input is ReLU((x + up(terms[0])) + up(terms[1])) -- fuse_up_add(x, terms, y) folded into the
+        staging of an fp32 Winograd conv (fuse_in_ok), which also writes that map to y; y must be a buffer of its own"""
         assert x.cs >= pc.cin_pad and x.c == pc.cin, "conv input channels %d/%d vs weight %d" % (x.c, x.cs, pc.cin)
         assert x.dt in (0, pc.dtype), "16-bit stored input needs the matching 16-bit conv (input %d, conv %d)" % (x.dt, pc.dtype)
-        if (LP1X1 and pc.w_lp1 is not None and group is None and in2 is None and up == 1 and out_step == 1 and tuple(out_off) == (0, 0)
+        if (LP1X1 and pc.w_lp1 is not None and fuse_in is None and group is None and in2 is None and up == 1 and out_step == 1 and tuple(out_off) == (0, 0)
                 and out_hw is None and x.n * x.h * x.w <= LP1X1_MAX_PIX and (out is None or (out.n, out.h, out.w) == (x.n, x.h, x.w))
                 # (the kernel's own limits, i2r_conv1x1_lp: whole output rows of cout_pad channels, residual rows laid out like the output)
                 and (out is None or out.cs >= pc.cout_pad) and all(r is None or out is None or r.cs == out.cs for r in (res1, res2, res_post))
@@ -779,6 +785,16 @@ class Program:
         d.in_f16, d.out_f16 = int(x.dt != 0), int(out.dt != 0)
         wino = (WINOGRAD and pc.w_wino is not None and pc.dtype == 0 and in2 is None and up == 1 and out_step == 1 and tuple(out_off) == (0, 0)
                 and (out.h, out.w) == (conv_h, conv_w) and d.relu in (0, 1))
+        if fuse_in is not None:
+            terms, y = fuse_in
+            if not (wino and self.fuse_in_ok(x, terms, pc)):
+                raise ValueError("fuse_in needs an fp32 Winograd conv over every channel of x and 1 or 2 terms at 1/2 or 1/4 of its map")
+            assert all(t.cs == x.cs and t.dt == 0 and t.n == x.n for t in terms) and (y.n, y.h, y.w, y.cs, y.dt) == (x.n, x.h, x.w, x.cs, 0)
+            sh = [{2: 1, 4: 2}[x.h // t.h] for t in terms]
+            assert all((t.h << k, t.w << k) == (x.h, x.w) for t, k in zip(terms, sh))
+            d.t1, d.t1_shift, d.y = terms[0].ptr, sh[0], y.ptr
+            if len(terms) > 1:
+                d.t2, d.t2_shift = terms[1].ptr, sh[1]
         if wino:
             # Winograd F(2x2, 3x3): 2.25x fewer matrix-pipe operations (csrc/i2r_conv_wino.hip); NT 3 or 4, two fragments per workgroup
             nfrag = pc.cout_pad // 16
@@ -808,6 +824,13 @@ class Program:
         else:
             self.ops.append((cabi.OP_CONV, lane, d))
         return out
+
+    @staticmethod
+    def fuse_in_ok(x, terms, pc):
+        """can conv(x, pc, fuse_in=(terms, y)) fold the closing pass?  fp32 Winograd only (csrc/i2r_conv_wino.hip), reading every channel of
+        x (so that y comes out complete), one or two terms at half or a quarter of the map"""
+        return (WINOGRAD and pc.w_wino is not None and pc.dtype == 0 and x.dt == 0 and x.c == pc.cin and x.cs == pc.cin_pad
+                and 1 <= len(terms) <= 2 and all((t.h * 2, t.w * 2) == (x.h, x.w) or (t.h * 4, t.w * 4) == (x.h, x.w) for t in terms))
 
     @staticmethod
     def _group_tiles(group):
@@ -1465,6 +1488,15 @@ class Program:
 # ------------------------------------------------------------------------------------------------
 # network assembly
 # ------------------------------------------------------------------------------------------------
+class _PendingFuse:
+    """a fuse output whose closing pass y = ReLU((base + up(t_a)) + up(t_b)) has not been emitted: the next module's first Winograd conv
+    folds it into its staging (Program.conv(fuse_in=...)); anything else closes it with Program.fuse_up_add (HRNetW48._close)"""
+    __slots__ = ("base", "terms")
+
+    def __init__(self, base, terms):
+        self.base, self.terms = base, terms
+
+
 class HRNetW48:
     """Packed HRNet-W48-S tower (reference interformer_pureMulti.py:675-699) + its program emitter."""
 
@@ -1499,22 +1531,46 @@ class HRNetW48:
         return mod
 
     @staticmethod
-    def _emit_module(P, mod, xs):
+    def _close(P, x):
+        """the closing pass of a deferred fuse output as a launch of its own"""
+        if not isinstance(x, _PendingFuse):
+            return x
+        y = P.alloc(x.base.n, x.base.h, x.base.w, x.base.c, x.base.dt)
+        P.fuse_up_add(x.base, x.terms, y, relu=True)
+        P.release(x.base, *x.terms)
+        return y
+
+    @staticmethod
+    def _emit_module(P, mod, xs, need=None, defer=None):
         """HighResolutionModule.forward (interformer_pureMulti.py:392-410) as grouped launches: block k of every branch
-        goes out in one launch, and the fuse sums are evaluated level by level (one launch per dependency depth)."""
+        goes out in one launch, and the fuse sums are evaluated level by level (one launch per dependency depth).
+        xs may hold deferred closing passes of the module before (_PendingFuse): the first block's conv1 folds them in.
+        need: indices of the outputs somebody reads (None = all); the fuse terms and closing passes of the others are not emitted and
+        their entries of the result are None.  defer: per output, the PackedConv that will read it first (or None): where that conv
+        can fold the closing pass (Program.fuse_in_ok) the output is returned as a _PendingFuse."""
         nb = mod["nb"]
         xs = list(xs)
+        need = set(range(nb)) if need is None else {i % nb for i in need}
         for k in range(max(len(b) for b in mod["blocks"])):
-            grp, ts = [], {}
+            grp, ts, folded = [], {}, []
             for i in range(nb):
                 if k < len(mod["blocks"][i]):
+                    if isinstance(xs[i], _PendingFuse):
+                        pf = xs[i]
+                        xs[i] = P.alloc(pf.base.n, pf.base.h, pf.base.w, pf.base.c, pf.base.dt)  # (its own buffer: the kernel's halo reads race with in-place stores)
+                        ts[i] = P.conv(pf.base, mod["blocks"][i][k][0], relu=True, group=grp, fuse_in=(pf.terms, xs[i]))
+                        folded.append(pf)
+                        continue
                     ts[i] = P.conv(xs[i], mod["blocks"][i][k][0], relu=True, group=grp)
             P.flush_group(grp)
+            for pf in folded:
+                P.release(pf.base, *pf.terms)
             for i, t in ts.items():
                 y = P.conv(t, mod["blocks"][i][k][1], relu=True, res1=xs[i], group=grp)
                 P.release(t, xs[i])
                 xs[i] = y
             P.flush_group(grp)
+        xs = [HRNetW48._close(P, x) for x in xs]  # (a branch without blocks)
         # fuse (interformer_pureMulti.py:392-410): y_i = ReLU(sum_j f_ij(x_j)), f_ii = identity, summed left to right.
         #  * down-sampling terms (j < i, chains of stride-2 convs) are evaluated level by level, one grouped launch per level: every
         #    chain advances one conv per level while, per output, at most one term whose source is ready is ACCUMULATED into y_i
@@ -1530,12 +1586,12 @@ class HRNetW48:
         terms, ups = [], []
         for i in range(nb):
             ts = []
-            for j in range(i):
+            for j in range(i if i in need else 0):
                 chain = mod["fuse"][(i, j)]
                 ts.append(dict(j=j, mids=list(chain[:-1]), last=chain[-1], cur=None))
             ts.sort(key=lambda t: (len(t["mids"]), t["j"]))
             terms.append(ts)
-            ups.append([(j, mod["fuse"][(i, j)]) for j in range(i + 1, nb)])
+            ups.append([(j, mod["fuse"][(i, j)]) for j in range(i + 1, nb)] if i in need else [])
         n_up = sum(len(u) for u in ups)
         ys = [None] * nb
         n_sum = [0] * nb
@@ -1575,10 +1631,16 @@ class HRNetW48:
             P.flush_group(grp)
             P.release(*rel)
         assert not any(terms)
+        kept = []  # inputs that live on as the base of a deferred closing pass
         for i in range(nb):
             if not tmaps[i]:
                 continue
             base = xs[i] if ys[i] is None else ys[i]
+            if FUSE_IN and defer is not None and defer[i] is not None and P.fuse_in_ok(base, tmaps[i], defer[i]):
+                if ys[i] is None:
+                    kept.append(xs[i])
+                ys[i] = _PendingFuse(base, list(tmaps[i]))
+                continue
             if ys[i] is None:
                 ys[i] = P.alloc(xs[i].n, xs[i].h, xs[i].w, xs[i].c, xs[i].dt)
             pend = list(tmaps[i])
@@ -1587,23 +1649,33 @@ class HRNetW48:
                 P.fuse_up_add(base, now, ys[i], relu=not pend)
                 base = ys[i]
             P.release(*tmaps[i])
-        P.release(*xs)
+        P.release(*[x for x in xs if not any(x is k for k in kept)])
         return ys
 
-    def emit(self, P, n, h, w, n_src=None):
-        """-> (list of branch Acts, stem StemArgs to patch the input pointer into)."""
+    def emit(self, P, n, h, w, n_src=None, need=None):
+        """-> (list of branch Acts, stem StemArgs to patch the input pointer into).  need: indices of the branch outputs the caller reads
+        (None = all): the last module then skips the fuse sums of the others, whose entries come back as None."""
         a, stem_args = P.stem(self.stem1, n, h, w, n_src=n_src, out_dt=P.store_dt)  # 16-bit modes: the whole tower stores 16 bit
         x = P.stem_conv2_layer1(a, self.conv2, self.layer1)
         grp = []  # the two transition convs read the same map: one grouped launch (304 -> 281 us at 32 crops, tools/group_try.py)
         xs = [P.conv(x, self.t1[0], relu=True, group=grp), P.conv(x, self.t1[1], relu=True, group=grp)]
         P.flush_group(grp)
         P.release(x)
-        for mod in self.stage2:
-            xs = self._emit_module(P, mod, xs)
+        if not PRUNE_FUSE:
+            need = None
+        # a module's closing passes are deferred to the first block convs of the module after it (branch i reads output i)
+        mods = list(self.stage2) + list(self.stage3)
+        def first_convs(m, nb):
+            nxt = mods[m + 1]["blocks"] if m + 1 < len(mods) else []
+            return [nxt[i][0][0] if i < len(nxt) and nxt[i] else None for i in range(nb)]
+        for m, mod in enumerate(self.stage2):
+            xs = self._emit_module(P, mod, xs, defer=first_convs(m, mod["nb"]))
+        xs[-1] = self._close(P, xs[-1])  # (the lowest branch has no up-sampling terms, so nothing is pending here today)
         t = P.conv(xs[-1], self.t2, relu=True)
         xs = [xs[0], xs[1], t]
-        for mod in self.stage3:
-            xs = self._emit_module(P, mod, xs)
+        for m, mod in enumerate(self.stage3, len(self.stage2)):
+            last = m + 1 == len(mods)
+            xs = self._emit_module(P, mod, xs, need=need if last else None, defer=None if last else first_convs(m, mod["nb"]))
         return xs, stem_args
 
 
@@ -2153,9 +2225,10 @@ class Engine:
 
     def _emit_single(self, P, S, H, W, n_src, capture=()):
         """-> (first-stage feature Act [S, H/4, W/4, d], stem args): tower (+ reduce + per-crop encoder for TransPose-H, :649-655)"""
-        xs, stem_args = self.tower.emit(P, S, H, W, n_src=n_src)
         if self.singleformer == "hrformer":
+            xs, stem_args = self.tower.emit(P, S, H, W, n_src=n_src)
             return xs[0], stem_args
+        xs, stem_args = self.tower.emit(P, S, H, W, n_src=n_src, need={self.res_layer})
         f = P.conv(xs[self.res_layer], self.reduce, out_dt=0)
         P.release(*xs)
         tok = f.h * f.w
@@ -2291,7 +2364,7 @@ class Engine:
             f.t.zero_()  # (capacity slots nobody fills must hold finite rows)
             single_feat = None
         elif bare:
-            xs, patch["x"] = self.tower.emit(P, S, H, W, n_src=n_src)
+            xs, patch["x"] = self.tower.emit(P, S, H, W, n_src=n_src, need={-1})  # (only the lowest branch is read below)
             if cat is not None:
                 assert (xs[-1].h, xs[-1].w) == (cat.h, cat.w), "cat_vec: the backbone output is not TRANS_SIZE"
             f = P.conv(xs[-1], self.reduce, out_dt=0, out=cat)
@@ -2416,7 +2489,7 @@ class Engine:
             def build():
                 P = Program(self.device)
                 P.store_dt = self.store_dt
-                xs, px = self.tower.emit(P, S, H, W, n_src=S)
+                xs, px = self.tower.emit(P, S, H, W, n_src=S, need={-1})
                 f = P.conv(xs[-1], self.reduce, out_dt=0)
                 P.release(*xs)
                 P.finalize()
