@@ -545,6 +545,37 @@ typedef struct i2r_attn_weights_args {
 } i2r_attn_weights_args;
 I2R_API int i2r_attn_weights(const i2r_attn_weights_args* a, void* stream);
 
+/* Attention maps at query points: what visualize.py reads of the maps above -- per query point one row (mode 0, "dependency":
+ * attn_map[y, x, :, :], :186-233) or one column (mode 1, "affect": attn_map[:, :, y, x], :333-388) of P = (1 / heads) sum_h softmax_j(q_h[i] .
+ * k_h[j]), optionally through F.interpolate(scale_factor=scale, mode="bilinear") -- without ever building [L_g, L_g].  Per group g:
+ *   mode 0: raw[k, j] = P[q_tok[g, k], j]        mode 1: raw[k, i] = P[i, q_tok[g, k]]        k < K_g, row-major [K_g, L_g]
+ *   scale == 1: out[out_off[g] + k * L_g + j] = raw[k, j]
+ *   scale  > 1: L_g = P_g h w; every raw row is P_g maps [h, w]; out block = [K_g, P_g, h scale, w scale], bilinear with
+ *               align_corners=False: source coordinate (dst + 0.5) / scale - 0.5 clamped at 0, neighbours clamped at the edge, fp32
+ *   qk, grp_off, heads, hp, k_off, qk_cs, out_off: exactly as i2r_attn_weights reads them
+ *   q_tok    device int32 [n_grp, K]: token indices inside the group (duplicates allowed).  A negative entry gives an all-zero row.
+ *            Precondition q_tok < L_g; the kernel clamps (a device array cannot be validated by the host entry point, cf. key_len)
+ *   q_cnt    optional device int32 [n_grp]: group g uses its first K_g = q_cnt[g] entries (clamped to [0, K]); NULL: K_g = K
+ *   ws       mode 0: ws_stride floats per (group, entry): n_grp * K rows; mode 1: ws_stride floats per token row, as i2r_attn_weights;
+ *            ws_stride >= 2 * heads * ceil(max L_g / 128)
+ *   rows     scale > 1 only: device workspace of K * grp_off[n_grp] floats (the raw rows before up-sampling)
+ *   grp_off_host  scale > 1 only: HOST copy of grp_off[0 .. n_grp] (every L_g must be a multiple of h w: checked here, and it sizes the
+ *            up-sampling grid; the kernels themselves read the device table only)
+ *   n_tiles  mode 0: sum over groups of ceil(K_g / 16) * ceil(L_g / 128); mode 1: as i2r_attn_weights
+ *   n_col_tiles  mode 1: sum over groups of ceil(L_g / 16) * ceil(K_g / 16)
+ * Only the first n_grp groups are computed; nothing outside their blocks is written.  Mode 0: row statistics of the K gathered rows, then
+ * a GEMM whose query side is gathered; mode 1: the statistics pass of i2r_attn_weights, then a GEMM whose key side is gathered, each
+ * column written as a contiguous vector; then the up-sampling pass.  fp32 matrix pipe, exp2-based softmax with fp32 statistics, heads
+ * summed in a fixed order, no atomics: deterministic.  I2R_E_ARG: null pointers, mode outside {0, 1}, scale < 1 or > 64, K < 1 or
+ * >= 2^20, n_grp outside 1 .. 65535, the heads / hp / stride / alignment conditions of i2r_attn_weights, and when scale > 1: h or w
+ * < 1, h w not dividing a group length (host table).  An empty group is skipped at every scale. */
+typedef struct i2r_attn_query_args {
+    const float* qk; float* out; const int32_t* grp_off; const int64_t* out_off; float* ws; const int32_t* q_tok; const int32_t* q_cnt;
+    float* rows; const int32_t* grp_off_host;
+    int32_t n_grp, heads, hp, k_off, qk_cs, n_tiles, ws_stride, mode, K, scale, h, w, n_col_tiles, reserved;
+} i2r_attn_query_args;
+I2R_API int i2r_attn_query_maps(const i2r_attn_query_args* a, void* stream);
+
 /* MODEL.ATTENTION_TYPE != 'default' (MODEL.NAME interformer: attention.py:991-1031,1046-1062) -- the inter-human "encoder" is ONE
  * GeneralTransformerBlock: a multi-head attention (q / k / v / out projections with bias, MHA_ :494-835; the relative position bias is
  * gathered but its addition is commented out, :780-786) over the (person, y, x) tokens of an image INCLUDING the padded persons' rows
@@ -586,7 +617,8 @@ enum {
     I2R_OP_LAYERNORM = 10, I2R_OP_WINATTN = 11, I2R_OP_DWCONV = 12, I2R_OP_UPSAMPLE = 13, /* 14: reserved */
     I2R_OP_PE_RES_STEM = 15, I2R_OP_HRT_ATTN = 16, I2R_OP_HRT_MLP = 17, /* 18: reserved */ I2R_OP_FUSE_UP = 19,
     I2R_OP_CONV1X1_PAIR = 20, I2R_OP_CONV1X1_LP = 21, I2R_OP_MH_ATTN = 22, I2R_OP_PE_CAT_VEC = 23, I2R_OP_ROWS_GATHER = 24, I2R_OP_VIEW_SCRAMBLE = 25,
-    I2R_OP_RECORD = 26, I2R_OP_WAIT = 27, I2R_OP_LANE_FLAGS = 28, I2R_OP_ATTN_WEIGHTS = 29
+    I2R_OP_RECORD = 26, I2R_OP_WAIT = 27, I2R_OP_LANE_FLAGS = 28, I2R_OP_ATTN_WEIGHTS = 29,
+    I2R_OP_ATTN_QUERY = 30
 };
 
 typedef struct i2r_stem_args {

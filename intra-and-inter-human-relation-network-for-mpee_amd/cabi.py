@@ -34,6 +34,7 @@ OP_LANE_FLAGS = 28          # args = device int32[64] flag buffer: the sync ops 
 # I2R_OP_ATTN_WEIGHTS: the attention maps of an encoder layer (i2r_attn_weights).  Only capture programs emit it (Engine.forward(...,
 # capture=)); bench.py never times those, so it stays outside the OP_ names that bench.op_model covers one by one.
 CAPTURE_OP_ATTN_WEIGHTS = 29
+CAPTURE_OP_ATTN_QUERY = 30  # I2R_OP_ATTN_QUERY: rows / columns of those maps at query points (i2r_attn_query_maps; capture programs with queries=)
 SYNC_OPS = (OP_FORK, OP_JOIN, OP_XSYNC, OP_RECORD, OP_WAIT, OP_LANE_FLAGS)  # ops that launch nothing (FORK / JOIN: `lane` is a lane mask)
 
 _fp = C.c_void_p  # device pointers travel as integers
@@ -108,6 +109,13 @@ class MhAttnArgs(C.Structure):
 class AttnWeightsArgs(C.Structure):
     _fields_ = [("qk", _fp), ("out", _fp), ("grp_off", _fp), ("out_off", _fp), ("ws", _fp),
                 ("n_grp", _i32), ("heads", _i32), ("hp", _i32), ("k_off", _i32), ("qk_cs", _i32), ("n_tiles", _i32), ("ws_stride", _i32)]
+
+
+class AttnQueryArgs(C.Structure):   # i2r_attn_query_args
+    _fields_ = [("qk", _fp), ("out", _fp), ("grp_off", _fp), ("out_off", _fp), ("ws", _fp), ("q_tok", _fp), ("q_cnt", _fp), ("rows", _fp),
+                ("grp_off_host", _fp),
+                ("n_grp", _i32), ("heads", _i32), ("hp", _i32), ("k_off", _i32), ("qk_cs", _i32), ("n_tiles", _i32), ("ws_stride", _i32),
+                ("mode", _i32), ("K", _i32), ("scale", _i32), ("h", _i32), ("w", _i32), ("n_col_tiles", _i32), ("reserved", _i32)]
 
 
 class GatherArgs(C.Structure):
@@ -202,7 +210,7 @@ class Op(C.Structure):
 
 # every symbol include/i2r_hip.h declares (tests/test_host.py::test_cabi_library_exports_every_declared_symbol checks the built library exports them all)
 EXPORTS = ("i2r_conv", "i2r_conv_grouped", "i2r_conv_kernel_name", "i2r_stem_conv", "i2r_pe_res_stem", "i2r_maxpool3x3s2", "i2r_head", "i2r_layernorm", "i2r_window_attn", "i2r_hrt_attn_block", "i2r_hrt_mlp_block", "i2r_dwconv3x3",
-           "i2r_upsample_bilinear_add", "i2r_upsample_bilinear_add_multi", "i2r_fuse_up_add", "i2r_conv1x1_pair", "i2r_conv1x1_lp", "i2r_flip_merge", "i2r_decode", "i2r_pose_nms", "i2r_joint_targets", "i2r_val_metrics", "i2r_crop_affine", "i2r_box_mask", "i2r_crop_affine_cv2", "i2r_box_mask_cv2", "i2r_person_inputs_cv2", "i2r_encoder_kv", "i2r_encoder_layer", "i2r_mh_attention", "i2r_attn_weights", "i2r_pe_cat_vec", "i2r_rows_gather", "i2r_view_scramble",
+           "i2r_upsample_bilinear_add", "i2r_upsample_bilinear_add_multi", "i2r_fuse_up_add", "i2r_conv1x1_pair", "i2r_conv1x1_lp", "i2r_flip_merge", "i2r_decode", "i2r_pose_nms", "i2r_joint_targets", "i2r_val_metrics", "i2r_crop_affine", "i2r_box_mask", "i2r_crop_affine_cv2", "i2r_box_mask_cv2", "i2r_person_inputs_cv2", "i2r_encoder_kv", "i2r_encoder_layer", "i2r_mh_attention", "i2r_attn_weights", "i2r_attn_query_maps", "i2r_pe_cat_vec", "i2r_rows_gather", "i2r_view_scramble",
            "i2r_run_program", "i2r_run_program_timed", "i2r_abi_version", "i2r_last_error", "i2r_device_check")
 
 _LIB = None
@@ -253,6 +261,7 @@ def load_library(path=LIB_PATH):
     L.i2r_pe_cat_vec.argtypes = [C.POINTER(PeCatVecArgs), C.c_void_p]
     L.i2r_mh_attention.argtypes = [C.POINTER(MhAttnArgs), C.c_void_p]
     L.i2r_attn_weights.argtypes = [C.POINTER(AttnWeightsArgs), C.c_void_p]
+    L.i2r_attn_query_maps.argtypes = [C.POINTER(AttnQueryArgs), C.c_void_p]
     L.i2r_run_program.argtypes = [C.POINTER(Op), _i32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.i2r_run_program_timed.argtypes = [C.POINTER(Op), _i32] + [C.POINTER(C.c_void_p)] * 4
     L.i2r_device_check.argtypes = [_i32, C.POINTER(_i32), C.POINTER(_i32)]

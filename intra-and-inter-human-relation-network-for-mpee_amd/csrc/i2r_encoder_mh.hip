@@ -317,6 +317,240 @@ __global__ __launch_bounds__(256) void aw_probs_k(const AwK p) {
     }
 }
 
+// ---- attention maps at query points: K rows (mode 0, "dependency") or K columns (mode 1, "affect") of the head-averaged map P ------------
+// The visualisation reads P[q, :] or P[:, q] for a handful of tokens q per group; neither form ever builds [L, L].  Same fragment forms,
+// statistics layout and fixed head order as the full capture above.
+//   mode 0  aq_row_stats_k / aq_rows_k: the passes above with the QUERY side gathered -- work item (group, 16 gathered queries, block of
+//           kAwKeys keys); workspace row = gi * K + k (K = row stride of q_tok), (m, l) per (key block, head) as above
+//   mode 1  aw_stats_k unchanged (every row's statistics), then aq_cols_k: the KEY side gathered, S = Q K^T (A = query rows, B = gathered
+//           key rows): lane (g, li) holds S[query 4g + r][gathered key li], i.e. 4 consecutive entries of column li -> one 16-byte store
+//   aq_upsample_k: each [P_g, h, w] row -> [P_g, h scale, w scale], F.interpolate's bilinear align_corners=False arithmetic
+// A negative token gives a zero row; a token >= L_g is clamped (the host validates; a device table cannot be checked by the entry point).
+struct AqK {
+    AwK a;
+    const int* q_tok;
+    const int* q_cnt;
+    float* rows;  // scale > 1: the raw [K_g, L_g] rows of group g at rows + K * grp_off[g], up-sampled into out by aq_upsample_k
+    int K, scale, h, w;
+};
+
+__device__ __forceinline__ int aq_count(const AqK& p, int gi) { return p.q_cnt ? min(max(p.q_cnt[gi], 0), p.K) : p.K; }
+
+// group gi's raw block: [K_g, L_g] row-major, in `out` (scale 1) or in the `rows` workspace
+__device__ __forceinline__ float* aq_block(const AqK& p, int gi, int g0) {
+    return p.scale > 1 ? p.rows + (long long)p.K * g0 : p.a.out + p.a.out_off[gi];
+}
+
+// mode 0 work item of wave `item`: group gi, gathered queries [k0q, k0q + 16) of its kq, key block kb of nkb
+__device__ __forceinline__ bool aq_row_item(const AqK& p, int item, int& gi, int& g0, int& g1, int& k0q, int& kq, int& kb, int& nkb) {
+    for (gi = 0; gi < p.a.n_grp; ++gi) {
+        g0 = p.a.grp_off[gi];
+        g1 = p.a.grp_off[gi + 1];
+        const int len = g1 - g0;
+        kq = aq_count(p, gi);
+        if (len <= 0 || kq <= 0) continue;
+        nkb = (len + kAwKeys - 1) / kAwKeys;
+        const int nt = (kq + 15) / 16 * nkb;
+        if (item < nt) {
+            k0q = item / nkb * 16;
+            kb = item - item / nkb * nkb;
+            return 2 * p.a.heads * nkb <= p.a.ws_stride;
+        }
+        item -= nt;
+    }
+    return false;
+}
+
+template <int HB>
+__global__ __launch_bounds__(256) void aq_row_stats_k(const AqK p) {
+    const int lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4;
+    int gi, g0, g1, k0q, kq, kb, nkb;
+    if (!aq_row_item(p, blockIdx.x * 4 + (threadIdx.x >> 6), gi, g0, g1, k0q, kq, kb, nkb)) return;
+    const int tok = p.q_tok[(size_t)gi * p.K + min(k0q + li, kq - 1)];
+    const int qrow = g0 + min(max(tok, 0), g1 - g0 - 1), k_beg = g0 + kb * kAwKeys, k_end = min(k_beg + kAwKeys, g1);
+    for (int head = 0; head < p.a.heads; ++head) {
+        f32x4 q[HB];
+        aw_load_q<HB>(p.a, qrow, head, g, q);
+        float m = -INFINITY, l = 0.f;
+        for (int k0 = k_beg; k0 < k_end; k0 += 16) {
+            f32x4 s = aw_scores<HB>(p.a, min(k0 + li, g1 - 1), head, g, q);
+            float mx = -INFINITY;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                if (k0 + 4 * g + r >= k_end) s[r] = -INFINITY;
+                mx = fmaxf(mx, s[r]);
+            }
+            mx = fmaxf(mx, __shfl_xor(mx, 16));
+            mx = fmaxf(mx, __shfl_xor(mx, 32));
+            const float m_new = fmaxf(m, mx);  // (finite: key k0 of every tile exists)
+            float ps = 0.f;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) ps += __builtin_amdgcn_exp2f(s[r] - m_new);
+            l = l * __builtin_amdgcn_exp2f(m - m_new) + ps;
+            m = m_new;
+        }
+        l += __shfl_xor(l, 16);
+        l += __shfl_xor(l, 32);
+        if (g == 0 && k0q + li < kq) p.a.ws[((size_t)gi * p.K + k0q + li) * (p.a.ws_stride / 2) + kb * p.a.heads + head] = make_float2(m, l);
+    }
+}
+
+template <int HB>
+__global__ __launch_bounds__(256) void aq_rows_k(const AqK p) {
+    const int lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4;
+    int gi, g0, g1, k0q, kq, kb, nkb;
+    if (!aq_row_item(p, blockIdx.x * 4 + (threadIdx.x >> 6), gi, g0, g1, k0q, kq, kb, nkb)) return;
+    const int kr = min(k0q + li, kq - 1);
+    const int tok = p.q_tok[(size_t)gi * p.K + kr];
+    const int qrow = g0 + min(max(tok, 0), g1 - g0 - 1), k_beg = g0 + kb * kAwKeys, k_end = min(k_beg + kAwKeys, g1);
+    const int n_kt = (k_end - k_beg + 15) / 16;
+    const float2* st = p.a.ws + ((size_t)gi * p.K + kr) * (p.a.ws_stride / 2);
+    f32x4 acc[kAwTiles];
+#pragma unroll
+    for (int t = 0; t < kAwTiles; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int head = 0; head < p.a.heads; ++head) {
+        float mm = -INFINITY;
+        for (int b = 0; b < nkb; ++b) mm = fmaxf(mm, st[b * p.a.heads + head].x);
+        float ll = 0.f;
+        for (int b = 0; b < nkb; ++b) {
+            const float2 e = st[b * p.a.heads + head];
+            ll += e.y * __builtin_amdgcn_exp2f(e.x - mm);
+        }
+        const float inv = 1.f / ll;
+        f32x4 q[HB];
+        aw_load_q<HB>(p.a, qrow, head, g, q);
+#pragma unroll
+        for (int t = 0; t < kAwTiles; ++t) {
+            if (t < n_kt) {
+                const f32x4 s = aw_scores<HB>(p.a, min(k_beg + 16 * t + li, g1 - 1), head, g, q);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) acc[t][r] += __builtin_amdgcn_exp2f(s[r] - mm) * inv;
+            }
+        }
+    }
+    if (k0q + li >= kq) return;
+    const float rh = tok < 0 ? 0.f : 1.f / (float)p.a.heads;  // (a skipped point: the row is written as zeros)
+    const long long len = g1 - g0;
+    float* blk = aq_block(p, gi, g0);
+    float* row = blk + (long long)(k0q + li) * len;
+    const bool whole = (len & 3) == 0 && (reinterpret_cast<uintptr_t>(blk) & 15) == 0;
+#pragma unroll
+    for (int t = 0; t < kAwTiles; ++t) {
+        const int k = k_beg + 16 * t + 4 * g - g0;  // first of the lane's 4 keys, relative to the group
+        if (t >= n_kt || k >= len) continue;
+        const f32x4 v = acc[t] * rh;
+        if (whole) {
+            *reinterpret_cast<f32x4*>(row + k) = v;
+        } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (k + r < len) row[k + r] = v[r];
+        }
+    }
+}
+
+// mode 1, behind aw_stats_k: work item (group, 16-query tile, 16 gathered keys), one wave each
+template <int HB>
+__global__ __launch_bounds__(256) void aq_cols_k(const AqK p) {
+    const int lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4;
+    int item = blockIdx.x * 4 + (threadIdx.x >> 6), gi, g0 = 0, g1 = 0, kq = 0, nkb = 0, q0 = 0, kt = 0;
+    for (gi = 0; gi < p.a.n_grp; ++gi) {
+        g0 = p.a.grp_off[gi];
+        g1 = p.a.grp_off[gi + 1];
+        kq = aq_count(p, gi);
+        if (g1 - g0 <= 0 || kq <= 0) continue;
+        nkb = (g1 - g0 + kAwKeys - 1) / kAwKeys;
+        const int nkt = (kq + 15) / 16, nt = (g1 - g0 + 15) / 16 * nkt;
+        if (item < nt) {
+            q0 = g0 + item / nkt * 16;
+            kt = item - item / nkt * nkt;
+            break;
+        }
+        item -= nt;
+    }
+    if (gi >= p.a.n_grp || 2 * p.a.heads * nkb > p.a.ws_stride) return;
+    const int kc = kt * 16 + li;  // the lane's column (as the B operand and as the owner of the results)
+    const int tok = p.q_tok[(size_t)gi * p.K + min(kc, kq - 1)];
+    const int krow = g0 + min(max(tok, 0), g1 - g0 - 1), qrow = min(q0 + li, g1 - 1);
+    const int hs2 = p.a.ws_stride / 2;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int head = 0; head < p.a.heads; ++head) {
+        float mm[4], inv[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {  // the statistics of the lane's 4 query rows
+            const float2* st = p.a.ws + (size_t)min(q0 + 4 * g + r, g1 - 1) * hs2;
+            float m = -INFINITY;
+            for (int b = 0; b < nkb; ++b) m = fmaxf(m, st[b * p.a.heads + head].x);
+            float ll = 0.f;
+            for (int b = 0; b < nkb; ++b) {
+                const float2 e = st[b * p.a.heads + head];
+                ll += e.y * __builtin_amdgcn_exp2f(e.x - m);
+            }
+            mm[r] = m;
+            inv[r] = 1.f / ll;
+        }
+        f32x4 q[HB];
+        aw_load_q<HB>(p.a, qrow, head, g, q);
+        const float* kp = p.a.qk + (size_t)krow * p.a.qk_cs + p.a.k_off + head * p.a.hp + 4 * g;
+        f32x4 s = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int u = 0; u < HB; ++u) {
+            const f32x4 kk = *reinterpret_cast<const f32x4*>(kp + 16 * u);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) s = mfma16(q[u][c], kk[c], s);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[r] += __builtin_amdgcn_exp2f(s[r] - mm[r]) * inv[r];
+    }
+    if (kc >= kq) return;
+    const float rh = tok < 0 ? 0.f : 1.f / (float)p.a.heads;
+    const long long len = g1 - g0;
+    float* blk = aq_block(p, gi, g0);
+    float* col = blk + (long long)kc * len;  // column kc as a contiguous vector over the query rows
+    const int i = q0 - g0 + 4 * g;
+    if (i >= len) return;
+    const f32x4 v = acc * rh;
+    if ((len & 3) == 0 && (reinterpret_cast<uintptr_t>(blk) & 15) == 0) {
+        *reinterpret_cast<f32x4*>(col + i) = v;
+    } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            if (i + r < len) col[i + r] = v[r];
+    }
+}
+
+// blockIdx.y = group; 4 consecutive floats of its [K_g, P_g, h scale, w scale] block per thread
+__global__ __launch_bounds__(256) void aq_upsample_k(const AqK p) {
+    const int gi = blockIdx.y;
+    const int g0 = p.a.grp_off[gi], len = p.a.grp_off[gi + 1] - g0, hw = p.h * p.w, kq = aq_count(p, gi);
+    if (len <= 0 || len % hw != 0) return;  // (the entry point checks the host's copy of the table; never a partial map)
+    const int H = p.h * p.scale, W = p.w * p.scale;
+    const long long n = (long long)kq * len * p.scale * p.scale;
+    const long long e0 = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (e0 >= n) return;
+    const float* src = p.rows + (long long)p.K * g0;  // [K_g * P_g][h][w]
+    float* dst = p.a.out + p.a.out_off[gi];
+    const float rs = 1.f / (float)p.scale;
+    float v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const long long e = min(e0 + j, n - 1);
+        const int ox = (int)(e % W), oy = (int)(e / W % H);
+        const float* m = src + e / ((long long)W * H) * hw;
+        const float sy = fmaxf(((float)oy + 0.5f) * rs - 0.5f, 0.f), sx = fmaxf(((float)ox + 0.5f) * rs - 0.5f, 0.f);
+        const int y0 = (int)sy, x0 = (int)sx, y1 = min(y0 + 1, p.h - 1), x1 = min(x0 + 1, p.w - 1);
+        const float ly = sy - (float)y0, lx = sx - (float)x0;
+        v[j] = (1.f - ly) * ((1.f - lx) * m[y0 * p.w + x0] + lx * m[y0 * p.w + x1]) + ly * ((1.f - lx) * m[y1 * p.w + x0] + lx * m[y1 * p.w + x1]);
+    }
+    if (e0 + 4 <= n && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
+        *reinterpret_cast<f32x4*>(dst + e0) = (f32x4){v[0], v[1], v[2], v[3]};
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (e0 + j < n) dst[e0 + j] = v[j];
+    }
+}
+
 }  // namespace
 
 extern "C" int i2r_rows_gather(const float* src, float* out, const int32_t* map, int32_t n_out, int32_t floats_per_crop, void* stream) {
@@ -398,5 +632,62 @@ extern "C" int i2r_attn_weights(const i2r_attn_weights_args* a, void* stream) {
     I2R_CHECK_LAUNCH("i2r_attn_weights (statistics)");
     i2r_launch(probs[a->hp / 16 - 1], grid, dim3(256), 0, (hipStream_t)stream, k);
     I2R_CHECK_LAUNCH("i2r_attn_weights (probabilities)");
+    return I2R_OK;
+}
+
+extern "C" int i2r_attn_query_maps(const i2r_attn_query_args* a, void* stream) {
+    I2R_CHECK_ARG(a && a->qk && a->out && a->grp_off && a->out_off && a->ws && a->q_tok, "i2r_attn_query_maps: null pointer");
+    I2R_CHECK_ARG(a->mode == 0 || a->mode == 1, "i2r_attn_query_maps: mode=%d (0: dependency rows, 1: affect columns)", a->mode);
+    I2R_CHECK_ARG(a->scale >= 1 && a->scale <= 64, "i2r_attn_query_maps: scale=%d (1 .. 64)", a->scale);
+    I2R_CHECK_ARG(a->K >= 1 && a->K < (1 << 20), "i2r_attn_query_maps: K=%d", a->K);
+    I2R_CHECK_ARG(a->heads > 0 && a->hp > 0 && a->hp % 16 == 0 && a->hp <= 256, "i2r_attn_query_maps: heads=%d hp=%d (hp: multiple of 16, <= 256)", a->heads, a->hp);
+    const int hs = a->heads * a->hp;
+    I2R_CHECK_ARG(a->k_off >= hs && a->k_off % 4 == 0 && a->qk_cs >= a->k_off + hs && a->qk_cs % 4 == 0,
+                  "i2r_attn_query_maps: row stride qk=%d (k at %d) for %d heads x %d", a->qk_cs, a->k_off, a->heads, a->hp);
+    I2R_CHECK_ARG(a->n_grp > 0 && a->n_grp < 65536 && a->n_tiles > 0 && a->ws_stride >= 2 * a->heads && a->ws_stride % 2 == 0 &&
+                      (a->mode == 0 || a->n_col_tiles > 0),
+                  "i2r_attn_query_maps: n_grp=%d n_tiles=%d n_col_tiles=%d ws_stride=%d", a->n_grp, a->n_tiles, a->n_col_tiles, a->ws_stride);
+    I2R_CHECK_ARG(reinterpret_cast<uintptr_t>(a->qk) % 16 == 0 && reinterpret_cast<uintptr_t>(a->ws) % 8 == 0, "i2r_attn_query_maps: alignment");
+    int max_len = 0;
+    if (a->scale > 1) {
+        I2R_CHECK_ARG(a->rows && a->grp_off_host, "i2r_attn_query_maps: null pointer (scale > 1 needs rows and grp_off_host)");
+        I2R_CHECK_ARG(a->h > 0 && a->w > 0 && (long long)a->h * a->w < (1 << 24), "i2r_attn_query_maps: h=%d w=%d", a->h, a->w);
+        for (int g = 0; g < a->n_grp; ++g) {
+            const int len = a->grp_off_host[g + 1] - a->grp_off_host[g];
+            I2R_CHECK_ARG(len >= 0 && len % (a->h * a->w) == 0, /* (an empty group is skipped, as at scale 1) */ "i2r_attn_query_maps: group %d has %d tokens, not a multiple of h w = %d x %d", g, len, a->h, a->w);
+            max_len = len > max_len ? len : max_len;
+        }
+    }
+    AqK k{{a->qk, a->out, a->grp_off, reinterpret_cast<const long long*>(a->out_off), reinterpret_cast<float2*>(a->ws), a->n_grp, a->heads, a->hp,
+           a->k_off, a->qk_cs, a->n_tiles, a->ws_stride},
+          a->q_tok, a->q_cnt, a->rows, a->K, a->scale, a->h, a->w};
+    typedef void (*aw_t)(const AwK);
+    typedef void (*aq_t)(const AqK);
+#define I2R_AW_TABLE(K) {K<1>, K<2>, K<3>, K<4>, K<5>, K<6>, K<7>, K<8>, K<9>, K<10>, K<11>, K<12>, K<13>, K<14>, K<15>, K<16>}
+    static const aw_t stats[16] = I2R_AW_TABLE(aw_stats_k);
+    static const aq_t row_stats[16] = I2R_AW_TABLE(aq_row_stats_k);
+    static const aq_t rows[16] = I2R_AW_TABLE(aq_rows_k);
+    static const aq_t cols[16] = I2R_AW_TABLE(aq_cols_k);
+#undef I2R_AW_TABLE
+    const int hb = a->hp / 16 - 1;
+    const dim3 grid((unsigned)((a->n_tiles + 3) / 4));
+    if (a->mode == 0) {
+        i2r_launch(row_stats[hb], grid, dim3(256), 0, (hipStream_t)stream, k);
+        I2R_CHECK_LAUNCH("i2r_attn_query_maps (row statistics)");
+        i2r_launch(rows[hb], grid, dim3(256), 0, (hipStream_t)stream, k);
+        I2R_CHECK_LAUNCH("i2r_attn_query_maps (rows)");
+    } else {
+        i2r_launch(stats[hb], grid, dim3(256), 0, (hipStream_t)stream, k.a);
+        I2R_CHECK_LAUNCH("i2r_attn_query_maps (statistics)");
+        i2r_launch(cols[hb], dim3((unsigned)((a->n_col_tiles + 3) / 4)), dim3(256), 0, (hipStream_t)stream, k);
+        I2R_CHECK_LAUNCH("i2r_attn_query_maps (columns)");
+    }
+    if (a->scale > 1) {
+        const long long n4 = ((long long)a->K * max_len * a->scale * a->scale + 3) / 4;
+        I2R_CHECK_ARG((n4 + 255) / 256 < (1ll << 31), "i2r_attn_query_maps: up-sampling grid");
+        if (n4 > 0)
+            i2r_launch(aq_upsample_k, dim3((unsigned)((n4 + 255) / 256), (unsigned)a->n_grp), dim3(256), 0, (hipStream_t)stream, k);
+        I2R_CHECK_LAUNCH("i2r_attn_query_maps (up-sampling)");
+    }
     return I2R_OK;
 }

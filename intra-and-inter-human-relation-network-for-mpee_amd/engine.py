@@ -682,6 +682,7 @@ class Program:
         self.enc_stacks = []
         self.split_counters = []  # hand-off counters of the encoder stacks (zero between launches; re-zeroed when a run fails)
         self.captures = []   # encoder stacks whose attention maps this program computes (_capture_begin)
+        self.query = None    # (mode, {stack: scale}): the captured layers emit i2r_attn_query_maps instead of i2r_attn_weights (set_query_capture)
         self.store_dt = 0    # storage type the conv TOWER keeps its maps in (set by the engine in the 16-bit modes: 1 bf16, 2 f16)
         self.in_fork = False
         self.nbytes = 0
@@ -1283,8 +1284,15 @@ class Program:
 
     def _capture_layer(self, cap, i, qk, L, goff, lane):
         assert qk.dt == 0 and qk.cs >= 2 * L["hs"]
-        a = cabi.AttnWeightsArgs(qk.ptr, 0, goff.data_ptr(), cap["out_off"].data_ptr(), 0, 0, L["heads"], L["hp"], L["hs"], qk.cs, 0, 0)
         self.keep.append(L)
+        if self.query is not None:  # rows / columns at query points: tokens, counts, workspaces and outputs are patched per call
+            mode, scale = self.query[0], self.query[1][cap["stack"]]
+            a = cabi.AttnQueryArgs(qk=qk.ptr, grp_off=goff.data_ptr(), out_off=cap["out_off"].data_ptr(), heads=L["heads"], hp=L["hp"], k_off=L["hs"],
+                                   qk_cs=qk.cs, mode=mode, K=1, scale=scale, h=cap["x"].h, w=cap["x"].w)
+            self.ops.append((cabi.CAPTURE_OP_ATTN_QUERY, lane, a))
+            cap["ops"].append((i, a))
+            return
+        a = cabi.AttnWeightsArgs(qk.ptr, 0, goff.data_ptr(), cap["out_off"].data_ptr(), 0, 0, L["heads"], L["hp"], L["hs"], qk.cs, 0, 0)
         self.ops.append((cabi.CAPTURE_OP_ATTN_WEIGHTS, lane, a))
         cap["ops"].append((i, a))
 
@@ -1317,6 +1325,72 @@ class Program:
                 a.n_grp, a.n_tiles, a.ws_stride = len(lens), tiles, need_ws
                 maps[(cap["stack"], i)] = [buf[base + o:base + o + n * n].view(n, n) for o, n in zip(offs, lens)]
                 base += n_layer
+        return buf, maps, {cap["stack"]: cap["x"] for cap in self.captures}
+
+    def set_query_capture(self, glens, queries):
+        """The query form of set_capture (a program built with `query`): per capture the token table queries.tokens[stack] (int32
+        [groups, K], -1 = skip) and optionally queries.counts[stack] (entries used per group).  -> (buffer, {(stack, layer): per group a
+        [K_g, P_g, h r, w r] view}, {stack: input Act}), r the stack's scale; the buffer holds exactly sum over layers and groups of K_g L_g r^2 floats (+ at most
+        3 floats between layers whose size is no multiple of 4).  No [L, L] block exists: the workspaces are O(K L)."""
+        mode, scales = self.query
+        plan, n_ws, n_rows = [], 2, 1
+        for cap, lens in zip(self.captures, glens):
+            scale = scales[cap["stack"]]
+            cur = cap["grouping"]["current"]
+            assert len(lens) >= 1 and list(lens) == [cur[g + 1] - cur[g] for g in range(len(lens))]
+            tok = torch.as_tensor(queries.tokens[cap["stack"]]).to("cpu", torch.int32).contiguous()
+            if tok.dim() != 2 or tok.shape[0] != len(lens) or tok.shape[1] < 1:
+                raise ValueError("query tokens of %r: shape %s, expected [%d groups, K]" % (cap["stack"], tuple(tok.shape), len(lens)))
+            K = tok.shape[1]
+            cnt = getattr(queries, "counts", None)
+            cnt = [int(c) for c in cnt[cap["stack"]]] if cnt and cnt.get(cap["stack"]) is not None else [K] * len(lens)
+            if len(cnt) != len(lens) or not all(1 <= c <= K for c in cnt):
+                raise ValueError("query counts of %r: %s for %d groups of up to %d entries" % (cap["stack"], cnt, len(lens), K))
+            for g, (n, c) in enumerate(zip(lens, cnt)):
+                if int(tok[g, :c].max()) >= n:
+                    raise ValueError("query token %d of group %d of %r is outside its %d tokens" % (int(tok[g, :c].max()), g, cap["stack"], n))
+            hw = cap["x"].h * cap["x"].w
+            assert all(n % hw == 0 for n in lens)
+            heads = max(a.heads for _, a in cap["ops"]) if cap["ops"] else 1
+            stride = 2 * heads * -(-max(lens) // self.AW_KEYS)
+            n_ws = max(n_ws, stride * (len(lens) * K if mode == 0 else sum(lens)))
+            if scale > 1:
+                n_rows = max(n_rows, K * sum(lens))
+            offs = [0]
+            for n, c in zip(lens, cnt):
+                offs.append(offs[-1] + c * n * scale * scale)
+            plan.append((tok, cnt, K, stride, offs, scale))
+        per_layer = [-(-p[4][-1] // 4) * 4 for p in plan]  # (layer blocks start on 16-byte boundaries)
+        starts, base = [], 0
+        for n, cap in zip(per_layer, self.captures):
+            starts.append([base + j * n for j in range(len(cap["ops"]))])
+            base += n * len(cap["ops"])
+        total = max((st[-1] + p[4][-1] for st, p in zip(starts, plan) if st), default=1)
+        buf = torch.empty(total, dtype=torch.float32, device=self.device)
+        ws = torch.empty(n_ws, dtype=torch.float32, device=self.device)
+        rows = torch.empty(n_rows, dtype=torch.float32, device=self.device)
+        held = [ws, rows]  # (kept until the next call: the launches read them asynchronously; torch's allocator orders reuse by stream)
+        maps = {}
+        for cap, lens, (tok, cnt, K, stride, offs, scale), st in zip(self.captures, glens, plan, starts):
+            cap["out_off"][:len(lens)].copy_(torch.tensor(offs[:-1], dtype=torch.int64).pin_memory(), non_blocking=True)
+            d_tok = tok.pin_memory().to(self.device, non_blocking=True)
+            d_cnt = torch.tensor(cnt, dtype=torch.int32).pin_memory().to(self.device, non_blocking=True)
+            cur = cap["grouping"]["current"]
+            host_off = (C.c_int32 * (len(lens) + 1))(*cur[:len(lens) + 1])
+            held += [d_tok, d_cnt, host_off]
+            h, w = cap["x"].h, cap["x"].w
+            if mode == 0:
+                tiles, col_tiles = sum(-(-c // 16) * -(-n // self.AW_KEYS) for n, c in zip(lens, cnt)), 0
+            else:
+                tiles = sum(-(-n // 16) * -(-n // self.AW_KEYS) for n in lens)
+                col_tiles = sum(-(-n // 16) * -(-c // 16) for n, c in zip(lens, cnt))
+            for (i, a), b0 in zip(cap["ops"], st):
+                a.out, a.ws, a.rows = buf.data_ptr() + 4 * b0, ws.data_ptr(), rows.data_ptr()
+                a.q_tok, a.q_cnt, a.grp_off_host = d_tok.data_ptr(), d_cnt.data_ptr(), C.cast(host_off, C.c_void_p)
+                a.n_grp, a.n_tiles, a.n_col_tiles, a.ws_stride, a.K = len(lens), tiles, col_tiles, stride, K
+                maps[(cap["stack"], i)] = [buf[b0 + o:b0 + o + c * n * scale * scale].view(c, n // (h * w), h * scale, w * scale)
+                                           for o, n, c in zip(offs, lens, cnt)]
+        self._capture_ws = held
         return buf, maps, {cap["stack"]: cap["x"] for cap in self.captures}
 
     def set_groups(self, grouping, grp_off_host):
@@ -2059,6 +2133,23 @@ def lane_report(device):
             "profiler_attached": PROFILER_ATTACHED}
 
 
+class AttnQueries:
+    """The query form of an attention-map capture (Engine.forward(..., capture=, queries=)).
+    tokens: {stack: int32 [groups, K]} token indices inside each group of that stack (intra-human: the crop's y * w + x; inter-human: the
+            image's (person * h + y) * w + x), -1 = skip (an all-zero row); counts: optionally {stack: entries used per group};
+    mode: 0 / "dependency" (rows: what the query token attends to) or 1 / "affect" (columns: who attends to it);
+    upsample: integer bilinear scale of the returned maps (1 = raw), or {stack: scale} when the stacks differ (each stack's down_rate);
+    capacity: the K a program is keyed by (default: the widest table) -- calls that differ only in points or grouping share a program."""
+    MODES = {"dependency": 0, "affect": 1, 0: 0, 1: 1}
+
+    def __init__(self, tokens, mode="dependency", upsample=1, counts=None, capacity=None):
+        if mode not in self.MODES:
+            raise ValueError("mode %r: 'dependency' or 'affect'" % (mode,))
+        self.tokens, self.mode, self.counts = dict(tokens), self.MODES[mode], counts
+        self.upsample = {st: int(r) for st, r in upsample.items()} if isinstance(upsample, dict) else int(upsample)
+        self.capacity = int(capacity) if capacity is not None else max(int(torch.as_tensor(t).shape[-1]) for t in self.tokens.values())
+
+
 class Engine:
     """Packed model + program cache for one device. Built by models/_base.I2RModule."""
 
@@ -2177,6 +2268,26 @@ class Engine:
             out["global_encoder" if self.name == "interformer_pureMulti" else "multi_global_encoder"] = len(self.layers)
         return out
 
+    def capture_map_sizes(self, H, W):
+        """token map (h, w) of every capture stack for [H, W] network inputs: stack -> (h, w); a group of that stack is persons * h * w tokens"""
+        M, out = self.cfg["MODEL"], {}
+        fh = fw = None
+        if getattr(self, "single_layers", None):
+            r = 4 * 2 ** self.res_layer
+            fh, fw = H // r, W // r
+            out[self.single_stack] = (fh, fw)
+        elif self.singleformer:  # (HRFormer first stage: its highest-resolution branch)
+            fh, fw = H // 4, W // 4
+        if getattr(self, "layers", None):
+            if fh is None:  # the bare tower's lowest branch (_build)
+                down = 4 * 2 ** (M["EXTRA"]["STAGE3"]["NUM_BRANCHES"] - 1)
+                fh, fw = H // down, W // down
+            else:
+                for _ in range(int(math.log(fw // M["TRANS_SIZE"][-1], 2))):  # (3x3 stride-2 max-pool steps down to TRANS_SIZE)
+                    fh, fw = (fh + 1) // 2, (fw + 1) // 2
+            out["global_encoder" if self.name == "interformer_pureMulti" else "multi_global_encoder"] = (fh, fw)
+        return out
+
     def _capture_spec(self, capture, stack, layers, d=None):
         """the Program.encoder capture argument for one stack: {layer i: a pack with fp32 q|k projection weights} -- the layer's own pack
         on the general path, else an fp32 Packer.encoder_layer_mh pack of the fused layer, built on first use"""
@@ -2223,7 +2334,7 @@ class Engine:
             self.tower = HRFormerB(pk, p)
             self.single_head = pk.head(p + "keypoint_head.final_layer")
 
-    def _emit_single(self, P, S, H, W, n_src, capture=()):
+    def _emit_single(self, P, S, H, W, n_src, capture=()):  # (a query capture: P.query is set by the caller)
         """-> (first-stage feature Act [S, H/4, W/4, d], stem args): tower (+ reduce + per-crop encoder for TransPose-H, :649-655)"""
         if self.singleformer == "hrformer":
             xs, stem_args = self.tower.emit(P, S, H, W, n_src=n_src)
@@ -2337,16 +2448,18 @@ class Engine:
             b = c
         return b, pe_args
 
-    def _build(self, S, H, W, length, flip=False, part=None, capture=()):
+    def _build(self, S, H, W, length, flip=False, part=None, capture=(), query=None):
         """flip: the flip test of validate() (lib/core/function.py:142-162) batched into the same forward -- crops S..2S-1 are
         the mirrored copies (mirroring happens inside the stem kernels), every image appears twice as a token group.
         part (models whose first stage is the bare HRNet tower): "tower" = the per-crop tower + reduce only -> (P, patch, features Act);
         "tail" = everything behind it (position branch, inter-human encoder, deconvs, head) reading a feature buffer that tower
         programs fill (patch["feat"]) -- the two halves of a part-batch forward (_forward_split).
-        capture: frozenset of (stack, layer) whose attention maps the program computes too (Program.set_capture)."""
+        capture: frozenset of (stack, layer) whose attention maps the program computes too (Program.set_capture); query: (mode, scale) --
+        their rows / columns at query points instead (Program.set_query_capture)."""
         M = self.cfg["MODEL"]
         P = Program(self.device, multi_lane=self.multi_lane)
         P.store_dt = self.store_dt
+        P.query = query
         patch = {}
         n_src = S
         if flip:
@@ -2500,19 +2613,21 @@ class Engine:
             # (NHWC arena buffer -> the reference's NCHW tensor: a torch view + copy, boundary plumbing only)
             return f.t.view(S, f.h, f.w, f.cs)[..., :f.c].permute(0, 3, 1, 2).contiguous()
 
-    def forward_single(self, x, capture=None):
+    def forward_single(self, x, capture=None, queries=None):
         """Stand-alone first stage, as the reference's InterFormer calls it (interformer.py:288): transpose_h.TransPoseH.forward
         (:649-655) / hrformer.HRFormer.forward (:2477-2480): x [S,3,H,W] -> (features [S,d,H/4,W/4], heatmaps [S,J,H/4,W/4]).
-        capture: see forward(); then -> ((features, heatmaps), maps)."""
+        capture, queries: see forward(); then -> ((features, heatmaps), maps)."""
         assert self.name in ("transpose_h", "hrformer") and x.dim() == 4 and x.shape[1] == 3 and x.dtype == torch.float32
         S, _, H, W = x.shape
         x = x.to(self.device).contiguous()
         capture = self._check_capture(capture) if capture else frozenset()
-        key = (S, H, W, "single") + (("capture", capture) if capture else ())
+        query = self._check_queries(queries, capture)
+        key = (S, H, W, "single") + (("capture", capture) if capture else ()) + (query or ())
         with torch.cuda.device(self.device):
             def build():
                 P = Program(self.device)
                 P.store_dt = self.store_dt
+                P.query = (query[1], dict(query[3])) if query else None
                 g, px = self._emit_single(P, S, H, W, S, capture)
                 hd = P.head(g, self.single_head)
                 P.finalize()
@@ -2522,7 +2637,10 @@ class Engine:
             J = self.cfg["MODEL"]["NUM_JOINTS"]
             hm = torch.empty(S, J, g.h, g.w, dtype=torch.float32, device=self.device)
             hd.out = hm.data_ptr()
-            if capture:
+            if query:
+                self._check_map_sizes(P, H, W)
+                _, maps, inputs = P.set_query_capture([[g.h * g.w] * S], queries)
+            elif capture:
                 _, maps, inputs = P.set_capture([[g.h * g.w] * S])
             P.run(self.side_streams if P.uses_lanes else None)
             # (NHWC arena buffer -> the reference's NCHW feature tensor: a torch view + copy, boundary plumbing only)
@@ -2530,6 +2648,33 @@ class Engine:
             if capture:
                 return (feat, hm), self._capture_result(maps, inputs, S)
         return feat, hm
+
+    def _check_queries(self, queries, capture):
+        """queries (AttnQueries) -> the program-key suffix ("query", mode, K capacity, scale), or None without queries"""
+        if queries is None:
+            return None
+        if not capture:
+            raise ValueError("queries= needs capture=: the (stack, layer) set whose maps to query")
+        mode, stacks = int(queries.mode), sorted({st for st, _ in capture})
+        missing = set(stacks) - set(queries.tokens)
+        if missing:
+            raise ValueError("queries.tokens has no table for %s" % sorted(missing))
+        up = queries.upsample
+        try:
+            scales = tuple((st, int(up[st] if isinstance(up, dict) else up)) for st in stacks)
+        except KeyError as e:
+            raise ValueError("queries.upsample has no scale for stack %s" % e)
+        if mode not in (0, 1) or not all(1 <= r <= 64 for _, r in scales):
+            raise ValueError("queries: mode %r (0 dependency, 1 affect), upsample %r (1 .. 64)" % (queries.mode, up))
+        return ("query", mode, int(queries.capacity), scales)
+
+    def _check_map_sizes(self, P, H, W):
+        """the token maps attention_at mapped its points onto (capture_map_sizes) are the ones the program was built with"""
+        sizes = self.capture_map_sizes(H, W)
+        for cap in P.captures:
+            if sizes.get(cap["stack"]) != (cap["x"].h, cap["x"].w):
+                raise RuntimeError("capture_map_sizes(%d, %d)[%r] = %s, but the program's stack input is %d x %d"
+                                   % (H, W, cap["stack"], sizes.get(cap["stack"]), cap["x"].h, cap["x"].w))
 
     @staticmethod
     def _capture_result(maps, inputs, S):
@@ -2557,13 +2702,18 @@ class Engine:
     MAX_PROGRAMS = 48
     MAX_PROGRAM_BYTES = 32 << 30
 
-    def forward(self, x, pos_mask, length, flip_joint_map=None, capture=None):
+    def forward(self, x, pos_mask, length, flip_joint_map=None, capture=None, queries=None):
         """flip_joint_map (device int32 [J], see caller.joint_map): run the flip test in the same forward and return the merged
         'multi' heatmaps (the reference merges only outputs['multi'], function.py:137-162).
         capture: a set of (stack, layer) -- stack a state-dict prefix of capture_stacks() -- whose attention maps to return as well:
         -> (output, maps), maps[(stack, layer)] = per batch entry of that stack (image: inter-human, crop: intra-human) the [L, L] fp32
         head-averaged softmax(q k^T) (views into one buffer per call), maps[(stack, "input")] = the stack's input features [S, c, h, w].
-        A capture forward is one program (no part-batches), built once per capture set; the default programs are not touched."""
+        A capture forward is one program (no part-batches), built once per capture set; the default programs are not touched.
+        queries (AttnQueries, with capture): instead of the [L, L] maps, their rows (mode 0) or columns (mode 1) at the token indices
+        queries.tokens[stack] (int32 [groups, K], -1 = skip), optionally up-sampled bilinearly by queries.upsample (an int, or one per
+        stack): maps[(stack, layer)] = per group a [K_g, persons, h r, w r] view.  One program per (capture set, mode, K capacity, scales) --
+        K is in the key although every K-dependent field is patched per call: a caller asks with one K; new points or another grouping
+        at the same capacity reuse it."""
         M = self.cfg["MODEL"]
         assert x.dim() == 4 and x.shape[1] == 3 and x.dtype == torch.float32
         S, _, H, W = x.shape
@@ -2573,8 +2723,11 @@ class Engine:
         if capture:
             capture = self._check_capture(capture)
             assert flip_joint_map is None and not self.window_attn, "attention maps: no flip test, no window-type block"
+            query = self._check_queries(queries, capture)
             with torch.cuda.device(self.device):
-                return self._forward_part(x, pos_mask, list(length), None, S, H, W, capture=capture)
+                return self._forward_part(x, pos_mask, list(length), None, S, H, W, capture=capture, queries=queries, query=query)
+        if queries is not None:
+            self._check_queries(queries, capture)
         if self.window_attn and flip_joint_map is not None:
             # the window type mixes the rows of ALL images of a call (attention.py:1025-1029): the mirrored batch must be a call of its
             # own, as in validate() (function.py:142-162), not extra token groups of this one
@@ -2762,7 +2915,7 @@ class Engine:
             return merged
         return out[:S]
 
-    def _forward_part(self, x, pos_mask, length, flip_joint_map, S, H, W, slot=0, capture=frozenset()):
+    def _forward_part(self, x, pos_mask, length, flip_joint_map, S, H, W, slot=0, capture=frozenset(), queries=None, query=None):
         M = self.cfg["MODEL"]
         x = x.to(self.device).contiguous()
         flip = flip_joint_map is not None
@@ -2773,8 +2926,9 @@ class Engine:
         if self.window_attn:  # the padded person layout IS the program: no capacity slots, one program per `length`
             cap, key = S, (S, H, W, flip, "window", tuple(length))
         if capture:
-            key = key + ("capture", capture)
-        P, patch = self._program(key, lambda: self._build(cap, H, W, list(length) + [1] * (cap - S), flip, capture=capture))
+            key = key + ("capture", capture) + (query or ())
+        P, patch = self._program(key, lambda: self._build(cap, H, W, list(length) + [1] * (cap - S), flip, capture=capture,
+                                                           query=(query[1], dict(query[3])) if query else None))
         self.last_concurrent = []
         self.last_programs = [P]  # the program(s) of the most recent forward (bench.py's per-launch timing pass replays them; _forward merges the parts')
         glen = list(length) + [1] * (cap - S)
@@ -2811,7 +2965,9 @@ class Engine:
             for c in P.captures:
                 tok = c["x"].h * c["x"].w
                 glens.append([tok] * S if c["stack"] == getattr(self, "single_stack", None) else [n * tok for n in length])
-            _, maps, inputs = P.set_capture(glens)
+            if query:
+                self._check_map_sizes(P, H, W)
+            _, maps, inputs = P.set_query_capture(glens, queries) if query else P.set_capture(glens)
         P.run(self.side_streams if P.uses_lanes else None)
         if flip:
             merged = torch.empty(S, J, H // 4, W // 4, dtype=torch.float32, device=self.device)

@@ -33,6 +33,37 @@ def unpad_attention_maps(weights, lens):
     return [weights[b, :n, :n] for b, n in enumerate(lens)]
 
 
+def points_to_tokens(points, in_h, in_w, fh, fw):
+    """points [S, K, 2] as (x, y) in the frame of each crop's [in_h, in_w] network input -> int32 [S, K] token indices row * fw + col of the
+    [fh, fw] token map: (row, col) = (int(y / down_rate), int(x / down_rate)), down_rate = in_h // fh (the reference's visualize.py:194-196).
+    A NaN point means "skip" (-1); a point outside the crop raises ValueError."""
+    pts = torch.as_tensor(points, dtype=torch.float64).cpu()
+    if pts.dim() != 3 or pts.shape[-1] != 2:
+        raise ValueError("points: shape %s, expected [crops, K, 2] holding (x, y)" % (tuple(pts.shape),))
+    down = in_h // fh
+    skip = torch.isnan(pts).any(-1)
+    x, y = pts[..., 0].masked_fill(skip, 0.0), pts[..., 1].masked_fill(skip, 0.0)
+    if bool(((x < 0) | (x >= in_w) | (y < 0) | (y >= in_h)).any()):
+        raise ValueError("points: a point lies outside its %d x %d (w x h) crop" % (in_w, in_h))
+    row, col = (y / down).long().clamp_(max=fh - 1), (x / down).long().clamp_(max=fw - 1)
+    return (row * fw + col).masked_fill(skip, -1).to(torch.int32)
+
+
+def group_tokens(tok, length, hw):
+    """per-crop tokens [S, K] -> the inter-human table: per image the points of all its persons as queries, token (person, y, x) =
+    person * hw + token, entry person * K + k; -> (int32 [images, max(length) * K] padded with -1, entries used per image)"""
+    S, K = tok.shape
+    assert S == sum(length)
+    out = torch.full((len(length), max(length) * K), -1, dtype=torch.int32)
+    s = 0
+    for b, n in enumerate(length):
+        t = tok[s:s + n].to(torch.int64)
+        shift = torch.arange(n).view(n, 1) * hw
+        out[b, :n * K] = torch.where(t >= 0, t + shift, t).reshape(-1).to(torch.int32)
+        s += n
+    return out, [n * K for n in length]
+
+
 def _call_forward_hooks(module, output):
     """the module's forward hooks, called as a forward of it would (inputs: none -- the fused forward has no per-module call)"""
     for hid, hook in list(module._forward_hooks.items()):
@@ -199,6 +230,68 @@ class I2RModule(nn.Module):
                 _call_forward_hooks(m, maps[(st, "input")])
         for st, i, m in hooked:
             _call_forward_hooks(m, (None, pad_attention_maps(maps[(st, i)])))
+
+    def _query_plan(self, eng, x, points, mode, layers, upsample, length=None):
+        """-> (capture set, AttnQueries) for attention_at"""
+        from ..engine import AttnQueries
+        stacks = eng.capture_stacks()
+        capture = {(st, i) for st, n in stacks.items() for i in range(n)} if layers is None else {(str(st), int(i)) for st, i in layers}
+        H, W = x.shape[2], x.shape[3]
+        sizes = eng.capture_map_sizes(H, W)
+        pts = torch.as_tensor(points)
+        if pts.dim() != 3 or pts.shape[0] != x.shape[0]:
+            raise ValueError("points: shape %s, expected [%d crops, K, 2]" % (tuple(pts.shape), x.shape[0]))
+        K = pts.shape[1]
+        tokens, counts, scales = {}, {}, {}
+        for st in sorted({st for st, _ in capture}):
+            if st not in sizes:
+                raise ValueError("attention_at: this model's encoder stacks are %s" % sorted(sizes))
+            fh, fw = sizes[st]
+            tok = points_to_tokens(pts, H, W, fh, fw)
+            r = H // fh if upsample is True else max(int(upsample), 1)
+            scales[st] = r
+            if length is None or st.startswith("singleformer."):
+                tokens[st], counts[st] = tok, None
+            else:
+                tokens[st], counts[st] = group_tokens(tok, length, fh * fw)
+        return capture, AttnQueries(tokens, mode, scales, counts, capacity=K)
+
+    @staticmethod
+    def _query_result(maps, intra):
+        """engine views -> per (stack, layer): [S, K, 1, h r, w r] for an intra-human stack (the per-crop blocks are consecutive in the
+        capture buffer: a view), the per-image list [P K, P, h r, w r] for an inter-human one"""
+        out = {}
+        for key, views in maps.items():
+            if key[1] == "input":
+                continue
+            if intra(key[0]):
+                v = views[0]
+                out[key] = v.as_strided((len(views),) + tuple(v.shape), (v.numel(),) + tuple(v.stride()), v.storage_offset())
+            else:
+                out[key] = views
+        return out
+
+    def attention_at(self, x, pos_mask, length, points, mode="dependency", layers=None, upsample=True):
+        """The attention maps at query points, computed on the device without ever building an [L, L] map (the reference's
+        visualize.py:186-233 / :333-388 reads exactly this of its hooks' output).
+        points: [S, K, 2] holding (x, y) in the frame of each crop's network input (what visualize.py builds from preds); NaN = skip (a
+          zero map), outside the crop: ValueError.  Token = (int(y / down_rate), int(x / down_rate)), down_rate = input height // feature
+          height -- visualize.py:194-196; its :343 divides the width by the feature HEIGHT under a "TO CHECK" comment, which is not followed.
+        mode: "dependency" (row: where the query point looks) or "affect" (column: which positions look at it).
+        layers: set of (stack, layer), default every layer of every encoder stack.  upsample: True = by each stack's own down_rate (every
+          stack comes back at input resolution: 4 for the intra-human and 16 for the inter-human stack of a 256 x 192 model), an int = that
+          scale for every stack, False / 1 = the raw token maps.
+        -> (model output, {(stack, layer): maps}): intra-human stack (the group is the crop) [S, K, 1, h r, w r]; inter-human stack (the
+          group is the image, all its persons' points are queries, entry person * K + k) a list with one [P_img K, P_img, h r, w r] per image.
+        Forward hooks keep working as before; this call serves none."""
+        if torch.is_tensor(length):
+            length = length.tolist()
+        length = [int(n) for n in length]
+        eng = self.engine()
+        capture, queries = self._query_plan(eng, x, points, mode, layers, upsample, length)
+        with torch.no_grad():
+            out, maps = eng.forward(x, pos_mask, length, capture=capture, queries=queries)
+        return out, self._query_result(maps, lambda st: st.startswith("singleformer."))
 
     def forward(self, x, pos_mask, length):
         """model(input, pos_mask, length) -- reference lib/core/function.py:135.  With forward hooks on <stack>.layers[i].self_attn the

@@ -30,6 +30,14 @@ class TransPoseH(I2RModule):
             self._serve_hooks(hooked, maps)
             return out
 
+    def attention_at(self, x, points, mode="dependency", layers=None, upsample=True):
+        """I2RModule.attention_at for the stand-alone stage: -> ((features, heatmaps), {("global_encoder", layer): [S, K, 1, h r, w r]})"""
+        eng = self.engine()
+        capture, queries = self._query_plan(eng, x, points, mode, layers, upsample)
+        with torch.no_grad():
+            out, maps = eng.forward_single(x, capture=capture, queries=queries)
+        return out, self._query_result(maps, lambda st: True)
+
 
 def get_pose_net(cfg, is_train, pretrained_path="", is_end2end=False, **kwargs):
     if is_train:
