@@ -168,15 +168,24 @@ I2R_API int i2r_conv_kernel_name(const i2r_conv_desc* const* descs, int32_t n, c
 /* ---- after the forward: flip-test merge and keypoint decode -------------------------------- */
 /* i2r_flip_merge -- out = (y + flip_back(y_flipped)) * 0.5  with flip_back = reverse W + swap left/right joints
  * (lib/core/function.py:142-162, lib/utils/transforms.py:16-30). joint_map: device int32[joints], the joint whose mirrored
- * heatmap lands in channel j (identity for unpaired joints). NCHW fp32 [n, joints, h, w]. */
+ * heatmap lands in channel j (identity for unpaired joints). NCHW fp32 [n, joints, h, w].  Every element reads only its own y, so
+ * out may be y itself (not y_flipped).  n == 0 returns I2R_OK without a launch and writes nothing.  n < 0, joints < 1, h < 1, w < 1,
+ * more than 2^31 - 1 workgroups of 256 elements: I2R_E_ARG. */
 I2R_API int i2r_flip_merge(const float* y, const float* y_flipped, const int32_t* joint_map, float* out, int32_t n, int32_t joints,
                    int32_t h, int32_t w, void* stream);
 
 /* i2r_decode -- get_final_preds (lib/core/inference.py:90-112): arg-max (:20-48), Gaussian blur with kernel TEST.BLUR_KERNEL
- * on a zero-bordered copy re-normalised to the original max (:73-87; cv2.GaussianBlur(sigma=0) => sigma =
- * 0.3*((k-1)*0.5-1)+0.8), log(max(.,1e-10)), second-order Taylor refinement (:51-70), inverse crop affine with rot 0
- * (lib/utils/transforms.py:50-101: scale about the centres by (scale[0]*200-1)/(w-1)).
- * heatmaps [n, joints, h, w]; center, scale [n, 2] (unused when transform_back == 0); preds [n, joints, 2]; maxvals [n, joints]. */
+ * on a zero-bordered copy re-normalised to the original max (:73-87), log(max(.,1e-10)), second-order Taylor refinement (:51-70),
+ * inverse crop affine with rot 0 (lib/utils/transforms.py:50-101: scale about the centres by (scale[0]*200-1)/(w-1)).
+ * The blur filters with the coefficients of cv2.GaussianBlur(dr, (k, k), 0), i.e. of getGaussianKernel(k, sigma <= 0): for k = 1, 3,
+ * 5, 7 OpenCV's fixed table (small_gaussian_tab, modules/imgproc/src/smooth.dispatch.cpp: {1}, {.25, .5, .25}, {.0625, .25, .375,
+ * .25, .0625}, {.03125, .109375, .21875, .28125, .21875, .109375, .03125}), from k = 9 on the Gaussian with sigma =
+ * 0.3*((k-1)*0.5-1)+0.8 normalised to sum 1.  Both are restated from the OpenCV source; parity with cv2 rests on that source and has
+ * not been run against cv2.  blur_kernel: odd, 1..31.  blur_kernel == 1 cannot run in the reference at all (its dr[0:-0] is empty);
+ * here it is accepted and defined as "no blur".
+ * heatmaps [n, joints, h, w]; center, scale [n, 2] (unused when transform_back == 0); preds [n, joints, 2]; maxvals [n, joints].
+ * One workgroup per map with 2*h*w floats of LDS: h*w <= 19200 (150 KB; 160 x 120).  n == 0 returns I2R_OK without a launch and
+ * writes nothing.  n < 0, joints < 1, h < 1, w < 2, n*joints beyond 2^31 - 1, a map above the LDS limit: I2R_E_ARG. */
 I2R_API int i2r_decode(const float* heatmaps, const float* center, const float* scale, float* preds, float* maxvals, int32_t n,
                int32_t joints, int32_t h, int32_t w, int32_t blur_kernel, int32_t transform_back, void* stream);
 

@@ -28,6 +28,15 @@ __device__ __forceinline__ ArgMax amax2(ArgMax a, ArgMax b) {  // np.argmax: fir
     return (b.v > a.v || (b.v == a.v && b.i < a.i)) ? b : a;
 }
 
+// cv2.getGaussianKernel(ksize, sigma <= 0) does not evaluate the Gaussian for odd ksize <= 7: it returns a fixed table
+// (small_gaussian_tab, OpenCV modules/imgproc/src/smooth.dispatch.cpp); only from ksize 9 on does it use sigma = 0.3*((ksize-1)*0.5-1)+0.8.
+// Row (ksize-1)/2, indexed by the distance from the centre tap.  ksize 1 is the identity: "no blur" (the reference itself cannot run it,
+// its dr[0:-0] is empty).  Taken from the OpenCV source; not compared against a cv2 run.
+__device__ const float kSmallGaussian[4][4] = {{1.f, 0.f, 0.f, 0.f},
+                                               {0.5f, 0.25f, 0.f, 0.f},
+                                               {0.375f, 0.25f, 0.0625f, 0.f},
+                                               {0.28125f, 0.21875f, 0.109375f, 0.03125f}};
+
 // one workgroup per (crop, joint). LDS: A[h*w] (heatmap, later the blurred map), B[h*w] (row-filtered)
 __global__ __launch_bounds__(256) void decode_k(const float* __restrict__ hm, const float* __restrict__ center,
                                                 const float* __restrict__ scale, float* __restrict__ preds, float* __restrict__ maxvals,
@@ -43,11 +52,16 @@ __global__ __launch_bounds__(256) void decode_k(const float* __restrict__ hm, co
     const int hw = h * w;
     const float* src = hm + (size_t)sj * hw;
     const int border = (ksize - 1) / 2;
-    if (tid < ksize) {  // cv2.getGaussianKernel(ksize, sigma<=0): sigma = 0.3*((ksize-1)*0.5 - 1) + 0.8, normalised to sum 1
-        const double sigma = 0.3 * ((ksize - 1) * 0.5 - 1.0) + 0.8;
-        double sum = 0.0;
-        for (int k = 0; k < ksize; ++k) sum += exp(-0.5 * (k - border) * (k - border) / (sigma * sigma));
-        gk[tid] = (float)(exp(-0.5 * (tid - border) * (tid - border) / (sigma * sigma)) / sum);
+    if (tid < ksize) {  // cv2.getGaussianKernel(ksize, sigma <= 0), see kSmallGaussian
+        if (ksize <= 7) {
+            const int d = tid < border ? border - tid : tid - border;
+            gk[tid] = kSmallGaussian[border][d];
+        } else {  // sigma = 0.3*((ksize-1)*0.5 - 1) + 0.8, normalised to sum 1
+            const double sigma = 0.3 * ((ksize - 1) * 0.5 - 1.0) + 0.8;
+            double sum = 0.0;
+            for (int k = 0; k < ksize; ++k) sum += exp(-0.5 * (k - border) * (k - border) / (sigma * sigma));
+            gk[tid] = (float)(exp(-0.5 * (tid - border) * (tid - border) / (sigma * sigma)) / sum);
+        }
     }
     ArgMax am = {-__builtin_inff(), 0x7fffffff};
     for (int i = tid; i < hw; i += 256) {
@@ -122,7 +136,10 @@ __global__ __launch_bounds__(256) void decode_k(const float* __restrict__ hm, co
 extern "C" int i2r_flip_merge(const float* y, const float* y_flipped, const int32_t* joint_map, float* out, int32_t n, int32_t joints,
                               int32_t h, int32_t w, void* stream) {
     I2R_CHECK_ARG(y && y_flipped && joint_map && out, "i2r_flip_merge: null pointer");
+    I2R_CHECK_ARG(n >= 0 && joints >= 1 && h >= 1 && w >= 1, "i2r_flip_merge: n %d joints %d heatmap %dx%d", n, joints, h, w);
+    if (n == 0) return I2R_OK;
     const long long tot = (long long)n * joints * h * w;
+    I2R_CHECK_ARG((tot + 255) / 256 <= 0x7fffffffLL, "i2r_flip_merge: %lld elements exceed the grid limit", tot);
     i2r_launch(flip_merge_k, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, y, y_flipped, joint_map,
                        out, n, joints, h, w);
     I2R_CHECK_LAUNCH("i2r_flip_merge");
@@ -133,8 +150,11 @@ extern "C" int i2r_decode(const float* heatmaps, const float* center, const floa
                           int32_t joints, int32_t h, int32_t w, int32_t blur_kernel, int32_t transform_back, void* stream) {
     I2R_CHECK_ARG(heatmaps && preds && maxvals && (!transform_back || (center && scale)), "i2r_decode: null pointer");
     I2R_CHECK_ARG(blur_kernel >= 1 && blur_kernel <= 31 && (blur_kernel & 1), "i2r_decode: blur kernel %d", blur_kernel);
+    I2R_CHECK_ARG(n >= 0 && joints >= 1 && h >= 1 && w > 1, "i2r_decode: n %d joints %d heatmap %dx%d", n, joints, h, w);
+    I2R_CHECK_ARG((long long)n * joints <= 0x7fffffffLL, "i2r_decode: %lld maps exceed the grid limit", (long long)n * joints);
+    I2R_CHECK_ARG((long long)h * w <= 150 * 1024 / 8, "i2r_decode: heatmap %dx%d too large", h, w);
+    if (n == 0) return I2R_OK;
     const size_t lds = (size_t)2 * h * w * sizeof(float);
-    I2R_CHECK_ARG(lds <= 150 * 1024 && w > 1, "i2r_decode: heatmap %dx%d too large", h, w);
     if (lds > 64 * 1024)
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(decode_k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     i2r_launch(decode_k, dim3((unsigned)(n * joints)), dim3(256), lds, (hipStream_t)stream, heatmaps, center, scale, preds,

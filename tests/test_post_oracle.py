@@ -1,9 +1,14 @@
 """CPU: the post-forward oracle (oracle/post_cpu.py) against stored outputs of the reference's own numpy functions (get_max_preds,
-taylor, flip_back: tests/golden/post_reference.npz); cv2 is absent, so GaussianBlur is checked against an independent scipy filter."""
+taylor, flip_back: tests/golden/post_reference.npz); cv2 is absent, so GaussianBlur is checked against an independent scipy filter and
+its coefficients against the table and formula of the OpenCV source.  And the decode case table (tests/_post_cases.py) against the two
+conditions that make the GPU comparison of tests/test_post_gpu.py meaningful: it tells the oracle from subtly wrong oracles by far
+more than the GPU tolerance, and none of its refined maps is ill-conditioned."""
 import os
 
 import numpy as np
+import pytest
 
+import _post_cases as pc
 import post_cpu
 from i2r_amd import caller, synth
 
@@ -34,18 +39,41 @@ def test_argmax_taylor_flip_back_match_reference_functions():
     assert np.array_equal(g["flip_back"], post_cpu.flip_back(hm.copy(), pairs))
 
 
+def test_gaussian_kernel_is_opencv_table_up_to_7_and_formula_from_9():
+    """getGaussianKernel(k, sigma <= 0): small_gaussian_tab for k = 1, 3, 5, 7 (OpenCV modules/imgproc/src/smooth.dispatch.cpp, copied
+    from the source, not from a cv2 run), the normalised Gaussian with sigma = 0.3*((k-1)*0.5-1)+0.8 from 9 on"""
+    tab = {1: [1.0], 3: [0.25, 0.5, 0.25], 5: [0.0625, 0.25, 0.375, 0.25, 0.0625],
+           7: [0.03125, 0.109375, 0.21875, 0.28125, 0.21875, 0.109375, 0.03125]}
+    for k, row in tab.items():
+        got = post_cpu.gaussian_kernel(k)
+        assert got.dtype == np.float64 and got.tolist() == row
+    assert post_cpu.gaussian_kernel(7)[3] == 0.28125
+    for k in (9, 11, 17, 31):
+        sigma = 0.3 * ((k - 1) * 0.5 - 1) + 0.8
+        e = np.array([np.exp(-((i - (k - 1) // 2) ** 2) / (2 * sigma * sigma)) for i in range(k)])
+        assert np.allclose(post_cpu.gaussian_kernel(k), e / e.sum(), rtol=1e-15, atol=0)
+    for k in (1, 3, 5, 7, 9, 11, 17, 31):
+        g = post_cpu.gaussian_kernel(k)
+        assert g.shape == (k,) and abs(g.sum() - 1) < 1e-12 and np.array_equal(g, g[::-1])
+    f3 = post_cpu.gaussian_kernel_formula(3)  # what the decode used before: not the table
+    assert abs(f3[1] - 0.522) < 1e-3 and abs(f3[0] - 0.239) < 1e-3
+
+
 def test_blur_matches_independent_separable_filter():
     from scipy import ndimage
     hm = _hm(2, 2, 20, 16)
     k = post_cpu.gaussian_kernel(11)
     assert abs(k.sum() - 1) < 1e-12 and abs(k[5] / k[4] - np.exp(0.5 / 4.0)) < 1e-12  # sigma = 2.0 for ksize 11
-    got = post_cpu.gaussian_blur(hm, 11)
-    for s in range(2):
-        for j in range(2):
-            ref = ndimage.correlate1d(ndimage.correlate1d(hm[s, j].astype(np.float64), k, axis=1, mode="constant"), k, axis=0,
-                                      mode="constant")
-            ref = (ref.astype(np.float32) * (hm[s, j].max() / ref.astype(np.float32).max()))
-            assert np.allclose(got[s, j], ref, rtol=1e-5, atol=1e-7)
+    for ksize in (11, 3, 17):
+        k = post_cpu.gaussian_kernel(ksize)
+        got = post_cpu.gaussian_blur(hm, ksize)
+        for s in range(2):
+            for j in range(2):
+                ref = ndimage.correlate1d(ndimage.correlate1d(hm[s, j].astype(np.float64), k, axis=1, mode="constant"), k, axis=0,
+                                          mode="constant")
+                ref = (ref.astype(np.float32) * (hm[s, j].max() / ref.astype(np.float32).max()))
+                assert np.allclose(got[s, j], ref, rtol=1e-5, atol=1e-7)
+    assert np.array_equal(post_cpu.gaussian_blur(hm, 1), hm)  # one tap: no blur
 
 
 def test_transform_preds_closed_form():
@@ -55,3 +83,154 @@ def test_transform_preds_closed_form():
     assert np.allclose(out[0], [100 + (10 - 23.5) * r, 200 + (20 - 31.5) * r])
     jm = caller.joint_map(caller.FLIP_PAIRS["crowdpose"], 14).tolist()
     assert jm[:4] == [1, 0, 3, 2] and jm[12:] == [12, 13]
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the decode case table (tests/_post_cases.py)
+# ------------------------------------------------------------------------------------------------------------------------------
+def _terms_with(gx_lo=1, gy_lo=1, gx_hi=2, gy_hi=2, dxy_sign=1.0):
+    """taylor_terms with another guard (a guard that is too wide reads whatever lies there: the indices wrap) or a negated dxy"""
+    def terms(hm, coord):
+        h, w = hm.shape
+        px, py = int(coord[0]), int(coord[1])
+        if not (gx_lo < px < w - gx_hi and gy_lo < py < h - gy_hi):
+            return None
+        v = lambda y, x: float(hm[y % h][x % w])
+        dx = 0.5 * (v(py, px + 1) - v(py, px - 1))
+        dy = 0.5 * (v(py + 1, px) - v(py - 1, px))
+        dxx = 0.25 * (v(py, px + 2) - 2 * v(py, px) + v(py, px - 2))
+        dxy = 0.25 * (v(py + 1, px + 1) - v(py - 1, px + 1) - v(py + 1, px - 1) + v(py - 1, px - 1))
+        dyy = 0.25 * (v(py + 2, px) - 2 * v(py, px) + v(py - 2, px))
+        return dx, dy, dxx, dxy_sign * dxy, dyy
+    return terms
+
+
+def _argmax_last(hm):
+    S, J, h, w = hm.shape
+    flat = hm.reshape(S, J, -1)
+    idx = (h * w - 1 - np.argmax(flat[:, :, ::-1], 2)).reshape(S, J, 1)
+    maxvals = np.amax(flat, 2).reshape(S, J, 1)
+    preds = np.tile(idx, (1, 1, 2)).astype(np.float32)
+    preds[:, :, 0] = preds[:, :, 0] % w
+    preds[:, :, 1] = np.floor(preds[:, :, 1] / w)
+    preds *= np.tile(np.greater(maxvals, 0.0), (1, 1, 2)).astype(np.float32)
+    return preds, maxvals
+
+
+def _log_unclamped(hm):
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.log(hm)
+
+
+_transform_preds = post_cpu.transform_preds
+
+
+def _transform_with_scale_y(coords, center, scale, w, h):
+    out = _transform_preds(coords, center, scale, w, h)
+    out[:, 1] = center[1] + (coords[:, 1] - (h - 1) * 0.5) * (scale[1] * 200.0 - 1.0) / (w - 1.0)
+    return out
+
+
+# name -> (attribute of post_cpu, replacement, cases it can show in (None: all), transform_back)
+MUTANTS = {
+    "formula kernel k=3": ("gaussian_kernel", post_cpu.gaussian_kernel_formula, lambda c: c.ksize == 3, False),
+    "formula kernel k=5": ("gaussian_kernel", post_cpu.gaussian_kernel_formula, lambda c: c.ksize == 5, False),
+    "formula kernel k=7": ("gaussian_kernel", post_cpu.gaussian_kernel_formula, lambda c: c.ksize == 7, False),
+    "dxy negated": ("taylor_terms", _terms_with(dxy_sign=-1.0), None, False),
+    "inverse Hessian off-diagonal sign": ("hessian_inverse", lambda dxx, dxy, dyy, det: np.array([[dyy, dxy], [dxy, dxx]]) / det, None, False),
+    "guard 0 < px": ("taylor_terms", _terms_with(gx_lo=0), None, False),
+    "guard 2 < px": ("taylor_terms", _terms_with(gx_lo=2), None, False),
+    "guard 0 < py": ("taylor_terms", _terms_with(gy_lo=0), None, False),
+    "guard 2 < py": ("taylor_terms", _terms_with(gy_lo=2), None, False),
+    "guard px < w-1": ("taylor_terms", _terms_with(gx_hi=1), None, False),
+    "guard px < w-3": ("taylor_terms", _terms_with(gx_hi=3), None, False),
+    "guard py < h-1": ("taylor_terms", _terms_with(gy_hi=1), None, False),
+    "guard py < h-3": ("taylor_terms", _terms_with(gy_hi=3), None, False),
+    "arg-max takes the last occurrence": ("get_max_preds", _argmax_last, None, False),
+    "1e-10 clamp removed": ("clamped_log", _log_unclamped, None, False),
+    "y transformed back with scale_y": ("transform_preds", _transform_with_scale_y, None, True),
+}
+
+
+@pytest.mark.parametrize("mutant", sorted(MUTANTS))
+def test_case_table_tells_the_oracle_from_a_wrong_one(mutant, monkeypatch):
+    """A condition on the table, not a measurement: each subtly wrong decode must move some coordinate of some case by more than ten
+    times the tolerance the GPU test allows (a coordinate that turns NaN has moved)."""
+    attr, repl, applies, tb = MUTANTS[mutant]
+    cases = [c for c in pc.CASES if applies is None or applies(c)]
+    refs = {c.name: pc.expected(c.name, tb)[0] for c in cases}   # (before the oracle is patched)
+    monkeypatch.setattr(post_cpu, attr, repl)
+    moved = {}
+    for c in cases:
+        with np.errstate(all="ignore"):
+            p, _ = post_cpu.get_final_preds(c.hm, c.center, c.scale, c.ksize, transform_back=tb)
+        d = np.abs(p.astype(np.float64) - refs[c.name])
+        far = ~(d <= 10 * pc.TOL * (c.ratio() if tb else 1.0))
+        if far.any():
+            moved[c.name] = float(np.nanmax(d)) if np.isfinite(d).any() else float("nan")
+    print("%s: moves %s" % (mutant, moved))
+    assert moved, "no case of the table notices: %s" % mutant
+    if mutant == "1e-10 clamp removed":  # (and not only by turning NaN)
+        p, _ = post_cpu.get_final_preds(pc.BY_NAME["degenerate-20x15-k11"].hm, None, None, 11, transform_back=False)
+        d = np.abs(p - pc.expected("degenerate-20x15-k11", False)[0])[1, 0]   # the 1e-12 bump
+        assert np.isfinite(d).all() and d.max() > 10 * pc.TOL
+
+
+def test_case_table_is_well_conditioned():
+    """A cap, not a measurement: every map that takes the Taylor branch has |det| / (|dxx dyy| + dxy^2) >= 1e-3 in the float64 oracle --
+    except the degenerate maps built to have det == 0 -- so that no map has to be left out of a GPU comparison.  The skewed family
+    really has a cross term: up to blur size 11, on a fifth of its maps and more |dxy| is above 0.25 sqrt(dxx dyy)."""
+    for c in pc.CASES:
+        refined, cond, cross = pc.terms(c.name)
+        p, _ = pc.expected(c.name, False)
+        assert np.isfinite(p).all(), c.name
+        if c.family == "degenerate":
+            zero_det = [pc.DEGENERATE.index(n) for n in ("1e-12 pixel", "1e-12 bump")]
+            r, cd = refined.reshape(-1), cond.reshape(-1)
+            assert all(r[i] and cd[i] == 0.0 for i in zero_det), c.name
+            rest = [i for i in range(r.size) if r[i] and i not in zero_det and not (c.ksize == 11 and pc.DEGENERATE[i] == "ringed")]
+            assert all(cd[i] >= pc.COND_MIN for i in rest), (c.name, cd)
+        else:
+            assert (cond[refined] >= pc.COND_MIN).all(), "%s: min %.3g" % (c.name, np.nanmin(cond))
+        if c.family in ("skewed", "shapes"):
+            assert refined.all(), c.name
+        if c.family == "skewed" and c.ksize <= 11:
+            assert (cross > 0.25).sum() >= refined.size // 5, (c.name, cross)
+        m = pc.integer_mask(c.name)
+        assert np.array_equal(p[m], np.floor(p[m])), c.name   # what the GPU test asks bit for bit is an integer position
+
+
+def test_case_table_covers_what_it_claims():
+    """guards: every position next to the guard is the arg-max of its map; ties: the equal maxima sit where the reductions of decode_k
+    could get their order wrong; shapes and blur sizes of the issue are present"""
+    for name in ("guards-12x9-k3", "guards-64x48-k11"):
+        c = pc.BY_NAME[name]
+        h, w = c.hm.shape[2:]
+        coords, _ = post_cpu.get_max_preds(c.hm)
+        assert coords.reshape(-1, 2).astype(int).tolist() == [list(p) for p in pc.guard_positions(h, w)]
+        refined = pc.terms(name)[0].reshape(-1)
+        want = [1 < x < w - 2 and 1 < y < h - 2 for x, y in pc.guard_positions(h, w)]
+        assert refined.tolist() == want and sum(want) == 6
+    for name, ties, w in (("ties-64x48-k11", pc.TIES_64x48, 48), ("ties-96x72-k11", pc.TIES_96x72, 72)):
+        c = pc.BY_NAME[name]
+        flat = c.hm.reshape(len(ties), -1)
+        for m, idx in enumerate(ties):
+            assert sorted(np.flatnonzero(flat[m] == flat[m].max()).tolist()) == list(idx)   # exactly these, exactly equal
+        coords, _ = post_cpu.get_max_preds(c.hm)
+        assert coords.reshape(-1, 2).astype(int).tolist() == [[i[0] % w, i[0] // w] for i in ties]
+    t = pc.TIES_64x48
+    assert any(b % 256 < a % 256 for a, b, *_ in t)                                      # the later pixel in a lower thread
+    assert any((b % 256) // 64 < (a % 256) // 64 for a, b, *_ in t)                      # ... in a lower wave
+    assert any((b - a) % 256 == 0 for a, b, *_ in t)                                     # the same thread's stride
+    assert any(len(i) == 3 for i in t) and pc.TIES_96x72[0][1] == 96 * 72 - 1
+    assert {c.ksize for c in pc.CASES if c.name.startswith("skewed-64x48")} == {1, 3, 5, 7, 9, 11, 17, 31}
+    assert pc.BY_NAME["skewed-96x72-k17"].ksize == 17
+    c = pc.BY_NAME["skewed-64x48-k1"]                         # blur size 1 is "no blur": the decode without its blur step
+    coords, _ = post_cpu.get_max_preds(c.hm)
+    lg = post_cpu.clamped_log(c.hm)
+    S, J = c.hm.shape[:2]
+    plain = np.array([[post_cpu.taylor(lg[s, j], coords[s, j]) for j in range(J)] for s in range(S)])
+    assert np.array_equal(plain, pc.expected(c.name, False)[0])
+    assert {c.hm.shape[2:] for c in pc.CASES if c.family == "shapes"} == {(8, 6), (5, 7), (17, 13), (128, 96), (160, 120)}
+    assert all(c.hm.shape[0] * c.hm.shape[1] <= 40 and c.hm.dtype == np.float32 for c in pc.CASES)
+    assert all((c.scale[:, 0] != c.scale[:, 1]).all() for c in pc.CASES)
