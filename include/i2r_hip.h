@@ -27,7 +27,8 @@ extern "C" {
 #endif
 
 /* Bumped when an existing entry point, struct layout or op code changes.  Entry points that are only ADDED (i2r_joint_targets,
- * i2r_val_metrics) do not bump it: a binding built against the older header keeps working with the newer library. */
+ * i2r_val_metrics, i2r_oks_match, i2r_oks_accumulate) do not bump it: no existing struct changes with them, and a binding built
+ * against the older header keeps working with the newer library. */
 #define I2R_ABI_VERSION 17
 
 /* The library is built with -fvisibility=hidden: the entry points declared in this header (marked I2R_API) are its ONLY exported
@@ -218,6 +219,71 @@ typedef struct i2r_pose_nms_args {
     int32_t n_crops, n_img, joints, max_persons, soft, max_dets, use_oks_vis, reserved;
 } i2r_pose_nms_args;
 I2R_API int i2r_pose_nms(const i2r_pose_nms_args* a, void* stream);
+
+/* ---- keypoint OKS evaluation: what COCOeval(gt, dt, 'keypoints') computes from the rows above (pycocotools cocoeval.py; the package is
+ * not part of this project, so parity with its output is unpinned: the yardstick is the float64 restatement tests/_cocoeval_ref.py) ----
+ * i2r_oks_match -- computeOks + evaluateImg of every image, every area range and every threshold.  One workgroup per image.
+ * Detections are fp32 (as i2r_decode / i2r_pose_nms write them; the conversion to double is exact), everything else is float64 and
+ * all arithmetic is fp64 without contraction, no floating-point atomics: two runs give the same bits.
+ *   order      per image by descending score, equal scores: the lower index first (pycocotools' mergesort on -score; a NaN score ranks
+ *              as -inf); only the first max_dets take part.  dt_valid (optional): a zero entry means the detection does not exist
+ *   det. area  (max x - min x) * (max y - min y) over its J points (loadRes, key-point branch)
+ *   OKS(d, g)  var_j = (2 sigma_j)^2, k1 = #{v_j > 0}.  k1 > 0: dx = xd - xg, dy = yd - yg.  k1 == 0: with the bbox (x, y, w, h),
+ *              x0 = x - w, x1 = x + 2 w, y0 = y - h, y1 = y + 2 h, dx = max(0, x0 - xd) + max(0, xd - x1), dy likewise.
+ *              e_j = (dx^2 + dy^2) / var_j / (area_g + 2^-52) / 2;  oks = sum of exp(-e_j) over the joints with v_j > 0 (k1 > 0) or over
+ *              all J (k1 == 0), joints in ascending order, divided by their number
+ *   gtIg       for area range a: gtIg[g] = ignore_g or area_g < lo_a or area_g > hi_a (bounds inclusive); the gts are walked
+ *              non-ignored first, each class in input order (a stable sort)
+ *   matching   for each threshold t, detections in score order: iou = min(t, 1 - 1e-10), m = -1; over the gts in walk order: skip a gt
+ *              already matched at t unless it is a crowd; BREAK when m is a non-ignored gt and this gt is ignored; skip when oks < iou;
+ *              else iou = oks, m = g.  A match marks the gt and gives the detection dtIg = gtIg[m]; an unmatched detection is ignored
+ *              when its own area lies outside [lo_a, hi_a]
+ * Inputs (device): dt_kpts fp32 [n_dt, joints, 2]; dt_score fp32 [n_dt]; dt_valid uint8 [n_dt] or null; dt_off int32 [n_img + 1]
+ * (detections grouped by image); gt_kpts f64 [n_gt, joints, 3] (x, y, v); gt_area f64 [n_gt]; gt_bbox f64 [n_gt, 4] (x, y, w, h);
+ * gt_flags int32 [n_gt]: bit 0 = iscrowd, bit 1 = ignore (= iscrowd or num_keypoints == 0, computed by the host); gt_off int32
+ * [n_img + 1]; sigmas f64 [joints]; thr f64 [n_thr], 1 <= n_thr <= 16; area_rng f64 [n_area, 2], 1 <= n_area <= 4.
+ * max_dets 1..32; max_dt_per_img (0..1024) and max_gt_per_img (0..256): HOST-side upper bounds of one image's counts (they size the
+ * LDS); 1 <= joints <= 32.  Anything beyond these: I2R_E_ARG and nothing is launched.
+ * Outputs (device, fixed size): dt_rank int32 [n_dt]: position in the image's score order, -1 = not valid or beyond max_dets;
+ * dt_match, dt_ignore uint32 [n_area, n_dt]: bit t = threshold t (0 for a detection of rank -1); gt_ignore uint8 [n_area, n_gt];
+ * oks (optional) f64 with oks_off int64 [n_img + 1] and oks_len, the element count of the buffer: the [D, G] matrix of image i lies
+ * row-major in INPUT order at oks_off[i]; rows of detections of rank -1 hold -1.0; an image whose matrix would not lie inside
+ * [0, oks_len) gets none.  Nothing outside [dt_off[0], dt_off[n_img]) / [gt_off[0], gt_off[n_img]) is written.  An image whose offsets
+ * do not describe the batch (negative count, beyond n_dt / n_gt, more than the host-side bounds) gets rank -1 for those of its own
+ * detections that lie inside [0, n_dt) and nothing else.  n_img == 0 returns I2R_OK without a launch. */
+typedef struct i2r_oks_match_args {
+    const float* dt_kpts; const float* dt_score; const uint8_t* dt_valid; const int32_t* dt_off;
+    const double* gt_kpts; const double* gt_area; const double* gt_bbox; const int32_t* gt_flags; const int32_t* gt_off;
+    const double* sigmas; const double* thr; const double* area_rng;
+    int32_t* dt_rank; uint32_t* dt_match; uint32_t* dt_ignore; uint8_t* gt_ignore; double* oks; const int64_t* oks_off;
+    int64_t oks_len;
+    int32_t n_dt, n_gt, n_img, joints, n_thr, n_area, max_dets, max_dt_per_img, max_gt_per_img, reserved;
+} i2r_oks_match_args;
+I2R_API int i2r_oks_match(const i2r_oks_match_args* a, void* stream);
+
+/* i2r_oks_accumulate -- COCOeval.accumulate for one category and one maxDets.  One workgroup per (group, area range, threshold); group
+ * index n_group is "every image", whatever img_group says.  Per (group, a, t):
+ *   npig = number of gts with gtIg == 0 in the group's images; npig == 0: precision and recall stay -1
+ *   tp, fp = cumulative counts of (match and not ignore), (not match and not ignore) along `order`, restricted to the group's images
+ *   rc = tp / npig, pr = tp / ((fp + tp) + 2^-52); recall = the last rc, 0 without detections; pr made non-increasing from the back;
+ *   precision[r] = pr[first i with rc[i] >= rec_thr[r]], 0 when there is none
+ * The counts are integers and every division is one fp64 division of exact operands: precision and recall equal numpy's bit for bit.
+ * The walk is a block-wide scan over chunks of 1024 entries from the back with a running maximum; the cumulative counts at a chunk's
+ * start are the totals of a first counting pass minus what lies behind, so the kernel needs NO workspace.
+ * Inputs (device): dt_match, dt_ignore [n_area, n_dt] and gt_ignore [n_area, n_gt] as i2r_oks_match writes them; dt_rank [n_dt] or
+ * null; order int32 [n_part]: detections in global stable descending-score order, the images in ascending order and inside an image
+ * the rank order as the pre-sort order (entries outside [0, n_dt), and entries whose dt_rank is negative, take no part); dt_img int32
+ * [n_dt]: image index of a detection; img_group int32 [n_img]: group of an image, -1 = in none (null when n_group == 0); gt_off int32
+ * [n_img + 1]; rec_thr f64 [n_rec], 1 <= n_rec <= 128.  1 <= n_thr <= 16, 1 <= n_area <= 4, n_group >= 0.
+ * Outputs (device): precision f64 [n_group + 1, n_thr, n_rec, n_area]; recall f64 [n_group + 1, n_thr, n_area]; npig int32
+ * [n_group + 1, n_area].  All of them are written by every call (n_part == 0 included). */
+typedef struct i2r_oks_accumulate_args {
+    const uint32_t* dt_match; const uint32_t* dt_ignore; const int32_t* dt_rank; const int32_t* order; const int32_t* dt_img;
+    const int32_t* img_group; const uint8_t* gt_ignore; const int32_t* gt_off; const double* rec_thr;
+    double* precision; double* recall; int32_t* npig;
+    int32_t n_dt, n_gt, n_img, n_part, n_group, n_thr, n_area, n_rec;
+} i2r_oks_accumulate_args;
+I2R_API int i2r_oks_accumulate(const i2r_oks_accumulate_args* a, void* stream);
 
 /* ---- the two numbers validate() logs per batch: loss and PCK accuracy (lib/core/function.py:167-174) ------------------------------
  * i2r_joint_targets -- JointsDataset.generate_target + adjust_target_weight (lib/dataset/JointsDataset.py:394-450), target_type

@@ -184,6 +184,24 @@ class PoseNmsArgs(C.Structure):   # i2r_pose_nms_args
                 ("use_oks_vis", _i32), ("reserved", _i32)]
 
 
+class OksMatchArgs(C.Structure):   # i2r_oks_match_args
+    _fields_ = [("dt_kpts", _fp), ("dt_score", _fp), ("dt_valid", _fp), ("dt_off", _fp),
+                ("gt_kpts", _fp), ("gt_area", _fp), ("gt_bbox", _fp), ("gt_flags", _fp), ("gt_off", _fp),
+                ("sigmas", _fp), ("thr", _fp), ("area_rng", _fp),
+                ("dt_rank", _fp), ("dt_match", _fp), ("dt_ignore", _fp), ("gt_ignore", _fp), ("oks", _fp), ("oks_off", _fp),
+                ("oks_len", C.c_int64),
+                ("n_dt", _i32), ("n_gt", _i32), ("n_img", _i32), ("joints", _i32), ("n_thr", _i32), ("n_area", _i32), ("max_dets", _i32),
+                ("max_dt_per_img", _i32), ("max_gt_per_img", _i32), ("reserved", _i32)]
+
+
+class OksAccumulateArgs(C.Structure):   # i2r_oks_accumulate_args
+    _fields_ = [("dt_match", _fp), ("dt_ignore", _fp), ("dt_rank", _fp), ("order", _fp), ("dt_img", _fp),
+                ("img_group", _fp), ("gt_ignore", _fp), ("gt_off", _fp), ("rec_thr", _fp),
+                ("precision", _fp), ("recall", _fp), ("npig", _fp),
+                ("n_dt", _i32), ("n_gt", _i32), ("n_img", _i32), ("n_part", _i32), ("n_group", _i32), ("n_thr", _i32), ("n_area", _i32),
+                ("n_rec", _i32)]
+
+
 class JointTargetsArgs(C.Structure):   # i2r_joint_targets_args
     _fields_ = [("joints_hm", _fp), ("joints_vis", _fp), ("joints_weight", _fp), ("target_weight", _fp), ("target", _fp),
                 ("sigma", C.c_double), ("n_crops", _i32), ("joints", _i32), ("h", _i32), ("w", _i32)]
@@ -210,7 +228,7 @@ class Op(C.Structure):
 
 # every symbol include/i2r_hip.h declares (tests/test_host.py::test_cabi_library_exports_every_declared_symbol checks the built library exports them all)
 EXPORTS = ("i2r_conv", "i2r_conv_grouped", "i2r_conv_kernel_name", "i2r_stem_conv", "i2r_pe_res_stem", "i2r_maxpool3x3s2", "i2r_head", "i2r_layernorm", "i2r_window_attn", "i2r_hrt_attn_block", "i2r_hrt_mlp_block", "i2r_dwconv3x3",
-           "i2r_upsample_bilinear_add", "i2r_upsample_bilinear_add_multi", "i2r_fuse_up_add", "i2r_conv1x1_pair", "i2r_conv1x1_lp", "i2r_flip_merge", "i2r_decode", "i2r_pose_nms", "i2r_joint_targets", "i2r_val_metrics", "i2r_crop_affine", "i2r_box_mask", "i2r_crop_affine_cv2", "i2r_box_mask_cv2", "i2r_person_inputs_cv2", "i2r_encoder_kv", "i2r_encoder_layer", "i2r_mh_attention", "i2r_attn_weights", "i2r_attn_query_maps", "i2r_pe_cat_vec", "i2r_rows_gather", "i2r_view_scramble",
+           "i2r_upsample_bilinear_add", "i2r_upsample_bilinear_add_multi", "i2r_fuse_up_add", "i2r_conv1x1_pair", "i2r_conv1x1_lp", "i2r_flip_merge", "i2r_decode", "i2r_pose_nms", "i2r_oks_match", "i2r_oks_accumulate", "i2r_joint_targets", "i2r_val_metrics", "i2r_crop_affine", "i2r_box_mask", "i2r_crop_affine_cv2", "i2r_box_mask_cv2", "i2r_person_inputs_cv2", "i2r_encoder_kv", "i2r_encoder_layer", "i2r_mh_attention", "i2r_attn_weights", "i2r_attn_query_maps", "i2r_pe_cat_vec", "i2r_rows_gather", "i2r_view_scramble",
            "i2r_run_program", "i2r_run_program_timed", "i2r_abi_version", "i2r_last_error", "i2r_device_check")
 
 _LIB = None
@@ -235,6 +253,8 @@ def load_library(path=LIB_PATH):
     L.i2r_flip_merge.argtypes = [_fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, C.c_void_p]
     L.i2r_decode.argtypes = [_fp, _fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, C.c_void_p]
     L.i2r_pose_nms.argtypes = [C.POINTER(PoseNmsArgs), C.c_void_p]
+    L.i2r_oks_match.argtypes = [C.POINTER(OksMatchArgs), C.c_void_p]
+    L.i2r_oks_accumulate.argtypes = [C.POINTER(OksAccumulateArgs), C.c_void_p]
     L.i2r_joint_targets.argtypes = [C.POINTER(JointTargetsArgs), C.c_void_p]
     L.i2r_val_metrics.argtypes = [C.POINTER(ValMetricsArgs), C.c_void_p]
     L.i2r_crop_affine.argtypes = [_fp, _i32, _i32, _i32, _i32, _fp, _fp, _fp, _fp, _i32, _i32, _i32, C.c_void_p]

@@ -312,3 +312,235 @@ def val_metrics_cfg(cfg, output, target=None, target_weight=None, **kw):
             raise cabi.I2RError("val_metrics_cfg: no joints_weight table for dataset %r -- pass joints_weight" % cfg.DATASET.DATASET)
         kw["joints_weight"] = JOINTS_WEIGHT[cfg.DATASET.DATASET]
     return val_metrics(output, target, target_weight, sigma=cfg.MODEL.SIGMA, use_target_weight=cfg.LOSS.USE_TARGET_WEIGHT, **kw)
+
+
+# ---- keypoint OKS evaluation: COCOeval(gt, dt, 'keypoints') and the per-person-count table of lib/utils/KeypointEvaluator.py, on the device
+OKS_THRS = tuple(float(v) for v in np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True))      # Params.iouThrs
+OKS_REC_THRS = tuple(float(v) for v in np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1, endpoint=True))  # Params.recThrs
+OKS_AREA_RNG = ((0.0, 1e5 ** 2), (32.0 ** 2, 96.0 ** 2), (96.0 ** 2, 1e5 ** 2))                                    # all, medium, large
+OKS_STATS_NAMES = ("AP", "Ap .5", "AP .75", "AP (M)", "AP (L)", "AR", "AR .5", "AR .75", "AR (M)", "AR (L)")        # coco.py:507
+OKS_MAX_DETS, OKS_MAX_GT_PER_IMG, OKS_MAX_DT_PER_IMG = 32, 256, 1024   # limits of i2r_oks_match
+
+
+class GtTable:
+    """The ground truth of an evaluation as i2r_oks_match reads it, built once on the host: images sorted by id, every image's person
+    annotations in file order.  Device tensors: kpts f64 [n_gt, J, 3], area f64 [n_gt], bbox f64 [n_gt, 4], flags int32 [n_gt] (bit 0
+    iscrowd, bit 1 ignore = iscrowd or num_keypoints == 0), off int32 [n_img + 1].  Host: image_ids int64 [n_img] (sorted), counts int64
+    [n_img] (annotations per image), max_gt (the largest count)."""
+
+    def __init__(self, image_ids, kpts, area, bbox, flags, counts, device):
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.image_ids = image_ids
+        self.counts = counts
+        self.n_img, self.n_gt, self.joints = int(image_ids.numel()), int(kpts.shape[0]), int(kpts.shape[1])
+        self.max_gt = int(counts.max()) if self.n_img else 0
+        off = torch.zeros(self.n_img + 1, dtype=torch.int32)
+        off[1:] = torch.cumsum(counts, 0)
+        pin = (lambda t: t.pin_memory()) if self.device.type == "cuda" else (lambda t: t)
+        up = lambda t: pin(t.contiguous()).to(self.device, non_blocking=True)
+        self.kpts, self.area, self.bbox, self.flags, self.off = up(kpts), up(area), up(bbox), up(flags), up(off)
+
+    @classmethod
+    def from_arrays(cls, image_ids, gt_image_id, keypoints, area, bbox, iscrowd=None, num_keypoints=None, device="cuda"):
+        """image_ids: every image of the set (one without annotations is still evaluated); per annotation: gt_image_id, keypoints
+        [n, J, 3] (x, y, v), area, bbox [n, 4] (x, y, w, h), iscrowd (default 0), num_keypoints (default: the number of v > 0)."""
+        ids = torch.as_tensor(np.asarray(image_ids, np.int64).reshape(-1))
+        ids, _ = torch.sort(ids)
+        if ids.numel() > 1 and bool((ids[1:] == ids[:-1]).any()):
+            raise ValueError("GtTable: an image id occurs twice")
+        kp = torch.as_tensor(np.asarray(keypoints, np.float64))
+        n = kp.shape[0]
+        kp = kp if kp.dim() == 3 else kp.reshape(n, -1, 3)
+        gid = torch.as_tensor(np.asarray(gt_image_id, np.int64).reshape(-1))
+        crowd = torch.zeros(n, dtype=torch.int64) if iscrowd is None else torch.as_tensor(np.asarray(iscrowd).astype(np.int64).reshape(-1))
+        nk = (kp[:, :, 2] > 0).sum(1) if num_keypoints is None else torch.as_tensor(np.asarray(num_keypoints, np.int64).reshape(-1))
+        idx = torch.searchsorted(ids, gid).clamp_(max=max(ids.numel() - 1, 0))
+        if n and (ids.numel() == 0 or bool((ids[idx] != gid).any())):
+            raise ValueError("GtTable: an annotation of an image that is not in the set")
+        order = torch.sort(idx, stable=True)[1]   # (grouped by image, file order inside an image)
+        flags = ((crowd != 0).to(torch.int32) | (((crowd != 0) | (nk == 0)).to(torch.int32) << 1))
+        counts = torch.bincount(idx, minlength=ids.numel()) if n else torch.zeros(ids.numel(), dtype=torch.int64)
+        area = torch.as_tensor(np.asarray(area, np.float64).reshape(-1))
+        bbox = torch.as_tensor(np.asarray(bbox, np.float64).reshape(n, 4))
+        return cls(ids, kp[order], area[order], bbox[order], flags[order], counts, device)
+
+    @classmethod
+    def from_coco(cls, dataset, device="cuda"):
+        """dataset: a COCO key-point annotation file (path) or its dict: `images`, `annotations`, `categories`.  Persons only."""
+        if not isinstance(dataset, dict):
+            import json
+            with open(dataset) as f:
+                dataset = json.load(f)
+        cats = [c["id"] for c in dataset.get("categories", []) if c.get("name") == "person"]
+        anns = [a for a in dataset.get("annotations", []) if not cats or a.get("category_id") in cats]
+        J = len(anns[0]["keypoints"]) // 3 if anns else 17
+        return cls.from_arrays([im["id"] for im in dataset["images"]], [a["image_id"] for a in anns],
+                               np.asarray([a["keypoints"] for a in anns], np.float64).reshape(len(anns), J, 3),
+                               [a["area"] for a in anns], np.asarray([a["bbox"] for a in anns], np.float64).reshape(len(anns), 4),
+                               [a.get("iscrowd", 0) for a in anns], [a["num_keypoints"] for a in anns], device=device)
+
+
+class OksEval:
+    """What oks_eval returns, device tensors: stats f64 [n_group + 1, 10] (row n_group = every image), precision f64 [n_group + 1, n_thr,
+    n_rec, n_area], recall f64 [n_group + 1, n_thr, n_area], npig int32 [n_group + 1, n_area]; names: the ten names of evaluate();
+    group_names: the level names of the groups + 'all'.  match: the per-detection outputs of i2r_oks_match in the grouped order
+    (perm: grouped position -> input index): plain tensors that dist.gather_poses-style gathers can carry."""
+
+    def __init__(self, stats, precision, recall, npig, group_names, match):
+        self.stats, self.precision, self.recall, self.npig = stats, precision, recall, npig
+        self.names, self.group_names, self.match = OKS_STATS_NAMES, tuple(group_names), match
+
+    def name_values(self, group=None):
+        """the OrderedDict evaluate() returns (coco.py:430); group: None = every image, else a group index or level name.
+        This is the copy to the host."""
+        from collections import OrderedDict
+        g = len(self.group_names) - 1 if group is None else (self.group_names.index(group) if isinstance(group, str) else int(group))
+        return OrderedDict(zip(self.names, self.stats[g].cpu().tolist()))
+
+
+def person_count_groups(counts, start_points=(1, 2, 6, 10)):
+    """ClusterMode.get_cluster_level (lib/utils/KeypointEvaluator.py:528-544) for every image: counts -> (int32 tensor of group indices,
+    level names).  Level c{i+1} holds the counts in [start_points[i], start_points[i + 1]), the last level everything from the last start
+    point on; a count below the first start point (0 persons) is in no group: -1."""
+    sp = [int(v) for v in start_points]
+    assert len(sp) >= 2 and all(b > a for a, b in zip(sp, sp[1:])), sp
+    c = torch.as_tensor(counts).to(torch.int64)
+    grp = torch.bucketize(c, torch.tensor(sp, dtype=torch.int64, device=c.device), right=True) - 1
+    return grp.to(torch.int32), ["c%d" % (i + 1) for i in range(len(sp))]
+
+
+_OKS_CONST = {}
+
+
+def _oks_const(key, values, dev):
+    """small float64 tables on the device, uploaded once per (values, device) with a blocking copy (see _SIGMAS_DEV)"""
+    k = (key, tuple(values), dev)
+    if k not in _OKS_CONST:
+        _OKS_CONST[k] = torch.tensor(list(values), dtype=torch.float64).to(dev)
+    return _OKS_CONST[k]
+
+
+def oks_eval(gt, image_ids, keypoints, scores, valid=None, *, sigmas=None, groups=None, max_dets=20, thr=None, area_rng=None, rec_thr=None,
+             want_oks=False):
+    """COCOeval(gt, dt, 'keypoints').evaluate() / accumulate() / summarize() on the current stream: i2r_oks_match + i2r_oks_accumulate,
+    the ten numbers from their arrays with torch.  Nothing is copied to the host and nothing waits for the device.
+    gt: GtTable.  image_ids: host list / array / tensor, one id per detection (a device tensor is copied to the host first); an id that is
+    not in the table is a ValueError (loadRes asserts the same).  keypoints [N, J, 2 or 3] and scores [N] on the device, e.g. decode()'s
+    preds and PoseNms.score; valid [N] (bool / uint8 / int), e.g. PoseNms.rank >= 0.
+    groups: (int tensor [n_img] of group indices in the table's image order, level names) as person_count_groups returns it.
+    The limits of i2r_oks_match (1024 detections and 256 gts of one image, max_dets <= 32) apply to the rows as given: `valid` lives on
+    the device, so rows it masks out still count towards the 1024 of their image; drop them before the call where that matters.
+    Defaults: COCOeval's key-point parameters (thresholds .5:.05:.95, 101 recall thresholds, areas all / medium / large, maxDets 20) and
+    the sigma table of J = 17 or 14; the stats rows follow summarize (AP / AR at thresholds .5 and .75 are -1 when `thr` lacks them;
+    area columns 1 and 2 are 'medium' and 'large').  -> OksEval."""
+    assert isinstance(gt, GtTable)
+    dev = gt.device
+    assert keypoints.device == dev and keypoints.dim() == 3 and keypoints.shape[2] in (2, 3), (keypoints.device, tuple(keypoints.shape))
+    N, J = int(keypoints.shape[0]), int(keypoints.shape[1])
+    if gt.n_gt and gt.joints != J:
+        raise ValueError("oks_eval: %d joints, the ground truth has %d" % (J, gt.joints))
+    if sigmas is None:
+        if J not in SIGMAS:
+            raise cabi.I2RError("oks_eval: no sigma table for %d joints -- pass sigmas" % J)
+        sigmas = SIGMAS[J]
+    sig = _oks_const("sigmas", [float(v) for v in sigmas], dev)
+    assert sig.numel() == J, (sig.numel(), J)
+    thr = OKS_THRS if thr is None else tuple(float(v) for v in thr)
+    rec_thr = OKS_REC_THRS if rec_thr is None else tuple(float(v) for v in rec_thr)
+    area_rng = OKS_AREA_RNG if area_rng is None else tuple((float(a), float(b)) for a, b in area_rng)
+    nT, nR, nA = len(thr), len(rec_thr), len(area_rng)
+    thr_d, rec_d = _oks_const("thr", thr, dev), _oks_const("rec", rec_thr, dev)
+    rng_d = _oks_const("rng", [v for ab in area_rng for v in ab], dev)
+    # host plumbing, vectorised: image index of every detection, the grouping permutation, the offsets
+    ids = image_ids.cpu() if torch.is_tensor(image_ids) else torch.as_tensor(np.asarray(image_ids, np.int64))
+    ids = ids.to(torch.int64).reshape(-1)
+    assert ids.numel() == N, (ids.numel(), N)
+    idx = torch.searchsorted(gt.image_ids, ids).clamp_(max=max(gt.n_img - 1, 0))
+    if N and (gt.n_img == 0 or bool((gt.image_ids[idx] != ids).any())):
+        raise ValueError("oks_eval: Results do not correspond to current coco set (an image id is not in the ground truth)")
+    idx_s, perm = torch.sort(idx, stable=True)
+    cnt = torch.bincount(idx, minlength=gt.n_img) if N else torch.zeros(gt.n_img, dtype=torch.int64)
+    max_dt = int(cnt.max()) if gt.n_img else 0
+    off = torch.zeros(gt.n_img + 1, dtype=torch.int64)
+    off[1:] = torch.cumsum(cnt, 0)
+    host = torch.cat([off, idx_s, perm]).to(torch.int32)   # (one upload)
+    if dev.type == "cuda":
+        host = host.pin_memory()
+    host = host.to(dev, non_blocking=True)
+    dt_off, dt_img, perm_d = host[:gt.n_img + 1], host[gt.n_img + 1:gt.n_img + 1 + N], host[gt.n_img + 1 + N:].to(torch.int64)
+    kp = keypoints[:, :, :2].to(torch.float32)[perm_d].contiguous()
+    sc = torch.as_tensor(scores).to(dev, non_blocking=True).to(torch.float32).reshape(N)[perm_d].contiguous()
+    va = None if valid is None else (torch.as_tensor(valid).to(dev, non_blocking=True).reshape(N) != 0).to(torch.uint8)[perm_d].contiguous()
+    if groups is None:
+        n_group, img_group, group_names = 0, None, []
+    else:
+        img_group, group_names = groups
+        group_names = list(group_names)
+        n_group = len(group_names)
+        img_group = torch.as_tensor(img_group).to(dev, non_blocking=True).to(torch.int32).contiguous()
+        assert img_group.numel() == gt.n_img, (img_group.numel(), gt.n_img)
+    dt_rank = torch.empty(N, dtype=torch.int32, device=dev)
+    dt_match = torch.empty(nA, N, dtype=torch.int32, device=dev)   # (uint32 bit rows held in int32 tensors)
+    dt_ignore = torch.empty(nA, N, dtype=torch.int32, device=dev)
+    gt_ignore = torch.empty(nA, gt.n_gt, dtype=torch.uint8, device=dev)
+    oks = oks_off = None
+    if want_oks:
+        o = torch.zeros(gt.n_img + 1, dtype=torch.int64)
+        o[1:] = torch.cumsum(cnt * gt.counts, 0)
+        oks = torch.empty(int(o[-1]), dtype=torch.float64, device=dev)
+        oks_off = o.to(dev, non_blocking=True)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+    m = cabi.OksMatchArgs(dt_kpts=ptr(kp), dt_score=ptr(sc), dt_valid=ptr(va), dt_off=dt_off.data_ptr(), gt_kpts=ptr(gt.kpts),
+                          gt_area=ptr(gt.area), gt_bbox=ptr(gt.bbox), gt_flags=ptr(gt.flags), gt_off=gt.off.data_ptr(),
+                          sigmas=sig.data_ptr(), thr=thr_d.data_ptr(), area_rng=rng_d.data_ptr(), dt_rank=ptr(dt_rank), dt_match=ptr(dt_match),
+                          dt_ignore=ptr(dt_ignore), gt_ignore=ptr(gt_ignore), oks=ptr(oks), oks_off=ptr(oks_off),
+                          oks_len=oks.numel() if oks is not None else 0, n_dt=N, n_gt=gt.n_gt, n_img=gt.n_img, joints=J, n_thr=nT, n_area=nA,
+                          max_dets=int(max_dets), max_dt_per_img=max_dt, max_gt_per_img=gt.max_gt)
+    cabi.check(cabi.lib().i2r_oks_match(ctypes.byref(m), st), "i2r_oks_match")
+    # the global score order (plumbing): a stable descending sort over the grouped detections; those that take no part go behind
+    key = torch.where((dt_rank >= 0) & (sc == sc), sc, torch.full_like(sc, float("-inf")))   # (a NaN score ranks as -inf, as in the kernel)
+    # (inside an image the pre-sort order has to be the rank order, which for equal scores is the input order: the grouped order)
+    order = torch.sort(key, descending=True, stable=True)[1].to(torch.int32)
+    precision = torch.empty(n_group + 1, nT, nR, nA, dtype=torch.float64, device=dev)
+    recall = torch.empty(n_group + 1, nT, nA, dtype=torch.float64, device=dev)
+    npig = torch.empty(n_group + 1, nA, dtype=torch.int32, device=dev)
+    acc = cabi.OksAccumulateArgs(dt_match=ptr(dt_match), dt_ignore=ptr(dt_ignore), dt_rank=ptr(dt_rank), order=ptr(order), dt_img=ptr(dt_img),
+                                 img_group=ptr(img_group), gt_ignore=ptr(gt_ignore), gt_off=gt.off.data_ptr(), rec_thr=rec_d.data_ptr(),
+                                 precision=precision.data_ptr(), recall=recall.data_ptr(), npig=npig.data_ptr(), n_dt=N, n_gt=gt.n_gt,
+                                 n_img=gt.n_img, n_part=N, n_group=n_group, n_thr=nT, n_area=nA, n_rec=nR)
+    cabi.check(cabi.lib().i2r_oks_accumulate(ctypes.byref(acc), st), "i2r_oks_accumulate")
+
+    # summarize (_summarizeKps): the mean over the entries > -1, -1 when there are none
+    def mean_valid(x):   # x [n_group + 1, ...]
+        x = x.reshape(n_group + 1, -1)
+        ok = x > -1
+        n = ok.sum(1)
+        return torch.where(n > 0, torch.where(ok, x, torch.zeros_like(x)).sum(1) / n.clamp(min=1), torch.full_like(x[:, 0], -1.0))
+    minus = torch.full((n_group + 1,), -1.0, dtype=torch.float64, device=dev)
+    t_of = lambda v: thr.index(v) if v in thr else None   # (a slice below, never an index list: that would be an upload that waits)
+    cols = []
+    for src, is_ap in ((precision, True), (recall, False)):
+        area = (lambda s, a: s[:, :, :, a]) if is_ap else (lambda s, a: s[:, :, a])
+        cols.append(mean_valid(area(src, 0)))
+        for v in (.5, .75):
+            i = t_of(v)
+            cols.append(mean_valid(area(src[:, i:i + 1], 0)) if i is not None else minus)
+        for a in (1, 2):
+            cols.append(mean_valid(area(src, a)) if a < nA else minus)
+    stats = torch.stack(cols, 1)
+    match = dict(rank=dt_rank, match=dt_match, ignore=dt_ignore, gt_ignore=gt_ignore, perm=perm_d, oks=oks, oks_off=oks_off)
+    return OksEval(stats, precision, recall, npig, group_names + ["all"], match)
+
+
+def oks_eval_cfg(cfg, gt, image_ids, keypoints, scores, valid=None, **kw):
+    """oks_eval with the sigma table of MODEL.NUM_JOINTS (17: COCO / OCHuman, 14: the table lib/nms/nms.py uses for CrowdPose)."""
+    J = cfg.MODEL.NUM_JOINTS
+    assert keypoints.shape[1] == J, (tuple(keypoints.shape), J)
+    if "sigmas" not in kw:
+        if J not in SIGMAS:
+            raise cabi.I2RError("oks_eval_cfg: no sigma table for MODEL.NUM_JOINTS = %d -- pass sigmas" % J)
+        kw["sigmas"] = SIGMAS[J]
+    return oks_eval(gt, image_ids, keypoints, scores, valid, **kw)
