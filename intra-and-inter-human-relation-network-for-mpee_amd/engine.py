@@ -1,15 +1,5 @@
-"""Execution engine of the hot path: packs reference-layout weights for the HIP kernels and replays a
-pre-built launch program through the C-ABI (cabi.py).  No arithmetic happens in Python/torch here: torch
-only owns device memory and streams.
-
-Weight packing (done once per load_state_dict / device move):
-  * every conv + eval-mode BatchNorm pair is folded:  w' = w * gamma/sqrt(var+eps),  b' = beta - mean*gamma/sqrt(var+eps)
-    (reference applies nn.Conv2d then nn.BatchNorm2d, e.g. interformer_pureMulti.py:53-60); folding is done in
-    float64 and rounded once to fp32.
-  * conv weights go to the "k4" layout  [tap][cin/4][cout_pad][4]  consumed by i2r_conv (include/i2r_hip.h).
-  * ConvTranspose2d(k4,s2,p1) is split into its four output-parity 2x2 convolutions.
-  * encoder matrices ([out][in], zero-padded to multiples of 16) are stored fragment-packed: every 16x16 block as the MFMA
-    A-operand image in lane order (pack_frag), so one 64-lane 16-byte load is 1 KB contiguous.
+"""Execution engine of the hot path: replays a pre-built launch program through the C-ABI (cabi.py) over the weights that pack.py
+laid out for the HIP kernels.  No arithmetic happens in Python/torch here: torch only owns device memory and streams.
 
 A Program is the static list of launches for one (S, H, W, length) signature: all intermediate NHWC buffers
 are pre-allocated (arena with reuse), so a forward is ONE call into i2r_run_program.
@@ -21,83 +11,8 @@ import os
 import torch
 
 from . import cabi
-
-
-def _m16(c):
-    return (c + 15) // 16 * 16
-
-
-def _r16(c):
-    """Channel count -> row width of an activation / padded width of a weight matrix: the next multiple of 16 whose number of
-    16-channel fragments the conv kernels can split (a multiple of 3, 4 or 5: conv_split, csrc/i2r_conv.hip).  Every width of the shipped
-    models is its own image (48, 64, 80 = 78 padded, 96, 160, 192, 256, 320, 384, 624, ...); 16 and 32 (HRNet-W32's first branch, W18)
-    become 48 with zero weights and zero activations in the pad channels."""
-    n = (c + 15) // 16
-    while not any(n % k == 0 for k in (3, 4, 5)):
-        n += 1
-    return 16 * n
-
-
-# ------------------------------------------------------------------------------------------------
-# packing
-# ------------------------------------------------------------------------------------------------
-def fold_bn(w, bn, conv_bias=None, eps=1e-5):
-    """w [Cout, ...] fp32 CPU; bn = (gamma, beta, mean, var) or None -> (w', b') float64."""
-    w = w.double()
-    cout = w.shape[0]
-    b = conv_bias.double() if conv_bias is not None else torch.zeros(cout, dtype=torch.float64)
-    if bn is not None:
-        gamma, beta, mean, var = [t.double() for t in bn]
-        scale = gamma / torch.sqrt(var + eps)
-        w = w * scale.view(-1, *([1] * (w.dim() - 1)))
-        b = (b - mean) * scale + beta
-    return w, b
-
-
-def pack_k4(w_taps, cin_pad, cout_pad):
-    """w_taps [ntaps, cin, cout] -> fp32 [ntaps, cin_pad/4, cout_pad, 4] (zero padded)."""
-    nt, cin, cout = w_taps.shape
-    full = torch.zeros(nt, cin_pad, cout_pad, dtype=torch.float64)
-    full[:, :cin, :cout] = w_taps
-    return full.view(nt, cin_pad // 4, 4, cout_pad).permute(0, 1, 3, 2).contiguous().float()
-
-
-PRECISIONS = {"fp32": 0, "bf16": 1, "fp16": 2}
-
-
-def pack_frag(m):
-    """[rows, cols] (both multiples of 16) -> MFMA A-operand images in lane order (csrc/i2r_encoder.hip header):
-    packed[((rb*KC + c)*64 + l)*4 + r] = m[16 rb + (l & 15)][16 c + 4 (l >> 4) + r]; one 64-lane 16-byte load = 1 KB contiguous."""
-    rows, cols = m.shape
-    assert rows % 16 == 0 and cols % 16 == 0
-    v = m.reshape(rows // 16, 16, cols // 16, 4, 4)              # [rb, li, c, g, r]
-    return v.permute(0, 2, 3, 1, 4).contiguous().reshape(rows, cols)  # [rb, c, g, li, r]
-
-
-def pack_frag32(m):
-    """[rows, cols] (rows a multiple of 16, cols of 32) -> A-operand images of the 32-deep 16-bit MFMA in lane order (csrc/i2r_conv1x1_lp.hip):
-    packed[((rb*KC + c)*64 + l)*8 + r] = m[16 rb + (l & 15)][32 c + 8 (l >> 4) + r]; one 64-lane 16-byte load = 1 KB contiguous."""
-    rows, cols = m.shape
-    assert rows % 16 == 0 and cols % 32 == 0
-    v = m.reshape(rows // 16, 16, cols // 32, 4, 8)              # [rb, li, c, g, r]
-    return v.permute(0, 2, 3, 1, 4).contiguous().reshape(rows, cols)  # [rb, c, g, li, r]
-
-
-def pack_k8(w_taps, cin_pad, cout_pad, tdtype):
-    """w_taps [ntaps, cin, cout] -> 16-bit [ntaps, g8_pad, cout_pad, 8] (cin zero-padded to whole 32-channel MFMA steps)."""
-    nt, cin, cout = w_taps.shape
-    g8_pad = (cin_pad // 8 + 3) // 4 * 4
-    full = torch.zeros(nt, g8_pad * 8, cout_pad, dtype=torch.float64)
-    full[:, :cin, :cout] = w_taps
-    return full.float().to(tdtype).view(nt, g8_pad, 8, cout_pad).permute(0, 1, 3, 2).contiguous()
-
-
-def winograd_weights(wf):
-    """[cout, cin, 3, 3] float64 -> U = G g G^T per (cout, cin) as [16, cin, cout] (position p = 4 i + j), the weight side of
-    Winograd F(2x2, 3x3) (csrc/i2r_conv_wino.hip); done in float64 and rounded once to fp32 by pack_k4"""
-    G = torch.tensor([[1.0, 0.0, 0.0], [0.5, 0.5, 0.5], [0.5, -0.5, 0.5], [0.0, 0.0, 1.0]], dtype=torch.float64)
-    U = torch.einsum("ia,ocab,jb->ijco", G, wf.double(), G)
-    return U.reshape(16, wf.shape[1], wf.shape[0])
+from .pack import (PRECISIONS, PackedConv, Packer, _m16, _r16, fold_bn, pack_frag, pack_frag32, pack_k4, pack_k8,  # noqa: F401 (the packing names stay importable from here)
+                   winograd_weights)
 
 
 def wino_fragment(conv_h, conv_w):
@@ -130,437 +45,6 @@ WINOGRAD = True  # fp32 3x3 stride-1 convs on the Winograd F(2x2, 3x3) kernels
 PROFILER_ATTACHED = bool(os.environ.get("ROCP_TOOL_LIBRARIES") or os.environ.get("ROCPROFILER_LIBRARY_CTOR") or os.environ.get("HSA_TOOLS_LIB")
                          or any(t in os.environ.get("LD_PRELOAD", "") for t in ("rocprof", "roctracer", "rocprofiler")))  # rocprofv3 / rocprofv2 / rocprof / preloaded tools
 DEVICE_SYNC = not PROFILER_ATTACHED
-
-
-class PackedConv:
-    __slots__ = ("w", "bias", "cin", "cin_pad", "cout", "cout_pad", "taps", "iy0", "ix0", "stride", "ksize", "dtype", "w_wino", "w_frag", "w_lp1")
-
-    def __init__(self, w, bias, cin, cout, taps, iy0, ix0, stride, ksize, cin_pad=None, dtype=0):
-        self.w, self.bias = w, bias
-        self.cin, self.cin_pad = cin, (w.shape[1] * 4 if cin_pad is None else cin_pad)
-        self.cout, self.cout_pad = cout, w.shape[2]
-        self.taps, self.iy0, self.ix0, self.stride, self.ksize = taps, iy0, ix0, stride, ksize
-        self.dtype = dtype
-        self.w_wino = None  # fp32 3x3 stride-1 convs: the Winograd-domain weights [16][cin/4][cout_pad][4] (Packer.conv)
-        self.w_lp1 = None   # 16-bit 1x1 stride-1 convs: the [cout_pad, cin_pad] matrix as 16-bit MFMA A-operand fragments for i2r_conv1x1_lp
-        self.w_frag = None  # fp32 1x1 convs of layer1: the [cout, cin] matrix as MFMA A-operand fragments (pack_frag) for i2r_conv1x1_pair
-
-
-class Packer:
-    def __init__(self, sd, device, precision="fp32"):
-        self.sd = {k: v.detach().to("cpu") for k, v in sd.items()}
-        self.device = device
-        self.dtype = PRECISIONS[precision]  # MFMA operand type of the conv kernels (accumulation / storage stay fp32)
-
-    def _pc(self, w_taps, bias, cin, cout, taps, iy0, ix0, stride, ksize):
-        """PackedConv in this packer's MFMA operand type."""
-        cin_pad, cout_pad = _r16(cin), _r16(cout)
-        if self.dtype == 0:
-            w = pack_k4(w_taps, cin_pad, cout_pad)
-        else:
-            w = pack_k8(w_taps, cin_pad, cout_pad, torch.bfloat16 if self.dtype == 1 else torch.float16)
-        pc = PackedConv(self._dev(w), bias, cin, cout, taps, iy0, ix0, stride, ksize, cin_pad=cin_pad, dtype=self.dtype)
-        if self.dtype != 0 and ksize == 1 and stride == 1 and w_taps.shape[0] == 1 and cin_pad >= 64 and any((cout_pad // 16) % k == 0 for k in (3, 4, 5, 6)):
-            full = torch.zeros(cout_pad, (cin_pad + 31) // 32 * 32, dtype=torch.float64)
-            full[:cout, :cin] = w_taps[0].t()
-            pc.w_lp1 = self._dev(pack_frag32(full).float().to(torch.bfloat16 if self.dtype == 1 else torch.float16))
-        return pc
-
-    def _bn(self, key):
-        if key is None:
-            return None
-        s = self.sd
-        return (s[key + ".weight"], s[key + ".bias"], s[key + ".running_mean"], s[key + ".running_var"])
-
-    def _dev(self, t):
-        return t.contiguous().to(self.device)
-
-    def conv(self, conv_key, bn_key=None, stride=1, eps=1e-5):
-        w = self.sd[conv_key + ".weight"]
-        cout, cin, kh, kw = w.shape
-        assert kh == kw and kh in (1, 3)
-        wf, bf = fold_bn(w, self._bn(bn_key), self.sd.get(conv_key + ".bias"), eps)
-        taps = [(dy, dx) for dy in range(kh) for dx in range(kw)]
-        w_taps = wf.permute(2, 3, 1, 0).reshape(kh * kw, cin, cout)
-        cout_pad = _r16(cout)
-        bias = torch.zeros(cout_pad, dtype=torch.float64)
-        bias[:cout] = bf
-        pad = kh // 2
-        pc = self._pc(w_taps, self._dev(bias.float()), cin, cout, taps, -pad, -pad, stride, kh)
-        nfrag = cout_pad // 16
-        if self.dtype == 0 and kh == 3 and stride == 1 and (nfrag % 3 == 0 or nfrag % 4 == 0):
-            pc.w_wino = self._dev(pack_k4(winograd_weights(wf), _r16(cin), cout_pad))
-        return pc
-
-    def conv_cat(self, parts, eps=1e-5):
-        """Sum of 1x1 convs (+BN each) over DIFFERENT inputs as ONE 1x1 conv over the channel concatenation of those inputs:
-        weights concatenated along cin (in the order of `parts`: (conv_key, bn_key)), folded biases added.  Used for the first
-        Bottleneck of layer1: relu(bn3(conv3(t2)) + bn_d(downsample(x))) = relu([W3' | Wd'] . [t2 ; x] + b3' + bd')."""
-        mats, bias_sum, cins = [], None, []
-        for conv_key, bn_key in parts:
-            w = self.sd[conv_key + ".weight"]
-            cout, cin, kh, kw = w.shape
-            assert kh == 1 and kw == 1
-            wf, bf = fold_bn(w, self._bn(bn_key), self.sd.get(conv_key + ".bias"), eps)
-            mats.append(wf.reshape(cout, cin).t())  # [cin, cout]
-            bias_sum = bf if bias_sum is None else bias_sum + bf
-            cins.append(cin)
-        assert all(c % 16 == 0 for c in cins), "concatenated inputs must keep whole 16-channel steps"
-        w_taps = torch.cat(mats, 0).unsqueeze(0)  # [1, sum cin, cout]
-        cout = w_taps.shape[2]
-        bias = torch.zeros(_r16(cout), dtype=torch.float64)
-        bias[:cout] = bias_sum
-        pc = self._pc(w_taps, self._dev(bias.float()), sum(cins), cout, [(0, 0)], 0, 0, 1, 1)
-        pc.w_frag = self._frag(w_taps)
-        return pc
-
-    def _frag(self, w_taps):
-        """fragment-packed [cout, cin] image of a 1x1 conv for i2r_conv1x1_pair (fp32, whole 16-channel fragments), else None"""
-        _, cin, cout = w_taps.shape
-        if self.dtype != 0 or w_taps.shape[0] != 1 or cin % 16 or cout % 16:
-            return None
-        return self._dev(pack_frag(w_taps[0].t().contiguous()).float())
-
-    def bottlenecks(self, prefix, n):
-        """layer1 of HRNet / HRFormer: n Bottleneck blocks (reference hrnet.py / hrformer.py `Bottleneck`, expansion 4); the first one
-        carries a 1x1 downsample on its identity path, folded into its conv3 (conv_cat)."""
-        blocks = []
-        for b in range(n):
-            q = "%s.%d" % (prefix, b)
-            blk = dict(c1=self.conv(q + ".conv1", q + ".bn1"), c2=self.conv(q + ".conv2", q + ".bn2"))
-            if (q + ".downsample.0.weight") in self.sd:
-                blk["c3ds"] = self.conv_cat([(q + ".downsample.0", q + ".downsample.1"), (q + ".conv3", q + ".bn3")])
-            else:
-                blk["c3"] = self.conv(q + ".conv3", q + ".bn3")
-            for key in ("c1", "c3"):
-                if key in blk:
-                    w = self.sd[q + ".conv%s.weight" % key[1]]
-                    wf, _ = fold_bn(w, self._bn(q + ".bn%s" % key[1]), None, 1e-5)
-                    blk[key].w_frag = self._frag(wf.reshape(1, w.shape[0], w.shape[1]).permute(0, 2, 1))
-            blocks.append(blk)
-        return blocks
-
-    def linear_as_conv(self, w, b):
-        """[out, in] matrix + bias -> 1x1 PackedConv."""
-        cout, cin = w.shape
-        cout_pad = _r16(cout)
-        bias = torch.zeros(cout_pad, dtype=torch.float64)
-        bias[:cout] = b.double()
-        return self._pc(w.double().t().reshape(1, cin, cout), self._dev(bias.float()), cin, cout, [(0, 0)], 0, 0, 1, 1)
-
-    def deconv(self, deconv_key, bn_key, eps=1e-5):
-        """ConvTranspose2d(k=4, s=2, p=1) [Cin, Cout, 4, 4] (+BN) -> {(py,px): PackedConv with 2x2 taps} (k = 3, 2: fewer taps, DECONV_TAPS).
-
-        out[2q+py] gathers in[q+iy0+dy]:  py=0: iy0=-1, ky = 3-2dy ;  py=1: iy0=0, ky = 2-2dy  (oy = 2*iy - 1 + ky).
-        """
-        w = self.sd[deconv_key + ".weight"]
-        cin, cout, kh, kw = w.shape
-        assert kh == kw and kh in self.DECONV_TAPS, "ConvTranspose2d kernel %dx%d (the reference's _get_deconv_cfg knows 2, 3, 4)" % (kh, kw)
-        wf, bf = fold_bn(w.permute(1, 0, 2, 3), self._bn(bn_key), self.sd.get(deconv_key + ".bias"), eps)  # [Cout,Cin,k,k]
-        cout_pad = _r16(cout)
-        bias = torch.zeros(cout_pad, dtype=torch.float64)
-        bias[:cout] = bf
-        bias = self._dev(bias.float())
-        out = {}
-        for py in (0, 1):
-            for px in (0, 1):
-                (iy0, kys), (ix0, kxs) = self.DECONV_TAPS[kh][py], self.DECONV_TAPS[kh][px]
-                taps = [(dy, dx) for dy in range(len(kys)) for dx in range(len(kxs))]
-                w_taps = torch.stack([wf[:, :, kys[dy], kxs[dx]].t() for dy, dx in taps], 0)  # [taps, Cin, Cout]
-                out[(py, px)] = self._pc(w_taps, bias, cin, cout, taps, iy0, ix0, 1, max(len(kys), len(kxs)))
-        return out
-
-    # ConvTranspose2d(k, stride 2, padding p, output_padding op) with the reference's (k, p, op) in {(4, 1, 0), (3, 1, 1), (2, 0, 0)}
-    # (_get_deconv_cfg, interformer_pureMulti.py:635-646): out[o] = sum in[i] w[o + p - 2i].  Per output parity o = 2q + par, along one
-    # axis: (first input offset i0 relative to q, kernel index of every tap d, i = q + i0 + d)
-    DECONV_TAPS = {4: {0: (-1, (3, 1)), 1: (0, (2, 0))},
-                   3: {0: (0, (1,)), 1: (0, (2, 0))},
-                   2: {0: (0, (0,)), 1: (0, (1,))}}
-
-    def stem(self, conv_key, bn_key, eps=1e-5):
-        w = self.sd[conv_key + ".weight"]  # [cout, cin, 3, 3]
-        cout, cin = w.shape[:2]
-        wf, bf = fold_bn(w, self._bn(bn_key), None, eps)
-        return dict(w=self._dev(wf.permute(2, 3, 1, 0).reshape(9, cin, cout).float()), bias=self._dev(bf.float()),
-                    cin=cin, cout=cout)
-
-    def pe_res(self, p):
-        """PositionEmbeddingImage mode 'res' (position_embedding.py:14-18): conv_pre 1->3 (3x3, no bias) and torchvision resnet18
-        children()[:5] = conv1 7x7-s2 3->64 + bn1 + relu + maxpool + layer1 (2 BasicBlocks of 64), then conv_end 64->d (3x3, no BN)."""
-        w_pre = self.sd[p + ".conv_pre.weight"]           # [3, 1, 3, 3]
-        assert tuple(w_pre.shape) == (3, 1, 3, 3)
-        w7 = self.sd[p + ".res.0.weight"]                 # [64, 3, 7, 7]
-        assert tuple(w7.shape) == (64, 3, 7, 7)
-        wf, bf = fold_bn(w7, self._bn(p + ".res.1"), None, 1e-5)
-        blocks = []
-        for b in range(2):
-            q = "%s.res.4.%d" % (p, b)
-            blocks.append((self.conv(q + ".conv1", q + ".bn1"), self.conv(q + ".conv2", q + ".bn2")))
-        return dict(w_pre=self._dev(w_pre.view(3, 9).t().contiguous().float()),               # [tap][c]
-                    w7=self._dev(wf.permute(2, 3, 1, 0).reshape(49 * 3, 64).float()), bias=self._dev(bf.float()), cout=64,
-                    blocks=blocks, conv_end=self.conv(p + ".conv_end"))
-
-    def head(self, key):
-        """final_layer (with bias) for i2r_head.  EXTRA.FINAL_CONV_KERNEL = 3 (padding 1; interformer.py:176-182, interformer_pureMulti.py:486-492,
-        transpose_h.py:472-478): the 3x3 conv runs on the conv kernel with its outputs padded to 48 channels (zero weights: a width the kernel
-        splits), and i2r_head -- the kernel that writes the boundary NCHW layout -- follows with an identity matrix and no bias (exact in fp32)."""
-        w = self.sd[key + ".weight"]
-        cout, cin, kh, kw = w.shape
-        assert kh == kw and kh in (1, 3), "final_layer kernel %dx%d" % (kh, kw)
-        if kh == 3:
-            cp = 48
-            assert cout <= 32
-            w_taps = torch.zeros(9, cin, cp, dtype=torch.float64)
-            w_taps[:, :, :cout] = w.double().permute(2, 3, 1, 0).reshape(9, cin, cout)
-            bias = torch.zeros(cp, dtype=torch.float64)
-            bias[:cout] = self.sd[key + ".bias"].double()
-            taps = [(dy, dx) for dy in range(3) for dx in range(3)]
-            pc = self._pc(w_taps, self._dev(bias.float()), cin, cp, taps, -1, -1, 1, 3)
-            if self.dtype == 0:
-                wf = torch.zeros(cp, cin, 3, 3, dtype=torch.float64)
-                wf[:cout] = w.double()
-                pc.w_wino = self._dev(pack_k4(winograd_weights(wf), _r16(cin), cp))
-            eye = torch.zeros(cout, cp)
-            eye[torch.arange(cout), torch.arange(cout)] = 1.0
-            return dict(w=self._dev(eye), bias=self._dev(torch.zeros(cout)), cin=cp, cout=cout, conv3=pc)
-        cin_pad = _r16(cin)
-        wp = torch.zeros(cout, cin_pad)
-        wp[:, :cin] = w.view(cout, cin)
-        return dict(w=self._dev(wp), bias=self._dev(self.sd[key + ".bias"].float()), cin=cin_pad, cout=cout)
-
-    def encoder_layer(self, p, d, dff):
-        cs, fs = _r16(d), _r16(dff)
-        s = self.sd
-
-        def padm(m, r, c):
-            o = torch.zeros(r, c)
-            o[:m.shape[0], :m.shape[1]] = m
-            return o
-
-        def padv(v, n):
-            o = torch.zeros(n)
-            o[:v.shape[0]] = v
-            return o
-
-        wi, bi = s[p + ".self_attn.in_proj_weight"], s[p + ".self_attn.in_proj_bias"]
-        w_in = torch.cat([padm(wi[i * d:(i + 1) * d], cs, cs) for i in range(3)], 0)
-        b_in = torch.cat([padv(bi[i * d:(i + 1) * d], cs) for i in range(3)], 0)
-        t = dict(
-            w_in=w_in, b_in=b_in,
-            w_out=padm(s[p + ".self_attn.out_proj.weight"], cs, cs), b_out=padv(s[p + ".self_attn.out_proj.bias"], cs),
-            ln1_w=padv(s[p + ".norm1.weight"], cs), ln1_b=padv(s[p + ".norm1.bias"], cs),
-            w1=padm(s[p + ".linear1.weight"], fs, cs), b1=padv(s[p + ".linear1.bias"], fs),
-            w2=padm(s[p + ".linear2.weight"], cs, fs), b2=padv(s[p + ".linear2.bias"], cs),
-            ln2_w=padv(s[p + ".norm2.weight"], cs), ln2_b=padv(s[p + ".norm2.bias"], cs))
-        lp = {}
-        if self.dtype != 0:
-            # 16-bit copies for the 16-bit MFMA encoder, model dim padded to csp = 96 (three 32-feature MFMA steps) for d = 96 and
-            # d = 78 alike; columns of every 32-block permuted to the operand order
-            # new position 8g + 4*half + r  <-  column 32c + 16*half + 4g + r   (csrc/i2r_encoder.hip)
-            tdt = torch.bfloat16 if self.dtype == 1 else torch.float16
-            csp = 96
-            assert cs <= csp and fs == 192
-
-            def perm(m):
-                rows, cols = m.shape
-                v = m.view(rows, cols // 32, 2, 4, 4)          # [row, c, half, g, r]
-                v = v.permute(0, 1, 3, 2, 4).reshape(rows // 16, 16, cols // 32, 4, 8)   # [rb, li, c, g, (half, r)]
-                # ... and fragment-packed like the fp32 matrices: [rb][c][g][li][8] = one 1 KB contiguous load per fragment
-                return v.permute(0, 2, 3, 1, 4).reshape(rows, cols).to(tdt).contiguous()
-            w_in_p = torch.cat([padm(wi[i * d:(i + 1) * d], csp, csp) for i in range(3)], 0)
-            b_in_p = torch.cat([padv(bi[i * d:(i + 1) * d], csp) for i in range(3)], 0)
-            lp = dict(w_in_lp=perm(w_in_p), w_out_lp=perm(padm(s[p + ".self_attn.out_proj.weight"], csp, csp)),
-                      w1_lp=perm(padm(s[p + ".linear1.weight"], fs, csp)), w2_lp=perm(padm(s[p + ".linear2.weight"], csp, fs)),
-                      vec_lp=torch.cat([b_in_p, padv(s[p + ".self_attn.out_proj.bias"], csp), padv(s[p + ".norm1.weight"], csp),
-                                        padv(s[p + ".norm1.bias"], csp), padv(s[p + ".linear1.bias"], fs), padv(s[p + ".linear2.bias"], csp),
-                                        padv(s[p + ".norm2.weight"], csp), padv(s[p + ".norm2.bias"], csp)]).float())
-            lp = {k: self._dev(v) for k, v in lp.items()}
-        for k in ("w_in", "w_out", "w1", "w2"):
-            t[k] = pack_frag(t[k])
-        t = {k: self._dev(v.float()) for k, v in t.items()}
-        t.update(lp)
-        t.update(d=d, cs=cs, dff_pad=fs, dtype=self.dtype if lp else 0)
-        return t
-
-    @staticmethod
-    def mh_width(heads, hd):
-        """(hp, hs): head dim padded to a multiple of 16 (csrc/i2r_encoder_mh.hip) and the width of a q / k / v / attention-output part,
-        heads*hp rounded up to a fragment count the conv kernels split (conv_split: a multiple of 3, 4 or 5 sixteen-channel blocks)"""
-        hp = _m16(hd)
-        f = heads * hp // 16
-        while not any(f % k == 0 for k in (3, 4, 5)):
-            f += 1
-        return hp, 16 * f
-
-    def encoder_layer_mh(self, p, d, dff, heads):
-        """General form of a DETR encoder layer (any MODEL.N_HEAD, post- or pre-norm; interformer_pureMulti.py:171-243, attention.py:37-112)
-        as 1x1 convs around i2r_mh_attention: q|k (head hh's dim j at channel hh*hp + j, k part hs further; head_dim^-0.5 folded into the q
-        rows), v, out-proj (zero columns for the head pads), linear1, linear2 and the two LayerNorms."""
-        assert self.dtype == 0, "the general encoder layer runs in fp32 (use a Packer(..., 'fp32'))"
-        s = self.sd
-        hd = d // heads
-        assert hd * heads == d, "nn.MultiheadAttention: embed_dim %d must be divisible by num_heads %d" % (d, heads)
-        hp, hs = self.mh_width(heads, hd)
-        rows = torch.tensor([hh * hp + j for hh in range(heads) for j in range(hd)])
-        wi, bi = s[p + ".self_attn.in_proj_weight"].double(), s[p + ".self_attn.in_proj_bias"].double()
-        wqk, bqk = torch.zeros(2 * hs, d, dtype=torch.float64), torch.zeros(2 * hs, dtype=torch.float64)
-        wqk[rows], bqk[rows] = wi[:d] * float(hd) ** -0.5, bi[:d] * float(hd) ** -0.5
-        wqk[hs + rows], bqk[hs + rows] = wi[d:2 * d], bi[d:2 * d]
-        wv, bv = torch.zeros(hs, d, dtype=torch.float64), torch.zeros(hs, dtype=torch.float64)
-        wv[rows], bv[rows] = wi[2 * d:], bi[2 * d:]
-        wo = torch.zeros(d, hs, dtype=torch.float64)
-        wo[:, rows] = s[p + ".self_attn.out_proj.weight"].double()
-        return dict(mh=True, heads=heads, hp=hp, hs=hs, d=d, cs=_r16(d),
-                    qk=self.linear_as_conv(wqk, bqk), v=self.linear_as_conv(wv, bv), o=self.linear_as_conv(wo, s[p + ".self_attn.out_proj.bias"]),
-                    w1=self.linear_as_conv(s[p + ".linear1.weight"], s[p + ".linear1.bias"]),
-                    w2=self.linear_as_conv(s[p + ".linear2.weight"], s[p + ".linear2.bias"]),
-                    ln1=self.ln(p + ".norm1", d), ln2=self.ln(p + ".norm2", d))
-
-    def window_block(self, a, d, heads):
-        """MHA_ of attention.py (:494-835) under key prefix a: separate q / k / v / out projections with bias, in the head-padded channel
-        order of encoder_layer_mh (head_dim^-0.5 folded into q); the relative position table is a parameter nobody reads (:780-786)"""
-        assert self.dtype == 0
-        s = self.sd
-        hd = d // heads
-        assert hd * heads == d
-        hp, hs = self.mh_width(heads, hd)
-        rows = torch.tensor([hh * hp + j for hh in range(heads) for j in range(hd)])
-        wqk, bqk = torch.zeros(2 * hs, d, dtype=torch.float64), torch.zeros(2 * hs, dtype=torch.float64)
-        wqk[rows], bqk[rows] = s[a + ".q_proj.weight"].double() * float(hd) ** -0.5, s[a + ".q_proj.bias"].double() * float(hd) ** -0.5
-        wqk[hs + rows], bqk[hs + rows] = s[a + ".k_proj.weight"].double(), s[a + ".k_proj.bias"].double()
-        wv, bv = torch.zeros(hs, d, dtype=torch.float64), torch.zeros(hs, dtype=torch.float64)
-        wv[rows], bv[rows] = s[a + ".v_proj.weight"].double(), s[a + ".v_proj.bias"].double()
-        wo = torch.zeros(d, hs, dtype=torch.float64)
-        wo[:, rows] = s[a + ".out_proj.weight"].double()
-        return dict(heads=heads, hp=hp, hs=hs, d=d, cs=_r16(d), qk=self.linear_as_conv(wqk, bqk), v=self.linear_as_conv(wv, bv),
-                    o=self.linear_as_conv(wo, s[a + ".out_proj.bias"]))
-
-    def dw(self, conv_key, bn_key, eps=1e-5):
-        """depth-wise 3x3 [C,1,3,3] (+bias) + BN -> tap-major [9][cs] weights + [cs] bias."""
-        w = self.sd[conv_key + ".weight"]
-        c = w.shape[0]
-        assert tuple(w.shape[1:]) == (1, 3, 3)
-        wf, bf = fold_bn(w, self._bn(bn_key), self.sd.get(conv_key + ".bias"), eps)
-        cs = _r16(c)
-        wp = torch.zeros(9, cs, dtype=torch.float64)
-        wp[:, :c] = wf.view(c, 9).t()
-        bp = torch.zeros(cs, dtype=torch.float64)
-        bp[:c] = bf
-        return dict(w=self._dev(wp.float()), bias=self._dev(bp.float()), c=c, cs=cs)
-
-    def ln(self, key, c):
-        cs = _r16(c)
-        w, b = torch.zeros(cs), torch.zeros(cs)
-        w[:c], b[:c] = self.sd[key + ".weight"], self.sd[key + ".bias"]
-        return dict(w=self._dev(w), b=self._dev(b), c=c, cs=cs)
-
-    HEAD_PAD = 40  # window attention: every head's channels padded to a 16-byte multiple (head_dim 39 -> 40)
-
-    def qkv(self, p, c, heads):
-        """stacked q/k/v_proj as one 1x1 conv with 3*hs outputs (q | k | v, each hs = heads*HEAD_PAD wide): head hh's dim d sits at
-        channel hh*HEAD_PAD + d, pad channels have zero weights and bias (they come out exactly 0).  The hd^-0.5 scale of the
-        queries (hrformer.py:780) is folded into the q rows."""
-        hd, hp = c // heads, self.HEAD_PAD
-        assert hd * heads == c and hp - 4 < hd <= hp
-        hs = heads * hp
-        W = torch.zeros(3 * hs, c, dtype=torch.float64)
-        b = torch.zeros(3 * hs, dtype=torch.float64)
-        rows = torch.tensor([hh * hp + d for hh in range(heads) for d in range(hd)])
-        for i, n in enumerate(("q_proj", "k_proj", "v_proj")):
-            sc = float(hd) ** -0.5 if i == 0 else 1.0
-            W[i * hs + rows] = self.sd["%s.%s.weight" % (p, n)].double() * sc
-            b[i * hs + rows] = self.sd["%s.%s.bias" % (p, n)].double() * sc
-        return self.linear_as_conv(W, b)
-
-    def attn_out(self, p, c, heads):
-        """out_proj as a 1x1 conv reading the head-padded attention output (cin = heads*HEAD_PAD, zero columns for the pads)."""
-        hd, hp = c // heads, self.HEAD_PAD
-        cols = torch.tensor([hh * hp + d for hh in range(heads) for d in range(hd)])
-        W = torch.zeros(c, heads * hp, dtype=torch.float64)
-        W[:, cols] = self.sd[p + ".out_proj.weight"].double()
-        return self.linear_as_conv(W, self.sd[p + ".out_proj.bias"])
-
-    @staticmethod
-    def _frag16(m, tdt):
-        """[rows, cols] (multiples of 16) -> v_mfma_f32_16x16x16 A-operand images: [rows/16][cols/16][64 lanes][4] 16-bit,
-        element r of lane l = m[16 rb + (l & 15)][16 cb + 4 (l >> 4) + r]  (include/i2r_hip.h, i2r_hrt_attn_block)"""
-        rows, cols = m.shape
-        v = m.reshape(rows // 16, 16, cols // 16, 4, 4)              # [rb, i, cb, g, r]
-        return v.permute(0, 2, 3, 1, 4).contiguous().to(tdt)         # [rb, cb, g, i, r] = lane (g, i) order
-
-    def attn_block_lp(self, p, c, heads):
-        """operands of the fused 16-bit attention half of a transformer block (i2r_hrt_attn_block); r = block key prefix"""
-        tdt = torch.bfloat16 if self.dtype == 1 else torch.float16
-        hd, cs = c // heads, _r16(c)
-        assert hd == 39
-        a = p + ".attn.attn"
-        wq = torch.zeros(heads, 3, 48, cs, dtype=torch.float64)
-        bq = torch.zeros(heads, 3, 48, dtype=torch.float64)
-        for i, n in enumerate(("q_proj", "k_proj", "v_proj")):
-            sc = float(hd) ** -0.5 * 1.4426950408889634 if i == 0 else 1.0   # softmax in base 2
-            W = self.sd["%s.%s.weight" % (a, n)].double() * sc
-            b = self.sd["%s.%s.bias" % (a, n)].double() * sc
-            for hh in range(heads):
-                wq[hh, i, :hd, :c] = W[hh * hd:(hh + 1) * hd]
-                bq[hh, i, :hd] = b[hh * hd:(hh + 1) * hd]
-        # 32-deep MFMA fragments (pack_frag32): input channels padded to whole 32-channel k-steps
-        csp = (cs + 31) // 32 * 32
-        wq_p = torch.zeros(heads * 3 * 48, csp, dtype=torch.float64)
-        wq_p[:, :cs] = wq.reshape(heads * 3 * 48, cs)
-        ks = csp // 32
-        wqkv = pack_frag32(wq_p.float()).view(heads * 3, 3, ks, 512).permute(0, 2, 1, 3).contiguous().to(tdt)  # [(h, part)][k-step][db][64 lanes x 8]
-        Wo = self.sd[a + ".out_proj.weight"].double()
-        wo = torch.zeros(cs, heads, 48, dtype=torch.float64)
-        for hh in range(heads):
-            wo[:c, hh, :hd] = Wo[:, hh * hd:(hh + 1) * hd]
-        # columns (head, dim) in the kernel's k-slot order: slot 8g + 4h + r of k-step s <- column 16 (2s + h) + 4g + r (two 16-dim
-        # D fragments packed into one 32-deep B operand, csrc/i2r_hrformer_lp.hip)
-        wo = wo.reshape(cs, heads * 48 // 32, 2, 4, 4).permute(0, 1, 3, 2, 4).reshape(cs, heads * 48)
-        wo = pack_frag32(wo.float()).to(tdt)                                         # [ob][k-step][64 lanes][8]
-        bo = torch.zeros(cs)
-        bo[:c] = self.sd[a + ".out_proj.bias"]
-        ln = self.ln(p + ".norm1", c)
-        return dict(wqkv=self._dev(wqkv), bqkv=self._dev(bq.float()), wo=self._dev(wo), bo=self._dev(bo), ln=ln, c=c, cs=cs, heads=heads,
-                    dtype=self.dtype)
-
-    def mlp_block_lp(self, p, c):
-        """operands of the fused 16-bit MLP half of a transformer block (i2r_hrt_mlp_block): fc1+BN1, dw3x3+BN2, fc2+BN3 folded in
-        float64, hidden dim padded to a multiple of 64 with zeros; p = block key prefix"""
-        tdt = torch.bfloat16 if self.dtype == 1 else torch.float16
-        cs, hid = _r16(c), 4 * c
-        hp = (hid + 63) // 64 * 64
-        m = p + ".mlp"
-        w1, b1 = fold_bn(self.sd[m + ".fc1.weight"], self._bn(m + ".norm1"), self.sd.get(m + ".fc1.bias"))      # [hid, c, 1, 1]
-        wd, bd = fold_bn(self.sd[m + ".dw3x3.weight"], self._bn(m + ".norm2"), self.sd.get(m + ".dw3x3.bias"))  # [hid, 1, 3, 3]
-        w2, b2 = fold_bn(self.sd[m + ".fc2.weight"], self._bn(m + ".norm3"), self.sd.get(m + ".fc2.bias"))      # [c, hid, 1, 1]
-        assert tuple(w1.shape[:2]) == (hid, c) and tuple(w2.shape[:2]) == (c, hid)
-        W1 = torch.zeros(hp, cs, dtype=torch.float64)
-        W1[:hid, :c] = w1.view(hid, c)
-        W2 = torch.zeros(cs, hp, dtype=torch.float64)
-        W2[:c, :hid] = w2.view(c, hid)
-        WD = torch.zeros(9, hp, dtype=torch.float64)
-        WD[:, :hid] = wd.view(hid, 9).t()
-
-        def padv(v, n):
-            o = torch.zeros(n, dtype=torch.float64)
-            o[:v.shape[0]] = v
-            return o.float()
-        # 32-deep MFMA fragments (pack_frag32): fc1's input channels padded to whole 32-channel k-steps; fc2's hidden columns in the
-        # kernel's slot order (slot 8g + 4h + r of a k-step <- hidden channel 16 (2 kstep + h) + 4g + r: a PAIR of 16-channel hidden blocks)
-        csp = (cs + 31) // 32 * 32
-        W1p = torch.zeros(hp, csp, dtype=torch.float64)
-        W1p[:, :cs] = W1
-        W2s = W2.reshape(cs, hp // 32, 2, 4, 4).permute(0, 1, 3, 2, 4).reshape(cs, hp)
-        return dict(w1=self._dev(pack_frag32(W1p.float()).to(tdt)), b1=self._dev(padv(b1, hp)), wdw=self._dev(WD.float()), bdw=self._dev(padv(bd, hp)),
-                    w2=self._dev(pack_frag32(W2s.float()).to(tdt)), b2=self._dev(padv(b2, cs)), ln=self.ln(p + ".norm2", c), c=c, cs=cs, hidden_pad=hp,
-                    dtype=self.dtype)
-
-    def table(self, key, rows, d):
-        """[rows, 1, d] parameter (TransPose-H pos_embedding) -> [rows, cs] device table."""
-        v = self.sd[key].reshape(rows, d)
-        o = torch.zeros(rows, _r16(d))
-        o[:, :d] = v
-        return self._dev(o)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -669,9 +153,8 @@ def conv_split(cout_pad):
 
 
 class Program:
-    def __init__(self, device, multi_lane=False):
+    def __init__(self, device):
         self.device = device
-        self.multi_lane = multi_lane
         self.ops = []        # (kind, lane, struct)
         self.keep = []       # everything the structs point to
         self.pool = {}       # numel -> [tensor]
@@ -686,7 +169,16 @@ class Program:
         self.store_dt = 0    # storage type the conv TOWER keeps its maps in (set by the engine in the 16-bit modes: 1 bf16, 2 f16)
         self.in_fork = False
         self.nbytes = 0
-        self._c_ops = None
+        self._snap = None       # (pending, lane_pool) as of the last records(), until all_waited()
+        self._next_slot = -1    # record slot handed out last (records)
+        self._c_ops = None      # the launch list as the library reads it (finalize)
+        self._flags_op = None   # index of the OP_LANE_FLAGS op, if the program forks
+        self.uses_lanes = False
+        self.device_sync = False  # the last run() used the device-side fork / join / record / wait
+        self._flags = None      # flag buffer of the device-side sync form (_lane_flags)
+        self._events = None     # the program's own fork / join / record events (_own_events)
+        self._tev = None        # timing events of _run_timed
+        self._capture_ws = None  # per-call workspaces of set_capture / set_query_capture, held until the next call
 
     # ---- buffers ----
     def alloc(self, n, h, w, c, dt=0):
@@ -1194,13 +686,7 @@ class Program:
             if cur is not x:
                 self.release(cur)
             cur = out
-        grouping = dict(descs=descs, goff=goff, current=None)
-        self.set_groups(grouping, grp_off_host)
-        if cap is not None:
-            cap["grouping"] = grouping
-        self.enc_stacks.append(grouping)  # every encoder stack of the program (bench.py: algorithmic FLOPs of the attention blocks)
-        if regroupable:
-            self.groupings.append((grouping, x.h * x.w))
+        self._register_stack(dict(descs=descs, goff=goff, current=None), grp_off_host, cap, x.h * x.w if regroupable else None)
         return cur
 
     def encoder_mh(self, x, layers, grp_off_host, pos=None, pos_period=0, lane=0, regroupable=False, pre_norm=False, pos_table=None, capture=None):
@@ -1248,14 +734,18 @@ class Program:
                 self.release(hdn, n1)
                 cur = self.layernorm(y, L["ln2"], eps=1e-5, lane=lane)
                 self.release(y)
-        grouping = dict(descs=[], mh=mh_args, goff=goff, current=None)
+        self._register_stack(dict(descs=[], mh=mh_args, goff=goff, current=None), grp_off_host, cap, x.h * x.w if regroupable else None)
+        return cur
+
+    def _register_stack(self, grouping, grp_off_host, cap=None, regroup_tok=None):
+        """an emitted encoder stack joins the program: its groups are set, a capture learns its grouping, and with regroup_tok (tokens
+        per crop) the engine may regroup it per call (groupings)"""
         self.set_groups(grouping, grp_off_host)
         if cap is not None:
             cap["grouping"] = grouping
-        self.enc_stacks.append(grouping)
-        if regroupable:
-            self.groupings.append((grouping, x.h * x.w))
-        return cur
+        self.enc_stacks.append(grouping)  # every encoder stack of the program (bench.py: algorithmic FLOPs of the attention blocks)
+        if regroup_tok is not None:
+            self.groupings.append((grouping, regroup_tok))
 
     def _pos_rows(self, x, pos, pos_period, pos_table):
         """the position embedding as a second conv input laid out like x (None without one): per-token rows as they are, a [pos_period, cs]
@@ -1298,27 +788,45 @@ class Program:
 
     AW_KEYS = 128  # key block of i2r_attn_weights (csrc/i2r_encoder_mh.hip kAwKeys)
 
+    # The front that set_capture and set_query_capture share, per capture: the groups asked for are checked against the stack's current
+    # grouping, every group's block gets its offset inside a layer's part of the output buffer, and those offsets go to the device.
+    @staticmethod
+    def _capture_groups(cap, lens):
+        """lens must be the first groups of the stack as it is grouped now -> the widest head count among the capture's launches"""
+        cur = cap["grouping"]["current"]
+        assert len(lens) >= 1 and list(lens) == [cur[g + 1] - cur[g] for g in range(len(lens))]
+        return max(a.heads for _, a in cap["ops"]) if cap["ops"] else 1
+
+    @staticmethod
+    def _capture_blocks(sizes):
+        """floats of every group's block -> (block offsets inside a layer [groups + 1], floats per layer: layer blocks start on 16-byte boundaries)"""
+        offs = [0]
+        for n in sizes:
+            offs.append(offs[-1] + n)
+        return offs, -(-offs[-1] // 4) * 4
+
+    @staticmethod
+    def _upload_out_off(cap, offs):
+        cap["out_off"][:len(offs) - 1].copy_(torch.tensor(offs[:-1], dtype=torch.int64).pin_memory(), non_blocking=True)
+
     def set_capture(self, glens):
         """glens: per capture (program order) the token count of every group to compute (the real images / crops of this call, a prefix of
         the stack's groups).  -> (buffer, {(stack, layer): [L_g x L_g views]}, {stack: input Act})."""
-        sizes, need_ws, rows = [], 2, 0
+        sizes, per_layer, need_ws, rows = [], [], 2, 0
         for cap, lens in zip(self.captures, glens):
-            assert len(lens) >= 1 and list(lens) == [cap["grouping"]["current"][g + 1] - cap["grouping"]["current"][g] for g in range(len(lens))]
-            heads = max(a.heads for _, a in cap["ops"]) if cap["ops"] else 1
+            heads = self._capture_groups(cap, lens)
             need_ws = max(need_ws, 2 * heads * -(-max(lens) // self.AW_KEYS))
             rows = max(rows, sum(lens))
-            offs = [0]
-            for n in lens:
-                offs.append(offs[-1] + n * n)
+            offs, n_layer = self._capture_blocks([n * n for n in lens])
             sizes.append(offs)
-        per_layer = [-(-offs[-1] // 4) * 4 for offs in sizes]  # (layer blocks start on 16-byte boundaries)
+            per_layer.append(n_layer)
         total = sum(n * len(cap["ops"]) for n, cap in zip(per_layer, self.captures))
         buf = torch.empty(max(total, 1), dtype=torch.float32, device=self.device)
         ws = torch.empty(rows * need_ws, dtype=torch.float32, device=self.device)
         self._capture_ws = ws  # (kept until the next call: the launches read it asynchronously; torch's allocator orders reuse by stream)
         maps, base = {}, 0
         for cap, lens, offs, n_layer in zip(self.captures, glens, sizes, per_layer):
-            cap["out_off"][:len(lens)].copy_(torch.tensor(offs[:-1], dtype=torch.int64).pin_memory(), non_blocking=True)
+            self._upload_out_off(cap, offs)
             tiles = sum(-(-n // 16) * -(-n // self.AW_KEYS) for n in lens)
             for i, a in cap["ops"]:
                 a.out, a.ws = buf.data_ptr() + 4 * base, ws.data_ptr()
@@ -1333,11 +841,10 @@ class Program:
         [K_g, P_g, h r, w r] view}, {stack: input Act}), r the stack's scale; the buffer holds exactly sum over layers and groups of K_g L_g r^2 floats (+ at most
         3 floats between layers whose size is no multiple of 4).  No [L, L] block exists: the workspaces are O(K L)."""
         mode, scales = self.query
-        plan, n_ws, n_rows = [], 2, 1
+        plan, per_layer, n_ws, n_rows = [], [], 2, 1
         for cap, lens in zip(self.captures, glens):
             scale = scales[cap["stack"]]
-            cur = cap["grouping"]["current"]
-            assert len(lens) >= 1 and list(lens) == [cur[g + 1] - cur[g] for g in range(len(lens))]
+            heads = self._capture_groups(cap, lens)
             tok = torch.as_tensor(queries.tokens[cap["stack"]]).to("cpu", torch.int32).contiguous()
             if tok.dim() != 2 or tok.shape[0] != len(lens) or tok.shape[1] < 1:
                 raise ValueError("query tokens of %r: shape %s, expected [%d groups, K]" % (cap["stack"], tuple(tok.shape), len(lens)))
@@ -1351,16 +858,13 @@ class Program:
                     raise ValueError("query token %d of group %d of %r is outside its %d tokens" % (int(tok[g, :c].max()), g, cap["stack"], n))
             hw = cap["x"].h * cap["x"].w
             assert all(n % hw == 0 for n in lens)
-            heads = max(a.heads for _, a in cap["ops"]) if cap["ops"] else 1
             stride = 2 * heads * -(-max(lens) // self.AW_KEYS)
             n_ws = max(n_ws, stride * (len(lens) * K if mode == 0 else sum(lens)))
             if scale > 1:
                 n_rows = max(n_rows, K * sum(lens))
-            offs = [0]
-            for n, c in zip(lens, cnt):
-                offs.append(offs[-1] + c * n * scale * scale)
+            offs, n_layer = self._capture_blocks([c * n * scale * scale for n, c in zip(lens, cnt)])
             plan.append((tok, cnt, K, stride, offs, scale))
-        per_layer = [-(-p[4][-1] // 4) * 4 for p in plan]  # (layer blocks start on 16-byte boundaries)
+            per_layer.append(n_layer)
         starts, base = [], 0
         for n, cap in zip(per_layer, self.captures):
             starts.append([base + j * n for j in range(len(cap["ops"]))])
@@ -1372,7 +876,7 @@ class Program:
         held = [ws, rows]  # (kept until the next call: the launches read them asynchronously; torch's allocator orders reuse by stream)
         maps = {}
         for cap, lens, (tok, cnt, K, stride, offs, scale), st in zip(self.captures, glens, plan, starts):
-            cap["out_off"][:len(lens)].copy_(torch.tensor(offs[:-1], dtype=torch.int64).pin_memory(), non_blocking=True)
+            self._upload_out_off(cap, offs)
             d_tok = tok.pin_memory().to(self.device, non_blocking=True)
             d_cnt = torch.tensor(cnt, dtype=torch.int32).pin_memory().to(self.device, non_blocking=True)
             cur = cap["grouping"]["current"]
@@ -1435,12 +939,12 @@ class Program:
     # recorded becomes reusable by every lane at `all_waited()` -- the point of the launch list behind which every lane has waited for
     # every record; what is released after the records waits for the next round.  tests/test_lanes.py replays the happens-before relation.
     def records(self, lanes):
-        assert self.in_fork and not getattr(self, "_snap", None)
+        assert self.in_fork and self._snap is None
         slots, region = {}, 0
         for l in lanes:
             region |= 1 << l
         for l in lanes:  # (every lane of the region waits for every record of the round -- _emit_module makes sure -- so every flag is consumed)
-            slot = self._next_slot = (getattr(self, "_next_slot", -1) + 1) % 8
+            slot = self._next_slot = (self._next_slot + 1) % 8
             self.ops.append((cabi.OP_RECORD, l | slot << 8 | region << 16, None))
             slots[l] = slot
         self._snap = (self.pending, self.lane_pool)
@@ -1460,7 +964,7 @@ class Program:
 
     def join(self, mask):
         """lane 0 continues after the lanes in `mask`; buffers freed inside the region become reusable"""
-        assert not getattr(self, "_snap", None)
+        assert self._snap is None
         self.ops.append((cabi.OP_JOIN, mask, None))
         self.in_fork = False
         self._flush_lane_pools()
@@ -1524,7 +1028,7 @@ class Program:
     def _run_timed(self, L, streams, evs):
         n = len(self.ops)
         key = (tuple(streams), Program.timing_markers)
-        if getattr(self, "_tev", (None,))[0] != key:  # events are created once per program (lane layout, marker mode)
+        if self._tev is None or self._tev[0] != key:  # events are created once per program (lane layout, marker mode)
             t0, t1, seen = [None] * n, [None] * n, set()
             for i, (kind, lane, st) in enumerate(self.ops):
                 if kind in cabi.SYNC_OPS:
@@ -1543,16 +1047,16 @@ class Program:
         Program.timing_log.append((self, t0, t1, key[0]))
 
     def _lane_flags(self):
-        if not hasattr(self, "_flags"):
+        if self._flags is None:
             self._flags = torch.zeros(64, dtype=torch.int32, device=self.device)
         return self._flags
 
     def sync_timed_out(self):
         """True if a device-side wait of this program ever gave up (50 ms): its results are then not ordered and must not be used"""
-        return hasattr(self, "_flags") and bool(self._flags[63].item())
+        return self._flags is not None and bool(self._flags[63].item())
 
     def _own_events(self):
-        if not hasattr(self, "_events"):
+        if self._events is None:
             self._events = [torch.cuda.Event(enable_timing=False) for _ in range(16)]  # 0..7: fork / join (rotating), 8..15: record slots
             for e in self._events:
                 e.record()  # forces creation of the underlying hipEvent_t
@@ -2166,13 +1670,26 @@ class Engine:
         cabi.require_gfx950(self.device.index)
         self.programs = {}
         self.n_builds = 0  # programs built so far (bench.py --ragged-stream reports them)
-        self.multi_lane = False  # (grouped launches replaced per-branch stream lanes)
+        self.last_programs = []   # the program(s) of the most recent forward (bench.py's per-launch timing pass replays them)
+        self.last_concurrent = []  # ... those of them that ran side by side on their own streams
         self.side_streams = lane_streams(self.device, 3)
+        self._part_streams, self._part_events = [], []  # streams / events of the concurrent part-batches (_fork_parts)
         M = cfg["MODEL"]
         self.name = name or M["NAME"]
         pk = Packer(state_dict, self.device, precision)
         d, dff = M["DIM_MODEL"], M["DIM_FEEDFORWARD"]
         self._pk = pk
+        self._pk32 = None          # the fp32 packer of the general encoder layer and the capture packs (_fp32_packer)
+        self._capture_packs = {}   # (stack, layer) -> fp32 q|k pack of a fused layer (_capture_spec)
+        self._sine_tables = {}     # (n, h, w, d) -> canvas table (_sine_table)
+        # what a model does not have stays None / empty: the first stage (_pack_single), the position branch (_pack_pos), the
+        # inter-human stack and the up-sampling layers below
+        self.tower = self.reduce = self.head = None
+        self.single_stack = self.single_pos = self.single_head = self.res_layer = self.single_tokens = None
+        self.single_layers, self.layers, self.deconvs = [], [], []
+        self.use_pos, self.pe_mode, self.return_dict = False, None, False
+        self.win_block = self.cat_fc = self.upconv = self.domain_trans = None
+        self.inter_stack = "global_encoder" if self.name == "interformer_pureMulti" else "multi_global_encoder"  # state-dict prefix of the inter-human stack
         # forward_pre exists in every copy of the layer class, but only attention.py:1040 (get_default_encoder: the inter-human stack of
         # MODEL.NAME interformer) passes cfg.MODEL.NORMALIZE_BEFORE on; the other constructors leave the default False
         self.pre_norm = bool(M["NORMALIZE_BEFORE"]) and self.name == "interformer"
@@ -2212,9 +1729,7 @@ class Engine:
                 self._pack_pos(pk, "multi_position_embedding", M["MULTI_POS_EMBEDDING"])
             wide = d + (M["MULTI_POS_EMBEDDING_DIM"] if self.cat_concat else 0)
             if self.window_attn:
-                self.layers = []
-                pk32 = pk if pk.dtype == 0 else Packer(pk.sd, self.device, "fp32")
-                self.win_block = pk32.window_block("multi_global_encoder.attn.attn", d, M["N_HEAD"])
+                self.win_block = self._fp32_packer().window_block("multi_global_encoder.attn.attn", d, M["N_HEAD"])
             else:
                 self.layers = [self._enc_layer("multi_global_encoder.layers.%d" % l, self.pre_norm, d=wide) for l in range(M["ENCODER_MULTI_LAYERS"])]
             if self.cat_concat:
@@ -2234,15 +1749,14 @@ class Engine:
                 # UpConv (interformer.py:25-64 as upsample_layer; interformer_2stage.py:174-206,244 as upsample_conv): 1x1 conv + BN, nearest
                 # upsampling by HEATMAP_SIZE[0] // TRANS_SIZE[1] (the conv kernel replicates its outputs), then (3x3 conv + BN + ReLU) twice
                 q = "upsample_layer" if self.name == "interformer" else "upsample_conv"
-                self.deconvs = []
                 self.upconv = dict(scale=M["HEATMAP_SIZE"][0] // M["TRANS_SIZE"][1], fuse=pk.conv(q + ".fuse_layers.0", q + ".fuse_layers.1"),
                                    c1=pk.conv(q + ".double_conv.0", q + ".double_conv.1"), c2=pk.conv(q + ".double_conv.3", q + ".double_conv.4"))
             else:
                 raise NotImplementedError("UPSAMPLE_TYPE=%r" % up)
             self.head = pk.head("final_layer")
             # interformer_2stage.py:277-279,413-414: x = domain_trans_1(single_res) + domain_trans_2(x) (two 1x1 convs with bias) instead of the sum
-            self.domain_trans = ((pk.conv("domain_trans_1"), pk.conv("domain_trans_2"))
-                                 if self.name == "interformer_2stage" and M["DOMAIN_TRANS"] else None)
+            if self.name == "interformer_2stage" and M["DOMAIN_TRANS"]:
+                self.domain_trans = (pk.conv("domain_trans_1"), pk.conv("domain_trans_2"))
             self.return_dict = bool(M["INTER_SUPERVISION"]) and not M["SINGLEFORMER_FIX"] and bool(sf)
         else:
             raise NotImplementedError("MODEL.NAME=%r" % self.name)
@@ -2254,38 +1768,42 @@ class Engine:
         d, dff, heads = d or M["DIM_MODEL"], M["DIM_FEEDFORWARD"], M["N_HEAD"]
         if heads == 1 and not pre_norm and _r16(d) in (96, 80) and _r16(dff) == 192:
             return self._pk.encoder_layer(p, d, dff)
-        if getattr(self, "_pk32", None) is None:
+        return self._fp32_packer().encoder_layer_mh(p, d, dff, heads)
+
+    def _fp32_packer(self):
+        """the packer of what always runs in fp32 (general encoder layer, window block, capture q|k): the model's own in fp32 mode"""
+        if self._pk32 is None:
             self._pk32 = self._pk if self._pk.dtype == 0 else Packer(self._pk.sd, self.device, "fp32")
-        return self._pk32.encoder_layer_mh(p, d, dff, heads)
+        return self._pk32
 
     def capture_stacks(self):
         """encoder stacks whose attention maps forward(..., capture=) / forward_single(..., capture=) can return: state-dict prefix ->
         number of layers (the window-type block and the HRFormer stage are not encoder stacks)"""
         out = {}
-        if getattr(self, "single_layers", None):
+        if self.single_layers:
             out[self.single_stack] = len(self.single_layers)
-        if getattr(self, "layers", None):
-            out["global_encoder" if self.name == "interformer_pureMulti" else "multi_global_encoder"] = len(self.layers)
+        if self.layers:
+            out[self.inter_stack] = len(self.layers)
         return out
 
     def capture_map_sizes(self, H, W):
         """token map (h, w) of every capture stack for [H, W] network inputs: stack -> (h, w); a group of that stack is persons * h * w tokens"""
         M, out = self.cfg["MODEL"], {}
         fh = fw = None
-        if getattr(self, "single_layers", None):
+        if self.single_layers:
             r = 4 * 2 ** self.res_layer
             fh, fw = H // r, W // r
             out[self.single_stack] = (fh, fw)
         elif self.singleformer:  # (HRFormer first stage: its highest-resolution branch)
             fh, fw = H // 4, W // 4
-        if getattr(self, "layers", None):
+        if self.layers:
             if fh is None:  # the bare tower's lowest branch (_build)
                 down = 4 * 2 ** (M["EXTRA"]["STAGE3"]["NUM_BRANCHES"] - 1)
                 fh, fw = H // down, W // down
             else:
                 for _ in range(int(math.log(fw // M["TRANS_SIZE"][-1], 2))):  # (3x3 stride-2 max-pool steps down to TRANS_SIZE)
                     fh, fw = (fh + 1) // 2, (fw + 1) // 2
-            out["global_encoder" if self.name == "interformer_pureMulti" else "multi_global_encoder"] = (fh, fw)
+            out[self.inter_stack] = (fh, fw)
         return out
 
     def _capture_spec(self, capture, stack, layers, d=None):
@@ -2294,16 +1812,14 @@ class Engine:
         want = sorted(i for st, i in capture if st == stack)
         if not want:
             return None
-        cache = self.__dict__.setdefault("_capture_packs", {})
+        cache = self._capture_packs
         packs = {}
         for i in want:
             L = layers[i]
             if not L.get("mh"):
                 if (stack, i) not in cache:
-                    if getattr(self, "_pk32", None) is None:
-                        self._pk32 = self._pk if self._pk.dtype == 0 else Packer(self._pk.sd, self.device, "fp32")
                     M = self.cfg["MODEL"]
-                    cache[(stack, i)] = self._pk32.encoder_layer_mh("%s.layers.%d" % (stack, i), L["d"] if d is None else d, M["DIM_FEEDFORWARD"], M["N_HEAD"])
+                    cache[(stack, i)] = self._fp32_packer().encoder_layer_mh("%s.layers.%d" % (stack, i), L["d"] if d is None else d, M["DIM_FEEDFORWARD"], M["N_HEAD"])
                 L = cache[(stack, i)]
             packs[i] = L
         return dict(stack=stack, layers=packs)
@@ -2381,7 +1897,7 @@ class Engine:
         of an image (a 3-D pos is not permuted, attention.py:131-137), so person q owns rows [q h w, (q + 1) h w).  Computed on the
         host with the reference's own sequence of torch CPU ops (it builds the table on the CPU in every forward) -> [n, h w, cs] on the device."""
         key = (n, h, w, d)
-        cache = self.__dict__.setdefault("_sine_tables", {})
+        cache = self._sine_tables
         if key not in cache:
             W = n * w
             area = torch.ones(1, h, W)
@@ -2404,12 +1920,13 @@ class Engine:
             cache[key] = out.to(self.device)
         return cache[key]
 
-    def _fill_sine(self, patch, glen):
-        """rows of the 'sine' multi-position embedding for the crops of this forward (glen: persons per token group, capacity groups included)"""
+    def _fill_sine(self, patch, glen, sine_n):
+        """rows of the 'sine' multi-position embedding for the crops of this forward (glen: persons per token group, capacity groups
+        included; sine_n: max(length) of the WHOLE batch -- the canvas is that many persons wide for every part of it)"""
         pos = patch.get("pos_sine")
         if pos is None:
             return
-        n = max(self._sine_n, 1)
+        n = max(sine_n, 1)
         key = (n, tuple(glen))
         if patch.get("_sine_key") == key:
             return
@@ -2448,18 +1965,23 @@ class Engine:
             b = c
         return b, pe_args
 
+    def _new_program(self, query=None):
+        """an empty Program of this engine's storage type; query: the program-key suffix of _check_queries, or None"""
+        P = Program(self.device)
+        P.store_dt = self.store_dt
+        P.query = (query[1], dict(query[3])) if query else None
+        return P
+
     def _build(self, S, H, W, length, flip=False, part=None, capture=(), query=None):
         """flip: the flip test of validate() (lib/core/function.py:142-162) batched into the same forward -- crops S..2S-1 are
         the mirrored copies (mirroring happens inside the stem kernels), every image appears twice as a token group.
         part (models whose first stage is the bare HRNet tower): "tower" = the per-crop tower + reduce only -> (P, patch, features Act);
         "tail" = everything behind it (position branch, inter-human encoder, deconvs, head) reading a feature buffer that tower
         programs fill (patch["feat"]) -- the two halves of a part-batch forward (_forward_split).
-        capture: frozenset of (stack, layer) whose attention maps the program computes too (Program.set_capture); query: (mode, scale) --
-        their rows / columns at query points instead (Program.set_query_capture)."""
+        capture: frozenset of (stack, layer) whose attention maps the program computes too (Program.set_capture); query: the key suffix
+        of _check_queries -- their rows / columns at query points instead (Program.set_query_capture)."""
         M = self.cfg["MODEL"]
-        P = Program(self.device, multi_lane=self.multi_lane)
-        P.store_dt = self.store_dt
-        P.query = query
+        P = self._new_program(query)
         patch = {}
         n_src = S
         if flip:
@@ -2513,13 +2035,8 @@ class Engine:
             pos, patch["pos_mask"] = self._pos_branch(P, S, H, W, M["TRANS_SIZE"][-1], n_src=n_src, cat=cat)
             assert (pos.h, pos.w, pos.cs) == (f.h, f.w, f.cs)
             pos_ptr = pos.ptr if cat is None else 0  # (concatenated: the encoder gets no additive embedding, interformer.py:299)
-        tok = f.h * f.w
-        offs = [0]
-        for n in length:
-            offs.append(offs[-1] + n * tok)
-        stack = "global_encoder" if self.name == "interformer_pureMulti" else "multi_global_encoder"
-        cap = self._capture_spec(capture, stack, self.layers, d=f.c) if capture else None
-        e = P.encoder(f, self.layers, offs, pos=pos_ptr, regroupable=True, pre_norm=self.pre_norm, capture=cap)
+        cap = self._capture_spec(capture, self.inter_stack, self.layers, d=f.c) if capture else None
+        e = P.encoder(f, self.layers, self._token_offsets(length, f.h * f.w), pos=pos_ptr, regroupable=True, pre_norm=self.pre_norm, capture=cap)
         if cat is not None:  # self.fc: Conv2d(DIM_MODEL + MULTI_POS_EMBEDDING_DIM, DIM_MODEL, 1) with bias (interformer.py:157-158,302-303)
             t = P.conv(e, self.cat_fc, out_dt=0)
             P.release(e)
@@ -2551,13 +2068,12 @@ class Engine:
         if pos_p is not None:
             P.release(pos_p)
         att = P.alloc(B * Pm, f.h, f.w, L["hs"])
-        goff = torch.tensor([b * Pm * hw for b in range(B + 1)], dtype=torch.int32).to(self.device)
+        goff = torch.zeros(B + 1, dtype=torch.int32, device=self.device)
         klen = torch.tensor([n * hw for n in length], dtype=torch.int32).to(self.device)
         P.keep += [goff, klen, L]
-        nq16, nq32, nq64 = (B * (-(-(Pm * hw) // t)) for t in (16, 32, 64))
-        a = cabi.MhAttnArgs(qk.ptr, v.ptr, att.ptr, goff.data_ptr(), B, L["heads"], L["hp"], L["hs"], qk.cs, v.cs, att.cs, nq16, nq32, nq64, klen.data_ptr())
+        a = cabi.MhAttnArgs(qk.ptr, v.ptr, att.ptr, goff.data_ptr(), 0, L["heads"], L["hp"], L["hs"], qk.cs, v.cs, att.cs, 0, 0, 0, klen.data_ptr())
         P.ops.append((cabi.OP_MH_ATTN, 0, a))
-        P.enc_stacks.append(dict(descs=[], mh=[a], goff=goff, current=tuple(b * Pm * hw for b in range(B + 1))))
+        P._register_stack(dict(descs=[], mh=[a], goff=goff, current=None), [b * Pm * hw for b in range(B + 1)])  # (groups = the padded images)
         P.release(qk, v)
         o = P.conv(att, L["o"])
         P.release(att)
@@ -2567,9 +2083,8 @@ class Engine:
 
     def _emit_tail(self, P, patch, e, single_feat):
         """up-sampling layers (+ the 2-stage residual / DOMAIN_TRANS) and final_layer behind the inter-human encoder output e"""
-        dtr = getattr(self, "domain_trans", None)
+        dtr, uc = self.domain_trans, self.upconv
         res_feat = single_feat if dtr is None else None
-        uc = getattr(self, "upconv", None)
         if uc is not None:
             u = P.conv(e, uc["fuse"], up=uc["scale"])
             P.release(e)
@@ -2600,8 +2115,7 @@ class Engine:
         key = (S, H, W, "backbone")
         with torch.cuda.device(self.device):
             def build():
-                P = Program(self.device)
-                P.store_dt = self.store_dt
+                P = self._new_program()
                 xs, px = self.tower.emit(P, S, H, W, n_src=S, need={-1})
                 f = P.conv(xs[-1], self.reduce, out_dt=0)
                 P.release(*xs)
@@ -2625,9 +2139,7 @@ class Engine:
         key = (S, H, W, "single") + (("capture", capture) if capture else ()) + (query or ())
         with torch.cuda.device(self.device):
             def build():
-                P = Program(self.device)
-                P.store_dt = self.store_dt
-                P.query = (query[1], dict(query[3])) if query else None
+                P = self._new_program(query)
                 g, px = self._emit_single(P, S, H, W, S, capture)
                 hd = P.head(g, self.single_head)
                 P.finalize()
@@ -2714,18 +2226,17 @@ class Engine:
         stack): maps[(stack, layer)] = per group a [K_g, persons, h r, w r] view.  One program per (capture set, mode, K capacity, scales) --
         K is in the key although every K-dependent field is patched per call: a caller asks with one K; new points or another grouping
         at the same capacity reuse it."""
-        M = self.cfg["MODEL"]
         assert x.dim() == 4 and x.shape[1] == 3 and x.dtype == torch.float32
         S, _, H, W = x.shape
         assert S == sum(length), "sum(length)=%d != number of crops %d" % (sum(length), S)
         assert all(n >= 1 for n in length), "every image needs at least one person"
-        self._sine_n = max(length)  # (MULTI_POS_EMBEDDING sine: the canvas is max(length) persons wide, for every part of this batch)
+        sine_n = max(length)  # (MULTI_POS_EMBEDDING sine: the canvas is max(length) persons wide, for every part of this batch)
         if capture:
             capture = self._check_capture(capture)
             assert flip_joint_map is None and not self.window_attn, "attention maps: no flip test, no window-type block"
             query = self._check_queries(queries, capture)
             with torch.cuda.device(self.device):
-                return self._forward_part(x, pos_mask, list(length), None, S, H, W, capture=capture, queries=queries, query=query)
+                return self._forward_part(x, pos_mask, list(length), None, S, H, W, sine_n, capture=capture, queries=queries, query=query)
         if queries is not None:
             self._check_queries(queries, capture)
         if self.window_attn and flip_joint_map is not None:
@@ -2734,16 +2245,28 @@ class Engine:
             with torch.cuda.device(self.device):
                 x = x.to(self.device)
                 pm = pos_mask.to(self.device) if pos_mask is not None else None
-                a = self._forward(x, pm, list(length), None, S, H, W)
-                b = self._forward(torch.flip(x, dims=[3]), torch.flip(pm, dims=[3]) if pm is not None else None, list(length), None, S, H, W)
+                a = self._forward(x, pm, list(length), None, S, H, W, sine_n)
+                b = self._forward(torch.flip(x, dims=[3]), torch.flip(pm, dims=[3]) if pm is not None else None, list(length), None, S, H, W, sine_n)
                 a, b = (a["multi"], b["multi"]) if isinstance(a, dict) else (a, b)
-                J = M["NUM_JOINTS"]
-                merged = torch.empty(S, J, H // 4, W // 4, dtype=torch.float32, device=self.device)
-                cabi.check(cabi.lib().i2r_flip_merge(a.contiguous().data_ptr(), b.contiguous().data_ptr(), flip_joint_map.data_ptr(), merged.data_ptr(),
-                                                     S, J, H // 4, W // 4, torch.cuda.current_stream(self.device).cuda_stream), "i2r_flip_merge")
-                return merged
+                return self._flip_merge(a.contiguous(), b.contiguous(), flip_joint_map, S, H, W)
         with torch.cuda.device(self.device):  # kernels and events go to the CURRENT device: make it this engine's
-            return self._forward(x, pos_mask, list(length), flip_joint_map, S, H, W)
+            return self._forward(x, pos_mask, list(length), flip_joint_map, S, H, W, sine_n)
+
+    def _flip_merge(self, a, b, flip_joint_map, S, H, W):
+        """i2r_flip_merge on the current stream: the heat maps a [>= S, J, H/4, W/4] merged with those of the mirrored crops b"""
+        J = self.cfg["MODEL"]["NUM_JOINTS"]
+        merged = torch.empty(S, J, H // 4, W // 4, dtype=torch.float32, device=self.device)
+        cabi.check(cabi.lib().i2r_flip_merge(a.data_ptr(), b.data_ptr(), flip_joint_map.data_ptr(), merged.data_ptr(),
+                                             S, J, H // 4, W // 4, torch.cuda.current_stream(self.device).cuda_stream), "i2r_flip_merge")
+        return merged
+
+    @staticmethod
+    def _token_offsets(glen, tok):
+        """persons per token group -> the groups' token offsets [groups + 1] at tok tokens per person"""
+        offs = [0]
+        for n in glen:
+            offs.append(offs[-1] + n * tok)
+        return offs
 
     # Part-batches on separate streams (round 4).  The images of a batch are independent: `_split_bounds` cuts a batch of the HRNet /
     # TransPose-H towers into SPLIT_PARTS contiguous image groups balanced by crop count (dist.shard_bounds) and `_forward` runs one
@@ -2761,7 +2284,7 @@ class Engine:
         tower's total stride; any other size takes the one-program path, which handles it)"""
         from .dist import shard_bounds
         parts = min(self.SPLIT_PARTS, len(length))
-        if parts < 2 or sum(length) < self.SPLIT_MIN_CROPS or not isinstance(getattr(self, "tower", None), HRNetW48):
+        if parts < 2 or sum(length) < self.SPLIT_MIN_CROPS or not isinstance(self.tower, HRNetW48):
             return None
         if H is not None and (H % 16 or W % 16):
             return None
@@ -2774,46 +2297,60 @@ class Engine:
             return None
         return bounds
 
-    def _forward(self, x, pos_mask, length, flip_joint_map, S, H, W):
+    def _forward(self, x, pos_mask, length, flip_joint_map, S, H, W, sine_n):
         bounds = self._split_bounds(length, H, W)
         if bounds is None:
-            return self._forward_part(x, pos_mask, length, flip_joint_map, S, H, W, slot=0)
+            return self._forward_part(x, pos_mask, length, flip_joint_map, S, H, W, sine_n, slot=0)
         if self.name == "interformer_pureMulti" or not self.singleformer:
-            return self._forward_split(x, pos_mask, length, flip_joint_map, S, H, W, bounds)
+            return self._forward_split(x, pos_mask, length, flip_joint_map, S, H, W, sine_n, bounds)
         parts = len(bounds) - 1
         offs = [sum(length[:b]) for b in bounds]
         x = x.to(self.device).contiguous()
         pm = pos_mask.to(self.device, torch.float32).contiguous() if pos_mask is not None else None
-        cur = torch.cuda.current_stream(self.device)
-        if len(getattr(self, "_part_streams", ())) < parts - 1:
-            self._part_streams = lane_streams(self.device, max(3, parts - 1))[:parts - 1]  # (programs that split use no lanes: the lane streams serve)
-            self._part_events = [torch.cuda.Event() for _ in range(parts)]
-        e_fork = self._part_events[0]
-        e_fork.record(cur)  # (the inputs are ready on the caller's stream)
-        self._phase_mark(cur, 0)
-        ys, progs = [None] * parts, []
-        for i in range(1, parts):
-            st = self._part_streams[i - 1]
-            x.record_stream(st)
-            if pm is not None:
-                pm.record_stream(st)
-            with torch.cuda.stream(st):
-                st.wait_event(e_fork)
-                ys[i] = self._forward_part(x[offs[i]:offs[i + 1]], pm[offs[i]:offs[i + 1]] if pm is not None else None,
-                                           length[bounds[i]:bounds[i + 1]], flip_joint_map, offs[i + 1] - offs[i], H, W, slot=i)
-                self._part_events[i].record(st)
-            progs += self.last_programs
-        ys[0] = self._forward_part(x[:offs[1]], pm[:offs[1]] if pm is not None else None, length[:bounds[1]], flip_joint_map, offs[1], H, W, slot=0)
-        self.last_programs = self.last_programs + progs
+        progs = [None] * parts
+
+        def run_part(i):
+            y = self._forward_part(x[offs[i]:offs[i + 1]], pm[offs[i]:offs[i + 1]] if pm is not None else None,
+                                   length[bounds[i]:bounds[i + 1]], flip_joint_map, offs[i + 1] - offs[i], H, W, sine_n, slot=i)
+            progs[i] = self.last_programs
+            return y
+        ys = self._fork_parts(range(1, parts), [x] if pm is None else [x, pm], run_part)
+        self.last_programs = [P for part in progs for P in part]
         self.last_concurrent = list(self.last_programs)
-        for i in range(1, parts):
-            cur.wait_event(self._part_events[i])
-            for t in (ys[i].values() if isinstance(ys[i], dict) else (ys[i],)):
+        cur = torch.cuda.current_stream(self.device)
+        for y in ys[1:]:
+            for t in (y.values() if isinstance(y, dict) else (y,)):
                 t.record_stream(cur)  # (allocated on the side stream, consumed on the caller's)
-        self._phase_mark(cur, 1)
         if isinstance(ys[0], dict):
             return {key: torch.cat([y[key] for y in ys], 0) for key in ys[0]}
         return torch.cat(ys, 0)
+
+    def _fork_parts(self, side, inputs, run_part):
+        """The fork / join of a part-batch forward.  run_part(i) issues part i on the current stream: first every side part i of `side`, in
+        that order, on its own stream behind an event that marks `inputs` ready on the caller's stream, then part 0 on the caller's
+        stream (its launches queue behind the side streams'), which finally waits for every side part.  -> [run_part(i)] by part."""
+        parts = len(side) + 1
+        cur = torch.cuda.current_stream(self.device)
+        if len(self._part_streams) < parts - 1:
+            self._part_streams = lane_streams(self.device, max(3, parts - 1))[:parts - 1]  # (programs that split use no lanes: the lane streams serve)
+            self._part_events = [torch.cuda.Event() for _ in range(parts)]
+        e_fork = self._part_events[0]
+        e_fork.record(cur)  # (the inputs are ready on the caller's stream, and what it ran before has read the buffers the parts write)
+        self._phase_mark(cur, 0)
+        res = [None] * parts
+        for i in side:
+            st = self._part_streams[i - 1]
+            for t in inputs:
+                t.record_stream(st)
+            with torch.cuda.stream(st):
+                st.wait_event(e_fork)
+                res[i] = run_part(i)
+                self._part_events[i].record(st)
+        res[0] = run_part(0)
+        for i in range(1, parts):
+            cur.wait_event(self._part_events[i])
+        self._phase_mark(cur, 1)
+        return res
 
     # bench.py: the span of the CONCURRENT part-batch programs of a forward (fork -> join) between two timing events on the caller's
     # stream -- two markers per forward instead of one per launch, so the forward runs at its product speed (phase_events = [e0, e1]
@@ -2839,84 +2376,38 @@ class Engine:
                 self.programs.pop(next(iter(self.programs)))
         return self.programs[key]
 
-    def _forward_split(self, x, pos_mask, length, flip_joint_map, S, H, W, bounds):
+    def _forward_split(self, x, pos_mask, length, flip_joint_map, S, H, W, sine_n, bounds):
         """Models whose first stage is the bare HRNet tower (vanilla I2R-Net): the per-crop TOWER of every image group runs as its own
         program on its own stream, the rest of the forward -- position branch, inter-human encoder over ALL images (one launch per
         layer: 384 query tiles with the partial key split instead of two launches of 192), deconvs, head -- as one tail program on
         the caller's stream behind the join.  The towers hand their features over with a row copy into the tail's buffer."""
-        M = self.cfg["MODEL"]
         parts = len(bounds) - 1
         flip = flip_joint_map is not None
         offs = [sum(length[:b]) for b in bounds]
         x = x.to(self.device).contiguous()
-        cur = torch.cuda.current_stream(self.device)
-        if len(getattr(self, "_part_streams", ())) < parts - 1:
-            self._part_streams = lane_streams(self.device, max(3, parts - 1))[:parts - 1]
-            self._part_events = [torch.cuda.Event() for _ in range(parts)]
         cap = self.capacity(S)
         Pt, patch = self._program((cap, H, W, flip, "tail"), lambda: self._build(cap, H, W, list(length) + [1] * (cap - S), flip, part="tail"))
         feat = patch["feat"].view()  # [cap (x 2 with the flip test), h, w, cs]
-        e_fork = self._part_events[0]
-        e_fork.record(cur)  # (the inputs are ready, and the tail of the previous forward has read the feature buffer)
-        self._phase_mark(cur, 0)
-        progs = []
-        for i in range(parts - 1, -1, -1):  # (the caller's stream takes part 0 last: its launches queue behind the side streams')
+
+        def run_tower(i):
             sp = offs[i + 1] - offs[i]
             capp = self.capacity(sp)
-            st = self._part_streams[i - 1] if i else cur
-            if i:
-                x.record_stream(st)
-            with torch.cuda.stream(st):
-                if i:
-                    st.wait_event(e_fork)
-                Pw, pw, f = self._program((capp, H, W, flip, "tower", i), lambda: self._build(capp, H, W, [1] * capp, flip, part="tower"))
-                xi = x[offs[i]:offs[i + 1]]
-                pw["x"].in_ = xi.data_ptr()
-                pw["x"].n_valid = sp
-                Pw.run()
-                fv = f.view()
-                feat[offs[i]:offs[i + 1]].copy_(fv[:sp])
-                if flip:
-                    feat[cap + offs[i]:cap + offs[i + 1]].copy_(fv[capp:capp + sp])
-                if i:
-                    self._part_events[i].record(st)
-            progs.append(Pw)
-        for i in range(1, parts):
-            cur.wait_event(self._part_events[i])
-        self._phase_mark(cur, 1)
-        # ---- the tail, as _forward_part runs a whole program ----
-        glen = list(length) + [1] * (cap - S)
-        if flip:
-            glen = glen + glen
-        for grouping, tok in Pt.groupings:
-            go = [0]
-            for n in glen:
-                go.append(go[-1] + n * tok)
-            Pt.set_groups(grouping, go)
-        self._fill_sine(patch, glen)
-        J = M["NUM_JOINTS"]
-        keep = [x]
-        if "pos_mask" in patch:
-            pm = pos_mask.to(self.device, torch.float32).contiguous()
-            assert pm.shape == (S, 1, H, W)
-            patch["pos_mask"].in_ = pm.data_ptr()
-            patch["pos_mask"].n_valid = S
-            keep.append(pm)
-        n_out = 2 * cap if flip else cap
-        out = torch.empty(n_out, J, H // 4, W // 4, dtype=torch.float32, device=self.device)
-        patch["multi"].out = out.data_ptr()
-        Pt.run()
-        self.last_programs = progs[::-1] + [Pt]
-        self.last_concurrent = progs[::-1]  # (ran side by side on their own streams: bench.py times them that way)
-        if flip:
-            merged = torch.empty(S, J, H // 4, W // 4, dtype=torch.float32, device=self.device)
-            cabi.check(cabi.lib().i2r_flip_merge(out.data_ptr(), out[cap:].data_ptr(), flip_joint_map.data_ptr(), merged.data_ptr(),
-                                                 S, J, H // 4, W // 4, cur.cuda_stream), "i2r_flip_merge")
-            return merged
-        return out[:S]
+            Pw, pw, f = self._program((capp, H, W, flip, "tower", i), lambda: self._build(capp, H, W, [1] * capp, flip, part="tower"))
+            xi = x[offs[i]:offs[i + 1]]
+            pw["x"].in_ = xi.data_ptr()
+            pw["x"].n_valid = sp
+            Pw.run()
+            fv = f.view()
+            feat[offs[i]:offs[i + 1]].copy_(fv[:sp])
+            if flip:
+                feat[cap + offs[i]:cap + offs[i + 1]].copy_(fv[capp:capp + sp])
+            return Pw
+        progs = self._fork_parts(range(parts - 1, 0, -1), [x], run_tower)
+        self.last_programs = progs + [Pt]
+        self.last_concurrent = progs  # (ran side by side on their own streams: bench.py times them that way)
+        return self._run_program(Pt, patch, None, pos_mask, length, flip_joint_map, S, cap, H, W, sine_n)
 
-    def _forward_part(self, x, pos_mask, length, flip_joint_map, S, H, W, slot=0, capture=frozenset(), queries=None, query=None):
-        M = self.cfg["MODEL"]
+    def _forward_part(self, x, pos_mask, length, flip_joint_map, S, H, W, sine_n, slot=0, capture=frozenset(), queries=None, query=None):
         x = x.to(self.device).contiguous()
         flip = flip_joint_map is not None
         # one program per (capacity, H, W, flip): the launch list and every buffer depend on the crop capacity only; the
@@ -2927,34 +2418,33 @@ class Engine:
             cap, key = S, (S, H, W, flip, "window", tuple(length))
         if capture:
             key = key + ("capture", capture) + (query or ())
-        P, patch = self._program(key, lambda: self._build(cap, H, W, list(length) + [1] * (cap - S), flip, capture=capture,
-                                                           query=(query[1], dict(query[3])) if query else None))
+        P, patch = self._program(key, lambda: self._build(cap, H, W, list(length) + [1] * (cap - S), flip, capture=capture, query=query))
         self.last_concurrent = []
-        self.last_programs = [P]  # the program(s) of the most recent forward (bench.py's per-launch timing pass replays them; _forward merges the parts')
+        self.last_programs = [P]  # (_forward merges the parts')
+        return self._run_program(P, patch, x, pos_mask, length, flip_joint_map, S, cap, H, W, sine_n, capture, queries, query)
+
+    def _run_program(self, P, patch, x, pos_mask, length, flip_joint_map, S, cap, H, W, sine_n, capture=frozenset(), queries=None, query=None):
+        """Bind one call into a built program of capacity `cap` and run it on the current stream: the token groups of `length` (capacity
+        slots as one-person groups), the sine rows, the inputs (x None: tower programs filled patch["feat"]), fresh outputs, the capture
+        buffers; then the flip merge and the slice to the S real crops.  -> what forward() returns."""
+        flip = flip_joint_map is not None
         glen = list(length) + [1] * (cap - S)
         if flip:
             glen = glen + glen
         for grouping, tok in P.groupings:
-            offs = [0]
-            for n in glen:
-                offs.append(offs[-1] + n * tok)
-            P.set_groups(grouping, offs)
-        self._fill_sine(patch, glen)
-        J = M["NUM_JOINTS"]
-        patch["x"].in_ = x.data_ptr()
-        patch["x"].n_valid = S
-        keep = [x]
+            P.set_groups(grouping, self._token_offsets(glen, tok))
+        self._fill_sine(patch, glen, sine_n)
+        if x is not None:
+            patch["x"].in_ = x.data_ptr()
+            patch["x"].n_valid = S
         if "pos_mask" in patch:
             pm = pos_mask.to(self.device, torch.float32).contiguous()
             assert pm.shape == (S, 1, H, W)
-            n_pm = S
             if self.window_attn:  # one more crop: the zero mask of the padded persons (_emit_window_block)
-                pm, n_pm = torch.cat([pm, pm.new_zeros(1, 1, H, W)], 0), S + 1
+                pm = torch.cat([pm, pm.new_zeros(1, 1, H, W)], 0)
             patch["pos_mask"].in_ = pm.data_ptr()
-            patch["pos_mask"].n_valid = n_pm
-            keep.append(pm)
-        n_out = 2 * cap if flip else cap
-        out = torch.empty(n_out, J, H // 4, W // 4, dtype=torch.float32, device=self.device)
+            patch["pos_mask"].n_valid = pm.shape[0]
+        out = torch.empty(2 * cap if flip else cap, self.cfg["MODEL"]["NUM_JOINTS"], H // 4, W // 4, dtype=torch.float32, device=self.device)
         patch["multi"].out = out.data_ptr()
         single = None
         if "single" in patch:
@@ -2964,18 +2454,14 @@ class Engine:
             glens = []
             for c in P.captures:
                 tok = c["x"].h * c["x"].w
-                glens.append([tok] * S if c["stack"] == getattr(self, "single_stack", None) else [n * tok for n in length])
+                glens.append([tok] * S if c["stack"] == self.single_stack else [n * tok for n in length])
             if query:
                 self._check_map_sizes(P, H, W)
             _, maps, inputs = P.set_query_capture(glens, queries) if query else P.set_capture(glens)
         P.run(self.side_streams if P.uses_lanes else None)
         if flip:
-            merged = torch.empty(S, J, H // 4, W // 4, dtype=torch.float32, device=self.device)
-            st = torch.cuda.current_stream(self.device).cuda_stream
-            cabi.check(cabi.lib().i2r_flip_merge(out.data_ptr(), out[cap:].data_ptr(), flip_joint_map.data_ptr(), merged.data_ptr(),
-                                                 S, J, H // 4, W // 4, st), "i2r_flip_merge")
-            return merged
-        res = {"single": single[:S], "multi": out[:S]} if self.name != "interformer_pureMulti" and self.return_dict else out[:S]
+            return self._flip_merge(out, out[cap:], flip_joint_map, S, H, W)
+        res = {"single": single[:S], "multi": out[:S]} if self.return_dict else out[:S]
         if capture:
             return res, self._capture_result(maps, inputs, S)
         return res

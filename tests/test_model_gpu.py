@@ -390,6 +390,39 @@ def test_sine_multi_position_embedding_follows_the_batch():
     assert (got - ref).abs().max().item() < TOL
 
 
+def test_sine_canvas_of_a_part_batch_forward_is_the_whole_batch_wide():
+    """MULTI_POS_EMBEDDING sine with a part-batch forward (TransPose-H first stage: Engine._forward's split), fp32: length [3, 1, 1, 1] is
+    cut into the parts [3] and [1, 1, 1], and the second part's own max(length) = 1 is not the batch's 3 -- its programs must still take
+    their rows from the canvas of the WHOLE batch (3 persons wide).  The split forward equals the one-program forward within 1e-4 (the
+    fp32 bound of test_tower_tail_split_flip_forward_matches_one_program) and the oracle within TOL."""
+    cfg, sd, _, _, _, _ = setup("ochtph_sine_l12")
+    net = eval("models." + cfg.MODEL.NAME + ".get_pose_net")(cfg, is_train=False)
+    net.load_state_dict(sd, strict=True)
+    net = net.cuda()
+    from i2r_amd import synth
+    x, m, length = synth.make_inputs([3, 1, 1, 1], 256, 192)
+    eng = net.engine()
+    saved = eng.SPLIT_MIN_CROPS, eng.SPLIT_MIN_PART
+    try:
+        eng.SPLIT_MIN_CROPS, eng.SPLIT_MIN_PART = 4, 1
+        assert eng._split_bounds(length, 256, 192) == [0, 1, 4]
+        y2 = net(x.cuda(), m.cuda(), length)
+        torch.cuda.synchronize()
+        assert len(eng.last_programs) == 2
+        eng.SPLIT_MIN_CROPS = 10 ** 9
+        y1 = net(x.cuda(), m.cuda(), length)
+        torch.cuda.synchronize()
+        assert len(eng.last_programs) == 1
+    finally:
+        eng.SPLIT_MIN_CROPS, eng.SPLIT_MIN_PART = saved
+    z = i2r_cpu.forward(sd, cfg, x, m, length)
+    for key in (y1 if isinstance(y1, dict) else {"multi": y1}):
+        a, b, ref = (y2[key], y1[key], z[key]) if isinstance(y1, dict) else (y2, y1, z)
+        assert a.shape == b.shape == ref.shape and torch.isfinite(a).all()
+        assert (a - b).abs().max().item() < 1e-4, key
+        assert (a.cpu() - ref).abs().max().item() < TOL, key
+
+
 def test_mismatched_two_stage_geometry_raises_instead_of_reading_out_of_bounds():
     """HRNET_RES_LAYER 1 makes the first stage emit 32x24 maps while the up-sampling path still ends at HEATMAP_SIZE 64x48: the reference
     fails on `single_res + x` (interformer.py:315); here the residual of the last deconv must be refused at program build (it used to be
