@@ -220,6 +220,24 @@ typedef struct i2r_pose_nms_args {
 } i2r_pose_nms_args;
 I2R_API int i2r_pose_nms(const i2r_pose_nms_args* a, void* stream);
 
+/* i2r_group_nearest -- the person groups of the reference's grouped test mode (PATCH_MODE main_target, lib/dataset/collater.py:28-51,
+ * 164-173).  Per image of n persons and p = max_patch: n == 1 gives one group [0]; otherwise every person t ("target") gets a group of
+ * k = min(n, p) members: t first, then the k - 1 other persons of the image smallest by the key (d(t, j), j), with
+ * d = (ax_t - ax_j)^2 + (ay_t - ay_j)^2 in float64, every operation rounded on its own.  That is the reference's order (np.linalg.norm
+ * of the anchor difference, a stable sort by it) whenever nobody else shares the target's anchor; with shared anchors the reference may
+ * put another person first, here the target always is.  One wave per target, no atomics: deterministic.
+ *   anchors     float64 [n_persons, 2] (device): the boxes' top-left corners (box[0], box[1])
+ *   person_off  int32 [n_img + 1] (device): the images' first persons; person_off[n_img] = n_persons
+ *   member_off  int32 [n_img + 1] (device): the images' first slots in `members`: member_off[b + 1] - member_off[b] = 1 for n = 1, else
+ *               n * min(n, p) -- known on the host from the person counts alone; member_off[n_img] = n_members
+ *   members     int32 [n_members] (device): global person indices, group after group (group g of the call is person g's).  A slot nobody
+ *               qualifies for (non-finite anchors) holds -1.  Nothing outside [0, n_members) and nothing outside an image's own slot
+ *               range is written; an image whose offsets do not describe the batch is skipped.
+ * max_patch outside 1..64, negative counts, n_members < n_persons: I2R_E_ARG.  n_persons == 0 or n_img == 0 returns I2R_OK without a
+ * launch; otherwise a null pointer is I2R_E_ARG. */
+I2R_API int i2r_group_nearest(const double* anchors, const int32_t* person_off, const int32_t* member_off, int32_t n_img, int32_t n_persons,
+                              int32_t n_members, int32_t max_patch, int32_t* members, void* stream);
+
 /* ---- keypoint OKS evaluation: what COCOeval(gt, dt, 'keypoints') computes from the rows above (pycocotools cocoeval.py; the package is
  * not part of this project, so parity with its output is unpinned: the yardstick is the float64 restatement tests/_cocoeval_ref.py) ----
  * i2r_oks_match -- computeOks + evaluateImg of every image, every area range and every threshold.  One workgroup per image.

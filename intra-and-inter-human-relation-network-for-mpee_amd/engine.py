@@ -463,6 +463,17 @@ class Program:
         self.ops.append((cabi.OP_ROWS_GATHER, lane, a))
         return out
 
+    def rows_gather_table(self, src, out, table, n_out, src_crop=0, out_crop=0, lane=0):
+        """crop out_crop + i of `out` = crop src_crop + table[i] of `src` (zeros for -1), i < n_out: the gather of rows_gather with a device
+        int32 table the CALLER owns and refills per call (the launch is fixed, the contents are not) and a window into both buffers"""
+        per = src.h * src.w * src.cs
+        assert src.dt == 0 and out.dt == 0 and (out.h, out.w, out.cs) == (src.h, src.w, src.cs), "rows_gather copies whole fp32 rows of one stride"
+        assert table.dtype == torch.int32 and table.numel() >= n_out and 0 <= out_crop and out_crop + n_out <= out.n and 0 <= src_crop < src.n
+        self.keep.append(table)
+        a = cabi.GatherArgs(src.ptr + 4 * per * src_crop, out.ptr + 4 * per * out_crop, table.data_ptr(), n_out, per)
+        self.ops.append((cabi.OP_ROWS_GATHER, lane, a))
+        return a
+
     def view_scramble(self, o, person_map, n_images, max_persons, c, lane=0):
         """GeneralTransformerBlock's re-viewing of the attention output (attention.py:1025-1029, i2r_view_scramble) + get_valid_output"""
         out = self.alloc(len(person_map), o.h, o.w, c)
@@ -2406,6 +2417,141 @@ class Engine:
         self.last_programs = progs + [Pt]
         self.last_concurrent = progs  # (ran side by side on their own streams: bench.py times them that way)
         return self._run_program(Pt, patch, None, pos_mask, length, flip_joint_map, S, cap, H, W, sine_n)
+
+    # ---- grouped forward: person groups that share crops (the reference's PATCH_MODE main_target, input.main_target_groups) ----
+    # The reference pushes every member of every group through the whole network.  The first stage is per crop, so here it runs once
+    # per DISTINCT crop; only the part behind it sees the expanded batch, and only the first member of every group reaches the
+    # up-sampling layers and the head.  Which crops make up which group is DATA of a call (two device tables), never part of a program.
+    def _groups_shared(self, H, W):
+        """True: the first stage is the bare HRNet tower and the tower / tail seam serves the groups; False: the expanded forward.
+        ValueError: a bare-tower model whose tail cannot take gathered rows."""
+        if self.name not in ("interformer_pureMulti", "interformer", "interformer_2stage"):
+            raise ValueError("forward_groups serves the inter-human models (MODEL.NAME %r has no person groups)" % self.name)
+        if not (self.name == "interformer_pureMulti" or not self.singleformer) or not isinstance(self.tower, HRNetW48):
+            return False
+        if self.use_pos and self.pe_mode == "sine":
+            raise ValueError("forward_groups: MULTI_POS_EMBEDDING sine is not served (its table depends on a crop's position inside the group)")
+        if self.cat_concat:
+            raise ValueError("forward_groups: MULTI_POS_EMBEDDING cat_vec concatenated is not served (the hand-over buffer is DIM_MODEL wide)")
+        if self.window_attn:
+            raise ValueError("forward_groups: ATTENTION_TYPE window is not served (its block re-views the whole batch's output)")
+        return not (H % 16 or W % 16)  # (the tower's and the tail's map sizes must agree, as in _split_bounds)
+
+    @staticmethod
+    def _first_rows(group_len):
+        """row of every group's first member in the expanded batch"""
+        out, r = [], 0
+        for n in group_len:
+            out.append(r)
+            r += n
+        return out
+
+    def forward_groups(self, x, pos_mask, members, group_len, flip_joint_map=None):
+        """x [S, 3, H, W], pos_mask [S, 1, H, W]: the DISTINCT crops of a batch; members: device int32 [sum(group_len)] of crop indices in
+        [0, S), group after group (input.main_target_groups); group_len: host list of the groups' sizes.  -> the 'multi' heat maps of the
+        FIRST member of every group, [len(group_len), J, H/4, W/4] -- what the reference's validate_main_target keeps of model(x[members],
+        pos_mask[members], group_len) (get_target_person, lib/core/function.py:309-334); with flip_joint_map merged with the flip test's.
+        Models whose first stage is the bare HRNet tower run it once per crop (S, not sum(group_len), times) and the tail on the gathered
+        rows; every other model runs the expanded forward.  Programs are keyed by capacities only: other groups of the same sizes build nothing."""
+        assert x.dim() == 4 and x.shape[1] == 3 and x.dtype == torch.float32
+        S, _, H, W = x.shape
+        group_len = [int(n) for n in group_len]
+        assert group_len and all(n >= 1 for n in group_len), "every group needs at least one member"
+        assert torch.is_tensor(members) and members.numel() == sum(group_len), "members: %d entries for groups of %d" % (members.numel(), sum(group_len))
+        members = members.to(self.device, torch.int32).contiguous().view(-1)
+        with torch.cuda.device(self.device):
+            x = x.to(self.device).contiguous()
+            pm = pos_mask.to(self.device, torch.float32).contiguous() if pos_mask is not None else None
+            if self._groups_shared(H, W):
+                return self._forward_groups_shared(x, pm, members, group_len, flip_joint_map, S, H, W)
+            # not shared: the reference's own arithmetic on the gathered inputs (index plumbing in torch, every launch in forward())
+            idx = members.long()
+            y = self.forward(x.index_select(0, idx), pm.index_select(0, idx) if pm is not None else None, group_len, flip_joint_map)
+            y = y["multi"] if isinstance(y, dict) else y
+            return y.index_select(0, torch.tensor(self._first_rows(group_len), dtype=torch.long).to(self.device))
+
+    def _build_groups(self, capS, capG, capN, H, W, flip):
+        """The tail program of a grouped forward: person features [capS] (filled by tower programs, patch["pfeat"]) -> rows gathered by the
+        member table into group layout [capG] -> position branch on the gathered masks, inter-human encoder -> the first row of every
+        group [capN] -> up-sampling layers, head.  With the flip test every buffer holds the mirrored half behind the plain one."""
+        M = self.cfg["MODEL"]
+        P = self._new_program()
+        patch, k = {}, (2 if flip else 1)
+        down = 4 * 2 ** (M["EXTRA"]["STAGE3"]["NUM_BRANCHES"] - 1)
+        pf = patch["pfeat"] = P.alloc(k * capS, H // down, W // down, self.reduce.cout)
+        pf.t.zero_()
+        mtab = patch["members"] = torch.full((capG,), -1, dtype=torch.int32, device=self.device)
+        ftab = patch["first"] = torch.full((capN,), -1, dtype=torch.int32, device=self.device)
+        f = P.alloc(k * capG, pf.h, pf.w, pf.c)
+        for half in range(k):
+            P.rows_gather_table(pf, f, mtab, capG, src_crop=half * capS, out_crop=half * capG)
+        pos_ptr = 0
+        if self.use_pos:
+            assert (H * W) % 4 == 0
+            gm = torch.zeros(capG * H * W, dtype=torch.float32, device=self.device)  # the members' masks [capG, 1, H, W]
+            P.keep.append(gm)
+            P.nbytes += gm.numel() * 4
+            patch["mask_gather"] = cabi.GatherArgs(0, gm.data_ptr(), mtab.data_ptr(), capG, H * W)  # (src: the call's pos_mask)
+            P.ops.append((cabi.OP_ROWS_GATHER, 0, patch["mask_gather"]))
+            pos, pe = self._pos_branch(P, k * capG, H, W, M["TRANS_SIZE"][-1], n_src=capG)
+            pe.in_, pe.n_valid = gm.data_ptr(), capG
+            assert (pos.h, pos.w, pos.cs) == (f.h, f.w, f.cs)
+            pos_ptr = pos.ptr
+        e = P.encoder(f, self.layers, self._token_offsets([1] * (k * capG), f.h * f.w), pos=pos_ptr, regroupable=True, pre_norm=self.pre_norm)
+        e1 = P.alloc(k * capN, e.h, e.w, e.c)
+        for half in range(k):
+            P.rows_gather_table(e, e1, ftab, capN, src_crop=half * capG, out_crop=half * capN)
+        P.release(e)
+        return self._emit_tail(P, patch, e1, None)
+
+    def _forward_groups_shared(self, x, pm, members, group_len, flip_joint_map, S, H, W):
+        flip = flip_joint_map is not None
+        G, N = sum(group_len), len(group_len)
+        capS, capG, capN = self.capacity(S), self.capacity(G), self.capacity(N)
+        Pt, patch = self._program((capG, capN, capS, H, W, flip, "groups"), lambda: self._build_groups(capS, capG, capN, H, W, flip))
+        pfeat = patch["pfeat"].view()  # [capS (x 2 with the flip test), h, w, cs]
+        bounds = self._split_bounds([1] * S, H, W) or [0, S]  # (the tower is per crop: any cut of the S crops serves)
+        parts = len(bounds) - 1
+
+        def run_tower(i):
+            sp = bounds[i + 1] - bounds[i]
+            capp = self.capacity(sp)
+            Pw, pw, f = self._program((capp, H, W, flip, "tower", i), lambda: self._build(capp, H, W, [1] * capp, flip, part="tower"))
+            xi = x[bounds[i]:bounds[i + 1]]
+            pw["x"].in_ = xi.data_ptr()
+            pw["x"].n_valid = sp
+            Pw.run()
+            fv = f.view()
+            pfeat[bounds[i]:bounds[i + 1]].copy_(fv[:sp])
+            if flip:
+                pfeat[capS + bounds[i]:capS + bounds[i + 1]].copy_(fv[capp:capp + sp])
+            return Pw
+        progs = self._fork_parts(range(parts - 1, 0, -1), [x], run_tower) if parts > 1 else [run_tower(0)]
+        self.last_programs = progs + [Pt]
+        self.last_concurrent = progs if parts > 1 else []
+        # bind the call: the two tables, the token groups (capacity slots: one-person groups of zero rows), the masks, a fresh output
+        patch["members"].fill_(-1)
+        patch["members"][:G].copy_(members)
+        fkey = tuple(group_len)
+        if patch.get("_first_key") != fkey:
+            first = self._first_rows(group_len) + [-1] * (capN - N)
+            patch["first"].copy_(torch.tensor(first, dtype=torch.int32).pin_memory(), non_blocking=True)
+            patch["_first_key"] = fkey
+        glen = group_len + [1] * (capG - G)
+        if flip:
+            glen = glen + glen
+        for grouping, tok in Pt.groupings:
+            Pt.set_groups(grouping, self._token_offsets(glen, tok))
+        if "mask_gather" in patch:
+            assert pm is not None and pm.shape == (S, 1, H, W)
+            patch["mask_gather"].src = pm.data_ptr()
+        k = 2 if flip else 1
+        out = torch.empty(k * capN, self.cfg["MODEL"]["NUM_JOINTS"], H // 4, W // 4, dtype=torch.float32, device=self.device)
+        patch["multi"].out = out.data_ptr()
+        Pt.run(self.side_streams if Pt.uses_lanes else None)
+        if flip:
+            return self._flip_merge(out, out[capN:], flip_joint_map, N, H, W)
+        return out[:N]
 
     def _forward_part(self, x, pos_mask, length, flip_joint_map, S, H, W, sine_n, slot=0, capture=frozenset(), queries=None, query=None):
         x = x.to(self.device).contiguous()

@@ -225,3 +225,72 @@ def collate(batch):
         ms.append(msk)
         length.append(int(inp.shape[0]))
     return torch.cat(xs), torch.cat(ms), length
+
+
+# ---- grouped test modes of the reference's collater (lib/dataset/collater.py:28-95 with DATASET.MAX_PATCH > 0) ----
+def window_lengths(length, max_patch):
+    """PATCH_MODE window (collater.py:68-91, extend_list): an image of more than max_patch persons is cut into consecutive chunks of
+    max_patch, the last one shorter.  The crops keep their order, so model(x, pos_mask, window_lengths(length, max_patch)) IS that mode."""
+    p = int(max_patch)
+    if p < 1:
+        raise ValueError("max_patch must be >= 1 (got %r)" % (max_patch,))
+    out = []
+    for n in length:
+        n = int(n)
+        out += [min(p, n - i) for i in range(0, n, p)] if n > p else [n]
+    return out
+
+
+def group_layout(length, max_patch):
+    """What the main_target grouping of a batch looks like, from the person counts alone: -> (group_len, person_off, member_off).  An
+    image of one person is one group of one; an image of n > 1 persons gives n groups of min(n, max_patch) members (collater.py:35-51).
+    group_len: members of every group, target by target (one group per person of the batch); person_off / member_off: the images' first
+    persons and first slots in the member table, [images + 1] each."""
+    p = int(max_patch)
+    if p < 1:
+        raise ValueError("max_patch must be >= 1 (got %r)" % (max_patch,))
+    group_len, person_off, member_off = [], [0], [0]
+    for n in length:
+        n = int(n)
+        if n < 1:
+            raise ValueError("every image needs at least one person (length %r)" % (list(length),))
+        k = 1 if n == 1 else min(n, p)
+        group_len += [k] * n
+        person_off.append(person_off[-1] + n)
+        member_off.append(member_off[-1] + n * k)
+    return group_len, person_off, member_off
+
+
+MAX_PATCH_LIMIT = 64  # i2r_group_nearest (include/i2r_hip.h)
+
+
+class PersonGroups:
+    """main_target_groups' result: members = device int32 [sum(group_len)] of global crop indices, group after group, every group's
+    target first; group_len = host list, one group per person of the batch in input order; n_groups = len(group_len)."""
+    __slots__ = ("members", "group_len", "n_groups", "_keep")
+
+    def __init__(self, members, group_len, keep=None):
+        self.members, self.group_len, self.n_groups, self._keep = members, list(group_len), len(group_len), keep
+
+
+def main_target_groups(boxes, length, max_patch, device="cuda:0"):
+    """PATCH_MODE main_target (collater.py:35-51): one group per person -- the person itself, then its min(n, max_patch) - 1 nearest
+    neighbours in the image by the distance between the boxes' top-left corners (i2r_group_nearest; equal distances: the lower index
+    first; the target always first, also where another person shares its corner).  boxes: [S, >= 2] (x, y, ...) per crop in batch order,
+    a host array or a device tensor of any float type; length: persons per image.  -> PersonGroups; nothing is read back from the device."""
+    dev = torch.device(device)
+    group_len, person_off, member_off = group_layout(length, max_patch)
+    if int(max_patch) > MAX_PATCH_LIMIT:
+        raise ValueError("max_patch %d: at most %d" % (int(max_patch), MAX_PATCH_LIMIT))
+    S, n_members, B = person_off[-1], member_off[-1], len(person_off) - 1
+    b = boxes if torch.is_tensor(boxes) else torch.from_numpy(np.asarray(boxes, dtype=np.float64).reshape(S, -1))
+    if b.dim() != 2 or b.shape[0] != S or b.shape[1] < 2 or not b.is_floating_point():
+        raise ValueError("boxes: shape %s %s, expected floating point [%d, >= 2]" % (tuple(b.shape), b.dtype, S))
+    anchors = b[:, :2].to(dev, torch.float64).contiguous()
+    offs = torch.tensor(person_off + member_off, dtype=torch.int32).to(dev)
+    members = torch.empty(n_members, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        cabi.check(cabi.lib().i2r_group_nearest(anchors.data_ptr(), offs.data_ptr(), offs.data_ptr() + 4 * (B + 1), B, S, n_members, int(max_patch),
+                                                members.data_ptr(), st), "i2r_group_nearest")
+    return PersonGroups(members, group_len, keep=(anchors, offs))  # (the tables must outlive the stream-ordered launch that reads them)

@@ -1,0 +1,212 @@
+"""-m gpu: the grouped forward (Engine.forward_groups / I2RModule.forward_main_target) at the golden tags' own 256 x 192 size, six
+persons: against the reference's validate_main_target output (tests/golden/w48_mt_p2_l213.npz, tools/make_golden_groups.py), against the
+existing goldens where every group is the whole image, and against the expanded forward of the same engine -- Engine.forward on
+x[members] with group_len, first rows kept: the code path the project had before the first stage was shared.
+Bars: the project's fp32 bar (1e-3 max-abs, BASELINE.json north_star) and bench.LP_TOL for bf16.
+
+Measured on MI355X (shared path against the expanded forward, fp32, max-abs over the six maps; printed by the test):
+    max_patch 1: 0 plain / 0 with the flip test;  max_patch 2: 6.7e-6 plain / 0 with the flip test (not bit-identical in general: 1e-3 is asserted);
+    24 persons in groups of 2 through the two part-batch tower programs: 0"""
+import numpy as np
+import pytest
+import torch
+
+from _golden import CASES, VARIANTS, load, setup
+from i2r_amd import cabi, caller, models
+from i2r_amd import input as i2r_input
+
+pytestmark = pytest.mark.gpu
+TOL = 1e-3
+FLIP_PAIRS = [[0, 1], [2, 3], [4, 5], [6, 7], [8, 9], [10, 11]]
+
+_NETS = {}
+
+
+def _net(tag, precision="fp32"):
+    """-> (net on the GPU, x, pos_mask, length, golden) -- one module per (config, precision) for the whole file"""
+    cfg, sd, x, m, length, g = setup(tag)
+    key = (tag if tag in VARIANTS else CASES[tag], precision)
+    if key not in _NETS:
+        net = eval("models." + cfg.MODEL.NAME + ".get_pose_net")(cfg, is_train=False)
+        net.load_state_dict(sd, strict=True)
+        _NETS[key] = net.cuda().set_precision(precision) if precision != "fp32" else net.cuda()
+    return _NETS[key], x.cuda(), m.cuda(), length, g
+
+
+def _mt():
+    g = load("w48_mt_p2_l213")
+    return g, g["boxes"], int(g["max_patch"][0])
+
+
+def _expanded(eng, x, m, groups, jm=None):
+    """the yardstick: the ordinary forward on the expanded batch, first row of every group """
+    idx = groups.members.long()
+    y = eng.forward(x[idx], m[idx], groups.group_len, flip_joint_map=jm)
+    y = y["multi"] if isinstance(y, dict) else y
+    first = np.concatenate([[0], np.cumsum(groups.group_len)[:-1]])
+    return y[torch.from_numpy(first).cuda()].clone()
+
+
+def test_reference_main_target_golden():
+    g, boxes, p = _mt()
+    net, x, m, length, _ = _net("w48_l213")
+    assert length == [int(v) for v in g["length"]] and p == 2
+    groups = i2r_input.main_target_groups(boxes, length, p)
+    assert groups.members.cpu().tolist() == g["members"].tolist() and groups.group_len == g["group_len"].tolist()
+    y = net.forward_main_target(x, m, length, boxes, max_patch=p)
+    torch.cuda.synchronize()
+    assert y.shape == g["out_multi"].shape and torch.isfinite(y).all()
+    err = np.abs(y.cpu().numpy() - g["out_multi"]).max()
+    print("w48_mt_p2_l213 vs reference max-abs %.3e" % err)
+    assert err < TOL, err
+
+
+@pytest.mark.parametrize("tag,p", [("w48_l213", 3), ("w48_l213", 7), ("bare_l21", 2)])
+def test_whole_image_groups_match_the_existing_goldens(tag, p):
+    """p >= max(length): every group is its whole image with the target moved to the front, so every person's map must be the one the
+    ordinary forward gives it (attention does not depend on the order of the persons; the position branch is per person)"""
+    net, x, m, length, g = _net(tag)
+    assert p >= max(length)
+    boxes = _mt()[1][:sum(length)]
+    y = net.forward_main_target(x, m, length, boxes, max_patch=p)
+    torch.cuda.synchronize()
+    err = np.abs(y.cpu().numpy() - g["out_multi"]).max(axis=(1, 2, 3))
+    print("%s p=%d vs reference golden, per person max-abs %s" % (tag, p, ["%.2e" % e for e in err]))
+    assert y.shape == g["out_multi"].shape and (err < TOL).all(), err
+
+
+@pytest.mark.parametrize("flip", [False, True])
+@pytest.mark.parametrize("p", [1, 2])
+def test_shared_path_against_the_expanded_forward(p, flip):
+    net, x, m, length, _ = _net("w48_l213")
+    eng = net.engine()
+    boxes = _mt()[1]
+    jm = caller.joint_map(FLIP_PAIRS, net.cfg.MODEL.NUM_JOINTS).to(eng.device) if flip else None
+    groups = i2r_input.main_target_groups(boxes, length, p)
+    want = _expanded(eng, x, m, groups, jm)
+    got = net.forward_main_target(x, m, length, boxes, max_patch=p, flip_pairs=FLIP_PAIRS if flip else None)
+    torch.cuda.synchronize()
+    err = (got - want).abs().max().item()
+    print("shared vs expanded forward: max_patch %d flip %s max-abs %.3e" % (p, flip, err))
+    assert got.shape == want.shape == (6, 14, 64, 48) and err < TOL, err
+
+
+def test_bf16_shared_path_within_the_16bit_bar():
+    import bench
+    g, boxes, p = _mt()
+    net, x, m, length, _ = _net("w48_l213", "bf16")
+    y = net.forward_main_target(x, m, length, boxes, max_patch=p)
+    torch.cuda.synchronize()
+    ref = g["out_multi"]
+    err = np.abs(y.cpu().numpy() - ref).max()
+    print("bf16 shared path vs fp32 reference golden: max-abs %.3e = %.2f %% of max|ref|" % (err, 100 * err / np.abs(ref).max()))
+    assert torch.isfinite(y).all() and err <= bench.LP_TOL["bf16"] * np.abs(ref).max()
+    assert err > 1e-4  # it really is the 16-bit path
+    towers = net.engine().last_programs[:-1]
+    assert towers and all(P.store_dt == 1 for P in towers)
+
+
+@pytest.mark.parametrize("flip", [False, True])
+def test_tower_runs_once_per_person_and_the_head_once_per_group(flip):
+    net, x, m, length, _ = _net("w48_l213")
+    eng = net.engine()
+    boxes = _mt()[1]
+    net.forward_main_target(x, m, length, boxes, max_patch=2, flip_pairs=FLIP_PAIRS if flip else None)
+    torch.cuda.synchronize()
+    *towers, tail = eng.last_programs
+    S, G, N = 6, 11, 6
+    stems = [a for P in towers for k, _, a in P.ops if k == cabi.OP_STEM]
+    assert len(stems) == len(towers) >= 1 and sum(a.n_valid for a in stems) == S
+    assert sum(a.n_img for a in stems) == eng.capacity(S) * (2 if flip else 1), "the tower saw S crops (and their mirrored copies), not sum(group_len)"
+    assert not any(k in (cabi.OP_ENC_LAYER, cabi.OP_HEAD) for P in towers for k, _, _ in P.ops)
+    heads = [a for k, _, a in tail.ops if k == cabi.OP_HEAD]
+    assert len(heads) == 1 and heads[0].n_img == eng.capacity(N) * (2 if flip else 1)
+    enc = [a for k, _, a in tail.ops if k == cabi.OP_ENC_LAYER]
+    assert enc and all(a.n_tok == eng.capacity(G) * (2 if flip else 1) * 16 * 12 for a in enc)
+    assert not any(k in (cabi.OP_STEM, cabi.OP_CONV_GROUP) and getattr(a, "cin", 0) == 3 for k, _, a in tail.ops), "no image stem in the tail"
+
+
+def test_part_batch_towers_from_24_crops_on():
+    """Engine.SPLIT_MIN_CROPS persons: the tower runs as the two part-batch programs on two streams, each filling its rows of the
+    person buffer; same bar against the expanded forward"""
+    from i2r_amd import synth
+    net, _, _, _, _ = _net("w48_l213")
+    eng = net.engine()
+    length = [4] * 6
+    assert sum(length) == eng.SPLIT_MIN_CROPS
+    x, m, _ = synth.make_inputs(length, 256, 192)
+    x, m = x.cuda(), m.cuda()
+    u = synth.uniform01(3, "test_main_target.boxes", 48).reshape(24, 2)
+    boxes = u * [560.0, 400.0]
+    groups = i2r_input.main_target_groups(boxes, length, 2)
+    want = _expanded(eng, x, m, groups)
+    got = net.forward_main_target(x, m, length, boxes, max_patch=2)
+    torch.cuda.synchronize()
+    *towers, tail = eng.last_programs
+    assert len(towers) == 2 and eng.last_concurrent == towers
+    stems = [a for P in towers for k, _, a in P.ops if k == cabi.OP_STEM]
+    assert [a.n_valid for a in stems] == [12, 12]
+    err = (got - want).abs().max().item()
+    print("24 persons, two tower programs: shared vs expanded forward max-abs %.3e" % err)
+    assert got.shape == want.shape == (24, 14, 64, 48) and err < TOL, err
+
+
+def test_other_boxes_rebuild_nothing_and_change_the_maps():
+    net, x, m, length, _ = _net("w48_l213")
+    eng = net.engine()
+    boxes = _mt()[1].copy()
+    a = net.forward_main_target(x, m, length, boxes, max_patch=2).clone()
+    n = eng.n_builds
+    other = boxes.copy()
+    other[4, :2] = (2000.0, 2000.0)  # person 1 of the last image moves far away: persons 0 and 2 of it become each other's neighbours
+    b = net.forward_main_target(x, m, length, other, max_patch=2)
+    torch.cuda.synchronize()
+    g0, g1 = i2r_input.main_target_groups(boxes, length, 2), i2r_input.main_target_groups(other, length, 2)
+    assert g0.group_len == g1.group_len and g0.members.cpu().tolist() != g1.members.cpu().tolist()
+    assert eng.n_builds == n, "new boxes of the same sizes must not build a program"
+    diff = (a - b).abs().amax(dim=(1, 2, 3)).cpu().numpy()
+    print("per person max-abs change with other boxes:", ["%.2e" % d for d in diff])
+    assert (diff[:3] == 0).all(), "images whose groups did not change give the same bits"
+    assert (diff[3:] > 1e-4).any()
+    assert torch.equal(net.forward_main_target(x, m, length, boxes, max_patch=2), a), "back to the first boxes: the first result"
+
+
+def test_single_person_images_equal_the_ordinary_forward():
+    net, x, m, length, _ = _net("w48_l213")
+    boxes = _mt()[1]
+    ones = [1] * 6
+    want = net(x, m, ones).clone()
+    got = net.forward_main_target(x, m, ones, boxes, max_patch=3)
+    torch.cuda.synchronize()
+    err = (got - want).abs().max().item()
+    print("six single-person images vs model(x, pos_mask, length): max-abs %.3e" % err)
+    assert err < TOL
+    want = net(x, m, length).clone()  # [2, 1, 3]: the single person of image 1
+    got = net.forward_main_target(x, m, length, boxes, max_patch=2)
+    assert (got[2] - want[2]).abs().max().item() < TOL
+
+
+def test_max_patch_defaults_to_the_config():
+    net, x, m, length, _ = _net("w48_l213")
+    boxes = _mt()[1]
+    p = int(net.cfg.DATASET.MAX_PATCH)
+    assert torch.equal(net.forward_main_target(x, m, length, boxes), net.forward_main_target(x, m, length, boxes, max_patch=p))
+
+
+def test_two_stage_model_runs_the_expanded_forward():
+    net, x, m, length, _ = _net("tph2s_l12")
+    eng = net.engine()
+    boxes = _mt()[1][:3]
+    groups = i2r_input.main_target_groups(boxes, length, 2)
+    assert groups.group_len == [1, 2, 2]
+    want = _expanded(eng, x, m, groups)
+    got = net.forward_main_target(x, m, length, boxes, max_patch=2)
+    torch.cuda.synchronize()
+    assert got.shape == (3,) + tuple(want.shape[1:]) and torch.equal(got, want)
+
+
+@pytest.mark.parametrize("tag", ["bare_sine_l213", "bare_win_l213"])
+def test_tails_that_depend_on_the_group_position_are_refused(tag):
+    net, x, m, length, _ = _net(tag)
+    with pytest.raises(ValueError, match="sine|window"):
+        net.forward_main_target(x, m, length, _mt()[1], max_patch=2)
