@@ -51,11 +51,13 @@ __global__ __launch_bounds__(256) void box_mask_k(const int* __restrict__ boxes,
     const int y = (int)((gid / ow) % oh);
     const int p = (int)(gid / ((long long)ow * oh));
     const int bx0 = boxes[p * 4], by0 = boxes[p * 4 + 1], bx1 = boxes[p * 4 + 2], by1 = boxes[p * 4 + 3];
-    const float sx = fmaxf(((float)x + 0.5f) * ((float)iw / (float)ow) - 0.5f, 0.f);
-    const float sy = fmaxf(((float)y + 0.5f) * ((float)ih / (float)oh) - 0.5f, 0.f);
+    // source coordinate in double: in fp32 it is off by 3 * 2^-24 * iw pixels (1e-5 at iw = 131, 3e-4 at 1920), which a mask edge
+    // inside the cell turns into that much of the output; the fraction is rounded to fp32 once
+    const double sx = fmax(((double)x + 0.5) * ((double)iw / (double)ow) - 0.5, 0.0);
+    const double sy = fmax(((double)y + 0.5) * ((double)ih / (double)oh) - 0.5, 0.0);
     const int x0 = min((int)sx, iw - 1), y0 = min((int)sy, ih - 1);
     const int x1 = min(x0 + 1, iw - 1), y1 = min(y0 + 1, ih - 1);
-    const float ax = x0 == iw - 1 ? 0.f : sx - (float)x0, ay = y0 == ih - 1 ? 0.f : sy - (float)y0;
+    const float ax = x0 == iw - 1 ? 0.f : (float)(sx - (double)x0), ay = y0 == ih - 1 ? 0.f : (float)(sy - (double)y0);
     const float ix0 = (x0 >= bx0 && x0 <= bx1) ? 1.f : 0.f, ix1 = (x1 >= bx0 && x1 <= bx1) ? 1.f : 0.f;
     const float iy0 = (y0 >= by0 && y0 <= by1) ? 1.f : 0.f, iy1 = (y1 >= by0 && y1 <= by1) ? 1.f : 0.f;
     out[((size_t)p * oh + y) * ow + x] = ((1.f - ax) * ix0 + ax * ix1) * ((1.f - ay) * iy0 + ay * iy1);

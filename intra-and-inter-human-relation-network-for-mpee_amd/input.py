@@ -7,7 +7,8 @@ cv2 for every person of an image (reference lib/dataset/JointsDataset.py:207-356
 The affine matrices are built on the host in float64 exactly as lib/utils/transforms.py:61-96 does (cv2.getAffineTransform is a
 3-point solve); interpolation runs in csrc/i2r_input.hip -- by default in cv2's own fixed-point arithmetic (restated from OpenCV's
 published algorithm: 1/32-pixel coordinates, 15-bit weights, 8-bit results, the half-pixel shift rotate_bound applies to masks of
-odd-sized images), optionally in plain fp32.  cv2 itself is absent here, so this step is NOT pinned against a cv2 output."""
+odd-sized images), optionally in plain fp32.  cv2 itself is absent here, so this step is NOT pinned against a cv2 output; its
+geometry is pinned to float64 models of the crop and the mask (tests/_input_cases.py)."""
 import ctypes as C
 
 import numpy as np

@@ -1,8 +1,9 @@
 """TEST INFRASTRUCTURE -- CPU restatement of the input side with the SAME definition the HIP kernels of
 csrc/i2r_input.hip implement: fp32 bilinear warp + ToTensor + Normalize, and the bbox mask rasterised at image resolution and resized
 bilinearly.  PARITY UNPINNED: the reference does these steps with cv2.warpAffine / cv2.rectangle / cv2.resize
-(lib/dataset/JointsDataset.py:296-333) and cv2 is absent from this image, so there is nothing to pin the definition against;
-cv2's INTER_LINEAR is a fixed-point bilinear (1/32-pixel coordinate grid, 8-bit rounded result) of the same geometry."""
+(lib/dataset/JointsDataset.py:296-333) and cv2 is absent from this image, so no cv2 output pins its rounding choices;
+cv2's INTER_LINEAR is a fixed-point bilinear (1/32-pixel coordinate grid, 8-bit rounded result) of the same geometry.  The GEOMETRY is
+pinned: tests/_input_cases.py holds cv2_warp_affine and box_mask_cv2 to float64 models of the crop and the mask within derived bounds."""
 import numpy as np
 
 
@@ -37,13 +38,14 @@ def box_mask(boxes, ih, iw, oh, ow):
     """boxes int [n, 4] = inclusive (x0, y0, x1, y1) -> [n, 1, oh, ow] fp32 in [0, 1]."""
     n = len(boxes)
     out = np.zeros((n, 1, oh, ow), dtype=np.float32)
-    sx = np.maximum((np.arange(ow, dtype=np.float32) + np.float32(0.5)) * (np.float32(iw) / np.float32(ow)) - np.float32(0.5), 0)
-    sy = np.maximum((np.arange(oh, dtype=np.float32) + np.float32(0.5)) * (np.float32(ih) / np.float32(oh)) - np.float32(0.5), 0)
+    # (source coordinates in float64 like the kernel: in fp32 they are off by 3 * 2^-24 * size pixels; the fraction is fp32)
+    sx = np.maximum((np.arange(ow, dtype=np.float64) + 0.5) * (float(iw) / float(ow)) - 0.5, 0)
+    sy = np.maximum((np.arange(oh, dtype=np.float64) + 0.5) * (float(ih) / float(oh)) - 0.5, 0)
 
     def axis(s, size, lo, hi):
         i0 = np.minimum(s.astype(np.int64), size - 1)
         i1 = np.minimum(i0 + 1, size - 1)
-        a = np.where(i0 == size - 1, np.float32(0), s - i0.astype(np.float32)).astype(np.float32)
+        a = np.where(i0 == size - 1, 0.0, s - i0.astype(np.float64)).astype(np.float32)
         in0 = ((i0 >= lo) & (i0 <= hi)).astype(np.float32)
         in1 = ((i1 >= lo) & (i1 <= hi)).astype(np.float32)
         return (1 - a) * in0 + a * in1

@@ -1,10 +1,13 @@
 """CPU: host logic of the input side (i2r_amd/input.py) and its CPU restatement (oracle/input_cpu.py).  collate() is pinned by a
-fixture the reference's own collater produced (oracle/make_golden_collate.py); the cv2 steps are parity-unpinned (cv2 absent)."""
+fixture the reference's own collater produced (oracle/make_golden_collate.py); the cv2 steps are held to float64 models of their
+geometry (tests/_input_cases.py); cv2's own rounding choices stay unpinned (cv2 absent)."""
 import os
 
 import numpy as np
+import pytest
 import torch
 
+import _input_cases as ic
 import input_cpu
 from i2r_amd import input as inp
 
@@ -81,3 +84,121 @@ def test_cv2_fixed_point_restatement_known_answers():
     assert set(np.unique(even)) == {0.0, 1.0} and even[10:40, 20:50].min() == 1.0   # even size, same size: the rectangle itself
     odd = input_cpu.box_mask_cv2([(20, 10, 49, 39)], 61, 81, 61, 81)[0, 0]
     assert abs(odd[25, 20] - 128 / 255) < 1e-6 and odd[25, 21] == 1.0 and abs(odd[10, 30] - 128 / 255) < 1e-6  # edges blurred by the 0.5 px shift
+
+
+# ---- the restatement against float64 models of the geometry (tests/_input_cases.py) ----
+def _crop_violations(levels, value, g):
+    return int((np.abs(levels.astype(np.float64) - value) > ic.crop_bound(g, 0.0)).sum())
+
+
+@pytest.mark.parametrize("name", ic.NAMES)
+def test_restatement_within_float64_geometry(name):
+    """oracle/input_cpu.py's fixed-point warp and mask over the whole case list: every crop pixel within 0.5 + (1/64 + 1/1024)(Gx + Gy)
+    levels of the bilinear interpolation at the exact coordinate (ic.crop_bound), every mask pixel within 1.5 levels of the shifted and
+    resized indicator (ic.mask_f64) -- no pixel is left out.  Measured: worst crop deviation 0.999 of its bound (a value on .5 in a flat
+    region, rounded up), median bound 0.53 levels on the smooth images; worst mask deviation 0.90 levels (2 x 3 image)."""
+    c = ic.BY_NAME[name]
+    levels, mask = ic.restated(name)
+    value, g, mask64 = ic.modelled(name)
+    assert levels.shape == value.shape == (c.n, 3, c.size[1], c.size[0]) and mask.shape == mask64.shape == (c.n, c.size[1], c.size[0])
+    dev = np.abs(levels.astype(np.float64) - value) / ic.crop_bound(g, 0.0)
+    mdev = np.abs(mask.astype(np.float64) - mask64)
+    print("%s: crop worst %.3f of its bound (median bound %.2f levels), mask worst %.3f levels" % (name, dev.max(), np.median(ic.crop_bound(g, 0.0)), mdev.max()))
+    assert _crop_violations(levels, value, g) == 0
+    assert mdev.max() <= ic.MASK_BOUND
+    for k, who in enumerate(c.who):
+        if who in ic.OUTSIDE:    # the whole crop outside the image: border value 0 everywhere, and a rectangle that clips to nothing
+            assert (levels[k] == 0).all() and (mask[k] == 0).all() and (value[k] == 0).all() and (mask64[k] == 0).all()
+        if who == "larger":      # the mask of a box larger than the image: 1 except the first row / column of an odd dimension, halved
+            ref = np.outer(np.where((np.arange(c.size[1]) + 0.5) * c.ih / c.size[1] - 0.5 < 1, np.nan, 1.0) if c.ih % 2 else np.ones(c.size[1]),
+                           np.where((np.arange(c.size[0]) + 0.5) * c.iw / c.size[0] - 0.5 < 1, np.nan, 1.0) if c.iw % 2 else np.ones(c.size[0]))
+            ok = ~np.isnan(ref)  # (outputs that touch source row / column 0 of an odd dimension are left to the bound above)
+            assert (mask[k][ok] == 255).all() and (mask64[k][ok] == 255.0).all()
+
+
+def test_float64_crop_bound_has_teeth():
+    """the crop bound tells a restatement whose inverse map is off by 1/8 px or by 1 px from a correct one (97 x 131 smooth image,
+    rotation 0, the interior person at 48 x 64: 9216 values; measured along x / y: 0 / 0, then 1010 / 1369 and 7198 / 7341 violations)"""
+    c = ic.BY_NAME["rot0-97x131-48x64"]
+    k = c.who.index("interior")
+    W, H = c.size
+    src = c.img[:, :, ::-1] if c.swap_rb else c.img
+    levels = ic.restated(c.name)[0][k]
+    counts = []
+    for d in (0.0, 1.0 / 8, 1.0):
+        for axis in (2, 5):
+            m = c.inv()[k].copy()
+            m[axis] += d
+            v, gx, gy = ic.crop_f64(src, m, H, W)
+            counts.append(_crop_violations(levels, v.transpose(2, 0, 1), (gx + gy).transpose(2, 0, 1)))
+    print("violations of %d at 0, 1/8, 1 px (x, y each):" % levels.size, counts)
+    assert levels.size == 9216 and counts[0] == counts[1] == 0
+    assert all(n > 0 for n in counts[2:])
+
+
+def test_float64_models_known_answers():
+    """the models themselves, on cases whose answer follows from the definition"""
+    img = np.arange(5 * 4 * 3, dtype=np.uint8).reshape(5, 4, 3) * 4
+    v, gx, gy = ic.crop_f64(img, (1, 0, 0, 0, 1, 0), 5, 4)                       # identity
+    assert np.array_equal(v, img.astype(np.float64))
+    assert gx[2, 1, 0] == 12 and gy[2, 1, 0] == 48 and gx[2, 0, 0] == img[1:5, 0, 0].max()   # (the last: the border's step)
+    v, _, _ = ic.crop_f64(img, (1, 0, 0.25, 0, 1, -0.5), 5, 4)                    # (x + 1/4, y - 1/2): the top row sees half a border row
+    assert v[0, 0, 0] == 0.5 * (0.75 * img[0, 0, 0] + 0.25 * img[0, 1, 0]) and v[1, 3, 1] == 0.75 * 0.5 * (float(img[0, 3, 1]) + img[1, 3, 1])
+    v, _, _ = ic.crop_f64(img, (0, -1, 4, 1, 0, 0), 4, 5)                         # a quarter turn: (x, y) <- (4 - y, x)
+    assert v[0, 0, 0] == 0 and v[1, 0, 0] == img[0, 3, 0] and v[1, 2, 0] == img[2, 3, 0] and v[3, 4, 0] == img[4, 1, 0]
+    m = ic.mask_f64((1, 1, 2, 3), 6, 4, 6, 4)                                     # even size, no resize: the rectangle itself
+    ref = np.zeros((6, 4))
+    ref[1:4, 1:3] = 1
+    assert np.array_equal(m, ref)
+    m = ic.mask_f64((1, 1, 2, 3), 5, 4, 5, 4)                                     # odd height: averaged with the row above
+    assert np.array_equal(m[:, 1], [0, 0.5, 1, 1, 0.5]) and np.array_equal(m[:, 0], np.zeros(5))
+    assert np.array_equal(ic.mask_f64((1, 1, 2, 3), 5, 4, 5, 4, shift=False)[:, 1], [0, 1, 1, 1, 0])
+    m = ic.mask_f64((0, 0, 3, 0), 2, 4, 4, 8)                                     # 2x magnification: quarter steps, replicated edges
+    assert np.array_equal(m[:, 3], [1, 0.75, 0.25, 0]) and np.array_equal(m[0], np.ones(8))
+    assert not ic.mask_f64((4, 0, 9, 1), 2, 4, 4, 8).any() and not ic.mask_f64((-5, -5, -1, 1), 2, 4, 4, 8).any()   # clipped to nothing
+
+
+def test_tie_cases_are_ties_and_round_half_to_even():
+    c = ic.BY_NAME["tie-exact-97x131-17x23"]
+    assert np.array_equal(c.inv()[0], np.array(ic.TIE_INV))                       # the closed-form inverse of the forward map is exact
+    assert (ic.TIE_INV[2] * 1024, ic.TIE_INV[5] * 1024) == (6144.5, 15361.5)
+    assert np.abs(ic.BY_NAME["tie-solved-97x131-17x23"].inv()[0] - np.array(ic.TIE_INV)).max() < 1e-14   # the solve: the same map to an ulp
+    c = ic.BY_NAME["tie-deciding-97x131-17x23"]
+    assert np.array_equal(c.inv()[0], np.array(ic.TIE2_INV))
+    assert (ic.TIE2_INV[2] * 1024, ic.TIE2_INV[5] * 1024) == (6144 + 15.5, -16.5)
+    e = 2.0 ** -30
+
+    def warp(dx, dy):   # the map whose exact inverse translation is (m2 + dx, m5 + dy)
+        return input_cpu.cv2_warp_affine(c.img, ic.tie_forward((0.5, 0, ic.TIE2_INV[2] + dx, 0, 0.5, ic.TIE2_INV[5] + dy))[0], c.size)
+    tie = ic.restated(c.name)[0][0].transpose(1, 2, 0)
+    assert np.array_equal(tie, warp(+e, +e))                                      # 6159.5 -> 6160 (up), -16.5 -> -16 (up): to even
+    assert not np.array_equal(tie, warp(-e, +e)) and not np.array_equal(tie, warp(+e, -e))   # and each tie decides pixels
+    assert np.array_equal(tie[0, 0], c.img[0, 6] + ((c.img[0, 7].astype(int) - c.img[0, 6]) * 1 + 16) // 32)   # row 0 at column 6 + 1/32
+
+
+def test_cv2_restatement_known_answers_at_the_new_edges():
+    """1 x 1 and 2 x 3 images, a rectangle that clips to nothing, a crop entirely outside the image"""
+    one = np.array([[[200, 100, 7]]], dtype=np.uint8)
+    out = input_cpu.cv2_warp_affine(one, np.array([[1.0, 0, 1.0], [0, 1.0, 1.0]]), (3, 3))     # the pixel lands on (1, 1), border elsewhere
+    ref = np.zeros((3, 3, 3), np.uint8)
+    ref[1, 1] = one[0, 0]
+    assert np.array_equal(out, ref)
+    half = input_cpu.cv2_warp_affine(one, np.array([[1.0, 0, 0.5], [0, 1.0, 0.5]]), (2, 2))     # a quarter of it on four outputs, rounded
+    assert np.array_equal(half, np.broadcast_to((one[0, 0].astype(int) * 8192 + 16384) >> 15, (2, 2, 3)))
+    # masks: 1 x 1 is odd both ways -> the covered pixel becomes (255 * 8192 + 16384) >> 15 = 64, replicated over any output
+    assert np.array_equal(input_cpu.box_mask_cv2([(0, 0, 0, 0)], 1, 1, 5, 4)[0, 0], np.full((5, 4), np.float32(64) * np.float32(1 / 255.0)))
+    # 2 x 3 (odd width): the full rectangle shifts to rows (128, 255, 255); same size: unchanged; twice the width: 1/4 steps between taps
+    full = input_cpu.box_mask_cv2([(-1, -1, 9, 9)], 2, 3, 2, 3)[0, 0]
+    assert np.array_equal(np.rint(full * 255), [[128, 255, 255]] * 2)
+    wide = np.rint(input_cpu.box_mask_cv2([(-1, -1, 9, 9)], 2, 3, 2, 6)[0, 0] * 255)
+    assert np.array_equal(wide, [[128, 160, 223, 255, 255, 255]] * 2)            # 128 + 127 / 4 = 159.75, 128 + 127 * 3 / 4 = 223.25
+    line = np.rint(input_cpu.box_mask_cv2([(1, 0, 1, 1)], 2, 3, 2, 3)[0, 0] * 255)   # a one-pixel column (w = 0): half of it moves right
+    assert np.array_equal(line, [[0, 128, 128]] * 2)
+    for box in ((-10, -10, -1, 5), (3, 0, 8, 1), (0, 2, 2, 9), (0, -7, 2, -1)):   # clip to nothing on each side
+        assert not input_cpu.box_mask_cv2([box], 2, 3, 7, 5).any()
+    img = np.full((9, 7, 3), 255, np.uint8)
+    far = np.array([[[1.0, 0, 500.0], [0, 1.0, 0]], [[1.0, 0, 0], [0, 1.0, -9.0]], [[0.5, 0, -4000.25], [0, 0.5, -3000.5]]])
+    out = input_cpu.crop_affine_cv2(img, far, inp.IMAGENET_MEAN, inp.IMAGENET_STD, 9, 7)
+    assert np.array_equal(out, np.broadcast_to(ic.zero_level()[None, :, None, None], out.shape))
+    near = input_cpu.cv2_warp_affine(img, np.array([[1.0, 0, 7.0 - 1 / 64], [0, 1.0, 0]]), (7, 9))   # 1/64 px from leaving: rounds up to 1/32 px
+    assert (near[:, :6] == 0).all() and (near[:, 6] == (255 * 1 * 32 * 32 + 16384) >> 15).all()      # (-63/64 -> cell -1, fraction 1/32: 8)
