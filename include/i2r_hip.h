@@ -101,6 +101,9 @@ typedef struct i2r_conv_desc {
     float* y;                      /*   t1 / t2 (optional): [n_img, in_h >> shift, in_w >> shift, in_cs], nearest-neighbour up-sampled; the map is
                                         also written to y (required with t1; laid out like `in`, in_cs == cin) for the consumers after this conv.
                                         y must not alias in, t1, t2, out or a residual.  All null = none. */
+    int32_t seq;                   /* algo 1 only: fragments (x mt) a workgroup runs one after the other on one set-up.  0 = the library chooses
+                                      (from the passes and workgroup counts of all members of the launch), 1 = one fragment per workgroup,
+                                      n = 2..8 forces n.  The results do not depend on it, bit for bit.  Other algorithms ignore it. */
 } i2r_conv_desc;
 
 I2R_API int i2r_conv(const i2r_conv_desc* d, void* stream);
@@ -112,7 +115,8 @@ I2R_API int i2r_conv(const i2r_conv_desc* d, void* stream);
 #define I2R_MAX_GROUP 4
 /* block_map (optional, device int32[map_len]): dispatch order of the workgroups, entry = (member << 24) | index of
  * the workgroup within that member; map_len must equal the total workgroup count
- * (sum over members of n_img * ceil(conv_h/tile_h) * ceil(conv_w/tile_w) * cout_blocks). */
+ * (sum over members of n_img * ceil(conv_h/tile_h) * ceil(conv_w/tile_w) * cout_blocks; an algo 1 member counts runs of `seq`
+ * fragments instead of fragments -- i2r_conv_grid reports the count). */
 I2R_API int i2r_conv_grouped(const i2r_conv_desc* const* descs, int32_t n, const int32_t* block_map, int32_t map_len,
                      void* stream);
 
@@ -165,6 +169,11 @@ I2R_API int i2r_head(const float* in, const float* w, const float* bias, float* 
 /* i2r_conv_kernel_name -- which instantiation conv_igemm_f32<MT, NT, CAP, PF> a (grouped) launch resolves to, as it
  * appears in rocprofv3 kernel traces (used by bench.py to key its per-kernel roofline numbers). No launch happens. */
 I2R_API int i2r_conv_kernel_name(const i2r_conv_desc* const* descs, int32_t n, char* buf, int32_t buflen);
+
+/* i2r_conv_grid -- the workgroup count of a (grouped) launch as i2r_conv_grouped would issue it, with (with_map != 0: the length its
+ * block_map must have) or without a dispatch table, and the run length it resolves for each member (seq: int32[n], may be null; 1 for
+ * everything but algo 1).  No launch happens. */
+I2R_API int i2r_conv_grid(const i2r_conv_desc* const* descs, int32_t n, int32_t with_map, int32_t* grid, int32_t* seq);
 
 /* ---- after the forward: flip-test merge and keypoint decode -------------------------------- */
 /* i2r_flip_merge -- out = (y + flip_back(y_flipped)) * 0.5  with flip_back = reverse W + swap left/right joints

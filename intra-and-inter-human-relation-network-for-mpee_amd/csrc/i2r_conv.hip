@@ -317,12 +317,18 @@ static void copy_desc(const i2r_conv_desc* d, ConvK& k) {
     k.out_step = d->out_step; k.out_off_y = d->out_off_y; k.out_off_x = d->out_off_x; k.rep = d->rep; k.relu = d->relu;
     k.dtype = d->dtype;
     k.in16 = d->in_f16; k.out16 = d->out_f16;
-    k.algo = d->algo; k.w_fwlog = k.w_pitch = k.w_half = k.w_nfrag = k.w_rcp = k.w_band = 0;
+    k.algo = d->algo; k.w_fwlog = k.w_pitch = k.w_half = k.w_nfrag = k.w_rcp = k.w_band = 0; k.w_seq = 1;
     k.w_m_cblk = k.w_m_img = k.w_m_tx = 0; k.in_bytes = k.w_bytes = k.out_bytes = 0;
     k.m_cblk = k.m_tx = k.m_ty = k.m_pw = k.m_tw = 0; k.wn_log = 0; k.npass = 0;
     k.dbg = 0;
     k.f_t1 = d->t1; k.f_t2 = d->t2; k.f_y = d->y; k.f_sh1 = d->t1_shift; k.f_sh2 = d->t2 ? d->t2_shift : 0; k.f_bytes1 = k.f_bytes2 = 0;
 }
+
+constexpr int kWinoMaxSeq = 8;       // longest run of fragments a workgroup takes (i2r_conv_desc.seq)
+constexpr int kWinoRunPasses = 6;    // passes a run is filled up to when the library chooses
+constexpr int kWinoMinWg = 512;      // ... and the workgroups such a launch keeps (of 1024 resident on 256 CUs)
+// runs of a member: its fragment groups in w_seq's
+static long long wino_runs(const ConvK& k, int mt) { return (((long long)k.w_nfrag + mt - 1) / mt + k.w_seq - 1) / k.w_seq; }
 
 // Winograd F(2x2, 3x3) launch geometry (i2r_conv_wino.hip): fragment shape, patch layout in LDS, workgroup count
 static int prepare_wino(const i2r_conv_desc* d, int force_mt, ConvK& k, int* nt_out, int* mt_out, int* cap_out, int* pf_out, size_t* lds_out,
@@ -354,6 +360,7 @@ static int prepare_wino(const i2r_conv_desc* d, int force_mt, ConvK& k, int* nt_
     I2R_CHECK_ARG(nt != 0, "i2r_conv: algo 1 needs cout_pad=%d to be a multiple of 48 or 64", d->cout_pad);
     const int mt = force_mt ? force_mt : (d->mt ? d->mt : 1);  // (one fragment per item = 4 waves per SIMD: the measured optimum, and the only form built)
     I2R_CHECK_ARG(mt == 1, "i2r_conv: algo 1 takes mt 1 (got %d)", mt);
+    I2R_CHECK_ARG(d->seq >= 0 && d->seq <= kWinoMaxSeq, "i2r_conv: algo 1 runs 1..%d fragments per workgroup (seq=%d; 0 = choose)", kWinoMaxSeq, d->seq);
     int fw = 0;  // Winograd tiles across a fragment of 16 (64 output pixels): the shape that covers the map with the fewest fragments
     if (d->tile_w) {
         I2R_CHECK_ARG(d->tile_w == 16 || d->tile_w == 8 || d->tile_w == 4, "i2r_conv: algo 1 fragment width %d (16, 8, 4)", d->tile_w);
@@ -390,6 +397,7 @@ static int prepare_wino(const i2r_conv_desc* d, int force_mt, ConvK& k, int* nt_
     const long long nf = (long long)d->n_img * k.tiles_y * k.tiles_x;
     I2R_CHECK_ARG(nf > 0 && nf * k.n_cblk < (1ll << 20) && k.tiles_y * k.tiles_x < 2048 && k.n_cblk < 2048, "i2r_conv: algo 1 grid (%lld fragments)", nf);
     k.w_nfrag = (int)nf;
+    k.w_seq = d->seq ? d->seq : 1;  // (seq 0: resolve() chooses, seeing the whole group -- wino_choose_seq)
 #ifdef I2R_TUNING
     {
         static const int dbg = getenv("I2R_CONV_DBG") ? atoi(getenv("I2R_CONV_DBG")) : 0;
@@ -398,8 +406,34 @@ static int prepare_wino(const i2r_conv_desc* d, int force_mt, ConvK& k, int* nt_
 #endif
     *nt_out = nt; *mt_out = mt; *cap_out = 0; *pf_out = 100;
     *lds_out = i2r_conv_wino_lds(nt, mt, k.plane);
-    *nblk_out = (nf + mt - 1) / mt * k.n_cblk;
+    *nblk_out = wino_runs(k, mt) * k.n_cblk;
     return I2R_OK;
+}
+
+// Run lengths of the members of a Winograd launch that leave the choice to the library (i2r_conv_desc.seq == 0).  A run saves the
+// set-up of every fragment after its first, but it is also a coarser unit of work: the launch is balanced over 256 CUs by the piece,
+// and runs of 12 passes (every member as long as a 192-channel item) measured 6 % SLOWER on the whole model than single fragments,
+// runs of up to 6 passes 1 % faster ("runs of fragments").  So only the short items are strung together, up to
+// kWinoRunPasses passes -- pairs of 48-channel fragments, up to six one-pass fragments; 64 channels and more run alone -- and a
+// launch that had kWinoMinWg workgroups at one fragment per workgroup keeps that many (one that had fewer keeps what it had): below
+// that floor the longest run (on a tie: of the member with the most passes per fragment) gives a fragment back.
+static void wino_choose_seq(ConvK* g, const i2r_conv_desc* const* descs, int n, int mt) {
+    auto total = [&]() { long long t = 0; for (int i = 0; i < n; ++i) t += wino_runs(g[i], mt) * g[i].n_cblk; return t; };
+    long long at_one = 0;
+    for (int i = 0; i < n; ++i) at_one += ((long long)g[i].w_nfrag + mt - 1) / mt * g[i].n_cblk;
+    const long long floor_wg = std::min<long long>(at_one, kWinoMinWg);
+    for (int i = 0; i < n; ++i)
+        if (descs[i]->seq == 0) g[i].w_seq = std::max(1, std::min(kWinoMaxSeq, kWinoRunPasses / (g[i].cin >> 4)));
+    while (total() < floor_wg) {
+        int pick = -1;
+        for (int i = 0; i < n; ++i) {
+            if (descs[i]->seq != 0 || g[i].w_seq == 1) continue;
+            const int len = g[i].w_seq * (g[i].cin >> 4);
+            if (pick < 0 || len > g[pick].w_seq * (g[pick].cin >> 4) || (len == g[pick].w_seq * (g[pick].cin >> 4) && g[i].cin > g[pick].cin)) pick = i;
+        }
+        if (pick < 0) break;  // (only forced members are left)
+        --g[pick].w_seq;
+    }
 }
 
 // validate one descriptor and derive its launch geometry; *nt_out/*mt_out: fragment blocking, *lds_out: LDS bytes
@@ -600,13 +634,22 @@ static int resolve(const i2r_conv_desc* const* descs, int32_t n, ConvGroupK& grp
         I2R_CHECK_ARG(nt == nt0 && mt == mt0, "i2r_conv_grouped: descriptor %d has fragment blocking (%d,%d) != (%d,%d)", i, mt, nt, mt0, nt0);
         I2R_CHECK_ARG(descs[i]->dtype == descs[0]->dtype, "i2r_conv_grouped: members mix compute dtypes");
         if (lds > lds_max) lds_max = lds;
-        if (descs[i]->algo == 1 && !table) {  // XCD-aware item numbering of the Winograd kernels (i2r_conv_wino.hip): whole rounds of 8 fragment groups
-            const long long groups = nblk / grp.g[i].n_cblk;
-            grp.g[i].w_band = (int)((groups + 7) / 8);
-            nblk = (long long)grp.g[i].w_band * 8 * grp.g[i].n_cblk;
-        }
+        if (descs[i]->algo == 1) continue;  // (counted below, once the run lengths are known)
         total += nblk;
         grp.blk_end[i] = (int)total;
+    }
+    if (descs[0]->algo == 1) {
+        wino_choose_seq(grp.g, descs, n, mt0);
+        for (int i = 0; i < n; ++i) {
+            const long long runs = wino_runs(grp.g[i], mt0);
+            long long nblk = runs * grp.g[i].n_cblk;
+            if (!table) {  // XCD-aware item numbering of the Winograd kernels (i2r_conv_wino.hip): whole rounds of 8 runs
+                grp.g[i].w_band = (int)((runs + 7) / 8);
+                nblk = (long long)grp.g[i].w_band * 8 * grp.g[i].n_cblk;
+            }
+            total += nblk;
+            grp.blk_end[i] = (int)total;
+        }
     }
     for (int i = n; i < kMaxGroups; ++i) { grp.g[i] = grp.g[0]; grp.blk_end[i] = (int)total; }
     grp.n = n;
@@ -645,6 +688,20 @@ extern "C" int i2r_conv_grouped(const i2r_conv_desc* const* descs, int32_t n, co
 }
 
 extern "C" int i2r_conv(const i2r_conv_desc* d, void* stream) { return i2r_conv_grouped(&d, 1, nullptr, 0, stream); }
+
+extern "C" int i2r_conv_grid(const i2r_conv_desc* const* descs, int32_t n, int32_t with_map, int32_t* grid, int32_t* seq) {
+    ConvGroupK grp;
+    int nt0, mt0, cap0, pf0;
+    size_t lds_max;
+    long long total;
+    int rc = resolve(descs, n, grp, &nt0, &mt0, &cap0, &pf0, &lds_max, &total, with_map != 0);
+    if (rc) return rc;
+    I2R_CHECK_ARG(grid != nullptr, "i2r_conv_grid: grid");
+    *grid = (int32_t)total;
+    if (seq)
+        for (int i = 0; i < n; ++i) seq[i] = descs[0]->algo == 1 ? grp.g[i].w_seq : 1;
+    return I2R_OK;
+}
 
 extern "C" int i2r_conv_kernel_name(const i2r_conv_desc* const* descs, int32_t n, char* buf, int32_t buflen) {
     ConvGroupK grp;

@@ -23,15 +23,18 @@
 //  * epilogue: the column half of the output transform (over j) is in-lane; the row half (over i) crosses the four waves: each
 //    wave writes its two partial tiles T_i[b] to LDS as [i][b][tile][cout] and every thread then owns (pixel, 4 channels) pieces:
 //    three 16-byte LDS reads, bias / residuals / ReLU, one 16-byte store (a quad of lanes = 64 contiguous bytes of one pixel).
-//  * Dispatch: one workgroup per item, in the order of a host-made table (longest-processing-time packing of the items of all
-//    members of a grouped launch; the hardware dispatcher hands out slots as they free up).
+//  * Dispatch: one workgroup per RUN of w_seq items of one channel block (w_seq = 1: per item), numbered member by member in XCD bands
+//    or in the order of a host-made table.  A run does the member selection, the item decode, the input-side descriptors, the LDS
+//    slots and the weight walk once and then works its fragments off one after the other in the same registers (see the run loop).
 //  * The kernel is bound by INSTRUCTION ISSUE as much as by the matrix pipe: an item is small (64 pixels x 48 channels x cin =
 //    48 MFMAs per wave and 16-channel chunk), and with every memory access and every MFMA compiled out the launch still took 35 of
 //    its 78 us (tools/one_conv.py with the -DI2R_TUNING ablation switches: a SIMD issues about one instruction per 4.7 cycles, and
 //    the 1450 non-MFMA instructions a wave executed cost as much issue time as its 247 MFMAs cost pipe time).  Hence: item decode
 //    through host-made reciprocals on the scalar ALU (no integer divisions), the first MFMA of every accumulator takes a literal
-//    zero (no clearing), one fragment per item at <= 128 registers (4 waves per SIMD; two fragments per item at 2 waves per SIMD
-//    measured 89 vs 78 us, a software-pipelined input transform and persistent workgroups walking an item table measured +-0).
+//    zero (no clearing), one fragment in registers at a time at <= 128 of them (4 waves per SIMD; two fragments held at once at 2
+//    waves per SIMD measured 89 vs 78 us, a software-pipelined input transform and persistent workgroups walking an item table
+//    measured +-0), and short items strung into runs (pairs of 48-channel fragments: -1 % on the whole model; longer runs balance
+//    worse over the CUs than they save -- DESIGN.md section 4).
 #include "i2r_conv.h"
 
 namespace {
@@ -43,8 +46,13 @@ constexpr int kWinoPatchMax = 108;  // patch pixels of a fragment: 6 x 18 (FW = 
 // block's second conv reads it as its residual): the non-halo pixels of the fragment patches are disjoint and cover the map, and
 // all cin channels pass through the staging, so the items of channel block 0 store every value exactly once.  f_y must not alias
 // `in`: the halo reads of neighbouring items are not ordered against those stores.  A member without f_t1 runs as in the plain form.
+// the members of the launch where the hardware put them: the kernel-argument block, read with scalar loads
+typedef const ConvK __attribute__((address_space(4)))* ConvKArg;
+
+// `args`: grp as it lies in the kernel-argument block.  Only a __global__ function knows where its parameters lie, so the two kernels
+// below pass it in (wino_args); the body reads the per-fragment descriptor fields through it (see the run loop).
 template <int MT, int NT, bool FIN>
-__device__ __forceinline__ void conv_wino_body(const ConvGroupK& grp) {
+__device__ __forceinline__ void conv_wino_body(const ConvGroupK& grp, ConvKArg args) {
     extern __shared__ __attribute__((aligned(16))) f32x4 lds[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wi = __builtin_amdgcn_readfirstlane(tid >> 6);  // Winograd row of this wave
@@ -65,11 +73,11 @@ __device__ __forceinline__ void conv_wino_body(const ConvGroupK& grp) {
         bid -= start;
     }
     const ConvK& p = grp.g[gi];
-    // tuning aid (I2R_CONV_DBG & 8, -DI2R_TUNING builds only): phase time stamps of the item into the buffer passed as res2
+    // tuning aid (I2R_CONV_DBG & 8, -DI2R_TUNING builds only): phase time stamps of the workgroup into the buffer passed as res2 (start, and of
+    // the run's LAST fragment: passes begin, passes end, stores done)
     const bool stamp = (I2R_DBG(p) & 8) != 0;
     unsigned long long ts0 = 0, ts1 = 0, ts2 = 0;
     if (stamp) ts0 = __builtin_amdgcn_s_memtime();
-    const float* const res2 = stamp ? nullptr : p.res2;
 
     // item -> (fragment group wg, output-channel block cb).  Without a table the items of a member are numbered XCD-aware: workgroup b of a
     // launch runs on XCD b % 8 (own L2 each) and the host pads every member to whole rounds of 8, so XCD x = bid % 8 is handed the
@@ -85,26 +93,19 @@ __device__ __forceinline__ void conv_wino_body(const ConvGroupK& grp) {
         const int q = bid >> 3, qq = div_m(q, p.n_cblk, p.w_m_cblk);
         cb = q - qq * p.n_cblk;
         wg = (bid & 7) * p.w_band + qq;
-        if (wg * MT >= p.w_nfrag) return;  // (padding of the last band; workgroup-uniform)
     }
+    // A workgroup is a RUN of w_seq consecutive fragment groups of one channel block, wg * w_seq .. + w_seq - 1, worked off one after the
+    // other on ONE set-up: member selection, item decode, the input-side buffer descriptors, LDS slots, gather bases, weight lane offset and
+    // walk are computed once (a 3-pass item spends more instructions around its passes than in them).  What names the fragment -- its decode,
+    // the global offsets of the staging items, the output pixel -- is redone per fragment from values read afresh (lane_now, ConvKArg): held
+    // through the pass loop instead, it does not fit 128 registers.  The run's fragments past w_nfrag do nothing: the trip count is cut
+    // here, workgroup-uniform and before the first barrier, like the return for an empty run.
+    const int run0 = wg * p.w_seq;
+    const int nrun = min(p.w_seq, (p.w_nfrag + MT - 1) / MT - run0);
+    if (nrun <= 0) return;  // (padding of the last band; workgroup-uniform)
     const int fwl = p.w_fwlog, FW = 1 << fwl;  // tiles across a fragment
-    const int PC = p.pw, PP = p.ph * p.pw;
-    const int per_img = p.tiles_y * p.tiles_x;
     const int pitch = p.w_pitch, half = p.w_half, plane = p.plane;
     const int n_base = cb * NT * 16;
-    int f_img[MT], f_oy[MT], f_ox[MT];
-    bool f_ok[MT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-        int fid = wg * MT + mt;
-        f_ok[mt] = fid < p.w_nfrag;
-        if (!f_ok[mt]) fid = 0;
-        f_img[mt] = div_m(fid, per_img, p.w_m_img);
-        const int rem = fid - f_img[mt] * per_img;
-        const int fy = div_m(rem, p.tiles_x, p.w_m_tx);
-        f_oy[mt] = fy * (32 >> fwl);
-        f_ox[mt] = (rem - fy * p.tiles_x) * (2 * FW);
-    }
 
     // ---- staging assignment: item = (fragment, patch pixel, channel group of the 16-channel chunk); the four lanes of a quad
     //      fetch the 64 contiguous bytes of one pixel (quad rule of the texture addresser, see i2r_conv.hip) ----
@@ -115,7 +116,8 @@ __device__ __forceinline__ void conv_wino_body(const ConvGroupK& grp) {
     const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.in), 0, p.in_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w), 0, p.w_bytes, 0x00020000);
     unsigned goff[NIT];  // byte offset of (pixel, channel group) in `in`, kOOB (out of range: reads zeros) outside the image
-    int lslot[NIT];      // LDS slot, -1 = no item
+    int lslot[NIT];      // LDS slot, -1 = no item; fused-input form: + kOwn when the item is an interior (non-halo) pixel of the patch
+    constexpr int kOwn = 1 << 30;  // (above every slot; the shift to a byte address drops it)
     // fused input: the same piece of the up-sampled terms sits at (iy >> s, ix >> s) of their (in_h >> s) x (in_w >> s) maps.  A lane
     // outside the image has all three offsets at kOOB and stages ReLU(0 + 0 + 0) = 0: the zero padding needs no select.  The value
     // goes to f_y from the lanes holding an interior (non-halo) pixel (own) in the items of channel block 0: at `goff`, f_y being laid out like `in`
@@ -123,38 +125,70 @@ __device__ __forceinline__ void conv_wino_body(const ConvGroupK& grp) {
     const __amdgpu_buffer_rsrc_t rs_t1 = make_rsrc(fin ? p.f_t1 : nullptr, p.f_bytes1), rs_t2 = make_rsrc(fin2 ? p.f_t2 : nullptr, p.f_bytes2),
                                  rs_y = make_rsrc(fin ? p.f_y : nullptr, p.in_bytes);
     unsigned goff1[FIN ? NIT : 1], goff2[FIN ? NIT : 1];
-    bool own[FIN ? NIT : 1];
-#pragma unroll
-    for (int k = 0; k < NIT; ++k) {
-        const int it = tid + k * 256;
-        const int cg = it & 3, pix = it >> 2;
-        int f = 0, pp = pix;  // (MT <= 2 and PP <= 108: compare / subtract instead of a division; rows through a 16-bit reciprocal)
+    // The LDS slot of staging item k is the same for every fragment of the run and stays in a register.  Its patch pixel (row, col) is
+    // worked out again per fragment, from a thread index the compiler cannot hoist: kept, row / col / offset would hold six more
+    // registers through the pass loop, which at 4 waves per SIMD (128 registers) means spills.
+    const int cg = tid & 3;  // (256 items per step: the channel group does not depend on k)
+    auto patch_pixel = [&](const auto& pq, int t, int k, int& f, int& row, int& col) {
+        const int PC = pq.pw, PP = pq.ph * pq.pw;
+        const int pix = (t + k * 256) >> 2;
+        int pp = pix;  // (MT <= 2 and PP <= 108: compare / subtract instead of a division; rows through a 16-bit reciprocal)
+        f = 0;
 #pragma unroll
         for (int m = 1; m <= MT; ++m)
             if (pix >= m * PP) { f = m; pp = pix - m * PP; }
-        const int row = (pp * p.w_rcp) >> 16, col = pp - row * PC;
-        goff[k] = kOOB;
-        lslot[k] = -1;
-        if constexpr (FIN) { goff1[k] = goff2[k] = kOOB; own[k] = false; }
-        if (f < MT) {
+        row = (pp * pq.w_rcp) >> 16;
+        col = pp - row * PC;
+    };
+#pragma unroll
+    for (int k = 0; k < NIT; ++k) {
+        int f, row, col;
+        patch_pixel(p, tid, k, f, row, col);
+        lslot[k] = f < MT ? (f * 4 + cg) * plane + row * pitch + (col & 1) * half + (col >> 1) : -1;
+        if constexpr (FIN) {  // (as a bit of the slot, not a lane mask per item: those are four more scalar registers through the pass loop)
+            if (f < MT && row >= 1 && row < p.ph - 1 && col >= 1 && col < p.pw - 1) lslot[k] |= kOwn;
+        }
+    }
+    // ---- per fragment of the run: decode (scalar) and the global offsets of the staging items ----
+    // (the lane index, read where it is used: two instructions, no register held through the passes, nothing hoisted out of the run loop)
+    auto lane_now = []() {
+        int l;
+        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+        return l;
+    };
+    int f_img[MT], f_oy[MT], f_ox[MT];
+    bool f_ok[MT];
+    auto set_fragment = [&](int fg, int t, const auto& ps) {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+            int fid = fg * MT + mt;
+            f_ok[mt] = fid < ps.w_nfrag;
+            if (!f_ok[mt]) fid = 0;
+            f_img[mt] = div_m(fid, (ps.tiles_y * ps.tiles_x), ps.w_m_img);
+            const int rem = fid - f_img[mt] * (ps.tiles_y * ps.tiles_x);
+            const int fy = div_m(rem, ps.tiles_x, ps.w_m_tx);
+            f_oy[mt] = fy * (32 >> fwl);
+            f_ox[mt] = (rem - fy * ps.tiles_x) * (2 * FW);
+        }
+#pragma unroll
+        for (int k = 0; k < NIT; ++k) {
+            int f, row, col;
+            patch_pixel(ps, t, k, f, row, col);
             int img = f_img[0], oy = f_oy[0], ox = f_ox[0];
-            bool ok = f_ok[0];
+            bool ok = f_ok[0] && f < MT;
 #pragma unroll
             for (int m = 1; m < MT; ++m)
                 if (f == m) { img = f_img[m]; oy = f_oy[m]; ox = f_ox[m]; ok = f_ok[m]; }
             const int iy = oy - 1 + row, ix = ox - 1 + col;
-            lslot[k] = (f * 4 + cg) * plane + row * pitch + (col & 1) * half + (col >> 1);
-            if (ok && iy >= 0 && iy < p.in_h && ix >= 0 && ix < p.in_w) {
-                goff[k] = (unsigned)(((img * p.in_h + iy) * p.in_w + ix) * p.in_cs + cg * 4) * 4u;
-                if constexpr (FIN) {
-                    const int s1 = p.f_sh1, s2 = p.f_sh2;
-                    goff1[k] = (unsigned)(((img * (p.in_h >> s1) + (iy >> s1)) * (p.in_w >> s1) + (ix >> s1)) * p.in_cs + cg * 4) * 4u;
-                    goff2[k] = (unsigned)(((img * (p.in_h >> s2) + (iy >> s2)) * (p.in_w >> s2) + (ix >> s2)) * p.in_cs + cg * 4) * 4u;
-                    own[k] = row >= 1 && row < p.ph - 1 && col >= 1 && col < PC - 1;
-                }
+            const bool in_img = ok && (unsigned)iy < (unsigned)ps.in_h && (unsigned)ix < (unsigned)ps.in_w;
+            goff[k] = in_img ? (unsigned)(((img * ps.in_h + iy) * ps.in_w + ix) * ps.in_cs + (t & 3) * 4) * 4u : kOOB;
+            if constexpr (FIN) {
+                const int s1 = ps.f_sh1, s2 = ps.f_sh2;
+                goff1[k] = in_img ? (unsigned)(((img * (ps.in_h >> s1) + (iy >> s1)) * (ps.in_w >> s1) + (ix >> s1)) * ps.in_cs + (t & 3) * 4) * 4u : kOOB;
+                goff2[k] = in_img ? (unsigned)(((img * (ps.in_h >> s2) + (iy >> s2)) * (ps.in_w >> s2) + (ix >> s2)) * ps.in_cs + (t & 3) * 4) * 4u : kOOB;
             }
         }
-    }
+    };
     f32x4 v[NIT];
     auto stage_load = [&](int c0) {
 #pragma unroll
@@ -191,13 +225,13 @@ __device__ __forceinline__ void conv_wino_body(const ConvGroupK& grp) {
                 for (int k = 0; k < NIT; ++k) {
                     v[k] += vt[k];
                     v[k][0] = fmaxf(v[k][0], 0.f); v[k][1] = fmaxf(v[k][1], 0.f); v[k][2] = fmaxf(v[k][2], 0.f); v[k][3] = fmaxf(v[k][3], 0.f);
-                    if (cb == 0) buf_st16(rs_y, own[k] ? goff[k] : kOOB, c0 * 4, v[k]);  // (uniform)
+                    if (cb == 0) buf_st16(rs_y, (unsigned)lslot[k] >= (unsigned)kOwn ? goff[k] : kOOB, c0 * 4, v[k]);  // (uniform; no item: goff is kOOB)
                 }
             }
         }
 #pragma unroll
         for (int k = 0; k < NIT; ++k)
-            if (lslot[k] >= 0) buf[lslot[k]] = v[k];
+            if (lslot[k] >= 0) buf[FIN ? lslot[k] & (kOwn - 1) : lslot[k]] = v[k];
     };
 
     // ---- A operand: lane (tile li, channel group g) gathers rows ra, rb of its tile's 4x4 patch and forms row i of B^T d B ----
@@ -207,11 +241,12 @@ __device__ __forceinline__ void conv_wino_body(const ConvGroupK& grp) {
     const float sg = wi == 1 ? 1.f : -1.f;
     const int ty = li >> fwl, tx = li & (FW - 1);
     const int abase = g * plane + 2 * ty * pitch + tx;
+    int abase_f;  // (the copy a fragment works with, see the run loop)
     const int oa = ra * pitch, ob = rb * pitch;
     auto load_a = [&](const f32x4* buf, f32x4 (&a)[MT][4]) {
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
-            const f32x4* q = buf + mt * 4 * plane + abase;
+            const f32x4* q = buf + mt * 4 * plane + abase_f;
             f32x4 R[4];
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
@@ -230,7 +265,8 @@ __device__ __forceinline__ void conv_wino_body(const ConvGroupK& grp) {
     //      the pointer walks j (stride cin4 * cout_pad slots) and wraps to the next chunk after j = 3 ----
     const int cin4 = p.cin >> 2;
     const unsigned wlane = (unsigned)(n_base + li + g * p.cout_pad) * 16u;   // per-lane byte offset (constant)
-    int wp = wi * 4 * cin4 * p.cout_pad * 16;                                   // scalar byte offset of (position 4 i + j, chunk)
+    const int wp0 = wi * 4 * cin4 * p.cout_pad * 16;                            // scalar byte offset of (position 4 i + j, chunk): every
+    int wp;                                                                     // fragment of the run walks the same weights from wp0
     const int inc_j = cin4 * p.cout_pad * 16;
     const int inc_wrap = (4 - 3 * cin4) * p.cout_pad * 16;  // from (pass, j = 3) to (pass + 1, j = 0)
     auto fetch_b = [&](f32x4 (&b)[NT]) {
@@ -269,6 +305,29 @@ __device__ __forceinline__ void conv_wino_body(const ConvGroupK& grp) {
         if (more) stage_store(nxt, (pass_ + 1) * 16);                                            \
         if (!(I2R_DBG(p) & 64)) __syncthreads();                                                 \
     }
+    // ---- output side ----
+    float* const Tl = reinterpret_cast<float*>(lds);
+    constexpr int TW = NT * 16;                    // floats per tile row of the exchange buffer
+    constexpr int TPL = MT * 16 * TW;              // floats per (i, b) plane
+    const bool tail = n_base + NT * 16 > p.cout || n_base + NT * 16 > p.out_cs;  // (uniform) the block holds padding channels
+    // The epilogue reads its descriptor fields (a dozen scalars and four buffer descriptors) again for every fragment, through a
+    // pointer the compiler cannot see through, as set_fragment does: held over the pass loop next to the staging's, they do not fit the
+    // scalar registers (the fused-input form spilled eight of them, and three vector registers with them).
+
+    for (int fs = 0; fs < nrun; ++fs) {
+    {
+        const int tid_s = wi * 64 + lane_now();  // (the thread index again, per fragment; see patch_pixel)
+        ConvKArg ps_ = args + gi;
+        asm volatile("" : "+s"(ps_));
+        set_fragment(run0 + fs, tid_s, *ps_);
+        // the LDS addresses derived from the slots and the gather base (one per buffer and item) start their lives here, per fragment, as
+        // they did per item: hoisted out of the run loop they are eight registers held through the epilogue, and the allocator spills
+        abase_f = abase;
+        asm volatile("" : "+v"(abase_f));
+#pragma unroll
+        for (int k = 0; k < NIT; ++k) asm volatile("" : "+v"(lslot[k]));
+    }
+    wp = wp0;
     stage_load(0);
     stage_load_t1(0);
     if constexpr (FIN) {  // first chunk: the accumulators do not exist yet, so both terms are in flight with the base piece (one latency)
@@ -284,26 +343,32 @@ __device__ __forceinline__ void conv_wino_body(const ConvGroupK& grp) {
         }
     }
     fetch_b(b0);
+    // the exchange buffer of the previous fragment's output transform aliases the staging buffers: its last reads come before this store
+    // (the loads above are already in flight under that barrier)
+    if (fs) __syncthreads();
     stage_store(lds, 0);
     __syncthreads();
     if (stamp) ts1 = __builtin_amdgcn_s_memtime();
     WINO_PASS(0, true)
     for (int pass = 1; pass < npass; ++pass) WINO_PASS(pass, false)
-#undef WINO_PASS
-#undef WINO_MMA
     if (stamp) ts2 = __builtin_amdgcn_s_memtime();
 
     // ---- output transform.  Over j in registers:  T[0] = m0 + m1 + m2,  T[1] = m1 - m2 - m3 ----
-    float* const Tl = reinterpret_cast<float*>(lds);
-    constexpr int TW = NT * 16;                    // floats per tile row of the exchange buffer
-    constexpr int TPL = MT * 16 * TW;              // floats per (i, b) plane
+    const int tid_f = wi * 64 + lane_now();  // (the epilogue's index math stays behind the passes, as the staging's stays in set_fragment)
+    ConvKArg pe_ = args + gi;
+    asm volatile("" : "+s"(pe_));
+    const auto& pe = *pe_;
+    const float* const res2e = stamp ? nullptr : pe.res2;
+    const unsigned out_bytes = pe.out_bytes;
+    const __amdgpu_buffer_rsrc_t rs_out = make_rsrc(pe.out, out_bytes), rs_r1 = make_rsrc(pe.res1, out_bytes), rs_r2 = make_rsrc(res2e, out_bytes),
+                                 rs_rp = make_rsrc(pe.res_post, out_bytes);
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
             const f32x4 t0 = acc[0][mt][nt] + acc[1][mt][nt] + acc[2][mt][nt];
             const f32x4 t1 = acc[1][mt][nt] - acc[2][mt][nt] - acc[3][mt][nt];
-            float* q = Tl + (wi * 2) * TPL + (mt * 16 + 4 * g) * TW + nt * 16 + li;  // D layout: rows 4g + r, column li
+            float* q = Tl + (wi * 2) * TPL + (mt * 16 + ((tid_f & 63) >> 4) * 4) * TW + nt * 16 + (tid_f & 15);  // D layout: rows 4g + r, column li
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 q[r * TW] = t0[r];
@@ -316,37 +381,30 @@ __device__ __forceinline__ void conv_wino_body(const ConvGroupK& grp) {
     // (buffer instructions here too: a pixel outside the map, or a piece in the padding of a tail block, gets the out-of-range offset --
     //  its loads return zeros and its stores are dropped, so the epilogue has no divergent branches)
     unsigned obase[MT];  // byte offset of the pixel's channel n0 in out / res*
-    const int q4 = tid & 3, px = tid >> 2;  // pixel px of the fragment: tile px >> 2, output row parity (px >> 1) & 1, column parity px & 1
+    const int q4 = tid_f & 3, px = tid_f >> 2;  // pixel px of the fragment: tile px >> 2, output row parity (px >> 1) & 1, column parity px & 1
     const bool hi = (px & 2) != 0;
     const int n0 = n_base + q4 * 4;  // (+ 16 k < cout_pad: a channel block never reaches past the padded width)
-    const bool tail = n_base + NT * 16 > p.cout || n_base + NT * 16 > p.out_cs;  // (uniform) the block holds padding channels
-    const unsigned out_bytes = p.out_bytes;
-    const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, out_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_r1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.res1), 0, p.res1 ? out_bytes : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_r2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(res2), 0, res2 ? out_bytes : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_rp = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.res_post), 0, p.res_post ? out_bytes : 0, 0x00020000);
-    auto ldb = [](const __amdgpu_buffer_rsrc_t& rs, unsigned off) { return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0)); };
     f32x4 r[MT][NT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
         const int t = px >> 2;
         const int oy = f_oy[mt] + 2 * (t >> fwl) + (hi ? 1 : 0);
         const int ox = f_ox[mt] + 2 * (t & (FW - 1)) + (px & 1);
-        const bool ok = f_ok[mt] && oy < p.conv_h && ox < p.conv_w;
-        obase[mt] = ok ? (unsigned)(((f_img[mt] * p.out_h + oy) * p.out_w + ox) * p.out_cs + n0) * 4u : kOOB;
+        const bool ok = f_ok[mt] && oy < pe.conv_h && ox < pe.conv_w;
+        obase[mt] = ok ? (unsigned)(((f_img[mt] * pe.out_h + oy) * pe.out_w + ox) * pe.out_cs + n0) * 4u : kOOB;
 #pragma unroll
         for (int k = 0; k < NT; ++k) {
-            r[mt][k] = *reinterpret_cast<const f32x4*>(p.bias + n0 + 16 * k);
+            r[mt][k] = *reinterpret_cast<const f32x4*>(pe.bias + n0 + 16 * k);
             if (!(I2R_DBG(p) & 1)) {
-                if (p.res1) r[mt][k] += ldb(rs_r1, obase[mt] + 64u * k);
-                if (res2) r[mt][k] += ldb(rs_r2, obase[mt] + 64u * k);
+                if (pe.res1) r[mt][k] += buf_ld16(rs_r1, obase[mt] + 64u * k, 0);
+                if (res2e) r[mt][k] += buf_ld16(rs_r2, obase[mt] + 64u * k, 0);
             }
         }
     }
-    __syncthreads();
     // T0[b] (even output rows) or T1[b] (odd rows) is the first of the three terms; the others follow two planes apart
     const float* const tq = Tl + ((px & 1) + (hi ? 2 : 0)) * TPL + (px >> 2) * TW + q4 * 4;
     const float sgn = hi ? -1.f : 1.f;  // Y = u0 + sgn (u1 + u2)
+    __syncthreads();
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
@@ -356,18 +414,21 @@ __device__ __forceinline__ void conv_wino_body(const ConvGroupK& grp) {
             const f32x4 u1 = *reinterpret_cast<const f32x4*>(q + 2 * TPL);   // T1 | T2
             const f32x4 u2 = *reinterpret_cast<const f32x4*>(q + 4 * TPL);   // T2 | T3
             f32x4 y = u0 + sgn * (u1 + u2) + r[mt][k];
-            if (p.relu) { y[0] = fmaxf(y[0], 0.f); y[1] = fmaxf(y[1], 0.f); y[2] = fmaxf(y[2], 0.f); y[3] = fmaxf(y[3], 0.f); }
+            if (pe.relu) { y[0] = fmaxf(y[0], 0.f); y[1] = fmaxf(y[1], 0.f); y[2] = fmaxf(y[2], 0.f); y[3] = fmaxf(y[3], 0.f); }
             unsigned off = obase[mt] + 64u * k;
-            if (p.res_post) y += ldb(rs_rp, off);
+            if (pe.res_post) y += buf_ld16(rs_rp, off, 0);
             if (tail) {  // (uniform) channels >= cout are padding: keep them exactly zero; pieces beyond the row are not written
                 const int n = n0 + 16 * k;
-                if (!(n + 4 <= p.cout || n + 4 <= p.out_cs)) off = kOOB;
+                if (!(n + 4 <= pe.cout || n + 4 <= pe.out_cs)) off = kOOB;
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
-                    if (n + e >= p.cout) y[e] = 0.f;
+                    if (n + e >= pe.cout) y[e] = 0.f;
             }
             if (!(I2R_DBG(p) & 1) || y[0] == 12345.678f) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, y), rs_out, off, 0, 0);
         }
+    }  // (fragments of the run)
+#undef WINO_PASS
+#undef WINO_MMA
     if (stamp) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         const unsigned long long ts3 = __builtin_amdgcn_s_memtime();
@@ -378,15 +439,22 @@ __device__ __forceinline__ void conv_wino_body(const ConvGroupK& grp) {
     }
 }
 
+// grp is the FIRST and ONLY parameter of both kernels, passed by value: it starts the kernel-argument block, and its members start grp.
+// A kernel with another signature must not use wino_args().
+__device__ __forceinline__ ConvKArg wino_args() {
+    static_assert(offsetof(ConvGroupK, g) == 0, "the members lead the kernel argument");
+    return (ConvKArg)__builtin_amdgcn_kernarg_segment_ptr();
+}
+
 template <int MT, int NT>
 __global__ __launch_bounds__(256, (MT == 1 ? (NT == 3 ? 4 : 3) : 2)) void conv_wino_f32(const ConvGroupK grp) {
-    conv_wino_body<MT, NT, false>(grp);
+    conv_wino_body<MT, NT, false>(grp, wino_args());
 }
 
 // the fused-input form (a grouped launch takes it when a member has f_t1)
 template <int MT, int NT>
 __global__ __launch_bounds__(256, (MT == 1 ? (NT == 3 ? 4 : 3) : 2)) void conv_wino_fin_f32(const ConvGroupK grp) {
-    conv_wino_body<MT, NT, true>(grp);
+    conv_wino_body<MT, NT, true>(grp, wino_args());
 }
 
 }  // namespace

@@ -39,6 +39,7 @@ PAIR1X1 = True  # layer1's conv3 + next conv1 as one i2r_conv1x1_pair launch (fp
 FUSE_IN = True  # the closing pass of an HRNet fuse layer rides in the staging of the next module's first Winograd conv (fp32)
 PRUNE_FUSE = True  # the last HRNet module computes only the fuse outputs its caller reads (HRNetW48.emit(need=...))
 WINOGRAD = True  # fp32 3x3 stride-1 convs on the Winograd F(2x2, 3x3) kernels
+WINO_SEQ = True  # ... whose workgroups run several fragments on one set-up, as many as the library chooses per launch (i2r_conv_desc.seq = 0; False: one)
 # fork / join / record / wait as device-side signal / wait kernels (csrc/i2r_api.hip) when the lanes are independent queues.  A wait kernel
 # spins until ANOTHER kernel signals it: under a tool that lets one kernel run at a time (rocprofv3 counter collection serialises dispatches)
 # it could only time out, so the event form is used whenever a profiler library is attached to the process.
@@ -296,6 +297,7 @@ class Program:
             d.algo, d.w = 1, pc.w_wino.data_ptr()
             mt = 1  # one fragment per item: 114 registers = 4 waves per SIMD (measured faster than two fragments at 2 waves per SIMD)
             d.tile_h, d.tile_w, d.mt, d.wn, d.ck = fh, fw, mt, 1, 0
+            d.seq = 0 if WINO_SEQ else 1
             n_frag = x.n * -(-conv_h // fh) * -(-conv_w // fw)
             geo = ("wino", -(-n_frag // mt) * (nfrag // nt))
             key = ("wino", nt, mt)
