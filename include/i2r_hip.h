@@ -694,6 +694,25 @@ I2R_API int i2r_view_scramble(const float* o, float* out, const int32_t* person_
 typedef struct i2r_gather_args { const float* src; float* out; const int32_t* map; int32_t n_out, floats_per_crop; } i2r_gather_args;
 typedef struct i2r_scramble_args { const float* o; float* out; const int32_t* person_map; int32_t n_out, n_images, max_persons, c, cs, hw; } i2r_scramble_args;
 
+/* i2r_rows_gather_multi: up to I2R_MAX_GATHER_SEGS row gathers in ONE launch -- the hand-over between the per-person and the per-group
+ * part of a grouped forward (Engine.forward_groups(share_first_stage=True): pooled features, position rows and first-member features of
+ * both flip halves; then the first row of every group).  Per segment: row i of out (i < n_out) = row map[i] of src when
+ * 0 <= map[i] < n_src, else a row of ZEROS (-1 and every out-of-range entry alike): the kernel forms no address from an entry it has
+ * not checked, so a wrong table costs zero rows, never a read outside src.  map: device int32 [n_out], read when the launch runs (the
+ * caller refills it per call).  Rows are row_bytes bytes of any type, copied as 16-byte chunks: row_bytes a positive multiple of 16,
+ * src and out 16-byte aligned, rows dense (row i at i * row_bytes).  A segment with n_out == 0 is skipped (its other fields are not
+ * read); when every segment is empty nothing is launched and the call returns 0.
+ * CALLER'S CONTRACT: the output ranges [out, out + n_out row_bytes) of the segments do not overlap each other or any segment's
+ * [src, src + n_src row_bytes); only src == out is checked.
+ * Flat 1-D grid, a row served by ceil(row_bytes / 16 KiB) workgroups of equal share (16 B to > 1 MiB rows), a workgroup never straddles
+ * two rows; no LDS, no atomics, vector stores only: deterministic.
+ * I2R_E_ARG: null a, n_seg outside 0 .. 8, and for a non-empty segment n_out < 0, a null pointer, src == out, n_src < 0, row_bytes not a
+ * positive multiple of 16, a misaligned src / out, more than 2^31 - 1 workgroups in all. */
+#define I2R_MAX_GATHER_SEGS 8
+typedef struct i2r_gather_seg { const void* src; void* out; const int32_t* map; int32_t n_out, n_src; int64_t row_bytes; } i2r_gather_seg;
+typedef struct i2r_gather_multi_args { i2r_gather_seg seg[I2R_MAX_GATHER_SEGS /* 8 */]; int32_t n_seg; } i2r_gather_multi_args;
+I2R_API int i2r_rows_gather_multi(const i2r_gather_multi_args* a, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Program runner: replay a pre-built list of launches from one C call (no per-op host overhead, and
  * capturable into a hipGraph by the caller).  Streams: ops carry a lane id 0..3; lane 0 is `stream`,
@@ -720,7 +739,8 @@ enum {
     I2R_OP_PE_RES_STEM = 15, I2R_OP_HRT_ATTN = 16, I2R_OP_HRT_MLP = 17, /* 18: reserved */ I2R_OP_FUSE_UP = 19,
     I2R_OP_CONV1X1_PAIR = 20, I2R_OP_CONV1X1_LP = 21, I2R_OP_MH_ATTN = 22, I2R_OP_PE_CAT_VEC = 23, I2R_OP_ROWS_GATHER = 24, I2R_OP_VIEW_SCRAMBLE = 25,
     I2R_OP_RECORD = 26, I2R_OP_WAIT = 27, I2R_OP_LANE_FLAGS = 28, I2R_OP_ATTN_WEIGHTS = 29,
-    I2R_OP_ATTN_QUERY = 30
+    I2R_OP_ATTN_QUERY = 30,
+    I2R_OP_ROWS_GATHER_MULTI = 31 /* args: i2r_gather_multi_args (additive: I2R_ABI_VERSION unchanged) */
 };
 
 typedef struct i2r_stem_args {

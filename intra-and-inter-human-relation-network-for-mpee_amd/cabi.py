@@ -35,6 +35,10 @@ OP_LANE_FLAGS = 28          # args = device int32[64] flag buffer: the sync ops 
 # capture=)); bench.py never times those, so it stays outside the OP_ names that bench.op_model covers one by one.
 CAPTURE_OP_ATTN_WEIGHTS = 29
 CAPTURE_OP_ATTN_QUERY = 30  # I2R_OP_ATTN_QUERY: rows / columns of those maps at query points (i2r_attn_query_maps; capture programs with queries=)
+# I2R_OP_ROWS_GATHER_MULTI: up to MAX_GATHER_SEGS row gathers by device tables in one launch (i2r_rows_gather_multi).  Only the grouped
+# programs emit it (Engine.forward_groups); bench.py never times those, so like the capture ops it stays outside the OP_ names.
+GROUPS_OP_ROWS_GATHER_MULTI = 31
+MAX_GATHER_SEGS = 8
 SYNC_OPS = (OP_FORK, OP_JOIN, OP_XSYNC, OP_RECORD, OP_WAIT, OP_LANE_FLAGS)  # ops that launch nothing (FORK / JOIN: `lane` is a lane mask)
 
 _fp = C.c_void_p  # device pointers travel as integers
@@ -121,6 +125,14 @@ class AttnQueryArgs(C.Structure):   # i2r_attn_query_args
 
 class GatherArgs(C.Structure):
     _fields_ = [("src", _fp), ("out", _fp), ("map", _fp), ("n_out", _i32), ("floats_per_crop", _i32)]
+
+
+class GatherSeg(C.Structure):   # i2r_gather_seg (40 bytes)
+    _fields_ = [("src", _fp), ("out", _fp), ("map", _fp), ("n_out", _i32), ("n_src", _i32), ("row_bytes", C.c_int64)]
+
+
+class GatherMultiArgs(C.Structure):   # i2r_gather_multi_args
+    _fields_ = [("seg", GatherSeg * MAX_GATHER_SEGS), ("n_seg", _i32)]
 
 
 class ScrambleArgs(C.Structure):
@@ -229,7 +241,7 @@ class Op(C.Structure):
 
 # every symbol include/i2r_hip.h declares (tests/test_host.py::test_cabi_library_exports_every_declared_symbol checks the built library exports them all)
 EXPORTS = ("i2r_conv", "i2r_conv_grouped", "i2r_conv_kernel_name", "i2r_conv_grid", "i2r_stem_conv", "i2r_pe_res_stem", "i2r_maxpool3x3s2", "i2r_head", "i2r_layernorm", "i2r_window_attn", "i2r_hrt_attn_block", "i2r_hrt_mlp_block", "i2r_dwconv3x3",
-           "i2r_upsample_bilinear_add", "i2r_upsample_bilinear_add_multi", "i2r_fuse_up_add", "i2r_conv1x1_pair", "i2r_conv1x1_lp", "i2r_flip_merge", "i2r_decode", "i2r_pose_nms", "i2r_group_nearest", "i2r_oks_match", "i2r_oks_accumulate", "i2r_joint_targets", "i2r_val_metrics", "i2r_crop_affine", "i2r_box_mask", "i2r_crop_affine_cv2", "i2r_box_mask_cv2", "i2r_person_inputs_cv2", "i2r_encoder_kv", "i2r_encoder_layer", "i2r_mh_attention", "i2r_attn_weights", "i2r_attn_query_maps", "i2r_pe_cat_vec", "i2r_rows_gather", "i2r_view_scramble",
+           "i2r_upsample_bilinear_add", "i2r_upsample_bilinear_add_multi", "i2r_fuse_up_add", "i2r_conv1x1_pair", "i2r_conv1x1_lp", "i2r_flip_merge", "i2r_decode", "i2r_pose_nms", "i2r_group_nearest", "i2r_oks_match", "i2r_oks_accumulate", "i2r_joint_targets", "i2r_val_metrics", "i2r_crop_affine", "i2r_box_mask", "i2r_crop_affine_cv2", "i2r_box_mask_cv2", "i2r_person_inputs_cv2", "i2r_encoder_kv", "i2r_encoder_layer", "i2r_mh_attention", "i2r_attn_weights", "i2r_attn_query_maps", "i2r_pe_cat_vec", "i2r_rows_gather", "i2r_rows_gather_multi", "i2r_view_scramble",
            "i2r_run_program", "i2r_run_program_timed", "i2r_abi_version", "i2r_last_error", "i2r_device_check")
 
 _LIB = None
@@ -280,6 +292,7 @@ def load_library(path=LIB_PATH):
     L.i2r_encoder_kv.argtypes = [C.POINTER(EncoderDesc), C.c_void_p]
     L.i2r_encoder_layer.argtypes = [C.POINTER(EncoderDesc), C.c_void_p]
     L.i2r_rows_gather.argtypes = [_fp, _fp, _fp, _i32, _i32, C.c_void_p]
+    L.i2r_rows_gather_multi.argtypes = [C.POINTER(GatherMultiArgs), C.c_void_p]
     L.i2r_view_scramble.argtypes = [_fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, C.c_void_p]
     L.i2r_pe_cat_vec.argtypes = [C.POINTER(PeCatVecArgs), C.c_void_p]
     L.i2r_mh_attention.argtypes = [C.POINTER(MhAttnArgs), C.c_void_p]

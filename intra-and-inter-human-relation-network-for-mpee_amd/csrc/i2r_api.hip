@@ -217,6 +217,7 @@ static int run_program(const i2r_op* ops, int32_t n_ops, void* const* streams, v
                 rc = i2r_rows_gather(a->src, a->out, a->map, a->n_out, a->floats_per_crop, st);
                 break;
             }
+            case I2R_OP_ROWS_GATHER_MULTI: rc = i2r_rows_gather_multi((const i2r_gather_multi_args*)op.args, st); break;
             case I2R_OP_VIEW_SCRAMBLE: {
                 const i2r_scramble_args* a = (const i2r_scramble_args*)op.args;
                 rc = i2r_view_scramble(a->o, a->out, a->person_map, a->n_out, a->n_images, a->max_persons, a->c, a->cs, a->hw, st);

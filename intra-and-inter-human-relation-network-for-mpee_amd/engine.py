@@ -476,6 +476,25 @@ class Program:
         self.ops.append((cabi.OP_ROWS_GATHER, lane, a))
         return a
 
+    def rows_gather_multi(self, segments, lane=0):
+        """ONE launch for up to cabi.MAX_GATHER_SEGS gathers (i2r_rows_gather_multi).  segments: (src, out, table, n_out, n_src, src_crop,
+        out_crop) -- crop out_crop + i of the Act `out` = crop src_crop + table[i] of the Act `src` for i < n_out, zeros where table[i] is
+        outside [0, n_src).  Rows of any storage type; the device int32 tables belong to the CALLER, who refills them per call and may
+        patch n_src of the returned args (the launch is fixed, the contents are not).  The output windows must not overlap."""
+        assert 1 <= len(segments) <= cabi.MAX_GATHER_SEGS, "rows_gather_multi: %d segments (1..%d)" % (len(segments), cabi.MAX_GATHER_SEGS)
+        a = cabi.GatherMultiArgs()
+        a.n_seg = len(segments)
+        for g, (src, out, table, n_out, n_src, src_crop, out_crop) in zip(a.seg, segments):
+            row = src.h * src.w * src.cs * (2 if src.dt else 4)
+            assert (out.h, out.w, out.cs, out.dt) == (src.h, src.w, src.cs, src.dt), "rows_gather_multi copies whole rows of one stride and type"
+            assert row % 16 == 0 and table.dtype == torch.int32 and table.numel() >= n_out
+            assert 0 <= out_crop and out_crop + n_out <= out.n and 0 <= src_crop and src_crop + n_src <= src.n
+            self.keep.append(table)
+            g.src, g.out, g.map = src.ptr + row * src_crop, out.ptr + row * out_crop, table.data_ptr()
+            g.n_out, g.n_src, g.row_bytes = n_out, n_src, row
+        self.ops.append((cabi.GROUPS_OP_ROWS_GATHER_MULTI, lane, a))
+        return a
+
     def view_scramble(self, o, person_map, n_images, max_persons, c, lane=0):
         """GeneralTransformerBlock's re-viewing of the attention output (attention.py:1025-1029, i2r_view_scramble) + get_valid_output"""
         out = self.alloc(len(person_map), o.h, o.w, c)
@@ -2424,20 +2443,31 @@ class Engine:
     # The reference pushes every member of every group through the whole network.  The first stage is per crop, so here it runs once
     # per DISTINCT crop; only the part behind it sees the expanded batch, and only the first member of every group reaches the
     # up-sampling layers and the head.  Which crops make up which group is DATA of a call (two device tables), never part of a program.
-    def _groups_shared(self, H, W):
-        """True: the first stage is the bare HRNet tower and the tower / tail seam serves the groups; False: the expanded forward.
-        ValueError: a bare-tower model whose tail cannot take gathered rows."""
+    def _groups_shared(self, H, W, share=None):
+        """How forward_groups runs: "tower" -- the first stage is the bare HRNet tower and the tower / tail seam serves the groups;
+        "first" -- a first stage of its own (TransPose-H, HRFormer) once per crop, its tail on the gathered rows (share=True only);
+        None -- the expanded forward.  share: forward_groups' share_first_stage.  ValueError: the stand-alone models, and a model whose
+        tail cannot take gathered rows where the first stage would be shared (always for the bare tower unless share is False)."""
         if self.name not in ("interformer_pureMulti", "interformer", "interformer_2stage"):
             raise ValueError("forward_groups serves the inter-human models (MODEL.NAME %r has no person groups)" % self.name)
-        if not (self.name == "interformer_pureMulti" or not self.singleformer) or not isinstance(self.tower, HRNetW48):
-            return False
+        if share is False:
+            return None
+        bare = (self.name == "interformer_pureMulti" or not self.singleformer) and isinstance(self.tower, HRNetW48)
+        if not bare and share is None:
+            return None
         if self.use_pos and self.pe_mode == "sine":
             raise ValueError("forward_groups: MULTI_POS_EMBEDDING sine is not served (its table depends on a crop's position inside the group)")
         if self.cat_concat:
             raise ValueError("forward_groups: MULTI_POS_EMBEDDING cat_vec concatenated is not served (the hand-over buffer is DIM_MODEL wide)")
         if self.window_attn:
             raise ValueError("forward_groups: ATTENTION_TYPE window is not served (its block re-views the whole batch's output)")
-        return not (H % 16 or W % 16)  # (the tower's and the tail's map sizes must agree, as in _split_bounds)
+        if bare:
+            return None if H % 16 or W % 16 else "tower"  # (the tower's and the tail's map sizes must agree, as in _split_bounds)
+        tok = (H // 2 ** self.res_layer // 4) * (W // 2 ** self.res_layer // 4) if self.singleformer == "transpose_h" else None
+        if H % 32 or W % 32 or (tok is not None and tok != self.single_tokens):
+            raise ValueError("forward_groups: share_first_stage does not serve %d x %d inputs (the first stage is built for MODEL.IMAGE_SIZE; "
+                             "maps of 1/32 of the input must exist)" % (H, W))
+        return "first"
 
     @staticmethod
     def _first_rows(group_len):
@@ -2448,14 +2478,20 @@ class Engine:
             r += n
         return out
 
-    def forward_groups(self, x, pos_mask, members, group_len, flip_joint_map=None):
+    def forward_groups(self, x, pos_mask, members, group_len, flip_joint_map=None, share_first_stage=None):
         """x [S, 3, H, W], pos_mask [S, 1, H, W]: the DISTINCT crops of a batch; members: device int32 [sum(group_len)] of crop indices in
         [0, S), group after group (input.main_target_groups); group_len: host list of the groups' sizes.  -> the 'multi' heat maps of the
         FIRST member of every group, [len(group_len), J, H/4, W/4] -- what the reference's validate_main_target keeps of model(x[members],
         pos_mask[members], group_len) (get_target_person, lib/core/function.py:309-334); with flip_joint_map merged with the flip test's.
-        Models whose first stage is the bare HRNet tower run it once per crop (S, not sum(group_len), times) and the tail on the gathered
-        rows; every other model runs the expanded forward.  Programs are keyed by capacities only: other groups of the same sizes build nothing."""
+        share_first_stage: None (default) -- models whose first stage is the bare HRNet tower run it once per crop (S, not
+        sum(group_len), times) and the tail on the gathered rows, every other model runs the expanded forward; True -- the models with
+        a first stage of their own (TransPose-H, HRFormer) share it too: first stage, pooling and position branch once per crop, ONE
+        i2r_rows_gather_multi into group layout, the inter-human encoder, one more for the groups' first rows, the tail per group
+        (ValueError where the tail cannot take gathered rows: sine, cat_vec concatenated, window, an unserved size); False -- always the
+        expanded forward.  Programs are keyed by capacities only: other groups of the same sizes build nothing.  A member index
+        outside [0, S) is never dereferenced on the True path: its rows are zeros."""
         assert x.dim() == 4 and x.shape[1] == 3 and x.dtype == torch.float32
+        assert share_first_stage in (None, True, False)
         S, _, H, W = x.shape
         group_len = [int(n) for n in group_len]
         assert group_len and all(n >= 1 for n in group_len), "every group needs at least one member"
@@ -2464,8 +2500,11 @@ class Engine:
         with torch.cuda.device(self.device):
             x = x.to(self.device).contiguous()
             pm = pos_mask.to(self.device, torch.float32).contiguous() if pos_mask is not None else None
-            if self._groups_shared(H, W):
+            mode = self._groups_shared(H, W, share_first_stage)
+            if mode == "tower":
                 return self._forward_groups_shared(x, pm, members, group_len, flip_joint_map, S, H, W)
+            if mode == "first":
+                return self._forward_groups_first(x, pm, members, group_len, flip_joint_map, S, H, W)
             # not shared: the reference's own arithmetic on the gathered inputs (index plumbing in torch, every launch in forward())
             idx = members.long()
             y = self.forward(x.index_select(0, idx), pm.index_select(0, idx) if pm is not None else None, group_len, flip_joint_map)
@@ -2547,6 +2586,91 @@ class Engine:
         if "mask_gather" in patch:
             assert pm is not None and pm.shape == (S, 1, H, W)
             patch["mask_gather"].src = pm.data_ptr()
+        k = 2 if flip else 1
+        out = torch.empty(k * capN, self.cfg["MODEL"]["NUM_JOINTS"], H // 4, W // 4, dtype=torch.float32, device=self.device)
+        patch["multi"].out = out.data_ptr()
+        Pt.run(self.side_streams if Pt.uses_lanes else None)
+        if flip:
+            return self._flip_merge(out, out[capN:], flip_joint_map, N, H, W)
+        return out[:N]
+
+    def _build_groups_first(self, capS, capG, capN, H, W, flip):
+        """The ONE program of a grouped forward of a model with a first stage of its own (share_first_stage=True): first stage (no
+        `single` head), pooling to TRANS_SIZE and position branch on the capS distinct crops -> one rows_gather_multi into group layout
+        [capG] by the member table (pooled features, position rows) and, for the tail, the full-resolution first-stage features of
+        every group's FIRST member [capN] by patch["first_member"] -> inter-human encoder -> one rows_gather_multi of the first row of
+        every group [capN] -> _emit_tail.  With the flip test every buffer holds the mirrored half behind the plain one."""
+        M = self.cfg["MODEL"]
+        P = self._new_program()
+        patch, k = {}, (2 if flip else 1)
+        g, patch["x"] = self._emit_single(P, k * capS, H, W, capS)
+        f = g
+        for _ in range(int(math.log(f.w // M["TRANS_SIZE"][-1], 2))):
+            c = P.maxpool(f)
+            if f is not g:
+                P.release(f)
+            f = c
+        pos = None
+        if self.use_pos:  # per crop like the first stage: on the distinct masks, bound straight to the call's pos_mask
+            pos, patch["pos_mask"] = self._pos_branch(P, k * capS, H, W, M["TRANS_SIZE"][-1], n_src=capS)
+            assert (pos.h, pos.w, pos.cs) == (f.h, f.w, f.cs)
+        # the member table carries one more entry, always -1: where the capacity slots of the first-row table point (_forward_groups_first)
+        mtab = patch["members"] = torch.full((capG + 1,), -1, dtype=torch.int32, device=self.device)
+        ftab = patch["first"] = torch.full((capN,), -1, dtype=torch.int32, device=self.device)
+        fmtab = patch["first_member"] = torch.full((capN,), -1, dtype=torch.int32, device=self.device)  # members[first row of group]
+        fg = P.alloc(k * capG, f.h, f.w, f.c, f.dt)
+        posg = P.alloc(k * capG, pos.h, pos.w, pos.c, pos.dt) if pos is not None else None
+        tail_reads_single = self.domain_trans is not None or self.upconv is not None or bool(self.deconvs)
+        sf = P.alloc(k * capN, g.h, g.w, g.c, g.dt) if tail_reads_single else None
+        segs = []
+        for half in range(k):
+            segs.append((f, fg, mtab, capG, capS, half * capS, half * capG))
+            if pos is not None:
+                segs.append((pos, posg, mtab, capG, capS, half * capS, half * capG))
+            if sf is not None:
+                segs.append((g, sf, fmtab, capN, capS, half * capS, half * capN))
+        patch["hand_over"] = P.rows_gather_multi(segs)  # (n_src of its segments: the S real crops of the call)
+        P.release(g)
+        if f is not g:
+            P.release(f)
+        if pos is not None:
+            P.release(pos)
+        e = P.encoder(fg, self.layers, self._token_offsets([1] * (k * capG), fg.h * fg.w), pos=posg.ptr if posg is not None else 0,
+                      regroupable=True, pre_norm=self.pre_norm)
+        e1 = P.alloc(k * capN, e.h, e.w, e.c, e.dt)
+        P.rows_gather_multi([(e, e1, ftab, capN, capG, half * capG, half * capN) for half in range(k)])
+        P.release(e)
+        return self._emit_tail(P, patch, e1, sf)
+
+    def _forward_groups_first(self, x, pm, members, group_len, flip_joint_map, S, H, W):
+        flip = flip_joint_map is not None
+        G, N = sum(group_len), len(group_len)
+        capS, capG, capN = self.capacity(S), self.capacity(G), self.capacity(N)
+        Pt, patch = self._program((capG, capN, capS, H, W, flip, "groups-first"), lambda: self._build_groups_first(capS, capG, capN, H, W, flip))
+        self.last_programs, self.last_concurrent = [Pt], []
+        # bind the call: the crops, the masks, the three tables, the token groups (capacity slots: one-person groups of zero rows), a fresh output
+        patch["x"].in_ = x.data_ptr()
+        patch["x"].n_valid = S
+        if "pos_mask" in patch:
+            assert pm is not None and pm.shape == (S, 1, H, W)
+            patch["pos_mask"].in_ = pm.data_ptr()
+            patch["pos_mask"].n_valid = S
+        for seg in patch["hand_over"].seg:
+            seg.n_src = S  # (a member index beyond the real crops gives a zero row, not a capacity slot's)
+        patch["members"].fill_(-1)
+        patch["members"][:G].copy_(members)
+        fkey = tuple(group_len)
+        if patch.get("_first_key") != fkey:
+            first = self._first_rows(group_len)
+            patch["first"].copy_(torch.tensor(first + [-1] * (capN - N), dtype=torch.int32).pin_memory(), non_blocking=True)
+            patch["_first_idx"] = torch.tensor(first + [capG] * (capN - N), dtype=torch.long).to(self.device)
+            patch["_first_key"] = fkey
+        torch.index_select(patch["members"], 0, patch["_first_idx"], out=patch["first_member"])  # (on the device: nothing is read back)
+        glen = group_len + [1] * (capG - G)
+        if flip:
+            glen = glen + glen
+        for grouping, tok in Pt.groupings:
+            Pt.set_groups(grouping, self._token_offsets(glen, tok))
         k = 2 if flip else 1
         out = torch.empty(k * capN, self.cfg["MODEL"]["NUM_JOINTS"], H // 4, W // 4, dtype=torch.float32, device=self.device)
         patch["multi"].out = out.data_ptr()

@@ -218,12 +218,15 @@ class I2RModule(nn.Module):
         with torch.no_grad():
             return eng.forward(x, pos_mask, [int(n) for n in length], flip_joint_map=jm)
 
-    def forward_main_target(self, x, pos_mask, length, boxes, max_patch=None, flip_pairs=None):
+    def forward_main_target(self, x, pos_mask, length, boxes, max_patch=None, flip_pairs=None, share_first_stage=None):
         """The model side of the reference's grouped test mode (PATCH_MODE main_target: collater.get_max_patch + validate_main_target,
         lib/dataset/collater.py:35-51, lib/core/function.py:289-468): every person is the target of a group of itself and its
         min(n, max_patch) - 1 nearest neighbours in the image (input.main_target_groups, by the boxes' top-left corners), the model runs
         on the groups and only the target's heat maps are kept.  x, pos_mask, length: the ordinary collated batch; boxes: [S, >= 2]
         (x, y, ...) per crop; max_patch: default cfg.DATASET.MAX_PATCH; flip_pairs: merge with the flip test as forward_flip does.
+        share_first_stage (Engine.forward_groups): None -- the HRNet-tower models share their first stage, every other model runs the
+        expanded batch; True -- the TransPose-H / HRFormer first stages run once per person too (ValueError where the tail cannot take
+        gathered rows); False -- always the expanded batch.
         -> [S, J, H/4, W/4], one row per person in input order, so decode / val_metrics / rescore_nms / oks_eval take it with the
         ordinary per-person centres and scales."""
         from ..input import main_target_groups
@@ -242,7 +245,7 @@ class I2RModule(nn.Module):
         assert x.shape[0] == sum(length), "sum(length)=%d != number of crops %d" % (sum(length), x.shape[0])
         with torch.no_grad():
             groups = main_target_groups(boxes, length, int(max_patch), eng.device)
-            return eng.forward_groups(x, pos_mask, groups.members, groups.group_len, flip_joint_map=jm)
+            return eng.forward_groups(x, pos_mask, groups.members, groups.group_len, flip_joint_map=jm, share_first_stage=share_first_stage)
 
     def _hooked(self):
         """(stack, layer, self_attn module) of every layer with forward hooks on its self_attn (usually none)"""
