@@ -70,11 +70,12 @@ class Act:
 
 
 class _RawAct:
-    """a device buffer laid out like the Act `like` that the program does not own (a conv's second input)"""
+    """a device buffer laid out like the Act `like` (of n crops, if given) that the program does not own: a conv's second input, the
+    source of a gather segment bound per call"""
     __slots__ = ("ptr", "n", "h", "w", "c", "cs", "dt")
 
-    def __init__(self, ptr, like):
-        self.ptr, self.n, self.h, self.w, self.c, self.cs, self.dt = ptr, like.n, like.h, like.w, like.c, like.cs, 0
+    def __init__(self, ptr, like, n=None):
+        self.ptr, self.n, self.h, self.w, self.c, self.cs, self.dt = ptr, like.n if n is None else n, like.h, like.w, like.c, like.cs, 0
 
 
 _MT_EFF = {1: 0.62, 2: 0.9, 3: 1.0, 4: 0.9}  # measured on MI355X (tools/sweep_conv.py): B-fragment reuse per wave
@@ -465,22 +466,12 @@ class Program:
         self.ops.append((cabi.OP_ROWS_GATHER, lane, a))
         return out
 
-    def rows_gather_table(self, src, out, table, n_out, src_crop=0, out_crop=0, lane=0):
-        """crop out_crop + i of `out` = crop src_crop + table[i] of `src` (zeros for -1), i < n_out: the gather of rows_gather with a device
-        int32 table the CALLER owns and refills per call (the launch is fixed, the contents are not) and a window into both buffers"""
-        per = src.h * src.w * src.cs
-        assert src.dt == 0 and out.dt == 0 and (out.h, out.w, out.cs) == (src.h, src.w, src.cs), "rows_gather copies whole fp32 rows of one stride"
-        assert table.dtype == torch.int32 and table.numel() >= n_out and 0 <= out_crop and out_crop + n_out <= out.n and 0 <= src_crop < src.n
-        self.keep.append(table)
-        a = cabi.GatherArgs(src.ptr + 4 * per * src_crop, out.ptr + 4 * per * out_crop, table.data_ptr(), n_out, per)
-        self.ops.append((cabi.OP_ROWS_GATHER, lane, a))
-        return a
-
     def rows_gather_multi(self, segments, lane=0):
         """ONE launch for up to cabi.MAX_GATHER_SEGS gathers (i2r_rows_gather_multi).  segments: (src, out, table, n_out, n_src, src_crop,
-        out_crop) -- crop out_crop + i of the Act `out` = crop src_crop + table[i] of the Act `src` for i < n_out, zeros where table[i] is
-        outside [0, n_src).  Rows of any storage type; the device int32 tables belong to the CALLER, who refills them per call and may
-        patch n_src of the returned args (the launch is fixed, the contents are not).  The output windows must not overlap."""
+        out_crop) -- crop out_crop + i of `out` = crop src_crop + table[i] of `src` for i < n_out, zeros where table[i] is outside
+        [0, n_src).  src, out: Acts, or anything else with ptr, n, h, w, cs, dt (_RawAct: a buffer the program does not own).  Rows of any
+        storage type; the device int32 tables belong to the CALLER, who refills them per call and may patch src and n_src of the returned
+        args (the launch is fixed, the contents are not).  The output windows must not overlap."""
         assert 1 <= len(segments) <= cabi.MAX_GATHER_SEGS, "rows_gather_multi: %d segments (1..%d)" % (len(segments), cabi.MAX_GATHER_SEGS)
         a = cabi.GatherMultiArgs()
         a.n_seg = len(segments)
@@ -1113,6 +1104,7 @@ class HRNetW48:
     def __init__(self, pk, p, extra):
         self.extra = extra
         s2, s3 = extra["STAGE2"], extra["STAGE3"]
+        self.stride = 4 * 2 ** (s3["NUM_BRANCHES"] - 1)  # input pixels per pixel of the lowest branch, the one `reduce` reads (interformer_pureMulti.py:702)
         self.stem1 = pk.stem(p + "conv1", p + "bn1")
         self.conv2 = pk.conv(p + "conv2", p + "bn2", stride=2)
         self.layer1 = pk.bottlenecks(p + "layer1", 4)
@@ -1686,6 +1678,11 @@ class AttnQueries:
         self.capacity = int(capacity) if capacity is not None else max(int(torch.as_tensor(t).shape[-1]) for t in self.tokens.values())
 
 
+def _multi(y):
+    """the 'multi' heat maps of what a forward returned (a dict where the model supervises its first stage too)"""
+    return y["multi"] if isinstance(y, dict) else y
+
+
 class Engine:
     """Packed model + program cache for one device. Built by models/_base.I2RModule."""
 
@@ -1830,8 +1827,7 @@ class Engine:
             fh, fw = H // 4, W // 4
         if self.layers:
             if fh is None:  # the bare tower's lowest branch (_build)
-                down = 4 * 2 ** (M["EXTRA"]["STAGE3"]["NUM_BRANCHES"] - 1)
-                fh, fw = H // down, W // down
+                fh, fw = H // self.tower.stride, W // self.tower.stride
             else:
                 for _ in range(int(math.log(fw // M["TRANS_SIZE"][-1], 2))):  # (3x3 stride-2 max-pool steps down to TRANS_SIZE)
                     fh, fw = (fh + 1) // 2, (fw + 1) // 2
@@ -1997,6 +1993,20 @@ class Engine:
             b = c
         return b, pe_args
 
+    def _pool_to_trans(self, P, g, out=None):
+        """the first-stage features g pooled down to TRANS_SIZE (3x3 stride-2 max-pool steps); g itself stays (the tail reads it).
+        out: the destination of the last step (the token buffer of a channel concatenation)"""
+        steps = int(math.log(g.w // self.cfg["MODEL"]["TRANS_SIZE"][-1], 2))
+        if out is not None and steps == 0:
+            raise NotImplementedError("cat_vec with a first stage whose maps already are TRANS_SIZE")
+        f = g
+        for i in range(steps):
+            c = P.maxpool(f, out=out if i == steps - 1 else None)
+            if f is not g:
+                P.release(f)
+            f = c
+        return f
+
     def _new_program(self, query=None):
         """an empty Program of this engine's storage type; query: the program-key suffix of _check_queries, or None"""
         P = Program(self.device)
@@ -2026,8 +2036,7 @@ class Engine:
             tw = M["TRANS_SIZE"][-1]
             cat = P.alloc(S, H // (W // tw), tw, d + self.pe_fc["vec"])
         if bare and part == "tail":
-            down = 4 * 2 ** (M["EXTRA"]["STAGE3"]["NUM_BRANCHES"] - 1)  # the lowest branch of the tower (interformer_pureMulti.py:702)
-            f = patch["feat"] = P.alloc(S, H // down, W // down, self.reduce.cout)
+            f = patch["feat"] = P.alloc(S, H // self.tower.stride, W // self.tower.stride, self.reduce.cout)
             f.t.zero_()  # (capacity slots nobody fills must hold finite rows)
             single_feat = None
         elif bare:
@@ -2045,15 +2054,7 @@ class Engine:
             single_feat = g
             if self.return_dict:
                 patch["single"] = P.head(g, self.single_head)
-            f = g
-            steps = int(math.log(f.w // M["TRANS_SIZE"][-1], 2))
-            if cat is not None and steps == 0:
-                raise NotImplementedError("cat_vec with a first stage whose maps already are TRANS_SIZE")
-            for i in range(steps):
-                c = P.maxpool(f, out=cat if i == steps - 1 else None)
-                if f is not single_feat:
-                    P.release(f)
-                f = c
+            f = self._pool_to_trans(P, g, out=cat)
         if self.window_attn:
             e = self._emit_window_block(P, patch, f, single_feat, S, H, W, length)
             return self._emit_tail(P, patch, e, single_feat)
@@ -2279,8 +2280,7 @@ class Engine:
                 pm = pos_mask.to(self.device) if pos_mask is not None else None
                 a = self._forward(x, pm, list(length), None, S, H, W, sine_n)
                 b = self._forward(torch.flip(x, dims=[3]), torch.flip(pm, dims=[3]) if pm is not None else None, list(length), None, S, H, W, sine_n)
-                a, b = (a["multi"], b["multi"]) if isinstance(a, dict) else (a, b)
-                return self._flip_merge(a.contiguous(), b.contiguous(), flip_joint_map, S, H, W)
+                return self._flip_merge(_multi(a).contiguous(), _multi(b).contiguous(), flip_joint_map, S, H, W)
         with torch.cuda.device(self.device):  # kernels and events go to the CURRENT device: make it this engine's
             return self._forward(x, pos_mask, list(length), flip_joint_map, S, H, W, sine_n)
 
@@ -2318,7 +2318,7 @@ class Engine:
         parts = min(self.SPLIT_PARTS, len(length))
         if parts < 2 or sum(length) < self.SPLIT_MIN_CROPS or not isinstance(self.tower, HRNetW48):
             return None
-        if H is not None and (H % 16 or W % 16):
+        if H is not None and (H % self.tower.stride or W % self.tower.stride):
             return None
         if self.cat_concat or self.window_attn:  # (the hand-over buffer is DIM_MODEL wide; the window type re-views the WHOLE batch's output)
             return None
@@ -2408,33 +2408,37 @@ class Engine:
                 self.programs.pop(next(iter(self.programs)))
         return self.programs[key]
 
+    def _run_towers(self, x, crop_bounds, H, W, flip, dest, dest_cap):
+        """The per-crop tower (+ reduce) on the crops [crop_bounds[i], crop_bounds[i + 1]) of x as part program i, every part but the first on
+        a stream of its own (_fork_parts; a single part runs on the caller's), each handing its features over with a row copy into
+        rows of dest [dest_cap (x 2 with the flip test), h, w, cs]: the plain rows at the crops' own indices, the mirrored ones dest_cap
+        behind them.  -> the part programs"""
+        def run_tower(i):
+            lo, hi = crop_bounds[i], crop_bounds[i + 1]
+            capp = self.capacity(hi - lo)
+            Pw, pw, f = self._program((capp, H, W, flip, "tower", i), lambda: self._build(capp, H, W, [1] * capp, flip, part="tower"))
+            xi = x[lo:hi]
+            pw["x"].in_ = xi.data_ptr()
+            pw["x"].n_valid = hi - lo
+            Pw.run()
+            fv = f.view()
+            dest[lo:hi].copy_(fv[:hi - lo])
+            if flip:
+                dest[dest_cap + lo:dest_cap + hi].copy_(fv[capp:capp + hi - lo])
+            return Pw
+        parts = len(crop_bounds) - 1
+        return self._fork_parts(range(parts - 1, 0, -1), [x], run_tower) if parts > 1 else [run_tower(0)]
+
     def _forward_split(self, x, pos_mask, length, flip_joint_map, S, H, W, sine_n, bounds):
         """Models whose first stage is the bare HRNet tower (vanilla I2R-Net): the per-crop TOWER of every image group runs as its own
         program on its own stream, the rest of the forward -- position branch, inter-human encoder over ALL images (one launch per
         layer: 384 query tiles with the partial key split instead of two launches of 192), deconvs, head -- as one tail program on
         the caller's stream behind the join.  The towers hand their features over with a row copy into the tail's buffer."""
-        parts = len(bounds) - 1
         flip = flip_joint_map is not None
-        offs = [sum(length[:b]) for b in bounds]
         x = x.to(self.device).contiguous()
         cap = self.capacity(S)
         Pt, patch = self._program((cap, H, W, flip, "tail"), lambda: self._build(cap, H, W, list(length) + [1] * (cap - S), flip, part="tail"))
-        feat = patch["feat"].view()  # [cap (x 2 with the flip test), h, w, cs]
-
-        def run_tower(i):
-            sp = offs[i + 1] - offs[i]
-            capp = self.capacity(sp)
-            Pw, pw, f = self._program((capp, H, W, flip, "tower", i), lambda: self._build(capp, H, W, [1] * capp, flip, part="tower"))
-            xi = x[offs[i]:offs[i + 1]]
-            pw["x"].in_ = xi.data_ptr()
-            pw["x"].n_valid = sp
-            Pw.run()
-            fv = f.view()
-            feat[offs[i]:offs[i + 1]].copy_(fv[:sp])
-            if flip:
-                feat[cap + offs[i]:cap + offs[i + 1]].copy_(fv[capp:capp + sp])
-            return Pw
-        progs = self._fork_parts(range(parts - 1, 0, -1), [x], run_tower)
+        progs = self._run_towers(x, [sum(length[:b]) for b in bounds], H, W, flip, patch["feat"].view(), cap)
         self.last_programs = progs + [Pt]
         self.last_concurrent = progs  # (ran side by side on their own streams: bench.py times them that way)
         return self._run_program(Pt, patch, None, pos_mask, length, flip_joint_map, S, cap, H, W, sine_n)
@@ -2462,7 +2466,7 @@ class Engine:
         if self.window_attn:
             raise ValueError("forward_groups: ATTENTION_TYPE window is not served (its block re-views the whole batch's output)")
         if bare:
-            return None if H % 16 or W % 16 else "tower"  # (the tower's and the tail's map sizes must agree, as in _split_bounds)
+            return None if H % self.tower.stride or W % self.tower.stride else "tower"  # (the tower's and the tail's map sizes must agree, as in _split_bounds)
         tok = (H // 2 ** self.res_layer // 4) * (W // 2 ** self.res_layer // 4) if self.singleformer == "transpose_h" else None
         if H % 32 or W % 32 or (tok is not None and tok != self.single_tokens):
             raise ValueError("forward_groups: share_first_stage does not serve %d x %d inputs (the first stage is built for MODEL.IMAGE_SIZE; "
@@ -2488,8 +2492,9 @@ class Engine:
         a first stage of their own (TransPose-H, HRFormer) share it too: first stage, pooling and position branch once per crop, ONE
         i2r_rows_gather_multi into group layout, the inter-human encoder, one more for the groups' first rows, the tail per group
         (ValueError where the tail cannot take gathered rows: sine, cat_vec concatenated, window, an unserved size); False -- always the
-        expanded forward.  Programs are keyed by capacities only: other groups of the same sizes build nothing.  A member index
-        outside [0, S) is never dereferenced on the True path: its rows are zeros."""
+        expanded forward.  Programs are keyed by capacities only: other groups of the same sizes build nothing.  On every shared path
+        (the default one of the HRNet tower included) a member index outside [0, S) is never dereferenced: the hand-over gathers are
+        bound to the S real crops of the call, so its rows -- features, mask -- are zeros, never what a capacity slot holds."""
         assert x.dim() == 4 and x.shape[1] == 3 and x.dtype == torch.float32
         assert share_first_stage in (None, True, False)
         S, _, H, W = x.shape
@@ -2501,140 +2506,64 @@ class Engine:
             x = x.to(self.device).contiguous()
             pm = pos_mask.to(self.device, torch.float32).contiguous() if pos_mask is not None else None
             mode = self._groups_shared(H, W, share_first_stage)
-            if mode == "tower":
-                return self._forward_groups_shared(x, pm, members, group_len, flip_joint_map, S, H, W)
-            if mode == "first":
-                return self._forward_groups_first(x, pm, members, group_len, flip_joint_map, S, H, W)
+            if mode is not None:
+                return self._forward_groups_shared(mode, x, pm, members, group_len, flip_joint_map, S, H, W)
             # not shared: the reference's own arithmetic on the gathered inputs (index plumbing in torch, every launch in forward())
             idx = members.long()
-            y = self.forward(x.index_select(0, idx), pm.index_select(0, idx) if pm is not None else None, group_len, flip_joint_map)
-            y = y["multi"] if isinstance(y, dict) else y
+            y = _multi(self.forward(x.index_select(0, idx), pm.index_select(0, idx) if pm is not None else None, group_len, flip_joint_map))
             return y.index_select(0, torch.tensor(self._first_rows(group_len), dtype=torch.long).to(self.device))
 
-    def _build_groups(self, capS, capG, capN, H, W, flip):
-        """The tail program of a grouped forward: person features [capS] (filled by tower programs, patch["pfeat"]) -> rows gathered by the
-        member table into group layout [capG] -> position branch on the gathered masks, inter-human encoder -> the first row of every
-        group [capN] -> up-sampling layers, head.  With the flip test every buffer holds the mirrored half behind the plain one."""
-        M = self.cfg["MODEL"]
+    def _build_groups(self, mode, capS, capG, capN, H, W, flip):
+        """The program of a grouped forward behind the first stage: person-level features and position rows [capS] -> ONE rows_gather_multi
+        (patch["hand_over"]) into group layout [capG] by the member table -> inter-human encoder -> one rows_gather_multi of the first row
+        of every group [capN] -> _emit_tail.  With the flip test every buffer holds the mirrored half behind the plain one.
+        mode "tower": the person features are a buffer that tower programs fill (patch["pfeat"], _run_towers); the members' MASKS are
+        gathered (a segment whose source is the call's pos_mask) and the position branch runs on them.
+        mode "first": the program holds the first stage too (no `single` head), pooling to TRANS_SIZE and the position branch on the
+        distinct crops, bound straight to the call's pos_mask; its rows are gathered like the features, and for the tail the
+        full-resolution first-stage features of every group's FIRST member [capN] by patch["first_member"]."""
         P = self._new_program()
-        patch, k = {}, (2 if flip else 1)
-        down = 4 * 2 ** (M["EXTRA"]["STAGE3"]["NUM_BRANCHES"] - 1)
-        pf = patch["pfeat"] = P.alloc(k * capS, H // down, W // down, self.reduce.cout)
-        pf.t.zero_()
-        mtab = patch["members"] = torch.full((capG,), -1, dtype=torch.int32, device=self.device)
-        ftab = patch["first"] = torch.full((capN,), -1, dtype=torch.int32, device=self.device)
-        f = P.alloc(k * capG, pf.h, pf.w, pf.c)
-        for half in range(k):
-            P.rows_gather_table(pf, f, mtab, capG, src_crop=half * capS, out_crop=half * capG)
-        pos_ptr = 0
-        if self.use_pos:
-            assert (H * W) % 4 == 0
-            gm = torch.zeros(capG * H * W, dtype=torch.float32, device=self.device)  # the members' masks [capG, 1, H, W]
-            P.keep.append(gm)
-            P.nbytes += gm.numel() * 4
-            patch["mask_gather"] = cabi.GatherArgs(0, gm.data_ptr(), mtab.data_ptr(), capG, H * W)  # (src: the call's pos_mask)
-            P.ops.append((cabi.OP_ROWS_GATHER, 0, patch["mask_gather"]))
-            pos, pe = self._pos_branch(P, k * capG, H, W, M["TRANS_SIZE"][-1], n_src=capG)
-            pe.in_, pe.n_valid = gm.data_ptr(), capG
-            assert (pos.h, pos.w, pos.cs) == (f.h, f.w, f.cs)
-            pos_ptr = pos.ptr
-        e = P.encoder(f, self.layers, self._token_offsets([1] * (k * capG), f.h * f.w), pos=pos_ptr, regroupable=True, pre_norm=self.pre_norm)
-        e1 = P.alloc(k * capN, e.h, e.w, e.c)
-        for half in range(k):
-            P.rows_gather_table(e, e1, ftab, capN, src_crop=half * capG, out_crop=half * capN)
-        P.release(e)
-        return self._emit_tail(P, patch, e1, None)
-
-    def _forward_groups_shared(self, x, pm, members, group_len, flip_joint_map, S, H, W):
-        flip = flip_joint_map is not None
-        G, N = sum(group_len), len(group_len)
-        capS, capG, capN = self.capacity(S), self.capacity(G), self.capacity(N)
-        Pt, patch = self._program((capG, capN, capS, H, W, flip, "groups"), lambda: self._build_groups(capS, capG, capN, H, W, flip))
-        pfeat = patch["pfeat"].view()  # [capS (x 2 with the flip test), h, w, cs]
-        bounds = self._split_bounds([1] * S, H, W) or [0, S]  # (the tower is per crop: any cut of the S crops serves)
-        parts = len(bounds) - 1
-
-        def run_tower(i):
-            sp = bounds[i + 1] - bounds[i]
-            capp = self.capacity(sp)
-            Pw, pw, f = self._program((capp, H, W, flip, "tower", i), lambda: self._build(capp, H, W, [1] * capp, flip, part="tower"))
-            xi = x[bounds[i]:bounds[i + 1]]
-            pw["x"].in_ = xi.data_ptr()
-            pw["x"].n_valid = sp
-            Pw.run()
-            fv = f.view()
-            pfeat[bounds[i]:bounds[i + 1]].copy_(fv[:sp])
-            if flip:
-                pfeat[capS + bounds[i]:capS + bounds[i + 1]].copy_(fv[capp:capp + sp])
-            return Pw
-        progs = self._fork_parts(range(parts - 1, 0, -1), [x], run_tower) if parts > 1 else [run_tower(0)]
-        self.last_programs = progs + [Pt]
-        self.last_concurrent = progs if parts > 1 else []
-        # bind the call: the two tables, the token groups (capacity slots: one-person groups of zero rows), the masks, a fresh output
-        patch["members"].fill_(-1)
-        patch["members"][:G].copy_(members)
-        fkey = tuple(group_len)
-        if patch.get("_first_key") != fkey:
-            first = self._first_rows(group_len) + [-1] * (capN - N)
-            patch["first"].copy_(torch.tensor(first, dtype=torch.int32).pin_memory(), non_blocking=True)
-            patch["_first_key"] = fkey
-        glen = group_len + [1] * (capG - G)
-        if flip:
-            glen = glen + glen
-        for grouping, tok in Pt.groupings:
-            Pt.set_groups(grouping, self._token_offsets(glen, tok))
-        if "mask_gather" in patch:
-            assert pm is not None and pm.shape == (S, 1, H, W)
-            patch["mask_gather"].src = pm.data_ptr()
-        k = 2 if flip else 1
-        out = torch.empty(k * capN, self.cfg["MODEL"]["NUM_JOINTS"], H // 4, W // 4, dtype=torch.float32, device=self.device)
-        patch["multi"].out = out.data_ptr()
-        Pt.run(self.side_streams if Pt.uses_lanes else None)
-        if flip:
-            return self._flip_merge(out, out[capN:], flip_joint_map, N, H, W)
-        return out[:N]
-
-    def _build_groups_first(self, capS, capG, capN, H, W, flip):
-        """The ONE program of a grouped forward of a model with a first stage of its own (share_first_stage=True): first stage (no
-        `single` head), pooling to TRANS_SIZE and position branch on the capS distinct crops -> one rows_gather_multi into group layout
-        [capG] by the member table (pooled features, position rows) and, for the tail, the full-resolution first-stage features of
-        every group's FIRST member [capN] by patch["first_member"] -> inter-human encoder -> one rows_gather_multi of the first row of
-        every group [capN] -> _emit_tail.  With the flip test every buffer holds the mirrored half behind the plain one."""
-        M = self.cfg["MODEL"]
-        P = self._new_program()
-        patch, k = {}, (2 if flip else 1)
-        g, patch["x"] = self._emit_single(P, k * capS, H, W, capS)
-        f = g
-        for _ in range(int(math.log(f.w // M["TRANS_SIZE"][-1], 2))):
-            c = P.maxpool(f)
-            if f is not g:
-                P.release(f)
-            f = c
-        pos = None
-        if self.use_pos:  # per crop like the first stage: on the distinct masks, bound straight to the call's pos_mask
-            pos, patch["pos_mask"] = self._pos_branch(P, k * capS, H, W, M["TRANS_SIZE"][-1], n_src=capS)
-            assert (pos.h, pos.w, pos.cs) == (f.h, f.w, f.cs)
-        # the member table carries one more entry, always -1: where the capacity slots of the first-row table point (_forward_groups_first)
+        patch, k, tw = {}, (2 if flip else 1), self.cfg["MODEL"]["TRANS_SIZE"][-1]
+        g = pos = posg = sf = None
+        if mode == "tower":
+            f = patch["pfeat"] = P.alloc(k * capS, H // self.tower.stride, W // self.tower.stride, self.reduce.cout)
+            f.t.zero_()
+        else:
+            g, patch["x"] = self._emit_single(P, k * capS, H, W, capS)
+            f = self._pool_to_trans(P, g)
+            if self.use_pos:
+                pos, patch["pos_mask"] = self._pos_branch(P, k * capS, H, W, tw, n_src=capS)
+                assert (pos.h, pos.w, pos.cs) == (f.h, f.w, f.cs)
+        # the member table carries one more entry, always -1: where the capacity slots of the first-row table point (_forward_groups_shared)
         mtab = patch["members"] = torch.full((capG + 1,), -1, dtype=torch.int32, device=self.device)
         ftab = patch["first"] = torch.full((capN,), -1, dtype=torch.int32, device=self.device)
-        fmtab = patch["first_member"] = torch.full((capN,), -1, dtype=torch.int32, device=self.device)  # members[first row of group]
         fg = P.alloc(k * capG, f.h, f.w, f.c, f.dt)
-        posg = P.alloc(k * capG, pos.h, pos.w, pos.c, pos.dt) if pos is not None else None
-        tail_reads_single = self.domain_trans is not None or self.upconv is not None or bool(self.deconvs)
-        sf = P.alloc(k * capN, g.h, g.w, g.c, g.dt) if tail_reads_single else None
-        segs = []
-        for half in range(k):
-            segs.append((f, fg, mtab, capG, capS, half * capS, half * capG))
-            if pos is not None:
-                segs.append((pos, posg, mtab, capG, capS, half * capS, half * capG))
-            if sf is not None:
-                segs.append((g, sf, fmtab, capN, capS, half * capS, half * capN))
-        patch["hand_over"] = P.rows_gather_multi(segs)  # (n_src of its segments: the S real crops of the call)
-        P.release(g)
-        if f is not g:
-            P.release(f)
+        pairs = [(f, fg, mtab, capG)]
         if pos is not None:
-            P.release(pos)
+            posg = P.alloc(k * capG, pos.h, pos.w, pos.c, pos.dt)
+            pairs.append((pos, posg, mtab, capG))
+        if mode == "first":
+            fmtab = patch["first_member"] = torch.full((capN,), -1, dtype=torch.int32, device=self.device)  # members[first row of group]
+            if self.domain_trans is not None or self.upconv is not None or self.deconvs:  # (the tail reads the first-stage features)
+                sf = P.alloc(k * capN, g.h, g.w, g.c, g.dt)
+                pairs.append((g, sf, fmtab, capN))
+        segs = [(src, out, tab, n, capS, half * capS, half * n) for half in range(k) for src, out, tab, n in pairs]
+        if mode == "tower" and self.use_pos:
+            assert (H * W) % 4 == 0
+            # the members' masks [capG, 1, H, W] (not mirrored: the stem kernel does that), outside the arena, whose rows are 16 channels wide
+            gm = Act(torch.zeros(capG * H * W, dtype=torch.float32, device=self.device), capG, H, W, 1, 1)
+            P.keep.append(gm.t)
+            P.nbytes += gm.t.numel() * 4
+            segs.append((_RawAct(0, gm, n=capS), gm, mtab, capG, capS, 0, 0))
+        # (per call: n_src of every segment = the S real crops, src of the mask segment = the call's pos_mask)
+        patch["hand_over"] = P.rows_gather_multi(segs)
+        if mode == "first":
+            P.release(g, f if f is not g else None, pos)
+        if mode == "tower" and self.use_pos:
+            patch["mask_seg"] = patch["hand_over"].seg[len(segs) - 1]
+            posg, pe = self._pos_branch(P, k * capG, H, W, tw, n_src=capG)
+            pe.in_, pe.n_valid = gm.ptr, capG
+            assert (posg.h, posg.w, posg.cs) == (fg.h, fg.w, fg.cs)
         e = P.encoder(fg, self.layers, self._token_offsets([1] * (k * capG), fg.h * fg.w), pos=posg.ptr if posg is not None else 0,
                       regroupable=True, pre_norm=self.pre_norm)
         e1 = P.alloc(k * capN, e.h, e.w, e.c, e.dt)
@@ -2642,42 +2571,37 @@ class Engine:
         P.release(e)
         return self._emit_tail(P, patch, e1, sf)
 
-    def _forward_groups_first(self, x, pm, members, group_len, flip_joint_map, S, H, W):
+    def _forward_groups_shared(self, mode, x, pm, members, group_len, flip_joint_map, S, H, W):
         flip = flip_joint_map is not None
         G, N = sum(group_len), len(group_len)
         capS, capG, capN = self.capacity(S), self.capacity(G), self.capacity(N)
-        Pt, patch = self._program((capG, capN, capS, H, W, flip, "groups-first"), lambda: self._build_groups_first(capS, capG, capN, H, W, flip))
-        self.last_programs, self.last_concurrent = [Pt], []
-        # bind the call: the crops, the masks, the three tables, the token groups (capacity slots: one-person groups of zero rows), a fresh output
-        patch["x"].in_ = x.data_ptr()
-        patch["x"].n_valid = S
-        if "pos_mask" in patch:
+        Pt, patch = self._program((capG, capN, capS, H, W, flip, "groups", mode), lambda: self._build_groups(mode, capS, capG, capN, H, W, flip))
+        progs = []
+        if mode == "tower":  # (the tower is per crop: any cut of the S crops serves)
+            progs = self._run_towers(x, self._split_bounds([1] * S, H, W) or [0, S], H, W, flip, patch["pfeat"].view(), capS)
+        self.last_programs = progs + [Pt]
+        self.last_concurrent = progs if len(progs) > 1 else []
+        # bind the call: the crops, the masks, the tables, the token groups (capacity slots: one-person groups of zero rows)
+        if self.use_pos:
             assert pm is not None and pm.shape == (S, 1, H, W)
-            patch["pos_mask"].in_ = pm.data_ptr()
-            patch["pos_mask"].n_valid = S
+        self._bind_inputs(patch, None if mode == "tower" else x, pm, S)
         for seg in patch["hand_over"].seg:
             seg.n_src = S  # (a member index beyond the real crops gives a zero row, not a capacity slot's)
+        if "mask_seg" in patch:
+            patch["mask_seg"].src = pm.data_ptr()
         patch["members"].fill_(-1)
         patch["members"][:G].copy_(members)
         fkey = tuple(group_len)
         if patch.get("_first_key") != fkey:
             first = self._first_rows(group_len)
             patch["first"].copy_(torch.tensor(first + [-1] * (capN - N), dtype=torch.int32).pin_memory(), non_blocking=True)
-            patch["_first_idx"] = torch.tensor(first + [capG] * (capN - N), dtype=torch.long).to(self.device)
+            if "first_member" in patch:
+                patch["_first_idx"] = torch.tensor(first + [capG] * (capN - N), dtype=torch.long).to(self.device)
             patch["_first_key"] = fkey
-        torch.index_select(patch["members"], 0, patch["_first_idx"], out=patch["first_member"])  # (on the device: nothing is read back)
-        glen = group_len + [1] * (capG - G)
-        if flip:
-            glen = glen + glen
-        for grouping, tok in Pt.groupings:
-            Pt.set_groups(grouping, self._token_offsets(glen, tok))
-        k = 2 if flip else 1
-        out = torch.empty(k * capN, self.cfg["MODEL"]["NUM_JOINTS"], H // 4, W // 4, dtype=torch.float32, device=self.device)
-        patch["multi"].out = out.data_ptr()
-        Pt.run(self.side_streams if Pt.uses_lanes else None)
-        if flip:
-            return self._flip_merge(out, out[capN:], flip_joint_map, N, H, W)
-        return out[:N]
+        if "first_member" in patch:
+            torch.index_select(patch["members"], 0, patch["_first_idx"], out=patch["first_member"])  # (on the device: nothing is read back)
+        self._bind_groups(Pt, group_len, capG - G, flip)
+        return self._run_bound(Pt, patch, capN, N, flip_joint_map, H, W)[0]
 
     def _forward_part(self, x, pos_mask, length, flip_joint_map, S, H, W, sine_n, slot=0, capture=frozenset(), queries=None, query=None):
         x = x.to(self.device).contiguous()
@@ -2699,29 +2623,15 @@ class Engine:
         """Bind one call into a built program of capacity `cap` and run it on the current stream: the token groups of `length` (capacity
         slots as one-person groups), the sine rows, the inputs (x None: tower programs filled patch["feat"]), fresh outputs, the capture
         buffers; then the flip merge and the slice to the S real crops.  -> what forward() returns."""
-        flip = flip_joint_map is not None
-        glen = list(length) + [1] * (cap - S)
-        if flip:
-            glen = glen + glen
-        for grouping, tok in P.groupings:
-            P.set_groups(grouping, self._token_offsets(glen, tok))
+        glen = self._bind_groups(P, length, cap - S, flip_joint_map is not None)
         self._fill_sine(patch, glen, sine_n)
-        if x is not None:
-            patch["x"].in_ = x.data_ptr()
-            patch["x"].n_valid = S
+        pm = None
         if "pos_mask" in patch:
             pm = pos_mask.to(self.device, torch.float32).contiguous()
             assert pm.shape == (S, 1, H, W)
             if self.window_attn:  # one more crop: the zero mask of the padded persons (_emit_window_block)
                 pm = torch.cat([pm, pm.new_zeros(1, 1, H, W)], 0)
-            patch["pos_mask"].in_ = pm.data_ptr()
-            patch["pos_mask"].n_valid = pm.shape[0]
-        out = torch.empty(2 * cap if flip else cap, self.cfg["MODEL"]["NUM_JOINTS"], H // 4, W // 4, dtype=torch.float32, device=self.device)
-        patch["multi"].out = out.data_ptr()
-        single = None
-        if "single" in patch:
-            single = torch.empty_like(out)
-            patch["single"].out = single.data_ptr()
+        self._bind_inputs(patch, x, pm, S)
         if capture:  # the real images / crops of this call: the capacity slots behind them cost nothing
             glens = []
             for c in P.captures:
@@ -2730,10 +2640,45 @@ class Engine:
             if query:
                 self._check_map_sizes(P, H, W)
             _, maps, inputs = P.set_query_capture(glens, queries) if query else P.set_capture(glens)
-        P.run(self.side_streams if P.uses_lanes else None)
-        if flip:
-            return self._flip_merge(out, out[cap:], flip_joint_map, S, H, W)
-        res = {"single": single[:S], "multi": out[:S]} if self.return_dict else out[:S]
+        multi, single = self._run_bound(P, patch, cap, S, flip_joint_map, H, W)
+        res = {"single": single, "multi": multi} if single is not None else multi
         if capture:
             return res, self._capture_result(maps, inputs, S)
         return res
+
+    # the per-call steps every bound forward shares (_run_program, _forward_groups_shared)
+    def _bind_groups(self, P, length, pad, flip):
+        """the token groups of a call: `length` persons per group, then `pad` capacity slots as one-person groups, all of it twice with the
+        flip test -> that list"""
+        glen = list(length) + [1] * pad
+        if flip:
+            glen = glen + glen
+        for grouping, tok in P.groupings:
+            P.set_groups(grouping, self._token_offsets(glen, tok))
+        return glen
+
+    @staticmethod
+    def _bind_inputs(patch, x, pm, S):
+        """the S crops x (None: tower programs read them) and the masks pm of a call, device tensors the caller holds until the run is
+        issued, into the stem args of the program that reads them"""
+        if x is not None:
+            patch["x"].in_ = x.data_ptr()
+            patch["x"].n_valid = S
+        if "pos_mask" in patch:
+            patch["pos_mask"].in_ = pm.data_ptr()
+            patch["pos_mask"].n_valid = pm.shape[0]
+
+    def _run_bound(self, P, patch, cap, S, flip_joint_map, H, W):
+        """fresh outputs for the heads of a bound program of `cap` output rows, the run on the current stream, then the flip merge or the
+        slice to the S real rows -> ('multi' maps, 'single' maps or None: a program without that head, the flip test)"""
+        flip = flip_joint_map is not None
+        out = torch.empty(2 * cap if flip else cap, self.cfg["MODEL"]["NUM_JOINTS"], H // 4, W // 4, dtype=torch.float32, device=self.device)
+        patch["multi"].out = out.data_ptr()
+        single = None
+        if "single" in patch:
+            single = torch.empty_like(out)
+            patch["single"].out = single.data_ptr()
+        P.run(self.side_streams if P.uses_lanes else None)
+        if flip:
+            return self._flip_merge(out, out[cap:], flip_joint_map, S, H, W), None
+        return out[:S], (single[:S] if single is not None else None)

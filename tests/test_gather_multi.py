@@ -1,10 +1,14 @@
 """No GPU: the declarations of i2r_rows_gather_multi in include/i2r_hip.h and their ctypes mirrors in cabi agree (struct layout, segment
-limit, program op, export name), and the additive change left I2R_ABI_VERSION at 17."""
+limit, program op, export name), the additive change left I2R_ABI_VERSION at 17, and Program.rows_gather_multi fills the segment
+fields from Acts and raw buffers as the kernel reads them."""
 import ctypes as C
 import os
 import re
 
-from i2r_amd import cabi
+import pytest
+import torch
+
+from i2r_amd import cabi, engine
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = open(os.path.join(ROOT, "include", "i2r_hip.h")).read()
@@ -58,3 +62,37 @@ def test_export_and_abi_version():
     L = cabi.load_library()
     assert L.i2r_abi_version() == 17
     assert L.i2r_rows_gather_multi.argtypes[0] is C.POINTER(cabi.GatherMultiArgs)
+
+
+def test_program_segments_carry_windows_sizes_and_row_bytes():
+    """three segments -- an fp32 Act pair, a 16-bit pair, a raw source the program does not own -- with windows into source and output"""
+    P = engine.Program(torch.device("cpu"))
+    tab = torch.zeros(8, dtype=torch.int32)
+    a32, o32 = P.alloc(6, 4, 3, 48), P.alloc(10, 4, 3, 48)             # rows of 4 * 3 * 48 floats
+    a16, o16 = P.alloc(6, 2, 2, 78, dt=1), P.alloc(8, 2, 2, 78, dt=1)  # rows of 2 * 2 * 80 bf16 (78 channels in rows of 80)
+    mask = engine.Act(torch.zeros(5 * 8 * 4), 5, 8, 4, 1, 1)           # [5, 1, 8, 4] masks: rows of 32 floats
+    raw = engine._RawAct(4096, mask, n=3)
+    a = P.rows_gather_multi([(a32, o32, tab, 5, 3, 2, 4), (a16, o16, tab, 8, 4, 1, 0), (raw, mask, tab, 5, 3, 0, 0)])
+    assert P.ops[-1] == (cabi.GROUPS_OP_ROWS_GATHER_MULTI, 0, a) and a.n_seg == 3
+    rows = [4 * 3 * 48 * 4, 2 * 2 * 80 * 2, 8 * 4 * 4]
+    want = [(a32.ptr + 2 * rows[0], o32.ptr + 4 * rows[0], 5, 3), (a16.ptr + rows[1], o16.ptr, 8, 4), (4096, mask.ptr, 5, 3)]
+    for g, row, (src, out, n_out, n_src) in zip(a.seg, rows, want):
+        assert (g.src, g.out, g.map, g.n_out, g.n_src, g.row_bytes) == (src, out, tab.data_ptr(), n_out, n_src, row)
+    assert all((g.src, g.out, g.n_out, g.row_bytes) == (None, None, 0, 0) for g in a.seg[3:])
+    assert any(t is tab for t in P.keep)
+
+
+def test_program_refuses_odd_rows_and_windows_past_the_output():
+    P = engine.Program(torch.device("cpu"))
+    tab = torch.zeros(8, dtype=torch.int32)
+    odd = engine.Act(torch.zeros(4 * 3), 4, 3, 1, 1, 1)  # rows of 3 floats: 12 bytes
+    with pytest.raises(AssertionError):
+        P.rows_gather_multi([(engine._RawAct(4096, odd), odd, tab, 4, 4, 0, 0)])
+    src, out = P.alloc(6, 2, 2, 16), P.alloc(6, 2, 2, 16)
+    P.rows_gather_multi([(src, out, tab, 4, 6, 0, 2)])  # crops 2..5: the last window that fits
+    with pytest.raises(AssertionError):
+        P.rows_gather_multi([(src, out, tab, 4, 6, 0, 3)])
+    with pytest.raises(AssertionError):
+        P.rows_gather_multi([(src, out, tab, 4, 6, 1, 0)])  # source window past src.n
+    with pytest.raises(AssertionError):
+        P.rows_gather_multi([(src, out, tab[:3], 4, 6, 0, 0)])  # table shorter than n_out

@@ -14,6 +14,7 @@ import torch
 from _golden import CASES, VARIANTS, load, setup
 from i2r_amd import cabi, caller, models
 from i2r_amd import input as i2r_input
+from i2r_amd.engine import _multi
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-3
@@ -41,8 +42,7 @@ def _mt():
 def _expanded(eng, x, m, groups, jm=None):
     """the yardstick: the ordinary forward on the expanded batch, first row of every group """
     idx = groups.members.long()
-    y = eng.forward(x[idx], m[idx], groups.group_len, flip_joint_map=jm)
-    y = y["multi"] if isinstance(y, dict) else y
+    y = _multi(eng.forward(x[idx], m[idx], groups.group_len, flip_joint_map=jm))
     first = np.concatenate([[0], np.cumsum(groups.group_len)[:-1]])
     return y[torch.from_numpy(first).cuda()].clone()
 
@@ -124,6 +124,8 @@ def test_tower_runs_once_per_person_and_the_head_once_per_group(flip):
     enc = [a for k, _, a in tail.ops if k == cabi.OP_ENC_LAYER]
     assert enc and all(a.n_tok == eng.capacity(G) * (2 if flip else 1) * 16 * 12 for a in enc)
     assert not any(k in (cabi.OP_STEM, cabi.OP_CONV_GROUP) and getattr(a, "cin", 0) == 3 for k, _, a in tail.ops), "no image stem in the tail"
+    kinds = [k for k, _, _ in tail.ops]
+    assert kinds.count(cabi.GROUPS_OP_ROWS_GATHER_MULTI) == 2 and cabi.OP_ROWS_GATHER not in kinds, "one hand-over launch (features and masks), one for the first rows"
 
 
 def test_part_batch_towers_from_24_crops_on():
@@ -149,6 +151,39 @@ def test_part_batch_towers_from_24_crops_on():
     err = (got - want).abs().max().item()
     print("24 persons, two tower programs: shared vs expanded forward max-abs %.3e" % err)
     assert got.shape == want.shape == (24, 14, 64, 48) and err < TOL, err
+
+
+def test_a_bad_member_index_reads_zeros_not_a_stale_capacity_slot():
+    """9 crops in a program of capacity 10, one member entry 9 (outside [0, S), inside the buffers): the hand-over is bound to the 9 real
+    crops, so that member's rows are zeros whatever an earlier 10-crop call left in slot 9 of the person buffer, and the groups without
+    the bad entry give the bits of the call with the valid table."""
+    from i2r_amd import synth
+    net, _, _, _, _ = _net("w48_l213")
+    eng = net.engine()
+    assert eng.capacity(9) == 10
+
+    def inputs(length, seed):
+        x, m, _ = synth.make_inputs(length, 256, 192, seed)
+        return x.cuda(), m.cuda()
+    x9, m9 = inputs([4, 5], 0)
+    glen9, glen10 = [2, 2, 2, 2, 1], [2] * 5
+    good = torch.tensor([0, 1, 2, 3, 4, 5, 6, 7, 8], dtype=torch.int32).cuda()
+    bad = good.clone()
+    bad[3] = 9  # the second entry of group 1
+    mem10 = torch.arange(10, dtype=torch.int32).cuda()
+    want = eng.forward_groups(x9, m9, good, glen9).clone()
+    got = []
+    for seed in (1, 2):  # inputs A, inputs B: slot 9 of the person buffer holds crop 9 of that call
+        xa, ma = inputs([5, 5], seed)
+        assert eng.forward_groups(xa, ma, mem10, glen10).shape[0] == 5
+        tail10 = eng.last_programs[-1]
+        got.append(eng.forward_groups(x9, m9, bad, glen9).clone())
+        assert eng.last_programs[-1] is tail10, "the 9-crop call runs in the 10-crop call's program"
+    torch.cuda.synchronize()
+    assert torch.isfinite(got[0]).all() and torch.equal(got[0], got[1]), "the result depends on what an earlier call left in a capacity slot"
+    keep = [0, 2, 3, 4]
+    assert torch.equal(got[0][keep], want[keep]), "groups without the bad entry"
+    print("group 1 with its second member zeroed vs the valid table: max-abs %.3e" % (got[0][1] - want[1]).abs().max().item())
 
 
 def test_other_boxes_rebuild_nothing_and_change_the_maps():

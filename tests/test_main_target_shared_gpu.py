@@ -16,6 +16,7 @@ import torch
 
 from i2r_amd import cabi, synth
 from i2r_amd import input as i2r_input
+from i2r_amd.engine import _multi
 from test_main_target_gpu import FLIP_PAIRS, TOL, _expanded, _mt, _net
 
 pytestmark = pytest.mark.gpu
@@ -37,10 +38,6 @@ def _boxes(n):
         return b[:n].copy()
     u = synth.uniform01(3, "test_main_target_shared.boxes", 2 * n).reshape(n, 2)
     return u * [560.0, 400.0]
-
-
-def _multi(y):
-    return y["multi"] if isinstance(y, dict) else y
 
 
 @pytest.mark.parametrize("tag", ["tph_l21", "hrt_l21", "hrt288_l2", "tph2s_l12", "ochtph_l21", "tph2s_dt_l12", "tph_up_l21", "tph2s_up_fk3_l12",
