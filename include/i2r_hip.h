@@ -27,7 +27,7 @@ extern "C" {
 #endif
 
 /* Bumped when an existing entry point, struct layout or op code changes.  Entry points that are only ADDED (i2r_joint_targets,
- * i2r_val_metrics, i2r_oks_match, i2r_oks_accumulate) do not bump it: no existing struct changes with them, and a binding built
+ * i2r_val_metrics, i2r_val_combine, i2r_oks_match, i2r_oks_accumulate) do not bump it: no existing struct changes with them, and a binding built
  * against the older header keeps working with the newer library. */
 #define I2R_ABI_VERSION 17
 
@@ -356,7 +356,8 @@ I2R_API int i2r_joint_targets(const i2r_joint_targets_args* a, void* stream);
  *   pred fp32 [n_crops, joints, 2]: the arg-max coordinates of the prediction (accuracy's fourth return value)
  *   meter (optional) float64 [4], caller-owned and caller-zeroed: += loss * n_crops, n_crops, avg_acc * cnt, cnt in stream order -- the
  *             sums and counts of validate()'s two AverageMeters
- * sse, hits and valid are raw so that shards of a data-parallel step can be combined exactly.
+ * sse, hits and valid are raw so that shards of a data-parallel step can be combined exactly: i2r_val_combine below takes the rows
+ * (n_crops, sse, hits, valid) of several parts and applies this entry's own finishing step to their totals.
  * ws: workspace of 16 * n_crops * joints bytes, 8-byte aligned, contents irrelevant before and after.
  * n_crops == 0 returns I2R_OK without a launch and writes nothing.  joints < 1, h < 1, w < 1, counts beyond 2^31 - 1: I2R_E_ARG. */
 typedef struct i2r_val_metrics_args {
@@ -369,6 +370,32 @@ typedef struct i2r_val_metrics_args {
     int32_t n_crops, joints, h, w, use_target_weight, reserved;
 } i2r_val_metrics_args;
 I2R_API int i2r_val_metrics(const i2r_val_metrics_args* a, void* stream);
+
+/* i2r_val_combine -- the finishing step of i2r_val_metrics over the raw sums of several parts (the shards of a data-parallel step, one
+ * row per rank as an all-gather stacks them): the loss, accuracy and meter update of the WHOLE batch, on every rank the same bits.
+ * Input (device): parts float64 [n_part, 1 + 3 * joints]; row r = n_crops_r, sse_r[joints], hits_r[joints], valid_r[joints] -- the
+ *   integers travel as doubles (exact below 2^53).  A part with n_crops <= 0 contributes nothing (a rank without images launches no
+ *   i2r_val_metrics and hands in zeros).  h, w: the heat-map size the parts were computed at.
+ * One launch of one workgroup, no workspace, no floating-point atomics: a thread owns joints j, j + blockDim, ... and adds the parts in
+ * ascending part index, so two runs -- and two ranks -- give the same bits.  One thread then forms loss, acc, avg_acc, cnt and the meter
+ * update with the expressions of i2r_val_metrics, in its order, with n_crops = the total: n_part == 1 reproduces i2r_val_metrics' own
+ * loss, acc, avg_acc, cnt and meter bit for bit.
+ * Results (device, all required but meter), shapes and meanings as i2r_val_metrics gives them:
+ *   sse float64 [joints], hits, valid int32 [joints]: the totals; loss float64 [1]; acc float64 [joints + 1]; avg_acc float64 [1];
+ *   cnt int32 [1]; n_crops int32 [1]: the total crop count S
+ *   meter (optional) float64 [4]: += loss * S, S, avg_acc * cnt, cnt in stream order
+ * hits, valid, acc, avg_acc, cnt and n_crops are exact; sse and loss are fp64 sums of non-negative terms in another order than one
+ * i2r_val_metrics call over the whole batch uses: within (number of terms - 1) * 2^-53 relative of it.
+ * Total crop count 0: every result is written as 0 (acc too), the meter is left alone, nothing is divided.
+ * Precondition: the total crop count (and with it every total of hits and valid) is <= 2^31 - 1.
+ * n_part < 1, joints < 1, h < 1, w < 1 or a null required pointer: I2R_E_ARG without a launch. */
+typedef struct i2r_val_combine_args {
+    const double* parts;
+    double* sse; int32_t* hits; int32_t* valid;
+    double* loss; double* acc; double* avg_acc; int32_t* cnt; int32_t* n_crops; double* meter;
+    int32_t n_part, joints, h, w;
+} i2r_val_combine_args;
+I2R_API int i2r_val_combine(const i2r_val_combine_args* a, void* stream);
 
 /* ---- input side (reference lib/dataset/JointsDataset.py:296-333) ------------------------
  * i2r_crop_affine -- cv2.warpAffine(image, trans, IMAGE_SIZE, INTER_LINEAR) + ToTensor + Normalize for the n persons of ONE

@@ -17,6 +17,10 @@ lib/core/evaluate.py:41-71), from the joint positions alone -- the target heat m
     jhm   = heatmap_joints(joints, center, scale, cfg.MODEL.HEATMAP_SIZE)          # JointsDataset.py:295-320 (host, float64)
     m     = val_metrics_cfg(cfg, out, joints_hm=jhm, joints_vis=vis, meter=meter)  # function.py:167-174; m.pred = accuracy's pred
     valid_loss, valid_acc = meter.result()                                         # end of the epoch: the one copy to the host
+
+and of both across the ranks of a data-parallel run: the raw sums of every rank's batch combined into the numbers of the whole batch
+(val_sums_row / val_combine; dist.val_metrics_all is the gather in front of them), and the rows of dist.gather_poses collected over the
+steps of an epoch on the device for one oks_eval at its end (PoseTable).
 """
 import ctypes
 
@@ -233,8 +237,10 @@ def joint_targets(joints_hm, joints_vis, heatmap_size, sigma=2, joints_weight=No
 
 class ValMetrics:
     """What i2r_val_metrics writes, device tensors: loss [1], acc [J + 1], avg_acc [1] float64; cnt [1] int32; pred [S, J, 2] fp32
-    (accuracy's fourth return value); sse [J] float64, hits [J], valid [J] int32 (raw sums: shards can be combined exactly)."""
-    __slots__ = ("loss", "acc", "avg_acc", "cnt", "pred", "sse", "hits", "valid")
+    (accuracy's fourth return value); sse [J] float64, hits [J], valid [J] int32 (raw sums: shards can be combined exactly, see
+    val_combine).  n_crops int32 [1], the total crop count, is set by val_combine alone (val_metrics' caller knows S; there it stays
+    unset), and val_combine's pred is None: the arg-max coordinates stay with the rank that computed them."""
+    __slots__ = ("loss", "acc", "avg_acc", "cnt", "pred", "sse", "hits", "valid", "n_crops")
 
 
 class ValMeter:
@@ -312,6 +318,42 @@ def val_metrics_cfg(cfg, output, target=None, target_weight=None, **kw):
             raise cabi.I2RError("val_metrics_cfg: no joints_weight table for dataset %r -- pass joints_weight" % cfg.DATASET.DATASET)
         kw["joints_weight"] = JOINTS_WEIGHT[cfg.DATASET.DATASET]
     return val_metrics(output, target, target_weight, sigma=cfg.MODEL.SIGMA, use_target_weight=cfg.LOSS.USE_TARGET_WEIGHT, **kw)
+
+
+def val_sums_row(m, n_crops):
+    """What one rank contributes to the all-gather in front of val_combine: float64 [1 + 3 J] = n_crops, sse[J], hits[J], valid[J] on
+    m's device (the integers as doubles: exact below 2^53).  n_crops is the host's number (output.shape[0]); a rank without images passes
+    the all-zero ValMetrics val_metrics returned and 0.  No host synchronisation."""
+    n = torch.full((1,), float(int(n_crops)), dtype=torch.float64, device=m.sse.device)
+    return torch.cat([n, m.sse.to(torch.float64), m.hits.to(torch.float64), m.valid.to(torch.float64)])
+
+
+def val_combine(parts, h, w, meter=None):
+    """The loss / accuracy of the WHOLE batch from the rows of its parts (i2r_val_combine): parts float64 [n_part, 1 + 3 J] cuda, one
+    val_sums_row per part stacked in rank order; (h, w) the heat-map size.  Runs on the current stream without a host synchronisation.
+    Totals are added in ascending part index, so every rank that holds the same rows gets the same bits; one part reproduces
+    val_metrics' own loss, acc, avg_acc, cnt and meter update bit for bit.  meter: a ValMeter, updated with the total crop count as
+    val_metrics would have been on the whole batch (left alone when there is no crop at all).
+    -> ValMetrics of the whole batch: sse, hits, valid the totals, n_crops int32 [1] the total crop count, pred None."""
+    assert parts.is_cuda and parts.dtype == torch.float64 and parts.dim() == 2 and parts.shape[0] >= 1, (parts.dtype, tuple(parts.shape))
+    assert parts.shape[1] >= 4 and (parts.shape[1] - 1) % 3 == 0, tuple(parts.shape)
+    parts = parts.contiguous()
+    n_part, J = int(parts.shape[0]), (int(parts.shape[1]) - 1) // 3
+    dev = parts.device
+    r = ValMetrics()
+    f64 = torch.empty(J + 1 + 1 + 1 + J, dtype=torch.float64, device=dev)    # (every element is written by the kernel)
+    i32 = torch.empty(2 + 2 * J, dtype=torch.int32, device=dev)
+    r.acc, r.avg_acc, r.loss, r.sse = f64[:J + 1], f64[J + 1:J + 2], f64[J + 2:J + 3], f64[J + 3:]
+    r.cnt, r.n_crops, r.hits, r.valid = i32[:1], i32[1:2], i32[2:2 + J], i32[2 + J:]
+    r.pred = None
+    if meter is not None:
+        assert meter.buf.device == dev
+    a = cabi.ValCombineArgs(parts=parts.data_ptr(), sse=r.sse.data_ptr(), hits=r.hits.data_ptr(), valid=r.valid.data_ptr(), loss=r.loss.data_ptr(),
+                            acc=r.acc.data_ptr(), avg_acc=r.avg_acc.data_ptr(), cnt=r.cnt.data_ptr(), n_crops=r.n_crops.data_ptr(),
+                            meter=meter.buf.data_ptr() if meter is not None else None, n_part=n_part, joints=J, h=int(h), w=int(w))
+    with torch.cuda.device(dev):
+        cabi.check(cabi.lib().i2r_val_combine(ctypes.byref(a), torch.cuda.current_stream(dev).cuda_stream), "i2r_val_combine")
+    return r
 
 
 # ---- keypoint OKS evaluation: COCOeval(gt, dt, 'keypoints') and the per-person-count table of lib/utils/KeypointEvaluator.py, on the device
@@ -544,3 +586,51 @@ def oks_eval_cfg(cfg, gt, image_ids, keypoints, scores, valid=None, **kw):
             raise cabi.I2RError("oks_eval_cfg: no sigma table for MODEL.NUM_JOINTS = %d -- pass sigmas" % J)
         kw["sigmas"] = SIGMAS[J]
     return oks_eval(gt, image_ids, keypoints, scores, valid, **kw)
+
+
+class PoseTable:
+    """The detections of an evaluation, collected on the device over the steps (and ranks) of a validation pass: a growable table of the
+    rows dist.gather_poses returns, [n, J * 3 + 2] (key points, rescored value, NMS rank as a float; -1 = suppressed), and one image id
+    per row on the host.  append() copies on the current stream and never waits for the device; the buffer doubles when it is full (one
+    device copy).  Images are never split across ranks or steps, so inside an image the rows keep their input order, which is all
+    oks_eval's result depends on: evaluate() gives the bits of one oks_eval call on the same detections."""
+
+    def __init__(self, joints, device, capacity=1024, dtype=torch.float32):
+        self.joints, self.n = int(joints), 0
+        self.buf = torch.empty(max(int(capacity), 1), self.joints * 3 + 2, dtype=dtype, device=device)
+        self.ids = np.empty(self.buf.shape[0], np.int64)
+
+    def __len__(self):
+        return self.n
+
+    def append(self, rows, image_ids):
+        """rows [k, J * 3 + 2] on the table's device (dist.gather_poses' result, or one rank's own rows), image_ids: k host integers"""
+        ids = np.asarray(image_ids, np.int64).reshape(-1)
+        k = int(rows.shape[0])
+        assert rows.dim() == 2 and rows.shape[1] == self.buf.shape[1] and ids.size == k, (tuple(rows.shape), tuple(self.buf.shape), ids.size)
+        if k == 0:
+            return
+        assert rows.device == self.buf.device and rows.dtype == self.buf.dtype, (rows.device, rows.dtype)
+        cap = self.buf.shape[0]
+        if self.n + k > cap:
+            while self.n + k > cap:
+                cap *= 2
+            buf = torch.empty(cap, self.buf.shape[1], dtype=self.buf.dtype, device=self.buf.device)
+            buf[:self.n].copy_(self.buf[:self.n])
+            self.buf = buf
+            self.ids = np.concatenate([self.ids[:self.n], np.empty(cap - self.n, np.int64)])
+        self.buf[self.n:self.n + k].copy_(rows)
+        self.ids[self.n:self.n + k] = ids
+        self.n += k
+
+    def rows(self):
+        """the live view [n, J * 3 + 2] (valid until the next append that grows the buffer)"""
+        return self.buf[:self.n]
+
+    def image_ids(self):
+        return self.ids[:self.n]
+
+    def evaluate(self, gt, **kw):
+        """oks_eval(gt, image ids, key points, rescored value, valid = rank >= 0, **kw) on what has been collected -> OksEval"""
+        J, rows = self.joints, self.rows()
+        return oks_eval(gt, self.image_ids(), rows[:, :J * 3].reshape(self.n, J, 3), rows[:, J * 3], rows[:, J * 3 + 1] >= 0, **kw)

@@ -1,6 +1,7 @@
 // The two numbers validate() logs per batch (lib/core/function.py:167-172), on device:
 //   i2r_joint_targets   JointsDataset.generate_target + adjust_target_weight (lib/dataset/JointsDataset.py:394-450)
 //   i2r_val_metrics     JointsMSELoss.forward (lib/core/loss.py:15-41) + accuracy (lib/core/evaluate.py:16-71) in ONE pass over the prediction
+//   i2r_val_combine     the finishing step of i2r_val_metrics over the raw sums of several parts (the shards of a data-parallel step)
 // One workgroup per (crop, joint) map: the map is read once and yields the squared-error sum (fp32 terms as torch rounds them, added up
 // in fp64), the first-index arg-max of the prediction and that of the target.  In analytic mode the target value of a pixel is evaluated
 // from (mu_x, mu_y, weight) and never stored or read.  A second launch of one workgroup adds the per-map partials up in a fixed order (no
@@ -19,6 +20,7 @@ namespace {
 
 constexpr int MET_NT = 256;   // 4 waves per map
 constexpr int FIN_NT = 1024;  // 16 waves: wave k finishes joints k, k + 16, ...
+constexpr int CMB_NT = 256;   // i2r_val_combine: thread k totals joints k, k + 256, ...
 
 // adjust_target_weight (JointsDataset.py:438-450) + the draw decision of generate_target (:418, :429) + joints_weight (:432-433).
 // int() truncates toward zero; the comparisons are made on the truncated doubles, so a far-away mu cannot overflow an int.
@@ -200,6 +202,67 @@ __global__ __launch_bounds__(FIN_NT) void val_metrics_finish_k(const i2r_val_met
     }
 }
 
+// The tail of val_metrics_finish_k over the totals of n_part rows (n_crops, sse[J], hits[J], valid[J]) of doubles.  A thread owns whole
+// joints and walks the parts in ascending order: no cross-lane sum, so the order of every addition is the part index and nothing else.
+// The counts are integers held in doubles, exact below 2^53; their totals fit an int by the entry's precondition.
+__global__ __launch_bounds__(CMB_NT) void val_combine_k(const i2r_val_combine_args a) {
+    const int J = a.joints, P = a.n_part, tid = threadIdx.x;
+    const size_t row = 1 + 3 * (size_t)J;
+    double crops = 0.0;  // (every thread adds the same integers in the same order: the same total)
+    for (int r = 0; r < P; ++r) {
+        const double n = a.parts[r * row];
+        if (n > 0.0) crops += n;
+    }
+    const bool any = crops > 0.0;
+    for (int j = tid; j < J; j += CMB_NT) {
+        double sse = 0.0, hits = 0.0, valid = 0.0;
+        for (int r = 0; r < P; ++r) {
+            const double* p = a.parts + r * row;
+            if (!(p[0] > 0.0)) continue;  // a rank without crops (or a NaN count) contributes nothing
+            sse += p[1 + j];
+            hits += p[1 + J + j];
+            valid += p[1 + 2 * (size_t)J + j];
+        }
+        const int h_i = (int)hits, v_i = (int)valid;
+        a.sse[j] = sse;
+        a.hits[j] = h_i;
+        a.valid[j] = v_i;
+        a.acc[j + 1] = !any ? 0.0 : v_i > 0 ? (double)h_i * 1.0 / (double)v_i : -1.0;  // dist_acc
+    }
+    __syncthreads();  // (the values above were written by this workgroup: visible to it behind the barrier)
+    if (tid == 0) {
+        const int S = (int)crops;
+        *a.n_crops = S;
+        if (!any) {  // no crop anywhere: zeros, the meter left alone, nothing divided
+            *a.loss = 0.0;
+            *a.avg_acc = 0.0;
+            *a.cnt = 0;
+            a.acc[0] = 0.0;
+            return;
+        }
+        const double n_px = (double)S * (double)a.h * (double)a.w;
+        double loss = 0.0, avg = 0.0;
+        int cnt = 0;
+        for (int j = 0; j < J; ++j) {
+            loss += 0.5 * (a.sse[j] / n_px);
+            const double v = a.acc[j + 1];
+            if (v >= 0.0) { avg += v; ++cnt; }
+        }
+        loss /= (double)J;
+        avg = cnt != 0 ? avg / (double)cnt : 0.0;
+        *a.loss = loss;
+        *a.avg_acc = avg;
+        *a.cnt = cnt;
+        a.acc[0] = avg;
+        if (a.meter) {
+            a.meter[0] += loss * (double)S;
+            a.meter[1] += (double)S;
+            a.meter[2] += avg * (double)cnt;
+            a.meter[3] += (double)cnt;
+        }
+    }
+}
+
 __global__ __launch_bounds__(MET_NT) void joint_targets_k(const i2r_joint_targets_args a) {
     const size_t map = blockIdx.x;
     const int j = (int)(map % a.joints), hw = a.h * a.w, w = a.w;
@@ -256,5 +319,16 @@ extern "C" int i2r_val_metrics(const i2r_val_metrics_args* a, void* stream) {
     I2R_CHECK_LAUNCH("i2r_val_metrics");
     i2r_launch(val_metrics_finish_k, dim3(1), dim3(FIN_NT), 0, (hipStream_t)stream, *a);
     I2R_CHECK_LAUNCH("i2r_val_metrics (finish)");
+    return I2R_OK;
+}
+
+extern "C" int i2r_val_combine(const i2r_val_combine_args* a, void* stream) {
+    I2R_CHECK_ARG(a, "i2r_val_combine: null args");
+    I2R_CHECK_ARG(a->n_part >= 1 && a->joints >= 1 && a->h >= 1 && a->w >= 1, "i2r_val_combine: %d parts, %d joints, %d x %d", a->n_part,
+                  a->joints, a->h, a->w);
+    I2R_CHECK_ARG(a->parts, "i2r_val_combine: null parts");
+    I2R_CHECK_ARG(a->sse && a->hits && a->valid && a->loss && a->acc && a->avg_acc && a->cnt && a->n_crops, "i2r_val_combine: null result pointer");
+    i2r_launch(val_combine_k, dim3(1), dim3(CMB_NT), 0, (hipStream_t)stream, *a);
+    I2R_CHECK_LAUNCH("i2r_val_combine");
     return I2R_OK;
 }

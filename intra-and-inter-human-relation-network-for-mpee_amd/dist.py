@@ -4,7 +4,8 @@ Persons interact only within an image (reference interformer.py:294-306: the enc
 so images are the independent unit: rank r runs the full forward on its images with replicated weights and the
 per-crop results are all-gathered once per step (RCCL over xGMI when backend == 'nccl'; gloo in the CPU tests): the decoded
 key points [S, J, 3] (gather_keypoints: what validate() keeps of a batch, function.py:190-200 -- 168 B per crop at J = 14) or,
-optionally, the heat maps themselves (gather_heatmaps: 172 KB per crop).
+optionally, the heat maps themselves (gather_heatmaps: 172 KB per crop).  The validation numbers of a step cross the ranks as one row of
+raw sums per rank (gather_val_sums / val_metrics_all: (1 + 3 J) * 8 bytes).
 The reference itself has no counterpart (its DataParallel/DDP eval does not shard).
 """
 import torch
@@ -118,6 +119,27 @@ def unpack_poses(rows):
     """rows [S, J * 3 + 2] of gather_poses -> (key points [S, J, 3], score [S] fp32, rank [S] int32)"""
     S, J = rows.shape[0], (rows.shape[1] - 2) // 3
     return rows[:, :J * 3].reshape(S, J, 3), rows[:, J * 3], rows[:, J * 3 + 1].to(torch.int32)
+
+
+def gather_val_sums(m, n_crops, group=None):
+    """The collective of the validation numbers: this rank's caller.val_sums_row (n_crops, sse, hits, valid of its caller.val_metrics; a
+    rank without images hands in zeros) -> float64 [world, 1 + 3 J], row r from rank r, identical on every rank.  One
+    all_gather_into_tensor of (1 + 3 J) * 8 bytes per rank: the row has one size on every rank, so nothing is padded.  On the caller's
+    stream; works on CPU tensors under gloo."""
+    from . import caller
+    row = caller.val_sums_row(m, n_crops).contiguous()
+    out = torch.empty(dist.get_world_size(group) * row.numel(), dtype=row.dtype, device=row.device)
+    dist.all_gather_into_tensor(out, row, group=group)
+    return out.view(dist.get_world_size(group), row.numel())
+
+
+def val_metrics_all(m, n_crops, h, w, meter=None, group=None):
+    """caller.val_metrics of this rank's crops -> the ValMetrics of the WHOLE batch, the same bits on every rank: gather_val_sums, then
+    caller.val_combine (one launch of one workgroup that adds the ranks' rows in rank order).  hits, valid, acc, avg_acc, cnt and n_crops
+    are what one val_metrics call over all crops gives; sse and loss are fp64 sums of the same terms in another order.  meter: a
+    caller.ValMeter that takes the whole batch's update -- pass it here and NOT to the rank's own val_metrics call."""
+    from . import caller
+    return caller.val_combine(gather_val_sums(m, n_crops, group), h, w, meter)
 
 
 class PostStep:
