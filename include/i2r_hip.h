@@ -175,6 +175,15 @@ I2R_API int i2r_conv_kernel_name(const i2r_conv_desc* const* descs, int32_t n, c
  * everything but algo 1).  No launch happens. */
 I2R_API int i2r_conv_grid(const i2r_conv_desc* const* descs, int32_t n, int32_t with_map, int32_t* grid, int32_t* seq);
 
+/* i2r_conv_wino_form -- the epilogue form an algo 1 (grouped) launch resolves to (additive: I2R_ABI_VERSION unchanged): 1 = bias + ReLU,
+ * 2 = bias + res1 + ReLU -- every member has relu, no res2 / res_post, cout == cout_pad <= out_cs, and the members agree on res1 -- compiled
+ * without flag tests; 0 = the general epilogue (everything else, other algorithms, and every launch while the forms are switched off).
+ * The results do not depend on the form, bit for bit; kernel names (i2r_conv_kernel_name) do not report it.  No launch happens. */
+I2R_API int i2r_conv_wino_form(const i2r_conv_desc* const* descs, int32_t n, int32_t* form);
+/* i2r_conv_wino_forms -- process-wide switch (atomic): on != 0 (the default) lets algo 1 launches take the forms 1 / 2, 0 makes every
+ * launch run the general epilogue.  Always I2R_OK. */
+I2R_API int i2r_conv_wino_forms(int32_t on);
+
 /* ---- after the forward: flip-test merge and keypoint decode -------------------------------- */
 /* i2r_flip_merge -- out = (y + flip_back(y_flipped)) * 0.5  with flip_back = reverse W + swap left/right joints
  * (lib/core/function.py:142-162, lib/utils/transforms.py:16-30). joint_map: device int32[joints], the joint whose mirrored

@@ -53,11 +53,45 @@ struct ConvK {
     float* f_y;
     int f_sh1, f_sh2;             // log2 of the terms' up-sampling factors
     unsigned f_bytes1, f_bytes2;  // byte sizes of the terms' maps
+    // Winograd kernels, host-made (prepare_wino): what depends only on the member, so that no workgroup works it out again, and copies
+    // of the fields a fragment reads afresh, side by side in the order of their use -- the scalar loads of a region then come as one or two
+    // wide ones with one wait instead of a dozen single dwords with a wait each (the kernel issues instructions, not bytes: i2r_conv_wino.hip)
+    struct Wino {
+        // epilogue of the compile-time forms (one output pixel per thread): destination, residual, bias, extent
+        float* out;
+        const float* res1;
+        const float* bias;
+        unsigned out_bytes, bias_bytes;
+        int conv_h, conv_w, out_cs, pad_;
+        // fragment decode and the staging offsets (set_fragment)
+        int frags_img, tiles_x;    // fragments per crop and per row of them
+        unsigned r_img, r_tx;      // their reciprocals (div_r)
+        int in_h, in_w, in_cs;
+        int pw, pp, w_rcp;         // patch width and pixels (ph * pw); patch row of a pixel index: (i * w_rcp) >> 16
+        int oy_step;               // output rows of a fragment: 32 >> w_fwlog
+        int f_sh1, f_sh2;          // (fused input: log2 of the terms' up-sampling factors)
+        int nfrag;                 // fragments of the member (w_nfrag)
+        // weight walk (byte offsets into the packed U): a Winograd row, position j -> j + 1, (chunk, j = 3) -> (chunk + 1, j = 0)
+        int w_row, w_inc_j, w_inc_wrap;
+        int npass, bufsz;          // 16-channel chunks; float4 slots of one staging buffer
+        // run set-up: item decode, LDS layout, input and weight descriptors
+        int nruns;                 // fragment groups of the member: ceil(w_nfrag / MT)
+        int n_cblk, w_seq, w_band;
+        unsigned r_cblk;           // reciprocal of n_cblk (div_r)
+        int fwlog, pitch, half, plane, cout_pad, ph;
+        unsigned in_bytes, w_bytes;
+        const float* in;
+        const float* w;
+    } wk;
 };
 
 // n / d through m = ceil(2^32 / d): exact while n * (m * d - 2^32) < 2^32, i.e. for every n < 2^32 / d (prepare() checks the ranges);
 // d == 1 has no 32-bit reciprocal
 __device__ __forceinline__ int div_m(int n, int d, unsigned m) { return d == 1 ? n : (int)__umulhi((unsigned)n, m); }
+
+// the same for the Winograd kernels' decode, with r = ceil(2^31 / d), which exists for d == 1 too (no special case, no branch): exact
+// for n < 2^20 + 2^14 and d < 2^11 (prepare_wino checks both): n (r d - 2^31) < 2^31
+__device__ __forceinline__ int div_r(int n, unsigned r) { return (int)__umulhi((unsigned)n << 1, r); }
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
@@ -295,5 +329,5 @@ typedef void (*conv_fn)(const ConvGroupK);
 void* i2r_pick_conv_bf16(int nt, int mt, int cap, int pf);
 void* i2r_pick_conv_f16(int nt, int mt, int cap, int pf);
 // Winograd F(2x2, 3x3) fp32 kernels (i2r_conv_wino.hip): MT fragments x NT channel fragments per workgroup; LDS bytes of a workgroup
-void* i2r_pick_conv_wino(int nt, int mt, int fin);
+void* i2r_pick_conv_wino(int nt, int mt, int fin, int epi);
 size_t i2r_conv_wino_lds(int nt, int mt, int plane);

@@ -19,6 +19,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <atomic>
 
 #include "i2r_conv.h"
 
@@ -322,6 +323,7 @@ static void copy_desc(const i2r_conv_desc* d, ConvK& k) {
     k.m_cblk = k.m_tx = k.m_ty = k.m_pw = k.m_tw = 0; k.wn_log = 0; k.npass = 0;
     k.dbg = 0;
     k.f_t1 = d->t1; k.f_t2 = d->t2; k.f_y = d->y; k.f_sh1 = d->t1_shift; k.f_sh2 = d->t2 ? d->t2_shift : 0; k.f_bytes1 = k.f_bytes2 = 0;
+    k.wk = ConvK::Wino{};  // (prepare_wino fills it)
 }
 
 constexpr int kWinoMaxSeq = 8;       // longest run of fragments a workgroup takes (i2r_conv_desc.seq)
@@ -395,7 +397,7 @@ static int prepare_wino(const i2r_conv_desc* d, int force_mt, ConvK& k, int* nt_
     k.tap_kw = k.tap_kh = 3;
     k.ck = 16; k.wn = 1;
     const long long nf = (long long)d->n_img * k.tiles_y * k.tiles_x;
-    I2R_CHECK_ARG(nf > 0 && nf * k.n_cblk < (1ll << 20) && k.tiles_y * k.tiles_x < 2048 && k.n_cblk < 2048, "i2r_conv: algo 1 grid (%lld fragments)", nf);
+    I2R_CHECK_ARG(nf > 0 && (nf + 8) * k.n_cblk < (1ll << 20) && k.tiles_y * k.tiles_x < 2048 && k.n_cblk < 2048, "i2r_conv: algo 1 grid (%lld fragments)", nf);
     k.w_nfrag = (int)nf;
     k.w_seq = d->seq ? d->seq : 1;  // (seq 0: resolve() chooses, seeing the whole group -- wino_choose_seq)
 #ifdef I2R_TUNING
@@ -404,6 +406,28 @@ static int prepare_wino(const i2r_conv_desc* d, int force_mt, ConvK& k, int* nt_
         k.dbg = dbg;
     }
 #endif
+    auto recip31 = [](int d) { return (unsigned)(((1ull << 31) + d - 1) / d); };  // (div_r)
+    {  // what the kernel would otherwise work out per workgroup or read field by field (ConvK::Wino)
+        ConvK::Wino& wk = k.wk;
+        wk.out = k.out; wk.res1 = k.res1; wk.bias = k.bias;
+        wk.out_bytes = k.out_bytes; wk.bias_bytes = (unsigned)d->cout_pad * 4; wk.conv_h = k.conv_h; wk.conv_w = k.conv_w; wk.out_cs = k.out_cs;
+        wk.frags_img = k.tiles_y * k.tiles_x; wk.tiles_x = k.tiles_x; wk.r_img = recip31(wk.frags_img); wk.r_tx = recip31(k.tiles_x);
+        wk.in_h = k.in_h; wk.in_w = k.in_w; wk.in_cs = k.in_cs;
+        wk.pw = k.pw; wk.pp = k.ph * k.pw; wk.w_rcp = k.w_rcp;
+        wk.oy_step = k.tile_h;
+        wk.f_sh1 = k.f_sh1; wk.f_sh2 = k.f_sh2;
+        wk.nfrag = k.w_nfrag;
+        const int cin4 = d->cin / 4;
+        wk.w_row = 4 * cin4 * d->cout_pad * 16;
+        wk.w_inc_j = cin4 * d->cout_pad * 16;
+        wk.w_inc_wrap = (4 - 3 * cin4) * d->cout_pad * 16;
+        wk.npass = d->cin / 16;
+        wk.bufsz = mt * 4 * k.plane;
+        wk.nruns = (k.w_nfrag + mt - 1) / mt;
+        wk.n_cblk = k.n_cblk; wk.r_cblk = recip31(k.n_cblk); wk.w_seq = k.w_seq;  // (w_seq and w_band: resolve(), once the run lengths are chosen)
+        wk.fwlog = k.w_fwlog; wk.pitch = k.w_pitch; wk.half = k.w_half; wk.plane = k.plane; wk.cout_pad = k.cout_pad; wk.ph = k.ph;
+        wk.in_bytes = k.in_bytes; wk.w_bytes = k.w_bytes; wk.in = k.in; wk.w = k.w;
+    }
     *nt_out = nt; *mt_out = mt; *cap_out = 0; *pf_out = 100;
     *lds_out = i2r_conv_wino_lds(nt, mt, k.plane);
     *nblk_out = wino_runs(k, mt) * k.n_cblk;
@@ -649,6 +673,7 @@ static int resolve(const i2r_conv_desc* const* descs, int32_t n, ConvGroupK& grp
             }
             total += nblk;
             grp.blk_end[i] = (int)total;
+            grp.g[i].wk.w_seq = grp.g[i].w_seq; grp.g[i].wk.w_band = grp.g[i].w_band;
         }
     }
     for (int i = n; i < kMaxGroups; ++i) { grp.g[i] = grp.g[0]; grp.blk_end[i] = (int)total; }
@@ -665,6 +690,40 @@ static bool any_fused_input(const i2r_conv_desc* const* descs, int32_t n) {
     return false;
 }
 
+// Epilogue form of a Winograd launch (conv_wino_body's EPI): the two shapes of the HRNet tower -- bias + ReLU (1), bias + res1 + ReLU
+// (2) -- are compiled without flag tests and taken when EVERY member has that shape: ReLU, no res2 / res_post, channel blocks exact in
+// cout and out_cs (no tail), and all members with or all without res1.  Everything else, a tuning build with ablation bits, and every
+// launch while the switch below is off run the general form 0.  The results do not depend on the form, bit for bit.
+static std::atomic<int> g_wino_forms{1};
+
+static int wino_form(const i2r_conv_desc* const* descs, int32_t n, const ConvGroupK& grp) {
+    if (!g_wino_forms.load(std::memory_order_relaxed)) return 0;
+    for (int i = 0; i < n; ++i) {
+        const i2r_conv_desc* d = descs[i];
+        if (d->relu != 1 || d->res2 || d->res_post || d->cout != d->cout_pad || d->cout_pad > d->out_cs) return 0;
+        if ((d->res1 != nullptr) != (descs[0]->res1 != nullptr)) return 0;
+        if (I2R_DBG(grp.g[i]) != 0) return 0;
+    }
+    return descs[0]->res1 ? 2 : 1;
+}
+
+extern "C" int i2r_conv_wino_forms(int32_t on) {
+    g_wino_forms.store(on ? 1 : 0, std::memory_order_relaxed);
+    return I2R_OK;
+}
+
+extern "C" int i2r_conv_wino_form(const i2r_conv_desc* const* descs, int32_t n, int32_t* form) {
+    ConvGroupK grp;
+    int nt0, mt0, cap0, pf0;
+    size_t lds_max;
+    long long total;
+    int rc = resolve(descs, n, grp, &nt0, &mt0, &cap0, &pf0, &lds_max, &total);
+    if (rc) return rc;
+    I2R_CHECK_ARG(form != nullptr, "i2r_conv_wino_form: form");
+    *form = descs[0]->algo == 1 ? wino_form(descs, n, grp) : 0;
+    return I2R_OK;
+}
+
 extern "C" int i2r_conv_grouped(const i2r_conv_desc* const* descs, int32_t n, const int32_t* block_map,
                                 int32_t map_len, void* stream) {
     ConvGroupK grp;
@@ -675,7 +734,7 @@ extern "C" int i2r_conv_grouped(const i2r_conv_desc* const* descs, int32_t n, co
     if (rc) return rc;
     grp.blk_map = block_map;
     I2R_CHECK_ARG(block_map == nullptr || map_len == (int32_t)total, "i2r_conv_grouped: block_map has %d entries, grid has %lld", map_len, total);
-    conv_fn fn = descs[0]->algo == 1 ? reinterpret_cast<conv_fn>(i2r_pick_conv_wino(nt0, mt0, any_fused_input(descs, n)))
+    conv_fn fn = descs[0]->algo == 1 ? reinterpret_cast<conv_fn>(i2r_pick_conv_wino(nt0, mt0, any_fused_input(descs, n), wino_form(descs, n, grp)))
                  : descs[0]->dtype == 0 ? pick_kernel(nt0, mt0, cap0, pf0)
                                       : reinterpret_cast<conv_fn>(descs[0]->dtype == 1 ? i2r_pick_conv_bf16(nt0, mt0, cap0, pf0) : i2r_pick_conv_f16(nt0, mt0, cap0, pf0));
     I2R_CHECK_ARG(fn != nullptr, "i2r_conv: no kernel for nt=%d mt=%d cap=%d pf=%d dtype=%d", nt0, mt0, cap0, pf0, descs[0]->dtype);

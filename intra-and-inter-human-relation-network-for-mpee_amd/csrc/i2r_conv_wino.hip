@@ -51,7 +51,10 @@ typedef const ConvK __attribute__((address_space(4)))* ConvKArg;
 
 // `args`: grp as it lies in the kernel-argument block.  Only a __global__ function knows where its parameters lie, so the two kernels
 // below pass it in (wino_args); the body reads the per-fragment descriptor fields through it (see the run loop).
-template <int MT, int NT, bool FIN>
+// EPI: the epilogue's form, chosen by the host per launch (i2r_conv.hip, wino_form): 1 = bias + ReLU, 2 = bias + res1 + ReLU, with every
+// member's channel blocks exact in cout and out_cs -- the two shapes of the HRNet tower -- compiled without a flag test; 0 = the general
+// epilogue (any mix of res1 / res2 / res_post / ReLU, tail blocks, the -DI2R_TUNING switches).  The results do not depend on the form, bit for bit.
+template <int MT, int NT, bool FIN, int EPI>
 __device__ __forceinline__ void conv_wino_body(const ConvGroupK& grp, ConvKArg args) {
     extern __shared__ __attribute__((aligned(16))) f32x4 lds[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -85,26 +88,24 @@ __device__ __forceinline__ void conv_wino_body(const ConvGroupK& grp, ConvKArg a
     // channel blocks back to back (q = bid / 8: cb = q % n_cblk, group = x * w_band + q / n_cblk): the n_cblk blocks of a fragment and
     // its row / column neighbours read their input patch and halos from ONE L2.  Plain numbering spreads them over the eight XCDs:
     // PMC FETCH_SIZE per launch 27.5 -> 22.4 MB (stage 3, 16 crops), 10.9 -> 7.2 MB (layer1's 64-channel convs); time -0.3 %.
-    int wg, cb;
-    if (grp.blk_map) {
-        wg = div_m(bid, p.n_cblk, p.w_m_cblk);
-        cb = bid - wg * p.n_cblk;
-    } else {
-        const int q = bid >> 3, qq = div_m(q, p.n_cblk, p.w_m_cblk);
-        cb = q - qq * p.n_cblk;
-        wg = (bid & 7) * p.w_band + qq;
-    }
+    // (the run's set-up reads the member through its Wino block, prepare_wino's digest of it: neighbouring fields, wide scalar loads)
+    const auto& pk = p.wk;
+    const int n_cblk = pk.n_cblk;
+    const int bq = grp.blk_map ? bid : bid >> 3;
+    const int qq = div_r(bq, pk.r_cblk);
+    const int cb = bq - qq * n_cblk;
+    const int wg = grp.blk_map ? qq : (bid & 7) * pk.w_band + qq;
     // A workgroup is a RUN of w_seq consecutive fragment groups of one channel block, wg * w_seq .. + w_seq - 1, worked off one after the
     // other on ONE set-up: member selection, item decode, the input-side buffer descriptors, LDS slots, gather bases, weight lane offset and
     // walk are computed once (a 3-pass item spends more instructions around its passes than in them).  What names the fragment -- its decode,
     // the global offsets of the staging items, the output pixel -- is redone per fragment from values read afresh (lane_now, ConvKArg): held
     // through the pass loop instead, it does not fit 128 registers.  The run's fragments past w_nfrag do nothing: the trip count is cut
     // here, workgroup-uniform and before the first barrier, like the return for an empty run.
-    const int run0 = wg * p.w_seq;
-    const int nrun = min(p.w_seq, (p.w_nfrag + MT - 1) / MT - run0);
+    const int run0 = wg * pk.w_seq;
+    const int nrun = min(pk.w_seq, pk.nruns - run0);
     if (nrun <= 0) return;  // (padding of the last band; workgroup-uniform)
-    const int fwl = p.w_fwlog, FW = 1 << fwl;  // tiles across a fragment
-    const int pitch = p.w_pitch, half = p.w_half, plane = p.plane;
+    const int fwl = pk.fwlog, FW = 1 << fwl;  // tiles across a fragment
+    const int pitch = pk.pitch, half = pk.half, plane = pk.plane;
     const int n_base = cb * NT * 16;
 
     // ---- staging assignment: item = (fragment, patch pixel, channel group of the 16-channel chunk); the four lanes of a quad
@@ -113,8 +114,8 @@ __device__ __forceinline__ void conv_wino_body(const ConvGroupK& grp, ConvKArg a
     // Global accesses go through buffer instructions: a 32-bit per-lane byte offset + a scalar offset that walks the channel chunks,
     // no 64-bit address arithmetic on the vector ALU, and a lane whose offset lies beyond the descriptor's range reads zeros -- which
     // is how the halo outside the image and the unused items are zero-filled without a select per load.
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.in), 0, p.in_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w), 0, p.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(pk.in), 0, pk.in_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(pk.w), 0, pk.w_bytes, 0x00020000);
     unsigned goff[NIT];  // byte offset of (pixel, channel group) in `in`, kOOB (out of range: reads zeros) outside the image
     int lslot[NIT];      // LDS slot, -1 = no item; fused-input form: + kOwn when the item is an interior (non-halo) pixel of the patch
     constexpr int kOwn = 1 << 30;  // (above every slot; the shift to a byte address drops it)
@@ -123,14 +124,14 @@ __device__ __forceinline__ void conv_wino_body(const ConvGroupK& grp, ConvKArg a
     // goes to f_y from the lanes holding an interior (non-halo) pixel (own) in the items of channel block 0: at `goff`, f_y being laid out like `in`
     const bool fin = FIN && p.f_t1 != nullptr, fin2 = fin && p.f_t2 != nullptr;  // (uniform)
     const __amdgpu_buffer_rsrc_t rs_t1 = make_rsrc(fin ? p.f_t1 : nullptr, p.f_bytes1), rs_t2 = make_rsrc(fin2 ? p.f_t2 : nullptr, p.f_bytes2),
-                                 rs_y = make_rsrc(fin ? p.f_y : nullptr, p.in_bytes);
+                                 rs_y = make_rsrc(fin ? p.f_y : nullptr, pk.in_bytes);
     unsigned goff1[FIN ? NIT : 1], goff2[FIN ? NIT : 1];
     // The LDS slot of staging item k is the same for every fragment of the run and stays in a register.  Its patch pixel (row, col) is
     // worked out again per fragment, from a thread index the compiler cannot hoist: kept, row / col / offset would hold six more
     // registers through the pass loop, which at 4 waves per SIMD (128 registers) means spills.
     const int cg = tid & 3;  // (256 items per step: the channel group does not depend on k)
-    auto patch_pixel = [&](const auto& pq, int t, int k, int& f, int& row, int& col) {
-        const int PC = pq.pw, PP = pq.ph * pq.pw;
+    auto patch_pixel = [&](const auto& pq, int t, int k, int& f, int& row, int& col) {  // (pq: the member's Wino block)
+        const int PC = pq.pw, PP = pq.pp;
         const int pix = (t + k * 256) >> 2;
         int pp = pix;  // (MT <= 2 and PP <= 108: compare / subtract instead of a division; rows through a 16-bit reciprocal)
         f = 0;
@@ -143,10 +144,11 @@ __device__ __forceinline__ void conv_wino_body(const ConvGroupK& grp, ConvKArg a
 #pragma unroll
     for (int k = 0; k < NIT; ++k) {
         int f, row, col;
-        patch_pixel(p, tid, k, f, row, col);
+        patch_pixel(pk, tid, k, f, row, col);
+        asm volatile("" : "+v"(row), "+v"(col));  // (worked out for every lane: as the arm of a select it becomes a masked block with scalar loads and waits of its own)
         lslot[k] = f < MT ? (f * 4 + cg) * plane + row * pitch + (col & 1) * half + (col >> 1) : -1;
         if constexpr (FIN) {  // (as a bit of the slot, not a lane mask per item: those are four more scalar registers through the pass loop)
-            if (f < MT && row >= 1 && row < p.ph - 1 && col >= 1 && col < p.pw - 1) lslot[k] |= kOwn;
+            if (f < MT && row >= 1 && row < pk.ph - 1 && col >= 1 && col < pk.pw - 1) lslot[k] |= kOwn;
         }
     }
     // ---- per fragment of the run: decode (scalar) and the global offsets of the staging items ----
@@ -162,12 +164,12 @@ __device__ __forceinline__ void conv_wino_body(const ConvGroupK& grp, ConvKArg a
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
             int fid = fg * MT + mt;
-            f_ok[mt] = fid < ps.w_nfrag;
+            f_ok[mt] = MT == 1 || fid < ps.nfrag;  // (one fragment per group: the run's trip count has cut the groups past the last)
             if (!f_ok[mt]) fid = 0;
-            f_img[mt] = div_m(fid, (ps.tiles_y * ps.tiles_x), ps.w_m_img);
-            const int rem = fid - f_img[mt] * (ps.tiles_y * ps.tiles_x);
-            const int fy = div_m(rem, ps.tiles_x, ps.w_m_tx);
-            f_oy[mt] = fy * (32 >> fwl);
+            f_img[mt] = div_r(fid, ps.r_img);
+            const int rem = fid - f_img[mt] * ps.frags_img;
+            const int fy = div_r(rem, ps.r_tx);
+            f_oy[mt] = fy * ps.oy_step;
             f_ox[mt] = (rem - fy * ps.tiles_x) * (2 * FW);
         }
 #pragma unroll
@@ -263,12 +265,11 @@ __device__ __forceinline__ void conv_wino_body(const ConvGroupK& grp, ConvKArg a
 
     // ---- B operand: U[pos = 4 i + j][cin / 4][cout_pad][4], lane (cout li, g) takes channels 4g..4g+3 of the 16-channel step;
     //      the pointer walks j (stride cin4 * cout_pad slots) and wraps to the next chunk after j = 3 ----
-    const int cin4 = p.cin >> 2;
-    const unsigned wlane = (unsigned)(n_base + li + g * p.cout_pad) * 16u;   // per-lane byte offset (constant)
-    const int wp0 = wi * 4 * cin4 * p.cout_pad * 16;                            // scalar byte offset of (position 4 i + j, chunk): every
+    const unsigned wlane = (unsigned)(n_base + li + g * pk.cout_pad) * 16u;   // per-lane byte offset (constant)
+    const int wp0 = wi * pk.w_row;                                            // scalar byte offset of (position 4 i + j, chunk): every
     int wp;                                                                     // fragment of the run walks the same weights from wp0
-    const int inc_j = cin4 * p.cout_pad * 16;
-    const int inc_wrap = (4 - 3 * cin4) * p.cout_pad * 16;  // from (pass, j = 3) to (pass + 1, j = 0)
+    const int inc_j = pk.w_inc_j;
+    const int inc_wrap = pk.w_inc_wrap;  // from (pass, j = 3) to (pass + 1, j = 0)
     auto fetch_b = [&](f32x4 (&b)[NT]) {
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
@@ -276,8 +277,8 @@ __device__ __forceinline__ void conv_wino_body(const ConvGroupK& grp, ConvKArg a
     };
 
     f32x4 acc[4][MT][NT];
-    const int npass = p.cin >> 4;
-    const int bufsz = MT * 4 * plane;
+    const int npass = pk.npass;
+    const int bufsz = pk.bufsz;
     f32x4 a[MT][4], b0[NT], b1[NT];
     // FIRST: the accumulators do not exist yet -- their first MFMA takes a literal zero as C (no clearing instructions)
 #define WINO_MMA(J, B, FIRST)                                                                                   \
@@ -319,11 +320,16 @@ __device__ __forceinline__ void conv_wino_body(const ConvGroupK& grp, ConvKArg a
         const int tid_s = wi * 64 + lane_now();  // (the thread index again, per fragment; see patch_pixel)
         ConvKArg ps_ = args + gi;
         asm volatile("" : "+s"(ps_));
-        set_fragment(run0 + fs, tid_s, *ps_);
+        set_fragment(run0 + fs, tid_s, ps_->wk);
         // the LDS addresses derived from the slots and the gather base (one per buffer and item) start their lives here, per fragment, as
         // they did per item: hoisted out of the run loop they are eight registers held through the epilogue, and the allocator spills
-        abase_f = abase;
-        asm volatile("" : "+v"(abase_f));
+        if constexpr (FIN) {  // (the fused-input form is at its 128 registers: the gather base is worked out again instead of held through the run)
+            const int l = tid_s & 63;
+            abase_f = (l >> 4) * plane + 2 * ((l & 15) >> fwl) * pitch + (l & (FW - 1));
+        } else {
+            abase_f = abase;
+            asm volatile("" : "+v"(abase_f));
+        }
 #pragma unroll
         for (int k = 0; k < NIT; ++k) asm volatile("" : "+v"(lslot[k]));
     }
@@ -353,6 +359,78 @@ __device__ __forceinline__ void conv_wino_body(const ConvGroupK& grp, ConvKArg a
     for (int pass = 1; pass < npass; ++pass) WINO_PASS(pass, false)
     if (stamp) ts2 = __builtin_amdgcn_s_memtime();
 
+    if constexpr (EPI != 0) {
+    // ---- output transform and epilogue, compile-time forms: the arithmetic of the general code below, operation for operation
+    //      (T over j in registers, Y over i across the waves, ((u0 + sgn (u1 + u2)) + (bias [+ res1])), max with 0), without its flag
+    //      tests.  The Wino block of the member hands over destination, residual, bias and extent side by side (wide scalar loads, one
+    //      wait), the two descriptors are formed once, and every bias and residual piece of the fragment is in flight before the
+    //      first wait: their sum is taken behind the exchange barrier, where the first of them is needed.
+    const int tid_f = wi * 64 + lane_now();
+    ConvKArg pe_ = args + gi;
+    asm volatile("" : "+s"(pe_));
+    const auto& we = pe_->wk;
+    const int conv_h = we.conv_h, conv_w = we.conv_w, out_cs = we.out_cs;
+    const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(we.out, 0, we.out_bytes, 0x00020000),
+                                 rs_bias = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(we.bias), 0, we.bias_bytes, 0x00020000);
+    const int q4 = tid_f & 3, px = tid_f >> 2;  // (pixel and piece as in the general code)
+    const bool hi = (px & 2) != 0;
+    const int n0 = n_base + q4 * 4;
+    float neg1_ = -1.f;
+    asm volatile("" : "+s"(neg1_));
+    const f32x4 neg1 = {neg1_, neg1_, neg1_, neg1_};
+    unsigned obase[MT];
+    f32x4 bs[NT], rr[EPI == 2 ? MT : 1][NT];  // (r = bias + res1 is summed where it is used: every piece is in flight before the first wait)
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+        const int t = px >> 2;
+        const int oy = f_oy[mt] + 2 * (t >> fwl) + (hi ? 1 : 0);
+        const int ox = f_ox[mt] + 2 * (t & (FW - 1)) + (px & 1);
+        const bool ok = (int)f_ok[mt] & (int)(oy < conv_h) & (int)(ox < conv_w);
+        obase[mt] = ok ? (unsigned)(((f_img[mt] * conv_h + oy) * conv_w + ox) * out_cs + n0) * 4u : kOOB;  // (out_h x out_w = conv_h x conv_w)
+        if constexpr (EPI == 2) {
+            const __amdgpu_buffer_rsrc_t rs_r1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(we.res1), 0, we.out_bytes, 0x00020000);
+#pragma unroll
+            for (int k = 0; k < NT; ++k) rr[mt][k] = buf_ld16(rs_r1, obase[mt] + 64u * k, 0);
+        }
+    }
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            f32x4 t0 = acc[0][mt][nt] + acc[1][mt][nt] + acc[2][mt][nt];
+            // (a - b as fma(b, -1, a): the same rounding, and with a multiplier the compiler cannot see it is a packed instruction, two elements
+            //  at a time, where the subtraction of a tile comes out as four scalar ones; the asm keeps the tiles whole for the same reason)
+            f32x4 t1 = __builtin_elementwise_fma(acc[3][mt][nt], neg1, __builtin_elementwise_fma(acc[2][mt][nt], neg1, acc[1][mt][nt]));
+            asm volatile("" : "+v"(t0), "+v"(t1));
+            float* q = Tl + (wi * 2) * TPL + (mt * 16 + ((tid_f & 63) >> 4) * 4) * TW + nt * 16 + (tid_f & 15);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                q[r * TW] = t0[r];
+                q[TPL + r * TW] = t1[r];
+            }
+        }
+    // (the bias pieces come from L2 and follow the exchange stores, when the accumulators have left their registers; the residual pieces above
+    //  may come from further away and were issued first)
+#pragma unroll
+    for (int k = 0; k < NT; ++k) bs[k] = buf_ld16(rs_bias, (unsigned)n0 * 4u + 64u * k, 0);
+    const float* const tq = Tl + ((px & 1) + (hi ? 2 : 0)) * TPL + (px >> 2) * TW + q4 * 4;
+    const float sgn = hi ? -1.f : 1.f;
+    __syncthreads();
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int k = 0; k < NT; ++k) {
+            const float* q = tq + mt * 16 * TW + 16 * k;
+            const f32x4 u0 = *reinterpret_cast<const f32x4*>(q);
+            const f32x4 u1 = *reinterpret_cast<const f32x4*>(q + 2 * TPL);
+            const f32x4 u2 = *reinterpret_cast<const f32x4*>(q + 4 * TPL);
+            f32x4 r = bs[k];
+            if constexpr (EPI == 2) r += rr[mt][k];
+            f32x4 y = u0 + sgn * (u1 + u2) + r;
+            y[0] = fmaxf(y[0], 0.f); y[1] = fmaxf(y[1], 0.f); y[2] = fmaxf(y[2], 0.f); y[3] = fmaxf(y[3], 0.f);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, y), rs_out, obase[mt] + 64u * k, 0, 0);
+        }
+    } else {
     // ---- output transform.  Over j in registers:  T[0] = m0 + m1 + m2,  T[1] = m1 - m2 - m3 ----
     const int tid_f = wi * 64 + lane_now();  // (the epilogue's index math stays behind the passes, as the staging's stays in set_fragment)
     ConvKArg pe_ = args + gi;
@@ -426,6 +504,7 @@ __device__ __forceinline__ void conv_wino_body(const ConvGroupK& grp, ConvKArg a
             }
             if (!(I2R_DBG(p) & 1) || y[0] == 12345.678f) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, y), rs_out, off, 0, 0);
         }
+    }  // (EPI == 0)
     }  // (fragments of the run)
 #undef WINO_PASS
 #undef WINO_MMA
@@ -446,23 +525,38 @@ __device__ __forceinline__ ConvKArg wino_args() {
     return (ConvKArg)__builtin_amdgcn_kernarg_segment_ptr();
 }
 
-template <int MT, int NT>
+template <int MT, int NT, int EPI>
 __global__ __launch_bounds__(256, (MT == 1 ? (NT == 3 ? 4 : 3) : 2)) void conv_wino_f32(const ConvGroupK grp) {
-    conv_wino_body<MT, NT, false>(grp, wino_args());
+    conv_wino_body<MT, NT, false, EPI>(grp, wino_args());
 }
 
 // the fused-input form (a grouped launch takes it when a member has f_t1)
-template <int MT, int NT>
+template <int MT, int NT, int EPI>
 __global__ __launch_bounds__(256, (MT == 1 ? (NT == 3 ? 4 : 3) : 2)) void conv_wino_fin_f32(const ConvGroupK grp) {
-    conv_wino_body<MT, NT, true>(grp, wino_args());
+    conv_wino_body<MT, NT, true, EPI>(grp, wino_args());
+}
+
+template <int NT>
+conv_fn pick_form(int fin, int epi) {
+    switch (epi + 3 * (fin != 0)) {
+        case 0: return conv_wino_f32<1, NT, 0>;
+        case 1: return conv_wino_f32<1, NT, 1>;
+        case 2: return conv_wino_f32<1, NT, 2>;
+        case 3: return conv_wino_fin_f32<1, NT, 0>;
+        case 4: return conv_wino_fin_f32<1, NT, 1>;
+        case 5: return conv_wino_fin_f32<1, NT, 2>;
+    }
+    return nullptr;
 }
 
 }  // namespace
 
-void* i2r_pick_conv_wino(int nt, int mt, int fin) {
+// epi: the epilogue form 0 / 1 / 2 (conv_wino_body); the names a trace shows carry it as a third template argument
+void* i2r_pick_conv_wino(int nt, int mt, int fin, int epi) {
     conv_fn fn = nullptr;
-    if (mt == 1 && nt == 3) fn = fin ? conv_wino_fin_f32<1, 3> : conv_wino_f32<1, 3>;
-    if (mt == 1 && nt == 4) fn = fin ? conv_wino_fin_f32<1, 4> : conv_wino_f32<1, 4>;
+    if (epi < 0 || epi > 2) return nullptr;
+    if (mt == 1 && nt == 3) fn = pick_form<3>(fin, epi);
+    if (mt == 1 && nt == 4) fn = pick_form<4>(fin, epi);
     return reinterpret_cast<void*>(fn);
 }
 

@@ -40,6 +40,7 @@ FUSE_IN = True  # the closing pass of an HRNet fuse layer rides in the staging o
 PRUNE_FUSE = True  # the last HRNet module computes only the fuse outputs its caller reads (HRNetW48.emit(need=...))
 WINOGRAD = True  # fp32 3x3 stride-1 convs on the Winograd F(2x2, 3x3) kernels
 WINO_SEQ = True  # ... whose workgroups run several fragments on one set-up, as many as the library chooses per launch (i2r_conv_desc.seq = 0; False: one)
+WINO_FORMS = True  # ... with the epilogue compiled per shape (bias + ReLU, bias + res1 + ReLU; i2r_conv_wino_forms); False: the general epilogue, same bits
 # fork / join / record / wait as device-side signal / wait kernels (csrc/i2r_api.hip) when the lanes are independent queues.  A wait kernel
 # spins until ANOTHER kernel signals it: under a tool that lets one kernel run at a time (rocprofv3 counter collection serialises dispatches)
 # it could only time out, so the event form is used whenever a profiler library is attached to the process.
@@ -152,6 +153,18 @@ def conv_split(cout_pad):
     nb = nfrag // nt
     wn = 4 if nb % 4 == 0 else 2 if nb % 2 == 0 else 1
     return nt, wn
+
+
+_wino_forms_pushed = None
+
+
+def push_wino_forms():
+    """WINO_FORMS -> the library's process-wide switch (i2r_conv_wino_forms), where a launch resolves its form; called where Winograd
+    descriptors are made and before a program runs, one comparison when nothing changed"""
+    global _wino_forms_pushed
+    if _wino_forms_pushed != bool(WINO_FORMS):
+        cabi.check(cabi.lib().i2r_conv_wino_forms(int(bool(WINO_FORMS))), "i2r_conv_wino_forms")
+        _wino_forms_pushed = bool(WINO_FORMS)
 
 
 class Program:
@@ -299,6 +312,7 @@ class Program:
             mt = 1  # one fragment per item: 114 registers = 4 waves per SIMD (measured faster than two fragments at 2 waves per SIMD)
             d.tile_h, d.tile_w, d.mt, d.wn, d.ck = fh, fw, mt, 1, 0
             d.seq = 0 if WINO_SEQ else 1
+            push_wino_forms()
             n_frag = x.n * -(-conv_h // fh) * -(-conv_w // fw)
             geo = ("wino", -(-n_frag // mt) * (nfrag // nt))
             key = ("wino", nt, mt)
@@ -1007,6 +1021,7 @@ class Program:
         """side_streams: 3 torch.cuda.Stream for lanes 1..3 (None -> everything on the current stream).  A Program owns its
         activation arena and hand-off counters: never replay one Program concurrently on two streams."""
         L = cabi.lib()
+        push_wino_forms()
         cur = torch.cuda.current_stream(self.device).cuda_stream
         if side_streams is None:
             streams = (C.c_void_p * 4)(cur, cur, cur, cur)
