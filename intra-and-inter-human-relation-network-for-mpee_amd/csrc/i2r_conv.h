@@ -1,5 +1,6 @@
 // Shared pieces of the implicit-GEMM convolution kernels (internal): kernel-side descriptor, epilogue, activation load / store helpers.
-// Included by i2r_conv.hip (fp32 matrix pipe + the launch logic) and by the 16-bit translation units (i2r_conv_lp.inc).
+// Included by i2r_conv.hip (fp32 matrix pipe; the launch logic of the family is i2r_conv_plan.h, included there) and by the 16-bit
+// translation units (i2r_conv_lp.inc).
 #pragma once
 #include "i2r_common.h"
 
@@ -325,7 +326,8 @@ typedef void (*conv_fn)(const ConvGroupK);
 
 }  // namespace
 
-// kernel pickers of the 16-bit translation units (one per operand type, so the three conv files compile in parallel); null = no such variant
+// kernel pickers of the implicit-GEMM translation units (one per operand type, so the three conv files compile in parallel); null = no such variant
+void* i2r_pick_conv_f32(int nt, int mt, int cap, int pf);
 void* i2r_pick_conv_bf16(int nt, int mt, int cap, int pf);
 void* i2r_pick_conv_f16(int nt, int mt, int cap, int pf);
 // Winograd F(2x2, 3x3) fp32 kernels (i2r_conv_wino.hip): MT fragments x NT channel fragments per workgroup; LDS bytes of a workgroup

@@ -51,7 +51,7 @@ typedef const ConvK __attribute__((address_space(4)))* ConvKArg;
 
 // `args`: grp as it lies in the kernel-argument block.  Only a __global__ function knows where its parameters lie, so the two kernels
 // below pass it in (wino_args); the body reads the per-fragment descriptor fields through it (see the run loop).
-// EPI: the epilogue's form, chosen by the host per launch (i2r_conv.hip, wino_form): 1 = bias + ReLU, 2 = bias + res1 + ReLU, with every
+// EPI: the epilogue's form, chosen by the host per launch (i2r_conv_plan.h, wino_form): 1 = bias + ReLU, 2 = bias + res1 + ReLU, with every
 // member's channel blocks exact in cout and out_cs -- the two shapes of the HRNet tower -- compiled without a flag test; 0 = the general
 // epilogue (any mix of res1 / res2 / res_post / ReLU, tail blocks, the -DI2R_TUNING switches).  The results do not depend on the form, bit for bit.
 template <int MT, int NT, bool FIN, int EPI>

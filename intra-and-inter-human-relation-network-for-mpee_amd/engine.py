@@ -17,7 +17,7 @@ from .pack import (PRECISIONS, PackedConv, Packer, _m16, _r16, fold_bn, pack_fra
 
 def wino_fragment(conv_h, conv_w):
     """(fragment width, height) in output pixels of the Winograd kernels for a map: 16 tiles as 8x2, 4x4 or 2x8 -- the shape that
-    covers the map with the fewest fragments (same rule as prepare_wino in csrc/i2r_conv.hip)"""
+    covers the map with the fewest fragments (same rule as prepare_wino in csrc/i2r_conv_plan.h)"""
     best = None
     for fw in (8, 4, 2):
         n = -(-conv_w // (2 * fw)) * -(-conv_h // (32 // fw))
@@ -149,7 +149,7 @@ def lpt_block_order(counts, works, n_cu=256):
 
 def conv_split(cout_pad):
     nfrag = cout_pad // 16
-    nt = next(c for c in (3, 4, 5) if nfrag % c == 0)  # same rule as csrc/i2r_conv.hip
+    nt = next(c for c in (3, 4, 5) if nfrag % c == 0)  # same rule as csrc/i2r_conv_plan.h
     nb = nfrag // nt
     wn = 4 if nb % 4 == 0 else 2 if nb % 2 == 0 else 1
     return nt, wn

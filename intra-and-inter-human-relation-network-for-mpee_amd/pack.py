@@ -18,7 +18,7 @@ def _m16(c):
 
 def _r16(c):
     """Channel count -> row width of an activation / padded width of a weight matrix: the next multiple of 16 whose number of
-    16-channel fragments the conv kernels can split (a multiple of 3, 4 or 5: conv_split, csrc/i2r_conv.hip).  Every width of the shipped
+    16-channel fragments the conv kernels can split (a multiple of 3, 4 or 5: conv_split, csrc/i2r_conv_plan.h).  Every width of the shipped
     models is its own image (48, 64, 80 = 78 padded, 96, 160, 192, 256, 320, 384, 624, ...); 16 and 32 (HRNet-W32's first branch, W18)
     become 48 with zero weights and zero activations in the pad channels."""
     n = (c + 15) // 16

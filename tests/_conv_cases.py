@@ -1,7 +1,7 @@
 """Descriptor-level cases for the implicit-GEMM convolution family (csrc/i2r_conv.hip, i2r_conv_lp.inc) and their float64 reference.
 
 The kernels are a family conv_igemm_f32<MT, NT, CAP, PF> / conv_igemm_lp<MT, NT, CAP, PF> (bf16, f16): MT 1..4 x NT 3, 4, 5 x
-(CAP, PF) in {(4, 0), (4, 1), (12 | 8, 1), (4, 2)} = 144 instantiations, picked at run time by prepare() / resolve() from the descriptor.
+(CAP, PF) in {(4, 0), (4, 1), (12 | 8, 1), (4, 2)} = 144 instantiations, picked at run time by prepare() / resolve() (csrc/i2r_conv_plan.h) from the descriptor.
 This module holds, for every instantiation, at least one descriptor that resolves to it and stresses what differs between the
 instantiations (partial M fragments, partial tiles, several channel chunks with odd and even counts, padded output channels, several
 channel blocks), plus grouped launches that force the members onto a common staging variant.  tests/test_conv_dispatch.py checks on the
@@ -28,7 +28,7 @@ MTS, NTS = (1, 2, 3, 4), (3, 4, 5)
 
 
 def variants(dtype):
-    """(CAP, PF) pairs the kernels are built for: pick_kernel (csrc/i2r_conv.hip) / pick_lp (csrc/i2r_conv_lp.inc)"""
+    """(CAP, PF) pairs the kernels are built for: i2r_pick_conv_f32 (csrc/i2r_conv.hip) / pick_lp (csrc/i2r_conv_lp.inc)"""
     wide = 12 if dtype == 0 else 8
     return ((4, 0), (4, 1), (wide, 1), (4, 2))
 

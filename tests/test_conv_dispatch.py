@@ -1,5 +1,5 @@
 """CPU: which conv instantiation a descriptor resolves to (i2r_conv_kernel_name launches nothing), for the case table of _conv_cases.py,
-for everything the engine's cost model proposes, and for the argument errors of prepare() / resolve() (csrc/i2r_conv.hip)."""
+for everything the engine's cost model proposes, and for the argument errors of prepare() / resolve() (csrc/i2r_conv_plan.h)."""
 import collections
 import ctypes as C
 import re

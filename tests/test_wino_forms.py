@@ -1,4 +1,4 @@
-"""CPU: the epilogue form a Winograd launch resolves to (i2r_conv_wino_form launches nothing; csrc/i2r_conv.hip wino_form), the switch that
+"""CPU: the epilogue form a Winograd launch resolves to (i2r_conv_wino_form launches nothing; csrc/i2r_conv_plan.h wino_form), the switch that
 forces the general form (i2r_conv_wino_forms, engine.WINO_FORMS), and that both exports are additive: header, binding and library agree,
 the ABI stays 17 and i2r_conv_desc still ends with seq."""
 import ctypes as C

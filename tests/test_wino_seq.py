@@ -12,7 +12,7 @@ from i2r_amd import cabi, engine
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_ARG = -1  # I2R_E_ARG of include/i2r_hip.h
 TAPS = [(t // 3, t % 3) for t in range(9)]
-# the rule's own constants (wino_choose_seq in csrc/i2r_conv.hip): a launch the library sizes keeps min(what it had at one fragment per
+# the rule's own constants (wino_choose_seq in csrc/i2r_conv_plan.h): a launch the library sizes keeps min(what it had at one fragment per
 # workgroup, MIN_WG) workgroups and fills its runs up to RUN_PASSES 16-channel passes, 8 fragments at the most
 MIN_WG, RUN_PASSES, MAX_SEQ = 512, 6, 8
 
