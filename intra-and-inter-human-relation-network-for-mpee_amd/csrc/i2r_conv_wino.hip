@@ -19,7 +19,9 @@
 //  * LDS holds the raw patch of a 16-channel chunk, double-buffered, the next chunk fetched into registers under the current
 //    chunk's MFMAs (as in i2r_conv.hip).  Columns are de-interleaved by parity (slot = row * pitch + (x & 1) * half + (x >> 1)) and
 //    the pitch is chosen per FW so that the stride-2 tile gathers of a 16-lane ds_read_b128 group hit 16 distinct 16-byte slots.
-//  * B operands (U, k-permuted k4 packing) stream from L2 straight into registers one position ahead, as in the direct kernel.
+//  * B operands (U, k-permuted k4 packing) stream from L2 straight into registers one position ahead, as in the direct kernel; in the
+//    plain form the order of those loads and of the next chunk's patch loads is pinned (WINO_PASS; tools/wino_sched.py reads the
+//    resulting load-to-wait distances off the assembly, tests/test_wino_sched.py holds them).
 //  * epilogue: the column half of the output transform (over j) is in-lane; the row half (over i) crosses the four waves: each
 //    wave writes its two partial tiles T_i[b] to LDS as [i][b][tile][cout] and every thread then owns (pixel, 4 channels) pieces:
 //    three 16-byte LDS reads, bias / residuals / ReLU, one 16-byte store (a quad of lanes = 64 contiguous bytes of one pixel).
@@ -263,6 +265,18 @@ __device__ __forceinline__ void conv_wino_body(const ConvGroupK& grp, ConvKArg a
         }
     };
 
+    // (the same, column by column, for the scheduled pass of the plain form: R[c] = row ra + sg * row rb of patch column c)
+    f32x4 R[MT][4];
+    auto gather = [&](const f32x4* buf, int c) {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+            const f32x4* q = buf + mt * 4 * plane + abase_f;
+            const int oc = (c & 1) * half + (c >> 1);
+            const f32x4 xa = q[oa + oc], xb = q[ob + oc];
+            R[mt][c] = xa + sg * xb;
+        }
+    };
+
     // ---- B operand: U[pos = 4 i + j][cin / 4][cout_pad][4], lane (cout li, g) takes channels 4g..4g+3 of the 16-channel step;
     //      the pointer walks j (stride cin4 * cout_pad slots) and wraps to the next chunk after j = 3 ----
     const unsigned wlane = (unsigned)(n_base + li + g * pk.cout_pad) * 16u;   // per-lane byte offset (constant)
@@ -286,7 +300,10 @@ __device__ __forceinline__ void conv_wino_body(const ConvGroupK& grp, ConvKArg a
     _Pragma("unroll") for (int s = 0; s < 4; ++s) _Pragma("unroll") for (int mt = 0; mt < MT; ++mt)             \
         _Pragma("unroll") for (int nt = 0; nt < NT; ++nt)                                                       \
             acc[J][mt][nt] = mfma16(a[mt][J][s], B[nt][s], ((FIRST) && s == 0) ? (f32x4){0.f, 0.f, 0.f, 0.f} : acc[J][mt][nt]);
-#define WINO_PASS(PASS, FIRST)                                                                   \
+    // ---- the pass: 16 input channels, four positions j of this wave's row, 12 NT MFMAs each ----
+    // Fused-input form: the compiler's own order (runtime `more`).  With the staging terms of two more maps in registers the explicit
+    // schedule below does not fit the 128 registers of 4 waves per SIMD (it spilled 26 of them), so this form keeps the order it had.
+#define WINO_PASS_FIN(PASS, FIRST)                                                               \
     {                                                                                            \
         const int pass_ = (PASS);                                                                \
         f32x4* cur = lds + (pass_ & 1) * bufsz;                                                  \
@@ -304,6 +321,55 @@ __device__ __forceinline__ void conv_wino_body(const ConvGroupK& grp, ConvKArg a
         if (more) { wp += inc_wrap; fetch_b(b0); }                                               \
         WINO_MMA(3, b1, FIRST)                                                                   \
         if (more) stage_store(nxt, (pass_ + 1) * 16);                                            \
+        if (!(I2R_DBG(p) & 64)) __syncthreads();                                                 \
+    }
+    // Plain form: the order of the vector-memory instructions is PINNED (WINO_FENCE: nothing is scheduled across), because the waits
+    // count loads in issue order (vmcnt): left to itself the compiler sinks a weight load to its first use to save registers, and then
+    // every position starts with a wait for L2, and the first such wait also covers the far patch loads issued ahead of it.
+    //   before position 0:  weights of position 1 (b1)                      [b0 came with the previous pass / the set-up]
+    //   before position 1:  weights of position 2 (b0), then the next chunk's patch pieces
+    //   before position 2:  weights of position 3 (b1)
+    //   before position 3:  weights of the next pass's position 0 (b0)
+    // So every weight fragment has the 12 NT MFMAs of a whole position to arrive, into registers that position does not read, and
+    // the first wait that covers the patch loads is position 3's, 24 MFMAs after their issue (issued at the head of the pass they would
+    // be live across all four positions: 8 registers too many).  MORE is a compile-time flag -- the last pass is a copy of its own --
+    // because a prefetch in a conditional block makes every wait behind the join count as if it had not been issued: vmcnt(0).
+    // The gather is written column by column in the group that can hide it: columns 0 and 2 (position 0) at the head, column 1
+    // (positions 1, 2) under position 0, column 3 (position 3) under position 1.  Inside a group the scheduler is free, and it moves
+    // the column-1 reads to the end of position 0 (as the parent's order had them); pinning them ahead costs the last two registers.
+#define WINO_FENCE __builtin_amdgcn_sched_barrier(0);
+#define WINO_A(J, EXPR) _Pragma("unroll") for (int mt = 0; mt < MT; ++mt) a[mt][J] = EXPR;
+#define WINO_PASS(PASS, FIRST, MORE)                                                             \
+    {                                                                                            \
+        const int pass_ = (PASS);                                                                \
+        asm volatile("; pass: first " #FIRST ", more " #MORE);  /* (keeps the copies apart: merged heads cost spills) */ \
+        f32x4* cur = lds + (pass_ & 1) * bufsz;                                                  \
+        f32x4* nxt = lds + ((pass_ + 1) & 1) * bufsz;                                            \
+        gather(cur, 0); gather(cur, 2);                                                          \
+        WINO_A(0, R[mt][0] - R[mt][2])                                                           \
+        wp += inc_j; fetch_b(b1);                                                                \
+        WINO_FENCE                                                                               \
+        gather(cur, 1);                                                                          \
+        WINO_MMA(0, b0, FIRST)                                                                   \
+        WINO_FENCE                                                                               \
+        wp += inc_j; fetch_b(b0);                                                                \
+        if (MORE) stage_load((pass_ + 1) * 16);                                                  \
+        WINO_FENCE                                                                               \
+        WINO_A(1, R[mt][1] + R[mt][2])                                                           \
+        gather(cur, 3);                                                                          \
+        WINO_MMA(1, b1, FIRST)                                                                   \
+        WINO_FENCE                                                                               \
+        wp += inc_j; fetch_b(b1);                                                                \
+        WINO_FENCE                                                                               \
+        WINO_A(2, R[mt][2] - R[mt][1])                                                           \
+        WINO_MMA(2, b0, FIRST)                                                                   \
+        WINO_FENCE                                                                               \
+        if (MORE) { wp += inc_wrap; fetch_b(b0); }                                               \
+        WINO_FENCE                                                                               \
+        WINO_A(3, R[mt][1] - R[mt][3])                                                           \
+        WINO_MMA(3, b1, FIRST)                                                                   \
+        WINO_FENCE                                                                               \
+        if (MORE) stage_store(nxt, (pass_ + 1) * 16);                                            \
         if (!(I2R_DBG(p) & 64)) __syncthreads();                                                 \
     }
     // ---- output side ----
@@ -355,8 +421,16 @@ __device__ __forceinline__ void conv_wino_body(const ConvGroupK& grp, ConvKArg a
     stage_store(lds, 0);
     __syncthreads();
     if (stamp) ts1 = __builtin_amdgcn_s_memtime();
-    WINO_PASS(0, true)
-    for (int pass = 1; pass < npass; ++pass) WINO_PASS(pass, false)
+    if constexpr (FIN) {
+        WINO_PASS_FIN(0, true)
+        for (int pass = 1; pass < npass; ++pass) WINO_PASS_FIN(pass, false)
+    } else if (npass == 1) {
+        WINO_PASS(0, true, false)
+    } else {
+        WINO_PASS(0, true, true)
+        for (int pass = 1; pass < npass - 1; ++pass) WINO_PASS(pass, false, true)
+        WINO_PASS(npass - 1, false, false)
+    }
     if (stamp) ts2 = __builtin_amdgcn_s_memtime();
 
     if constexpr (EPI != 0) {
@@ -507,6 +581,9 @@ __device__ __forceinline__ void conv_wino_body(const ConvGroupK& grp, ConvKArg a
     }  // (EPI == 0)
     }  // (fragments of the run)
 #undef WINO_PASS
+#undef WINO_PASS_FIN
+#undef WINO_A
+#undef WINO_FENCE
 #undef WINO_MMA
     if (stamp) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

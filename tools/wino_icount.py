@@ -13,6 +13,9 @@ the run's set-up stands alone.  The compiler lays the loop out differently per f
                   output transform over j + index math + bias / residual loads (to the exchange barrier) | over i + epilogue
     forms 1, 2:   run set-up | output transform over j + index math + loads (to the exchange barrier) | over i + epilogue |
                   fragment set-up | staging store of chunk 0 | first pass | further pass | end of the kernel
+The plain form's pass exists in four copies since its load schedule became explicit (first | middle, whose closing barrier the rotated
+loop puts ABOVE its body in the text | last | only), so there the pass regions are more and the middle one is split in two;
+tools/wino_sched.py names the pass regions by what they hold and reads their load / wait schedule.
 usage: tools/wino_icount.py [--match conv_wino_f32<1, 3] [--src other/i2r_conv_wino.hip] [--json out.json] [extra hipcc flags]
 """
 import json
