@@ -714,6 +714,34 @@ typedef struct i2r_attn_query_args {
 } i2r_attn_query_args;
 I2R_API int i2r_attn_query_maps(const i2r_attn_query_args* a, void* stream);
 
+/* Attention per person: the maps above reduced over the persons of an inter-human group, without ever building [L_g, L_g] (additive:
+ * I2R_ABI_VERSION unchanged).  Group g = one image: L_g = P_g seg tokens, token (person p, y, x) = p seg + y w + x; P as i2r_attn_weights
+ * defines it.  Per group:
+ *   dependency  D[i, k] = (1 / seg) sum_{q in person i} P[q, k]     [P_g, L_g]: where person i looks; every row sums to 1
+ *   affect      F[j, q] = sum_{k in person j} P[q, k]               [P_g, L_g]: the share of token q's attention on person j; sum_j = 1
+ *   relation    R[i, j] = (1 / seg) sum_{q in person i} F[j, q]     [P_g, P_g]: every row sums to 1
+ *   rel[rel_off[g] + i P_g + j] = R[i, j], always; mode 1: the maps block of group g holds D, mode 2: F, mode 0: maps is not touched
+ *   scale == 1: maps[maps_off[g] + p L_g + t] = D / F[p, t]
+ *   scale  > 1: seg = h w; every row is P_g maps [h, w]; maps block = [P_g, P_g, h scale, w scale], the bilinear up-sampling of
+ *               i2r_attn_query_maps
+ *   qk, grp_off, heads, hp, k_off, qk_cs, ws, ws_stride: exactly as i2r_attn_weights reads them
+ *   rel_off, maps_off  device int64 [n_grp]: float offsets of the groups' blocks (maps, maps_off: may be NULL in mode 0)
+ *   rows     device workspace of Pmax * grp_off[n_grp] floats, Pmax = max L_g / seg (F, which R is reduced from in every mode; mode 2 at
+ *            scale 1 writes F straight into maps and leaves rows alone); twice that for mode 1 at scale > 1 (the raw D rows behind F)
+ *   grp_off_host  HOST copy of grp_off[0 .. n_grp], always: every L_g must be a multiple of seg (checked here), and it sizes the launches
+ * Only the first n_grp groups are computed; an empty group is skipped; nothing outside the computed groups' blocks is written.  Passes:
+ * the statistics pass of i2r_attn_weights; F, one wave per (16-query tile, person j) over j's key tiles (a person boundary may lie
+ * inside a key tile or a 128-key block: masked); mode 1: D, one wave per (person i, 32-key block) over i's query tiles; R from F; then
+ * the up-sampling pass.  fp32 matrix pipe, fixed summation orders, no atomics: deterministic.  I2R_E_ARG: null pointers, mode outside
+ * {0, 1, 2}, scale < 1 or > 64, seg < 1, n_grp outside 1 .. 65535, a group length that seg does not divide, scale > 1 with seg != h w,
+ * ws_stride < 2 heads ceil(max L_g / 128), and the heads / hp / stride / alignment conditions of i2r_attn_weights. */
+typedef struct i2r_attn_person_args {
+    const float* qk; const int32_t* grp_off; float* ws; float* rel; const int64_t* rel_off; float* maps; const int64_t* maps_off;
+    float* rows; const int32_t* grp_off_host;
+    int32_t n_grp, heads, hp, k_off, qk_cs, ws_stride, seg, mode, scale, h, w, reserved;
+} i2r_attn_person_args;
+I2R_API int i2r_attn_person_maps(const i2r_attn_person_args* a, void* stream);
+
 /* MODEL.ATTENTION_TYPE != 'default' (MODEL.NAME interformer: attention.py:991-1031,1046-1062) -- the inter-human "encoder" is ONE
  * GeneralTransformerBlock: a multi-head attention (q / k / v / out projections with bias, MHA_ :494-835; the relative position bias is
  * gathered but its addition is commented out, :780-786) over the (person, y, x) tokens of an image INCLUDING the padded persons' rows
@@ -776,7 +804,8 @@ enum {
     I2R_OP_CONV1X1_PAIR = 20, I2R_OP_CONV1X1_LP = 21, I2R_OP_MH_ATTN = 22, I2R_OP_PE_CAT_VEC = 23, I2R_OP_ROWS_GATHER = 24, I2R_OP_VIEW_SCRAMBLE = 25,
     I2R_OP_RECORD = 26, I2R_OP_WAIT = 27, I2R_OP_LANE_FLAGS = 28, I2R_OP_ATTN_WEIGHTS = 29,
     I2R_OP_ATTN_QUERY = 30,
-    I2R_OP_ROWS_GATHER_MULTI = 31 /* args: i2r_gather_multi_args (additive: I2R_ABI_VERSION unchanged) */
+    I2R_OP_ROWS_GATHER_MULTI = 31, /* args: i2r_gather_multi_args (additive: I2R_ABI_VERSION unchanged) */
+    I2R_OP_ATTN_PERSON = 32 /* args: i2r_attn_person_args (additive as well) */
 };
 
 typedef struct i2r_stem_args {

@@ -332,6 +332,7 @@ struct AqK {
     const int* q_cnt;
     float* rows;  // scale > 1: the raw [K_g, L_g] rows of group g at rows + K * grp_off[g], up-sampled into out by aq_upsample_k
     int K, scale, h, w;
+    int seg;  // > 0 (the per-person maps below): K_g = L_g / seg rows instead of q_cnt / K
 };
 
 __device__ __forceinline__ int aq_count(const AqK& p, int gi) { return p.q_cnt ? min(max(p.q_cnt[gi], 0), p.K) : p.K; }
@@ -522,7 +523,7 @@ __global__ __launch_bounds__(256) void aq_cols_k(const AqK p) {
 // blockIdx.y = group; 4 consecutive floats of its [K_g, P_g, h scale, w scale] block per thread
 __global__ __launch_bounds__(256) void aq_upsample_k(const AqK p) {
     const int gi = blockIdx.y;
-    const int g0 = p.a.grp_off[gi], len = p.a.grp_off[gi + 1] - g0, hw = p.h * p.w, kq = aq_count(p, gi);
+    const int g0 = p.a.grp_off[gi], len = p.a.grp_off[gi + 1] - g0, hw = p.h * p.w, kq = p.seg > 0 ? len / p.seg : aq_count(p, gi);
     if (len <= 0 || len % hw != 0) return;  // (the entry point checks the host's copy of the table; never a partial map)
     const int H = p.h * p.scale, W = p.w * p.scale;
     const long long n = (long long)kq * len * p.scale * p.scale;
@@ -549,6 +550,150 @@ __global__ __launch_bounds__(256) void aq_upsample_k(const AqK p) {
         for (int j = 0; j < 4; ++j)
             if (e0 + j < n) dst[e0 + j] = v[j];
     }
+}
+
+// ---- attention per person: P reduced over the persons of an inter-human group (L_g = P_g seg tokens, person p = tokens [p seg, (p + 1) seg)) ----
+//   F[j, q] = sum_{k in j} P[q, k]          ap_affect_k, behind aw_stats_k: work item (group, 16-query tile, person j), S^T = K Q^T as above
+//   D[i, k] = (1 / seg) sum_{q in i} P[q, k]  ap_depend_k: work item (group, person i, block of kApKeys keys) over i's query tiles (a wave
+//                                             walks ALL of i's query tiles: narrower key blocks than kAwKeys keep the chip filled)
+//   R[i, j] = (1 / seg) sum_{q in i} F[j, q]  ap_relation_k: one wave per (group, i, j), read back from F
+// No [L, L] block: F and D are [P_g, L_g].  Fixed head, tile and lane orders, no atomics.  A person's end may lie inside a 16-key tile or a
+// key block: the keys (F) or queries (D) past it are masked.  A group whose length seg does not divide is skipped (the host validates).
+constexpr int kApKeys = 32, kApTiles = kApKeys / 16;
+
+struct ApK {
+    AwK a;  // a.out / a.out_off: the maps blocks (modes 1 and 2)
+    float* rel;
+    const long long* rel_off;
+    float* rows;        // F of group g at rows + pmax * grp_off[g]; the raw D rows (mode 1, scale > 1) d_shift floats behind
+    long long d_shift;
+    int seg, mode, scale, pmax;
+};
+
+// group gi's raw [P_g, L_g] block of D (what = 1) or F (what = 2): the maps block where it is the mode's output at scale 1, else the workspace
+__device__ __forceinline__ float* ap_block(const ApK& p, int what, int gi, int g0) {
+    if (p.mode == what && p.scale == 1) return p.a.out + p.a.out_off[gi];
+    return p.rows + (long long)p.pmax * g0 + (what == 1 ? p.d_shift : 0);
+}
+
+// work items per group of the three passes (L_g tokens, P_g persons); the host entry point counts with the same functions
+__host__ __device__ __forceinline__ int ap_items(int pass, int len, int np) {
+    return pass == 0 ? (len + 15) / 16 * np : pass == 1 ? np * ((len + kApKeys - 1) / kApKeys) : np * np;
+}
+
+// the group of wave `item` in pass `pass`: false past the last one; item becomes the index inside the group
+__device__ __forceinline__ bool ap_item(const ApK& p, int pass, int& item, int& gi, int& g0, int& g1, int& np) {
+    for (gi = 0; gi < p.a.n_grp; ++gi) {
+        g0 = p.a.grp_off[gi];
+        g1 = p.a.grp_off[gi + 1];
+        const int len = g1 - g0;
+        if (len <= 0 || len % p.seg != 0) continue;
+        np = len / p.seg;
+        const int nt = ap_items(pass, len, np);
+        if (item < nt) return 2 * p.a.heads * ((len + kAwKeys - 1) / kAwKeys) <= p.a.ws_stride;
+        item -= nt;
+    }
+    return false;
+}
+
+// (M, 1 / L) of one query row and head from its block statistics, as aw_probs_k combines them
+__device__ __forceinline__ void ap_row_stats(const float2* st, int nkb, int heads, int head, float& mm, float& inv) {
+    mm = -INFINITY;
+    for (int b = 0; b < nkb; ++b) mm = fmaxf(mm, st[b * heads + head].x);
+    float ll = 0.f;
+    for (int b = 0; b < nkb; ++b) {
+        const float2 e = st[b * heads + head];
+        ll += e.y * __builtin_amdgcn_exp2f(e.x - mm);
+    }
+    inv = 1.f / ll;
+}
+
+template <int HB>
+__global__ __launch_bounds__(256) void ap_affect_k(const ApK p) {
+    const int lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4;
+    int item = blockIdx.x * 4 + (threadIdx.x >> 6), gi, g0, g1, np;
+    if (!ap_item(p, 0, item, gi, g0, g1, np)) return;
+    const int q0 = g0 + item / np * 16, j = item - item / np * np, len = g1 - g0, nkb = (len + kAwKeys - 1) / kAwKeys;
+    const int qrow = min(q0 + li, g1 - 1), k_beg = g0 + j * p.seg, k_end = k_beg + p.seg;
+    const float2* st = p.a.ws + (size_t)qrow * (p.a.ws_stride / 2);
+    float acc = 0.f;
+    for (int head = 0; head < p.a.heads; ++head) {
+        float mm, inv;
+        ap_row_stats(st, nkb, p.a.heads, head, mm, inv);
+        f32x4 q[HB];
+        aw_load_q<HB>(p.a, qrow, head, g, q);
+        float hsum = 0.f;
+        for (int k0 = k_beg; k0 < k_end; k0 += 16) {
+            const f32x4 s = aw_scores<HB>(p.a, min(k0 + li, k_end - 1), head, g, q);
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (k0 + 4 * g + r < k_end) hsum += __builtin_amdgcn_exp2f(s[r] - mm);
+        }
+        acc += hsum * inv;
+    }
+    acc += __shfl_xor(acc, 16);
+    acc += __shfl_xor(acc, 32);
+    if (g == 0 && q0 + li < g1) ap_block(p, 2, gi, g0)[(long long)j * len + (q0 + li - g0)] = acc * (1.f / (float)p.a.heads);
+}
+
+template <int HB>
+__global__ __launch_bounds__(256) void ap_depend_k(const ApK p) {
+    const int lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4;
+    int item = blockIdx.x * 4 + (threadIdx.x >> 6), gi, g0, g1, np;
+    if (!ap_item(p, 1, item, gi, g0, g1, np)) return;
+    const int len = g1 - g0, nkb = (len + kAwKeys - 1) / kAwKeys, nb = (len + kApKeys - 1) / kApKeys, i = item / nb, kb = item - i * nb;
+    const int k_beg = g0 + kb * kApKeys, k_end = min(k_beg + kApKeys, g1), n_kt = (k_end - k_beg + 15) / 16;
+    const int q_beg = g0 + i * p.seg, q_end = q_beg + p.seg;
+    f32x4 acc[kApTiles];
+#pragma unroll
+    for (int t = 0; t < kApTiles; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int qt = q_beg; qt < q_end; qt += 16) {
+        const int qrow = min(qt + li, q_end - 1);
+        const float2* st = p.a.ws + (size_t)qrow * (p.a.ws_stride / 2);
+        for (int head = 0; head < p.a.heads; ++head) {
+            float mm, inv;
+            ap_row_stats(st, nkb, p.a.heads, head, mm, inv);
+            if (qt + li >= q_end) inv = 0.f;  // (a query lane past the person's end adds nothing)
+            f32x4 q[HB];
+            aw_load_q<HB>(p.a, qrow, head, g, q);
+#pragma unroll
+            for (int t = 0; t < kApTiles; ++t) {
+                if (t < n_kt) {
+                    const f32x4 s = aw_scores<HB>(p.a, min(k_beg + 16 * t + li, g1 - 1), head, g, q);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) acc[t][r] += __builtin_amdgcn_exp2f(s[r] - mm) * inv;
+                }
+            }
+        }
+    }
+    const float rs = 1.f / ((float)p.a.heads * (float)p.seg);
+    float* row = ap_block(p, 1, gi, g0) + (long long)i * len;
+#pragma unroll
+    for (int t = 0; t < kApTiles; ++t) {
+        f32x4 v = acc[t];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {  // the 16 query lanes of key 4g + r, butterfly order
+            v[r] += __shfl_xor(v[r], 1);
+            v[r] += __shfl_xor(v[r], 2);
+            v[r] += __shfl_xor(v[r], 4);
+            v[r] += __shfl_xor(v[r], 8);
+        }
+        const int k = k_beg + 16 * t + 4 * g + li;  // lanes li < 4 store key 4g + li: 16 consecutive floats per tile
+        if (t < n_kt && li < 4 && k < k_end) row[k - g0] = (li == 0 ? v[0] : li == 1 ? v[1] : li == 2 ? v[2] : v[3]) * rs;
+    }
+}
+
+__global__ __launch_bounds__(256) void ap_relation_k(const ApK p) {
+    const int lane = threadIdx.x & 63;
+    int item = blockIdx.x * 4 + (threadIdx.x >> 6), gi, g0, g1, np;
+    if (!ap_item(p, 2, item, gi, g0, g1, np)) return;
+    const int i = item / np, j = item - i * np;
+    const float* f = ap_block(p, 2, gi, g0) + (long long)j * (g1 - g0) + (long long)i * p.seg;
+    float s = 0.f;
+    for (int t = lane; t < p.seg; t += 64) s += f[t];
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) s += __shfl_xor(s, m);
+    if (lane == 0) p.rel[p.rel_off[gi] + (long long)i * np + j] = s / (float)p.seg;
 }
 
 }  // namespace
@@ -660,7 +805,7 @@ extern "C" int i2r_attn_query_maps(const i2r_attn_query_args* a, void* stream) {
     }
     AqK k{{a->qk, a->out, a->grp_off, reinterpret_cast<const long long*>(a->out_off), reinterpret_cast<float2*>(a->ws), a->n_grp, a->heads, a->hp,
            a->k_off, a->qk_cs, a->n_tiles, a->ws_stride},
-          a->q_tok, a->q_cnt, a->rows, a->K, a->scale, a->h, a->w};
+          a->q_tok, a->q_cnt, a->rows, a->K, a->scale, a->h, a->w, 0};
     typedef void (*aw_t)(const AwK);
     typedef void (*aq_t)(const AqK);
 #define I2R_AW_TABLE(K) {K<1>, K<2>, K<3>, K<4>, K<5>, K<6>, K<7>, K<8>, K<9>, K<10>, K<11>, K<12>, K<13>, K<14>, K<15>, K<16>}
@@ -688,6 +833,70 @@ extern "C" int i2r_attn_query_maps(const i2r_attn_query_args* a, void* stream) {
         if (n4 > 0)
             i2r_launch(aq_upsample_k, dim3((unsigned)((n4 + 255) / 256), (unsigned)a->n_grp), dim3(256), 0, (hipStream_t)stream, k);
         I2R_CHECK_LAUNCH("i2r_attn_query_maps (up-sampling)");
+    }
+    return I2R_OK;
+}
+
+extern "C" int i2r_attn_person_maps(const i2r_attn_person_args* a, void* stream) {
+    I2R_CHECK_ARG(a && a->qk && a->grp_off && a->ws && a->rel && a->rel_off && a->rows && a->grp_off_host, "i2r_attn_person_maps: null pointer");
+    I2R_CHECK_ARG(a->mode >= 0 && a->mode <= 2, "i2r_attn_person_maps: mode=%d (0: relation only, 1: + dependency maps, 2: + affect maps)", a->mode);
+    I2R_CHECK_ARG(a->mode == 0 || (a->maps && a->maps_off), "i2r_attn_person_maps: null pointer (modes 1 and 2 need maps and maps_off)");
+    I2R_CHECK_ARG(a->scale >= 1 && a->scale <= 64, "i2r_attn_person_maps: scale=%d (1 .. 64)", a->scale);
+    I2R_CHECK_ARG(a->seg >= 1 && a->seg < (1 << 24), "i2r_attn_person_maps: seg=%d", a->seg);
+    I2R_CHECK_ARG(a->heads > 0 && a->hp > 0 && a->hp % 16 == 0 && a->hp <= 256, "i2r_attn_person_maps: heads=%d hp=%d (hp: multiple of 16, <= 256)", a->heads, a->hp);
+    const int hs = a->heads * a->hp;
+    I2R_CHECK_ARG(a->k_off >= hs && a->k_off % 4 == 0 && a->qk_cs >= a->k_off + hs && a->qk_cs % 4 == 0,
+                  "i2r_attn_person_maps: row stride qk=%d (k at %d) for %d heads x %d", a->qk_cs, a->k_off, a->heads, a->hp);
+    I2R_CHECK_ARG(a->n_grp > 0 && a->n_grp < 65536 && a->ws_stride >= 2 * a->heads && a->ws_stride % 2 == 0,
+                  "i2r_attn_person_maps: n_grp=%d ws_stride=%d", a->n_grp, a->ws_stride);
+    I2R_CHECK_ARG(reinterpret_cast<uintptr_t>(a->qk) % 16 == 0 && reinterpret_cast<uintptr_t>(a->ws) % 8 == 0, "i2r_attn_person_maps: alignment");
+    if (a->scale > 1)
+        I2R_CHECK_ARG(a->h > 0 && a->w > 0 && (long long)a->h * a->w == a->seg, "i2r_attn_person_maps: seg=%d is not h w = %d x %d", a->seg, a->h, a->w);
+    long long n_stats = 0, n_pass[3] = {0, 0, 0};
+    int max_len = 0;
+    for (int g = 0; g < a->n_grp; ++g) {
+        const int len = a->grp_off_host[g + 1] - a->grp_off_host[g];
+        I2R_CHECK_ARG(len >= 0 && len % a->seg == 0, /* (an empty group is skipped) */ "i2r_attn_person_maps: group %d has %d tokens, not a multiple of seg = %d", g, len, a->seg);
+        if (len == 0) continue;
+        n_stats += (long long)((len + 15) / 16) * ((len + kAwKeys - 1) / kAwKeys);
+        for (int pass = 0; pass < 3; ++pass) n_pass[pass] += ap_items(pass, len, len / a->seg);
+        max_len = len > max_len ? len : max_len;
+    }
+    const int pmax = max_len / a->seg;
+    I2R_CHECK_ARG(a->ws_stride >= 2 * a->heads * ((max_len + kAwKeys - 1) / kAwKeys), "i2r_attn_person_maps: ws_stride=%d for %d heads and groups of up to %d tokens",
+                  a->ws_stride, a->heads, max_len);
+    I2R_CHECK_ARG(n_stats < (1ll << 31) && n_pass[0] < (1ll << 31) && n_pass[1] < (1ll << 31) && n_pass[2] < (1ll << 31), "i2r_attn_person_maps: grid");
+    const long long n4 = ((long long)pmax * max_len * a->scale * a->scale + 3) / 4;
+    I2R_CHECK_ARG((n4 + 255) / 256 < (1ll << 31), "i2r_attn_person_maps: up-sampling grid");
+    if (max_len == 0) return I2R_OK;  // (every group is empty)
+    const bool up = a->mode != 0 && a->scale > 1;
+    const long long total = (long long)pmax * a->grp_off_host[a->n_grp];
+    ApK k{{a->qk, a->maps, a->grp_off, reinterpret_cast<const long long*>(a->maps_off), reinterpret_cast<float2*>(a->ws), a->n_grp, a->heads, a->hp,
+           a->k_off, a->qk_cs, (int)n_stats, a->ws_stride},
+          a->rel, reinterpret_cast<const long long*>(a->rel_off), a->rows, total, a->seg, a->mode, up ? a->scale : 1, pmax};
+    typedef void (*aw_t)(const AwK);
+    typedef void (*ap_t)(const ApK);
+#define I2R_AW_TABLE(K) {K<1>, K<2>, K<3>, K<4>, K<5>, K<6>, K<7>, K<8>, K<9>, K<10>, K<11>, K<12>, K<13>, K<14>, K<15>, K<16>}
+    static const aw_t stats[16] = I2R_AW_TABLE(aw_stats_k);
+    static const ap_t affect[16] = I2R_AW_TABLE(ap_affect_k);
+    static const ap_t depend[16] = I2R_AW_TABLE(ap_depend_k);
+#undef I2R_AW_TABLE
+    const int hb = a->hp / 16 - 1;
+    const hipStream_t st = (hipStream_t)stream;
+    i2r_launch(stats[hb], dim3((unsigned)((n_stats + 3) / 4)), dim3(256), 0, st, k.a);
+    I2R_CHECK_LAUNCH("i2r_attn_person_maps (statistics)");
+    i2r_launch(affect[hb], dim3((unsigned)((n_pass[0] + 3) / 4)), dim3(256), 0, st, k);
+    I2R_CHECK_LAUNCH("i2r_attn_person_maps (affect)");
+    if (a->mode == 1) {
+        i2r_launch(depend[hb], dim3((unsigned)((n_pass[1] + 3) / 4)), dim3(256), 0, st, k);
+        I2R_CHECK_LAUNCH("i2r_attn_person_maps (dependency)");
+    }
+    i2r_launch(ap_relation_k, dim3((unsigned)((n_pass[2] + 3) / 4)), dim3(256), 0, st, k);
+    I2R_CHECK_LAUNCH("i2r_attn_person_maps (relation)");
+    if (up) {  // the raw rows of the mode's maps (D behind F in the workspace) -> maps: the row layout of the query maps, K_g = P_g
+        const AqK u{k.a, nullptr, nullptr, a->rows + (a->mode == 1 ? total : 0), pmax, a->scale, a->h, a->w, a->seg};
+        i2r_launch(aq_upsample_k, dim3((unsigned)((n4 + 255) / 256), (unsigned)a->n_grp), dim3(256), 0, st, u);
+        I2R_CHECK_LAUNCH("i2r_attn_person_maps (up-sampling)");
     }
     return I2R_OK;
 }

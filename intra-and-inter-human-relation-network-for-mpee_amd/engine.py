@@ -181,6 +181,7 @@ class Program:
         self.split_counters = []  # hand-off counters of the encoder stacks (zero between launches; re-zeroed when a run fails)
         self.captures = []   # encoder stacks whose attention maps this program computes (_capture_begin)
         self.query = None    # (mode, {stack: scale}): the captured layers emit i2r_attn_query_maps instead of i2r_attn_weights (set_query_capture)
+        self.persons = None  # (mode, scale): the captured layers emit i2r_attn_person_maps instead (set_person_capture)
         self.store_dt = 0    # storage type the conv TOWER keeps its maps in (set by the engine in the 16-bit modes: 1 bf16, 2 f16)
         self.in_fork = False
         self.nbytes = 0
@@ -819,6 +820,17 @@ class Program:
             self.ops.append((cabi.CAPTURE_OP_ATTN_QUERY, lane, a))
             cap["ops"].append((i, a))
             return
+        if self.persons is not None:  # relation matrices and per-person maps: outputs, workspaces and the host group table are patched per call
+            mode, scale = self.persons
+            if "rel_off" not in cap:
+                cap["rel_off"] = torch.zeros_like(cap["out_off"])
+                self.keep.append(cap["rel_off"])
+            a = cabi.AttnPersonArgs(qk=qk.ptr, grp_off=goff.data_ptr(), rel_off=cap["rel_off"].data_ptr(), maps_off=cap["out_off"].data_ptr(),
+                                    heads=L["heads"], hp=L["hp"], k_off=L["hs"], qk_cs=qk.cs, seg=cap["x"].h * cap["x"].w, mode=mode, scale=scale,
+                                    h=cap["x"].h, w=cap["x"].w)
+            self.ops.append((cabi.CAPTURE_OP_ATTN_PERSON, lane, a))
+            cap["ops"].append((i, a))
+            return
         a = cabi.AttnWeightsArgs(qk.ptr, 0, goff.data_ptr(), cap["out_off"].data_ptr(), 0, 0, L["heads"], L["hp"], L["hs"], qk.cs, 0, 0)
         self.ops.append((cabi.CAPTURE_OP_ATTN_WEIGHTS, lane, a))
         cap["ops"].append((i, a))
@@ -933,6 +945,50 @@ class Program:
                                            for o, n, c in zip(offs, lens, cnt)]
         self._capture_ws = held
         return buf, maps, {cap["stack"]: cap["x"] for cap in self.captures}
+
+    def set_person_capture(self, glens):
+        """The per-person form of set_capture (a program built with `persons`): every group is an image of P_g persons of h w tokens.
+        -> (buffer, {(stack, layer): per group a [P_g, P_g] relation matrix}, {(stack, layer): per group a [P_g, P_g, h r, w r] view, mode 0:
+        nothing}, {stack: input Act}), all views of the one buffer: per layer the relation blocks, then the map blocks.  No [L, L] block
+        exists: the workspaces are O(P L)."""
+        mode, scale = self.persons
+        plan, per_layer, n_ws, n_rows = [], [], 2, 1
+        for cap, lens in zip(self.captures, glens):
+            heads = self._capture_groups(cap, lens)
+            hw = cap["x"].h * cap["x"].w
+            assert all(n % hw == 0 for n in lens)
+            pers = [n // hw for n in lens]
+            stride = 2 * heads * -(-max(lens) // self.AW_KEYS)
+            n_ws = max(n_ws, stride * sum(lens))
+            n_rows = max(n_rows, (2 if mode == 1 and scale > 1 else 1) * max(pers) * sum(lens))
+            r_offs, n_rel = self._capture_blocks([p * p for p in pers])
+            m_offs, n_maps = self._capture_blocks([p * n * scale * scale if mode else 0 for p, n in zip(pers, lens)])
+            plan.append((pers, stride, r_offs, m_offs, n_rel))
+            per_layer.append(n_rel + n_maps)
+        total = sum(n * len(cap["ops"]) for n, cap in zip(per_layer, self.captures))
+        buf = torch.empty(max(total, 1), dtype=torch.float32, device=self.device)
+        ws = torch.empty(n_ws, dtype=torch.float32, device=self.device)
+        rows = torch.empty(n_rows, dtype=torch.float32, device=self.device)
+        held = [ws, rows]  # (kept until the next call: the launches read them asynchronously; torch's allocator orders reuse by stream)
+        rel, maps, base = {}, {}, 0
+        for cap, lens, (pers, stride, r_offs, m_offs, n_rel), n_layer in zip(self.captures, glens, plan, per_layer):
+            self._upload_out_off(cap, m_offs)
+            cap["rel_off"][:len(pers)].copy_(torch.tensor(r_offs[:-1], dtype=torch.int64).pin_memory(), non_blocking=True)
+            cur = cap["grouping"]["current"]
+            host_off = (C.c_int32 * (len(lens) + 1))(*cur[:len(lens) + 1])
+            held.append(host_off)
+            h, w = cap["x"].h, cap["x"].w
+            for i, a in cap["ops"]:
+                a.rel, a.maps = buf.data_ptr() + 4 * base, buf.data_ptr() + 4 * (base + n_rel)
+                a.ws, a.rows, a.grp_off_host = ws.data_ptr(), rows.data_ptr(), C.cast(host_off, C.c_void_p)
+                a.n_grp, a.ws_stride = len(lens), stride
+                rel[(cap["stack"], i)] = [buf[base + o:base + o + p * p].view(p, p) for o, p in zip(r_offs, pers)]
+                if mode:
+                    maps[(cap["stack"], i)] = [buf[base + n_rel + o:base + n_rel + o + p * n * scale * scale].view(p, p, h * scale, w * scale)
+                                               for o, p, n in zip(m_offs, pers, lens)]
+                base += n_layer
+        self._capture_ws = held
+        return buf, rel, maps, {cap["stack"]: cap["x"] for cap in self.captures}
 
     def set_groups(self, grouping, grp_off_host):
         """(Re)define the token groups of an encoder stack: uploads the offset table and patches the per-layer descriptors."""
@@ -1693,6 +1749,21 @@ class AttnQueries:
         self.capacity = int(capacity) if capacity is not None else max(int(torch.as_tensor(t).shape[-1]) for t in self.tokens.values())
 
 
+class PersonMaps:
+    """The per-person form of an attention-map capture (Engine.forward(..., capture=, persons=)): of every captured layer of the
+    inter-human stack the relation matrix R[i, j] (how much of person i's attention lands on person j) per image, and with
+    mode: 0 / None nothing else, 1 / "dependency" the maps D[i] (where person i looks, averaged over its tokens), 2 / "affect" the maps
+    F[j] (the share of every token's attention that lands on person j); upsample: integer bilinear scale of those maps (1 = raw)."""
+    MODES = {None: 0, "dependency": 1, "affect": 2, 0: 0, 1: 1, 2: 2}
+
+    def __init__(self, mode=None, upsample=1):
+        if isinstance(mode, bool) or mode not in self.MODES:
+            raise ValueError("mode %r: None, 'dependency' or 'affect'" % (mode,))
+        self.mode, self.upsample = self.MODES[mode], int(upsample)
+        if not 1 <= self.upsample <= 64:
+            raise ValueError("upsample %r (1 .. 64)" % (upsample,))
+
+
 def _multi(y):
     """the 'multi' heat maps of what a forward returned (a dict where the model supervises its first stage too)"""
     return y["multi"] if isinstance(y, dict) else y
@@ -2022,23 +2093,25 @@ class Engine:
             f = c
         return f
 
-    def _new_program(self, query=None):
-        """an empty Program of this engine's storage type; query: the program-key suffix of _check_queries, or None"""
+    def _new_program(self, query=None, persons=None):
+        """an empty Program of this engine's storage type; query / persons: the program-key suffix of _check_queries / _check_persons, or None"""
         P = Program(self.device)
         P.store_dt = self.store_dt
         P.query = (query[1], dict(query[3])) if query else None
+        P.persons = (persons[1], persons[2]) if persons else None
         return P
 
-    def _build(self, S, H, W, length, flip=False, part=None, capture=(), query=None):
+    def _build(self, S, H, W, length, flip=False, part=None, capture=(), query=None, persons=None):
         """flip: the flip test of validate() (lib/core/function.py:142-162) batched into the same forward -- crops S..2S-1 are
         the mirrored copies (mirroring happens inside the stem kernels), every image appears twice as a token group.
         part (models whose first stage is the bare HRNet tower): "tower" = the per-crop tower + reduce only -> (P, patch, features Act);
         "tail" = everything behind it (position branch, inter-human encoder, deconvs, head) reading a feature buffer that tower
         programs fill (patch["feat"]) -- the two halves of a part-batch forward (_forward_split).
         capture: frozenset of (stack, layer) whose attention maps the program computes too (Program.set_capture); query: the key suffix
-        of _check_queries -- their rows / columns at query points instead (Program.set_query_capture)."""
+        of _check_queries -- their rows / columns at query points instead (Program.set_query_capture); persons: that of _check_persons
+        -- their per-person reductions instead (Program.set_person_capture)."""
         M = self.cfg["MODEL"]
-        P = self._new_program(query)
+        P = self._new_program(query, persons)
         patch = {}
         n_src = S
         if flip:
@@ -2228,6 +2301,22 @@ class Engine:
             raise ValueError("queries: mode %r (0 dependency, 1 affect), upsample %r (1 .. 64)" % (queries.mode, up))
         return ("query", mode, int(queries.capacity), scales)
 
+    def _check_persons(self, persons, capture, flip_joint_map=None, queries=None):
+        """persons (PersonMaps) -> the program-key suffix ("persons", mode, scale), or None without persons"""
+        if persons is None:
+            return None
+        if self.window_attn:
+            raise ValueError("persons=: ATTENTION_TYPE window has no encoder stack to capture")
+        if flip_joint_map is not None or queries is not None:
+            raise ValueError("persons=: not with the flip test, not with queries=")
+        if not capture:
+            raise ValueError("persons= needs capture=: the (stack, layer) set of the inter-human stack to reduce")
+        other = sorted({str(st) for st, _ in capture} - {self.inter_stack})
+        if other or not self.layers:
+            raise ValueError("persons=: %s is not this model's inter-human stack %r (an intra-human stack has one person per group)"
+                             % (other or "a capture", self.inter_stack if self.layers else None))
+        return ("persons", int(persons.mode), int(persons.upsample))
+
     def _check_map_sizes(self, P, H, W):
         """the token maps attention_at mapped its points onto (capture_map_sizes) are the ones the program was built with"""
         sizes = self.capture_map_sizes(H, W)
@@ -2262,7 +2351,7 @@ class Engine:
     MAX_PROGRAMS = 48
     MAX_PROGRAM_BYTES = 32 << 30
 
-    def forward(self, x, pos_mask, length, flip_joint_map=None, capture=None, queries=None):
+    def forward(self, x, pos_mask, length, flip_joint_map=None, capture=None, queries=None, persons=None):
         """flip_joint_map (device int32 [J], see caller.joint_map): run the flip test in the same forward and return the merged
         'multi' heatmaps (the reference merges only outputs['multi'], function.py:137-162).
         capture: a set of (stack, layer) -- stack a state-dict prefix of capture_stacks() -- whose attention maps to return as well:
@@ -2273,18 +2362,23 @@ class Engine:
         queries.tokens[stack] (int32 [groups, K], -1 = skip), optionally up-sampled bilinearly by queries.upsample (an int, or one per
         stack): maps[(stack, layer)] = per group a [K_g, persons, h r, w r] view.  One program per (capture set, mode, K capacity, scales) --
         K is in the key although every K-dependent field is patched per call: a caller asks with one K; new points or another grouping
-        at the same capacity reuse it."""
+        at the same capacity reuse it.
+        persons (PersonMaps, with capture of layers of the inter-human stack only): instead of the [L, L] maps, their reduction per person
+        -> (output, (relation, maps)): relation[(stack, layer)] = per image the [P, P] matrix, maps[(stack, layer)] = per image a
+        [P, P, h r, w r] view (persons.mode 1: dependency maps, 2: affect maps, 0: no entry).  One program per (capture set, mode, scale);
+        another grouping at the same capacity reuses it.  ValueError: another stack, the window-type block, the flip test, queries."""
         assert x.dim() == 4 and x.shape[1] == 3 and x.dtype == torch.float32
         S, _, H, W = x.shape
         assert S == sum(length), "sum(length)=%d != number of crops %d" % (sum(length), S)
         assert all(n >= 1 for n in length), "every image needs at least one person"
         sine_n = max(length)  # (MULTI_POS_EMBEDDING sine: the canvas is max(length) persons wide, for every part of this batch)
+        pkey = self._check_persons(persons, capture, flip_joint_map, queries)
         if capture:
             capture = self._check_capture(capture)
             assert flip_joint_map is None and not self.window_attn, "attention maps: no flip test, no window-type block"
             query = self._check_queries(queries, capture)
             with torch.cuda.device(self.device):
-                return self._forward_part(x, pos_mask, list(length), None, S, H, W, sine_n, capture=capture, queries=queries, query=query)
+                return self._forward_part(x, pos_mask, list(length), None, S, H, W, sine_n, capture=capture, queries=queries, query=query, persons=pkey)
         if queries is not None:
             self._check_queries(queries, capture)
         if self.window_attn and flip_joint_map is not None:
@@ -2497,7 +2591,7 @@ class Engine:
             r += n
         return out
 
-    def forward_groups(self, x, pos_mask, members, group_len, flip_joint_map=None, share_first_stage=None):
+    def forward_groups(self, x, pos_mask, members, group_len, flip_joint_map=None, share_first_stage=None, persons=None):
         """x [S, 3, H, W], pos_mask [S, 1, H, W]: the DISTINCT crops of a batch; members: device int32 [sum(group_len)] of crop indices in
         [0, S), group after group (input.main_target_groups); group_len: host list of the groups' sizes.  -> the 'multi' heat maps of the
         FIRST member of every group, [len(group_len), J, H/4, W/4] -- what the reference's validate_main_target keeps of model(x[members],
@@ -2509,7 +2603,10 @@ class Engine:
         (ValueError where the tail cannot take gathered rows: sine, cat_vec concatenated, window, an unserved size); False -- always the
         expanded forward.  Programs are keyed by capacities only: other groups of the same sizes build nothing.  On every shared path
         (the default one of the HRNet tower included) a member index outside [0, S) is never dereferenced: the hand-over gathers are
-        bound to the S real crops of the call, so its rows -- features, mask -- are zeros, never what a capacity slot holds."""
+        bound to the S real crops of the call, so its rows -- features, mask -- are zeros, never what a capacity slot holds.
+        persons: ValueError when given -- the grouped forward has no attention-map capture (forward(..., capture=, persons=) has)."""
+        if persons is not None:
+            raise ValueError("forward_groups: persons= is not served (no attention-map capture on the grouped forward)")
         assert x.dim() == 4 and x.shape[1] == 3 and x.dtype == torch.float32
         assert share_first_stage in (None, True, False)
         S, _, H, W = x.shape
@@ -2618,7 +2715,7 @@ class Engine:
         self._bind_groups(Pt, group_len, capG - G, flip)
         return self._run_bound(Pt, patch, capN, N, flip_joint_map, H, W)[0]
 
-    def _forward_part(self, x, pos_mask, length, flip_joint_map, S, H, W, sine_n, slot=0, capture=frozenset(), queries=None, query=None):
+    def _forward_part(self, x, pos_mask, length, flip_joint_map, S, H, W, sine_n, slot=0, capture=frozenset(), queries=None, query=None, persons=None):
         x = x.to(self.device).contiguous()
         flip = flip_joint_map is not None
         # one program per (capacity, H, W, flip): the launch list and every buffer depend on the crop capacity only; the
@@ -2628,13 +2725,14 @@ class Engine:
         if self.window_attn:  # the padded person layout IS the program: no capacity slots, one program per `length`
             cap, key = S, (S, H, W, flip, "window", tuple(length))
         if capture:
-            key = key + ("capture", capture) + (query or ())
-        P, patch = self._program(key, lambda: self._build(cap, H, W, list(length) + [1] * (cap - S), flip, capture=capture, query=query))
+            key = key + ("capture", capture) + (query or ()) + (persons or ())
+        P, patch = self._program(key, lambda: self._build(cap, H, W, list(length) + [1] * (cap - S), flip, capture=capture, query=query, persons=persons))
         self.last_concurrent = []
         self.last_programs = [P]  # (_forward merges the parts')
-        return self._run_program(P, patch, x, pos_mask, length, flip_joint_map, S, cap, H, W, sine_n, capture, queries, query)
+        return self._run_program(P, patch, x, pos_mask, length, flip_joint_map, S, cap, H, W, sine_n, capture, queries, query, persons)
 
-    def _run_program(self, P, patch, x, pos_mask, length, flip_joint_map, S, cap, H, W, sine_n, capture=frozenset(), queries=None, query=None):
+    def _run_program(self, P, patch, x, pos_mask, length, flip_joint_map, S, cap, H, W, sine_n, capture=frozenset(), queries=None, query=None,
+                     persons=None):
         """Bind one call into a built program of capacity `cap` and run it on the current stream: the token groups of `length` (capacity
         slots as one-person groups), the sine rows, the inputs (x None: tower programs filled patch["feat"]), fresh outputs, the capture
         buffers; then the flip merge and the slice to the S real crops.  -> what forward() returns."""
@@ -2654,9 +2752,14 @@ class Engine:
                 glens.append([tok] * S if c["stack"] == self.single_stack else [n * tok for n in length])
             if query:
                 self._check_map_sizes(P, H, W)
-            _, maps, inputs = P.set_query_capture(glens, queries) if query else P.set_capture(glens)
+            if persons:
+                _, rel, maps, _ = P.set_person_capture(glens)
+            else:
+                _, maps, inputs = P.set_query_capture(glens, queries) if query else P.set_capture(glens)
         multi, single = self._run_bound(P, patch, cap, S, flip_joint_map, H, W)
         res = {"single": single, "multi": multi} if single is not None else multi
+        if persons:
+            return res, (rel, maps)
         if capture:
             return res, self._capture_result(maps, inputs, S)
         return res

@@ -64,6 +64,13 @@ def group_tokens(tok, length, hw):
     return out, [n * K for n in length]
 
 
+class PersonRelations:
+    """what I2RModule.person_relations returns: relation {(stack, layer): [per image [P, P]]}, maps {(stack, layer): [per image [P, P, h r, w r]]}"""
+
+    def __init__(self, relation, maps):
+        self.relation, self.maps = relation, maps
+
+
 def _call_forward_hooks(module, output):
     """the module's forward hooks, called as a forward of it would (inputs: none -- the fused forward has no per-module call)"""
     for hid, hook in list(module._forward_hooks.items()):
@@ -321,6 +328,40 @@ class I2RModule(nn.Module):
         with torch.no_grad():
             out, maps = eng.forward(x, pos_mask, length, capture=capture, queries=queries)
         return out, self._query_result(maps, lambda st: st.startswith("singleformer."))
+
+    def person_relations(self, x, pos_mask, length, layers=None, maps=None, upsample=False):
+        """The inter-human attention per person, computed on the device without ever building an [L, L] map: how much person i attends to
+        person j, and where on j it looks.  With P the head-averaged softmax(q k^T) of a layer of the inter-human stack over the image's
+        persons * h * w tokens (what the forward hooks get):
+          relation   R[i, j] = mean over the tokens q of person i of the sum over the tokens k of person j of P[q, k]   (rows sum to 1)
+          dependency D[i, k] = mean over the tokens q of person i of P[q, k]: where person i looks                     (rows sum to 1)
+          affect     F[j, q] = sum over the tokens k of person j of P[q, k]: token q's share for person j              (sum over j = 1)
+        layers: set of (stack, layer) of the inter-human stack (Engine.inter_stack), default all its layers; maps: None, "dependency" or
+        "affect"; upsample: True = by the stack's own down_rate (input resolution), an int = that scale, False / 1 = the raw token maps.
+        -> (model output, result): result.relation[(stack, layer)] = a list with one [P_img, P_img] tensor per image;
+          result.maps[(stack, layer)] = a list with one [P_img, P_img, h r, w r] tensor per image -- first index i (dependency) or j
+          (affect), second index the person whose token map it is; empty without maps.  All are views of one buffer.
+        ValueError: a stand-alone first stage (no inter-human stack), ATTENTION_TYPE window, a layer of another stack.
+        Forward hooks keep working as before; this call serves none."""
+        from ..engine import PersonMaps
+        name = self._engine_name() or self.cfg["MODEL"]["NAME"]
+        if name in ("transpose_h", "hrformer", "hrnet"):
+            raise ValueError("person_relations: %s has no inter-human stack" % name)
+        if name == "interformer" and self.cfg["MODEL"]["ATTENTION_TYPE"] != "default":
+            raise ValueError("person_relations: ATTENTION_TYPE %r has no encoder stack to capture" % (self.cfg["MODEL"]["ATTENTION_TYPE"],))
+        if maps not in (None, "dependency", "affect"):
+            raise ValueError("maps %r: None, 'dependency' or 'affect'" % (maps,))
+        if torch.is_tensor(length):
+            length = length.tolist()
+        length = [int(n) for n in length]
+        eng = self.engine()
+        st = eng.inter_stack
+        capture = {(st, i) for i in range(eng.capture_stacks().get(st, 0))} if layers is None else {(str(s), int(i)) for s, i in layers}
+        if upsample is True:
+            upsample = x.shape[2] // eng.capture_map_sizes(x.shape[2], x.shape[3])[st][0]
+        with torch.no_grad():
+            out, (rel, views) = eng.forward(x, pos_mask, length, capture=capture, persons=PersonMaps(maps, max(int(upsample), 1)))
+        return out, PersonRelations(rel, views)
 
     def forward(self, x, pos_mask, length):
         """model(input, pos_mask, length) -- reference lib/core/function.py:135.  With forward hooks on <stack>.layers[i].self_attn the
