@@ -4,7 +4,7 @@ import torch
 import torch.nn.functional as F
 
 import i2r_cpu
-from _gpu_util import from_act, run, to_act
+from _gpu_util import from_act, run, run_poisoned, to_act, tracked_program
 from i2r_amd import engine, synth
 
 pytestmark = pytest.mark.gpu
@@ -924,9 +924,10 @@ def test_layernorm(c, h, w):
     sd = {"n.weight": _rand((c,), "lnw%d" % c, 0.3) + 1.0, "n.bias": _rand((c,), "lnb%d" % c, 0.2)}
     x = _rand((3, c, h, w), "lnx%d" % c, 2.0)
     ref = F.layer_norm(x.permute(0, 2, 3, 1), (c,), sd["n.weight"], sd["n.bias"], 1e-6).permute(0, 3, 1, 2)
-    P = engine.Program(torch.device(DEV))
-    out = P.layernorm(to_act(P, x), engine.Packer(sd, torch.device(DEV)).ln("n", c))
-    run(P)
+    P = tracked_program(torch.device(DEV))
+    xa = to_act(P, x)
+    out = P.layernorm(xa, engine.Packer(sd, torch.device(DEV)).ln("n", c))
+    run_poisoned(P, [xa], [out])  # (the output buffer holds NaN before the run: the pad assertion below is about what the kernel wrote)
     assert (from_act(out) - ref).abs().max().item() < 2e-5
     assert out.t.view(-1, out.cs)[:, c:].abs().max().item() == 0.0 if out.cs > c else True
 
@@ -1146,9 +1147,10 @@ def test_conv_gelu_and_post_residual():
     ref = F.batch_norm(F.conv2d(x, sd["c.weight"], sd["c.bias"]), sd["b.running_mean"], sd["b.running_var"], sd["b.weight"],
                        sd["b.bias"], False, 0.0, 1e-5)
     ref = F.gelu(ref) + post
-    P = engine.Program(torch.device(DEV))
-    out = P.conv(to_act(P, x), engine.Packer(sd, torch.device(DEV)).conv("c", "b"), act=2, res_post=to_act(P, post))
-    run(P)
+    P = tracked_program(torch.device(DEV))
+    xa, pa = to_act(P, x), to_act(P, post)
+    out = P.conv(xa, engine.Packer(sd, torch.device(DEV)).conv("c", "b"), act=2, res_post=pa)
+    run_poisoned(P, [xa, pa], [out])  # (the output buffer holds NaN before the run)
     assert (from_act(out) - ref).abs().max().item() < 1e-4
     assert out.t.view(-1, out.cs)[:, 78:].abs().max().item() == 0.0
 
