@@ -178,10 +178,16 @@ __global__ __launch_bounds__(256) void view_scramble_k(const float* __restrict__
 // S^T[key 4g + r][query li], r < 4), fp32 matrix pipe, no LDS:
 //   pass 1 (aw_stats_k)  per head: the running max m and the sum of exp2(s - m) of every query row over the block's keys -> ws
 //   pass 2 (aw_probs_k)  per head: combine the row's block statistics into (M, 1 / L), recompute s, p = exp2(s - M) / L, add into the
-//                        block's accumulators (fixed head order, no atomics); then one 16-byte store per lane and key tile: 4
-//                        consecutive keys of one query row (4-float pieces when the row length and the group's offset are multiples of
-//                        4, element stores otherwise -- no piece ever straddles a row end or touches a byte outside the block)
+//                        block's accumulators (fixed head order, no atomics); then one store per lane and key tile: 4 consecutive
+//                        keys of one query row
 // ws: per query row (token index) ws_stride floats = (m, l) per (key block, head).
+// The query-point and per-person forms further down are these passes around other work items.  Every kernel of the family is a thin
+// caller of the same pieces, so each piece of arithmetic exists once and the forms agree bit for bit:
+//   aw_group        the walk over grp_off from a wave index to its group, with the workspace-stride guard
+//   aw_block_stats  pass 1 of a 16-query tile over one key block (the online-softmax loop)
+//   aw_row_stats    the combine: (M, 1 / L) of a row and head from its block statistics
+//   aw_block_probs  pass 2 of a 16-query tile over the key tiles of one block, added into the caller's accumulators over the heads
+//   aw_store4       the store tail: 4 consecutive floats of a row, one 16-byte piece or guarded elements
 constexpr int kAwKeys = 128, kAwTiles = kAwKeys / 16;
 
 struct AwK {
@@ -190,26 +196,33 @@ struct AwK {
     const int* grp_off;
     const long long* out_off;
     float2* ws;
-    int n_grp, heads, hp, k_off, qk_cs, n_tiles, ws_stride;
+    int n_grp, heads, hp, k_off, qk_cs, ws_stride;
 };
 
-// the work item of wave `item`: group gi (rows [g0, g1)), query rows [q0, q0 + 16), keys [k0, k0 + kAwKeys); false past the last one
-__device__ __forceinline__ bool aw_item(const AwK& p, int item, int& gi, int& g0, int& g1, int& q0, int& kb, int& nkb) {
+__host__ __device__ __forceinline__ int aw_key_blocks(int len) { return (len + kAwKeys - 1) / kAwKeys; }
+
+// The group of wave `item` in a launch whose group gi (rows [g0, g1), len of them) has items(gi, len) work items; item becomes the index
+// inside the group.  An empty group and one without items are skipped.  false past the last item, and for a group whose statistics do not
+// fit a workspace row (compute nothing rather than overrun it).
+template <class F>
+__device__ __forceinline__ bool aw_group(const AwK& p, int& item, int& gi, int& g0, int& g1, F items) {
     for (gi = 0; gi < p.n_grp; ++gi) {
         g0 = p.grp_off[gi];
         g1 = p.grp_off[gi + 1];
-        const int len = g1 - g0;
-        if (len <= 0) continue;
-        nkb = (len + kAwKeys - 1) / kAwKeys;
-        const int nt = (len + 15) / 16 * nkb;
-        if (item < nt) {
-            q0 = g0 + item / nkb * 16;
-            kb = item - item / nkb * nkb;
-            return 2 * p.heads * nkb <= p.ws_stride;  // (a workspace row too short for this group: compute nothing rather than overrun it)
-        }
+        const int nt = g1 > g0 ? items(gi, g1 - g0) : 0;
+        if (item < nt) return 2 * p.heads * aw_key_blocks(g1 - g0) <= p.ws_stride;
         item -= nt;
     }
     return false;
+}
+
+// the work item of wave `item`: group gi (rows [g0, g1)), query rows [q0, q0 + 16), key block kb of the group's nkb; false past the last one
+__device__ __forceinline__ bool aw_item(const AwK& p, int item, int& gi, int& g0, int& g1, int& q0, int& kb, int& nkb) {
+    if (!aw_group(p, item, gi, g0, g1, [](int, int len) { return (len + 15) / 16 * aw_key_blocks(len); })) return false;
+    nkb = aw_key_blocks(g1 - g0);
+    q0 = g0 + item / nkb * 16;
+    kb = item - item / nkb * nkb;
+    return true;
 }
 
 template <int HB>
@@ -233,12 +246,11 @@ __device__ __forceinline__ f32x4 aw_scores(const AwK& p, int krow, int head, int
     return s;
 }
 
+// Block statistics: per head the running max m and the sum l of exp2(s - m) of query row qrow (lane (g, li): query li, keys 4g + r) over the
+// keys [k_beg, k_end) of key block kb of its group (rows end at g1), online over tiles of 16 -> workspace row ws_row, if the lane's query
+// is a valid one
 template <int HB>
-__global__ __launch_bounds__(256) void aw_stats_k(const AwK p) {
-    const int lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4;
-    int gi, g0, g1, q0, kb, nkb;
-    if (!aw_item(p, blockIdx.x * 4 + (threadIdx.x >> 6), gi, g0, g1, q0, kb, nkb)) return;
-    const int qrow = min(q0 + li, g1 - 1), k_beg = g0 + kb * kAwKeys, k_end = min(k_beg + kAwKeys, g1);
+__device__ __forceinline__ void aw_block_stats(const AwK& p, int li, int g, int qrow, int g1, int k_beg, int k_end, bool valid, size_t ws_row, int kb) {
     for (int head = 0; head < p.heads; ++head) {
         f32x4 q[HB];
         aw_load_q<HB>(p, qrow, head, g, q);
@@ -262,34 +274,35 @@ __global__ __launch_bounds__(256) void aw_stats_k(const AwK p) {
         }
         l += __shfl_xor(l, 16);
         l += __shfl_xor(l, 32);
-        if (g == 0 && q0 + li < g1) p.ws[(size_t)(q0 + li) * (p.ws_stride / 2) + kb * p.heads + head] = make_float2(m, l);
+        if (g == 0 && valid) p.ws[ws_row * (p.ws_stride / 2) + kb * p.heads + head] = make_float2(m, l);
     }
 }
 
-template <int HB>
-__global__ __launch_bounds__(256) void aw_probs_k(const AwK p) {
-    const int lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4;
-    int gi, g0, g1, q0, kb, nkb;
-    if (!aw_item(p, blockIdx.x * 4 + (threadIdx.x >> 6), gi, g0, g1, q0, kb, nkb)) return;
-    const int qrow = min(q0 + li, g1 - 1), k_beg = g0 + kb * kAwKeys, k_end = min(k_beg + kAwKeys, g1);
-    const int n_kt = (k_end - k_beg + 15) / 16;
-    const float2* st = p.ws + (size_t)qrow * (p.ws_stride / 2);
-    f32x4 acc[kAwTiles];
-#pragma unroll
-    for (int t = 0; t < kAwTiles; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+// The combine: (M, 1 / L) of one query row and head from the (m, l) of the row's nkb key blocks
+__device__ __forceinline__ void aw_row_stats(const float2* st, int nkb, int heads, int head, float& mm, float& inv) {
+    mm = -INFINITY;
+    for (int b = 0; b < nkb; ++b) mm = fmaxf(mm, st[b * heads + head].x);
+    float ll = 0.f;
+    for (int b = 0; b < nkb; ++b) {
+        const float2 e = st[b * heads + head];
+        ll += e.y * __builtin_amdgcn_exp2f(e.x - mm);
+    }
+    inv = 1.f / ll;
+}
+
+// Block probabilities: acc[t][r] += exp2(s - M) / L of query row qrow (statistics row st) and key k_beg + 16 t + 4g + r, t < n_kt, over the
+// heads in order; a lane that is not live (no query of its own) adds zeros
+template <int HB, int TILES>
+__device__ __forceinline__ void aw_block_probs(const AwK& p, int li, int g, int qrow, const float2* st, int nkb, bool live, int g1, int k_beg, int n_kt,
+                                               f32x4 (&acc)[TILES]) {
     for (int head = 0; head < p.heads; ++head) {
-        float mm = -INFINITY;
-        for (int b = 0; b < nkb; ++b) mm = fmaxf(mm, st[b * p.heads + head].x);
-        float ll = 0.f;
-        for (int b = 0; b < nkb; ++b) {
-            const float2 e = st[b * p.heads + head];
-            ll += e.y * __builtin_amdgcn_exp2f(e.x - mm);
-        }
-        const float inv = 1.f / ll;
+        float mm, inv;
+        aw_row_stats(st, nkb, p.heads, head, mm, inv);
+        if (!live) inv = 0.f;
         f32x4 q[HB];
         aw_load_q<HB>(p, qrow, head, g, q);
 #pragma unroll
-        for (int t = 0; t < kAwTiles; ++t) {
+        for (int t = 0; t < TILES; ++t) {
             if (t < n_kt) {
                 const f32x4 s = aw_scores<HB>(p, min(k_beg + 16 * t + li, g1 - 1), head, g, q);
 #pragma unroll
@@ -297,33 +310,55 @@ __global__ __launch_bounds__(256) void aw_probs_k(const AwK p) {
             }
         }
     }
-    if (q0 + li >= g1) return;
-    const float rh = 1.f / (float)p.heads;
-    const long long len = g1 - g0;
-    float* row = p.out + p.out_off[gi] + (long long)(q0 + li - g0) * len;
-    const bool whole = (len & 3) == 0 && (p.out_off[gi] & 3) == 0 && (reinterpret_cast<uintptr_t>(p.out) & 15) == 0;
+}
+
+// The store tail: v = 4 consecutive floats of row `row` of the [*, len] block blk, at offset k (a multiple of 4) -- one 16-byte piece when the
+// block is 16-byte aligned and 4 divides len (every piece then lies whole inside its row), guarded element stores otherwise: no store ever
+// straddles a row end or touches a byte outside the block
+__device__ __forceinline__ void aw_store4(float* blk, long long row, long long len, int k, f32x4 v) {
+    if (k >= len) return;
+    float* dst = blk + row * len + k;
+    if ((len & 3) == 0 && (reinterpret_cast<uintptr_t>(blk) & 15) == 0) {
+        *reinterpret_cast<f32x4*>(dst) = v;
+    } else {
 #pragma unroll
-    for (int t = 0; t < kAwTiles; ++t) {
-        const int k = k_beg + 16 * t + 4 * g - g0;  // first of the lane's 4 keys, relative to the group
-        if (t >= n_kt || k >= len) continue;
-        const f32x4 v = acc[t] * rh;
-        if (whole) {
-            *reinterpret_cast<f32x4*>(row + k) = v;
-        } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if (k + r < len) row[k + r] = v[r];
-        }
+        for (int r = 0; r < 4; ++r)
+            if (k + r < len) dst[r] = v[r];
     }
 }
 
+template <int HB>
+__global__ __launch_bounds__(256) void aw_stats_k(const AwK p) {
+    const int lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4;
+    int gi, g0, g1, q0, kb, nkb;
+    if (!aw_item(p, blockIdx.x * 4 + (threadIdx.x >> 6), gi, g0, g1, q0, kb, nkb)) return;
+    const int k_beg = g0 + kb * kAwKeys;
+    aw_block_stats<HB>(p, li, g, min(q0 + li, g1 - 1), g1, k_beg, min(k_beg + kAwKeys, g1), q0 + li < g1, q0 + li, kb);
+}
+
+template <int HB>
+__global__ __launch_bounds__(256) void aw_probs_k(const AwK p) {
+    const int lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4;
+    int gi, g0, g1, q0, kb, nkb;
+    if (!aw_item(p, blockIdx.x * 4 + (threadIdx.x >> 6), gi, g0, g1, q0, kb, nkb)) return;
+    const int qrow = min(q0 + li, g1 - 1), k_beg = g0 + kb * kAwKeys, n_kt = (min(k_beg + kAwKeys, g1) - k_beg + 15) / 16;
+    f32x4 acc[kAwTiles] = {};
+    aw_block_probs<HB>(p, li, g, qrow, p.ws + (size_t)qrow * (p.ws_stride / 2), nkb, true, g1, k_beg, n_kt, acc);
+    if (q0 + li >= g1) return;
+    const float rh = 1.f / (float)p.heads;
+    float* blk = p.out + p.out_off[gi];  // (read once: a load behind a store is not hoisted)
+#pragma unroll
+    for (int t = 0; t < kAwTiles; ++t)  // k: the first of the lane's 4 keys, relative to the group
+        if (t < n_kt) aw_store4(blk, q0 + li - g0, g1 - g0, k_beg + 16 * t + 4 * g - g0, acc[t] * rh);
+}
+
 // ---- attention maps at query points: K rows (mode 0, "dependency") or K columns (mode 1, "affect") of the head-averaged map P ------------
-// The visualisation reads P[q, :] or P[:, q] for a handful of tokens q per group; neither form ever builds [L, L].  Same fragment forms,
-// statistics layout and fixed head order as the full capture above.
-//   mode 0  aq_row_stats_k / aq_rows_k: the passes above with the QUERY side gathered -- work item (group, 16 gathered queries, block of
-//           kAwKeys keys); workspace row = gi * K + k (K = row stride of q_tok), (m, l) per (key block, head) as above
+// The visualisation reads P[q, :] or P[:, q] for a handful of tokens q per group; neither form ever builds [L, L].
+//   mode 0  aq_row_stats_k / aq_rows_k: aw_block_stats / aw_block_probs with the QUERY side gathered -- work item (group, 16 gathered
+//           queries, block of kAwKeys keys); workspace row = gi * K + k (K = row stride of q_tok), (m, l) per (key block, head) as above
 //   mode 1  aw_stats_k unchanged (every row's statistics), then aq_cols_k: the KEY side gathered, S = Q K^T (A = query rows, B = gathered
-//           key rows): lane (g, li) holds S[query 4g + r][gathered key li], i.e. 4 consecutive entries of column li -> one 16-byte store
+//           key rows): lane (g, li) holds S[query 4g + r][gathered key li], i.e. 4 consecutive entries of column li -> one aw_store4; the
+//           one kernel of the family with a score form of its own (its 4 rows' statistics come from aw_row_stats)
 //   aq_upsample_k: each [P_g, h, w] row -> [P_g, h scale, w scale], F.interpolate's bilinear align_corners=False arithmetic
 // A negative token gives a zero row; a token >= L_g is clamped (the host validates; a device table cannot be checked by the entry point).
 struct AqK {
@@ -344,22 +379,12 @@ __device__ __forceinline__ float* aq_block(const AqK& p, int gi, int g0) {
 
 // mode 0 work item of wave `item`: group gi, gathered queries [k0q, k0q + 16) of its kq, key block kb of nkb
 __device__ __forceinline__ bool aq_row_item(const AqK& p, int item, int& gi, int& g0, int& g1, int& k0q, int& kq, int& kb, int& nkb) {
-    for (gi = 0; gi < p.a.n_grp; ++gi) {
-        g0 = p.a.grp_off[gi];
-        g1 = p.a.grp_off[gi + 1];
-        const int len = g1 - g0;
-        kq = aq_count(p, gi);
-        if (len <= 0 || kq <= 0) continue;
-        nkb = (len + kAwKeys - 1) / kAwKeys;
-        const int nt = (kq + 15) / 16 * nkb;
-        if (item < nt) {
-            k0q = item / nkb * 16;
-            kb = item - item / nkb * nkb;
-            return 2 * p.a.heads * nkb <= p.a.ws_stride;
-        }
-        item -= nt;
-    }
-    return false;
+    const auto items = [&](int grp, int len) { return ((kq = aq_count(p, grp)) + 15) / 16 * aw_key_blocks(len); };  // (kq: of the group the walk ends at)
+    if (!aw_group(p.a, item, gi, g0, g1, items)) return false;
+    nkb = aw_key_blocks(g1 - g0);
+    k0q = item / nkb * 16;
+    kb = item - item / nkb * nkb;
+    return true;
 }
 
 template <int HB>
@@ -368,32 +393,8 @@ __global__ __launch_bounds__(256) void aq_row_stats_k(const AqK p) {
     int gi, g0, g1, k0q, kq, kb, nkb;
     if (!aq_row_item(p, blockIdx.x * 4 + (threadIdx.x >> 6), gi, g0, g1, k0q, kq, kb, nkb)) return;
     const int tok = p.q_tok[(size_t)gi * p.K + min(k0q + li, kq - 1)];
-    const int qrow = g0 + min(max(tok, 0), g1 - g0 - 1), k_beg = g0 + kb * kAwKeys, k_end = min(k_beg + kAwKeys, g1);
-    for (int head = 0; head < p.a.heads; ++head) {
-        f32x4 q[HB];
-        aw_load_q<HB>(p.a, qrow, head, g, q);
-        float m = -INFINITY, l = 0.f;
-        for (int k0 = k_beg; k0 < k_end; k0 += 16) {
-            f32x4 s = aw_scores<HB>(p.a, min(k0 + li, g1 - 1), head, g, q);
-            float mx = -INFINITY;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if (k0 + 4 * g + r >= k_end) s[r] = -INFINITY;
-                mx = fmaxf(mx, s[r]);
-            }
-            mx = fmaxf(mx, __shfl_xor(mx, 16));
-            mx = fmaxf(mx, __shfl_xor(mx, 32));
-            const float m_new = fmaxf(m, mx);  // (finite: key k0 of every tile exists)
-            float ps = 0.f;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) ps += __builtin_amdgcn_exp2f(s[r] - m_new);
-            l = l * __builtin_amdgcn_exp2f(m - m_new) + ps;
-            m = m_new;
-        }
-        l += __shfl_xor(l, 16);
-        l += __shfl_xor(l, 32);
-        if (g == 0 && k0q + li < kq) p.a.ws[((size_t)gi * p.K + k0q + li) * (p.a.ws_stride / 2) + kb * p.a.heads + head] = make_float2(m, l);
-    }
+    const int qrow = g0 + min(max(tok, 0), g1 - g0 - 1), k_beg = g0 + kb * kAwKeys;
+    aw_block_stats<HB>(p.a, li, g, qrow, g1, k_beg, min(k_beg + kAwKeys, g1), k0q + li < kq, (size_t)gi * p.K + k0q + li, kb);
 }
 
 template <int HB>
@@ -403,73 +404,24 @@ __global__ __launch_bounds__(256) void aq_rows_k(const AqK p) {
     if (!aq_row_item(p, blockIdx.x * 4 + (threadIdx.x >> 6), gi, g0, g1, k0q, kq, kb, nkb)) return;
     const int kr = min(k0q + li, kq - 1);
     const int tok = p.q_tok[(size_t)gi * p.K + kr];
-    const int qrow = g0 + min(max(tok, 0), g1 - g0 - 1), k_beg = g0 + kb * kAwKeys, k_end = min(k_beg + kAwKeys, g1);
-    const int n_kt = (k_end - k_beg + 15) / 16;
-    const float2* st = p.a.ws + ((size_t)gi * p.K + kr) * (p.a.ws_stride / 2);
-    f32x4 acc[kAwTiles];
-#pragma unroll
-    for (int t = 0; t < kAwTiles; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    for (int head = 0; head < p.a.heads; ++head) {
-        float mm = -INFINITY;
-        for (int b = 0; b < nkb; ++b) mm = fmaxf(mm, st[b * p.a.heads + head].x);
-        float ll = 0.f;
-        for (int b = 0; b < nkb; ++b) {
-            const float2 e = st[b * p.a.heads + head];
-            ll += e.y * __builtin_amdgcn_exp2f(e.x - mm);
-        }
-        const float inv = 1.f / ll;
-        f32x4 q[HB];
-        aw_load_q<HB>(p.a, qrow, head, g, q);
-#pragma unroll
-        for (int t = 0; t < kAwTiles; ++t) {
-            if (t < n_kt) {
-                const f32x4 s = aw_scores<HB>(p.a, min(k_beg + 16 * t + li, g1 - 1), head, g, q);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) acc[t][r] += __builtin_amdgcn_exp2f(s[r] - mm) * inv;
-            }
-        }
-    }
+    const int qrow = g0 + min(max(tok, 0), g1 - g0 - 1), k_beg = g0 + kb * kAwKeys, n_kt = (min(k_beg + kAwKeys, g1) - k_beg + 15) / 16;
+    f32x4 acc[kAwTiles] = {};
+    aw_block_probs<HB>(p.a, li, g, qrow, p.a.ws + ((size_t)gi * p.K + kr) * (p.a.ws_stride / 2), nkb, true, g1, k_beg, n_kt, acc);
     if (k0q + li >= kq) return;
     const float rh = tok < 0 ? 0.f : 1.f / (float)p.a.heads;  // (a skipped point: the row is written as zeros)
-    const long long len = g1 - g0;
     float* blk = aq_block(p, gi, g0);
-    float* row = blk + (long long)(k0q + li) * len;
-    const bool whole = (len & 3) == 0 && (reinterpret_cast<uintptr_t>(blk) & 15) == 0;
 #pragma unroll
-    for (int t = 0; t < kAwTiles; ++t) {
-        const int k = k_beg + 16 * t + 4 * g - g0;  // first of the lane's 4 keys, relative to the group
-        if (t >= n_kt || k >= len) continue;
-        const f32x4 v = acc[t] * rh;
-        if (whole) {
-            *reinterpret_cast<f32x4*>(row + k) = v;
-        } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if (k + r < len) row[k + r] = v[r];
-        }
-    }
+    for (int t = 0; t < kAwTiles; ++t)  // k: the first of the lane's 4 keys, relative to the group
+        if (t < n_kt) aw_store4(blk, k0q + li, g1 - g0, k_beg + 16 * t + 4 * g - g0, acc[t] * rh);
 }
 
 // mode 1, behind aw_stats_k: work item (group, 16-query tile, 16 gathered keys), one wave each
 template <int HB>
 __global__ __launch_bounds__(256) void aq_cols_k(const AqK p) {
     const int lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4;
-    int item = blockIdx.x * 4 + (threadIdx.x >> 6), gi, g0 = 0, g1 = 0, kq = 0, nkb = 0, q0 = 0, kt = 0;
-    for (gi = 0; gi < p.a.n_grp; ++gi) {
-        g0 = p.a.grp_off[gi];
-        g1 = p.a.grp_off[gi + 1];
-        kq = aq_count(p, gi);
-        if (g1 - g0 <= 0 || kq <= 0) continue;
-        nkb = (g1 - g0 + kAwKeys - 1) / kAwKeys;
-        const int nkt = (kq + 15) / 16, nt = (g1 - g0 + 15) / 16 * nkt;
-        if (item < nt) {
-            q0 = g0 + item / nkt * 16;
-            kt = item - item / nkt * nkt;
-            break;
-        }
-        item -= nt;
-    }
-    if (gi >= p.a.n_grp || 2 * p.a.heads * nkb > p.a.ws_stride) return;
+    int item = blockIdx.x * 4 + (threadIdx.x >> 6), gi, g0, g1, kq = 0;
+    if (!aw_group(p.a, item, gi, g0, g1, [&](int grp, int len) { return (len + 15) / 16 * (((kq = aq_count(p, grp)) + 15) / 16); })) return;
+    const int nkb = aw_key_blocks(g1 - g0), nkt = (kq + 15) / 16, q0 = g0 + item / nkt * 16, kt = item - item / nkt * nkt;
     const int kc = kt * 16 + li;  // the lane's column (as the B operand and as the owner of the results)
     const int tok = p.q_tok[(size_t)gi * p.K + min(kc, kq - 1)];
     const int krow = g0 + min(max(tok, 0), g1 - g0 - 1), qrow = min(q0 + li, g1 - 1);
@@ -478,18 +430,8 @@ __global__ __launch_bounds__(256) void aq_cols_k(const AqK p) {
     for (int head = 0; head < p.a.heads; ++head) {
         float mm[4], inv[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {  // the statistics of the lane's 4 query rows
-            const float2* st = p.a.ws + (size_t)min(q0 + 4 * g + r, g1 - 1) * hs2;
-            float m = -INFINITY;
-            for (int b = 0; b < nkb; ++b) m = fmaxf(m, st[b * p.a.heads + head].x);
-            float ll = 0.f;
-            for (int b = 0; b < nkb; ++b) {
-                const float2 e = st[b * p.a.heads + head];
-                ll += e.y * __builtin_amdgcn_exp2f(e.x - m);
-            }
-            mm[r] = m;
-            inv[r] = 1.f / ll;
-        }
+        for (int r = 0; r < 4; ++r)  // the statistics of the lane's 4 query rows
+            aw_row_stats(p.a.ws + (size_t)min(q0 + 4 * g + r, g1 - 1) * hs2, nkb, p.a.heads, head, mm[r], inv[r]);
         f32x4 q[HB];
         aw_load_q<HB>(p.a, qrow, head, g, q);
         const float* kp = p.a.qk + (size_t)krow * p.a.qk_cs + p.a.k_off + head * p.a.hp + 4 * g;
@@ -505,19 +447,7 @@ __global__ __launch_bounds__(256) void aq_cols_k(const AqK p) {
     }
     if (kc >= kq) return;
     const float rh = tok < 0 ? 0.f : 1.f / (float)p.a.heads;
-    const long long len = g1 - g0;
-    float* blk = aq_block(p, gi, g0);
-    float* col = blk + (long long)kc * len;  // column kc as a contiguous vector over the query rows
-    const int i = q0 - g0 + 4 * g;
-    if (i >= len) return;
-    const f32x4 v = acc * rh;
-    if ((len & 3) == 0 && (reinterpret_cast<uintptr_t>(blk) & 15) == 0) {
-        *reinterpret_cast<f32x4*>(col + i) = v;
-    } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            if (i + r < len) col[i + r] = v[r];
-    }
+    aw_store4(aq_block(p, gi, g0), kc, g1 - g0, q0 - g0 + 4 * g, acc * rh);  // column kc as a contiguous vector over the query rows
 }
 
 // blockIdx.y = group; 4 consecutive floats of its [K_g, P_g, h scale, w scale] block per thread
@@ -553,9 +483,11 @@ __global__ __launch_bounds__(256) void aq_upsample_k(const AqK p) {
 }
 
 // ---- attention per person: P reduced over the persons of an inter-human group (L_g = P_g seg tokens, person p = tokens [p seg, (p + 1) seg)) ----
-//   F[j, q] = sum_{k in j} P[q, k]          ap_affect_k, behind aw_stats_k: work item (group, 16-query tile, person j), S^T = K Q^T as above
-//   D[i, k] = (1 / seg) sum_{q in i} P[q, k]  ap_depend_k: work item (group, person i, block of kApKeys keys) over i's query tiles (a wave
-//                                             walks ALL of i's query tiles: narrower key blocks than kAwKeys keep the chip filled)
+//   F[j, q] = sum_{k in j} P[q, k]          ap_affect_k, behind aw_stats_k: work item (group, 16-query tile, person j), S^T = K Q^T as above;
+//                                             aw_row_stats, then a sum of its own over j's keys (normalised once per head)
+//   D[i, k] = (1 / seg) sum_{q in i} P[q, k]  ap_depend_k: work item (group, person i, block of kApKeys keys): aw_block_probs over ALL of i's
+//                                             query tiles into one set of accumulators (narrower key blocks than kAwKeys keep the chip
+//                                             filled), then a butterfly over the 16 query lanes
 //   R[i, j] = (1 / seg) sum_{q in i} F[j, q]  ap_relation_k: one wave per (group, i, j), read back from F
 // No [L, L] block: F and D are [P_g, L_g].  Fixed head, tile and lane orders, no atomics.  A person's end may lie inside a 16-key tile or a
 // key block: the keys (F) or queries (D) past it are masked.  A group whose length seg does not divide is skipped (the host validates).
@@ -581,31 +513,11 @@ __host__ __device__ __forceinline__ int ap_items(int pass, int len, int np) {
     return pass == 0 ? (len + 15) / 16 * np : pass == 1 ? np * ((len + kApKeys - 1) / kApKeys) : np * np;
 }
 
-// the group of wave `item` in pass `pass`: false past the last one; item becomes the index inside the group
+// the group of wave `item` in pass `pass` and its np persons: false past the last one; item becomes the index inside the group
 __device__ __forceinline__ bool ap_item(const ApK& p, int pass, int& item, int& gi, int& g0, int& g1, int& np) {
-    for (gi = 0; gi < p.a.n_grp; ++gi) {
-        g0 = p.a.grp_off[gi];
-        g1 = p.a.grp_off[gi + 1];
-        const int len = g1 - g0;
-        if (len <= 0 || len % p.seg != 0) continue;
-        np = len / p.seg;
-        const int nt = ap_items(pass, len, np);
-        if (item < nt) return 2 * p.a.heads * ((len + kAwKeys - 1) / kAwKeys) <= p.a.ws_stride;
-        item -= nt;
-    }
-    return false;
-}
-
-// (M, 1 / L) of one query row and head from its block statistics, as aw_probs_k combines them
-__device__ __forceinline__ void ap_row_stats(const float2* st, int nkb, int heads, int head, float& mm, float& inv) {
-    mm = -INFINITY;
-    for (int b = 0; b < nkb; ++b) mm = fmaxf(mm, st[b * heads + head].x);
-    float ll = 0.f;
-    for (int b = 0; b < nkb; ++b) {
-        const float2 e = st[b * heads + head];
-        ll += e.y * __builtin_amdgcn_exp2f(e.x - mm);
-    }
-    inv = 1.f / ll;
+    if (!aw_group(p.a, item, gi, g0, g1, [&](int, int len) { return len % p.seg != 0 ? 0 : ap_items(pass, len, len / p.seg); })) return false;
+    np = (g1 - g0) / p.seg;
+    return true;
 }
 
 template <int HB>
@@ -613,13 +525,13 @@ __global__ __launch_bounds__(256) void ap_affect_k(const ApK p) {
     const int lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4;
     int item = blockIdx.x * 4 + (threadIdx.x >> 6), gi, g0, g1, np;
     if (!ap_item(p, 0, item, gi, g0, g1, np)) return;
-    const int q0 = g0 + item / np * 16, j = item - item / np * np, len = g1 - g0, nkb = (len + kAwKeys - 1) / kAwKeys;
+    const int q0 = g0 + item / np * 16, j = item - item / np * np, len = g1 - g0, nkb = aw_key_blocks(len);
     const int qrow = min(q0 + li, g1 - 1), k_beg = g0 + j * p.seg, k_end = k_beg + p.seg;
     const float2* st = p.a.ws + (size_t)qrow * (p.a.ws_stride / 2);
     float acc = 0.f;
     for (int head = 0; head < p.a.heads; ++head) {
         float mm, inv;
-        ap_row_stats(st, nkb, p.a.heads, head, mm, inv);
+        aw_row_stats(st, nkb, p.a.heads, head, mm, inv);
         f32x4 q[HB];
         aw_load_q<HB>(p.a, qrow, head, g, q);
         float hsum = 0.f;
@@ -641,30 +553,13 @@ __global__ __launch_bounds__(256) void ap_depend_k(const ApK p) {
     const int lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4;
     int item = blockIdx.x * 4 + (threadIdx.x >> 6), gi, g0, g1, np;
     if (!ap_item(p, 1, item, gi, g0, g1, np)) return;
-    const int len = g1 - g0, nkb = (len + kAwKeys - 1) / kAwKeys, nb = (len + kApKeys - 1) / kApKeys, i = item / nb, kb = item - i * nb;
+    const int len = g1 - g0, nkb = aw_key_blocks(len), nb = (len + kApKeys - 1) / kApKeys, i = item / nb, kb = item - i * nb;
     const int k_beg = g0 + kb * kApKeys, k_end = min(k_beg + kApKeys, g1), n_kt = (k_end - k_beg + 15) / 16;
     const int q_beg = g0 + i * p.seg, q_end = q_beg + p.seg;
-    f32x4 acc[kApTiles];
-#pragma unroll
-    for (int t = 0; t < kApTiles; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    for (int qt = q_beg; qt < q_end; qt += 16) {
+    f32x4 acc[kApTiles] = {};
+    for (int qt = q_beg; qt < q_end; qt += 16) {  // (a query lane past the person's end adds nothing)
         const int qrow = min(qt + li, q_end - 1);
-        const float2* st = p.a.ws + (size_t)qrow * (p.a.ws_stride / 2);
-        for (int head = 0; head < p.a.heads; ++head) {
-            float mm, inv;
-            ap_row_stats(st, nkb, p.a.heads, head, mm, inv);
-            if (qt + li >= q_end) inv = 0.f;  // (a query lane past the person's end adds nothing)
-            f32x4 q[HB];
-            aw_load_q<HB>(p.a, qrow, head, g, q);
-#pragma unroll
-            for (int t = 0; t < kApTiles; ++t) {
-                if (t < n_kt) {
-                    const f32x4 s = aw_scores<HB>(p.a, min(k_beg + 16 * t + li, g1 - 1), head, g, q);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) acc[t][r] += __builtin_amdgcn_exp2f(s[r] - mm) * inv;
-                }
-            }
-        }
+        aw_block_probs<HB>(p.a, li, g, qrow, p.a.ws + (size_t)qrow * (p.a.ws_stride / 2), nkb, qt + li < q_end, g1, k_beg, n_kt, acc);
     }
     const float rs = 1.f / ((float)p.a.heads * (float)p.seg);
     float* row = ap_block(p, 1, gi, g0) + (long long)i * len;
@@ -696,6 +591,32 @@ __global__ __launch_bounds__(256) void ap_relation_k(const ApK p) {
     if (lane == 0) p.rel[p.rel_off[gi] + (long long)i * np + j] = s / (float)p.seg;
 }
 
+// ---- host side: what the entry points share ----
+#define I2R_AW_TABLE(K) {K<1>, K<2>, K<3>, K<4>, K<5>, K<6>, K<7>, K<8>, K<9>, K<10>, K<11>, K<12>, K<13>, K<14>, K<15>, K<16>}  // [hp / 16 - 1]
+
+int mh_check_heads(const char* who, int heads, int hp) {
+    I2R_CHECK_ARG(heads > 0 && hp > 0 && hp % 16 == 0 && hp <= 256, "%s: heads=%d hp=%d (hp: multiple of 16, <= 256)", who, heads, hp);
+    return I2R_OK;
+}
+
+// the fields the attention-map entry points read alike (a non-null, its own pointers checked by the caller)
+template <class A>
+int aw_check(const char* who, const A* a) {
+    if (const int e = mh_check_heads(who, a->heads, a->hp)) return e;
+    const int hs = a->heads * a->hp;
+    I2R_CHECK_ARG(a->k_off >= hs && a->k_off % 4 == 0 && a->qk_cs >= a->k_off + hs && a->qk_cs % 4 == 0, "%s: row stride qk=%d (k at %d) for %d heads x %d", who,
+                  a->qk_cs, a->k_off, a->heads, a->hp);
+    I2R_CHECK_ARG(a->n_grp > 0 && a->ws_stride >= 2 * a->heads && a->ws_stride % 2 == 0, "%s: n_grp=%d ws_stride=%d", who, a->n_grp, a->ws_stride);
+    I2R_CHECK_ARG(reinterpret_cast<uintptr_t>(a->qk) % 16 == 0 && reinterpret_cast<uintptr_t>(a->ws) % 8 == 0, "%s: alignment", who);
+    return I2R_OK;
+}
+
+template <class A>
+AwK aw_args(const A* a, float* out, const int64_t* out_off) {
+    return AwK{a->qk, out, a->grp_off, reinterpret_cast<const long long*>(out_off), reinterpret_cast<float2*>(a->ws), a->n_grp, a->heads, a->hp,
+               a->k_off, a->qk_cs, a->ws_stride};
+}
+
 }  // namespace
 
 extern "C" int i2r_rows_gather(const float* src, float* out, const int32_t* map, int32_t n_out, int32_t floats_per_crop, void* stream) {
@@ -722,7 +643,7 @@ extern "C" int i2r_view_scramble(const float* o, float* out, const int32_t* pers
 
 extern "C" int i2r_mh_attention(const i2r_mh_attn_args* a, void* stream) {
     I2R_CHECK_ARG(a && a->qk && a->v && a->out && a->grp_off, "i2r_mh_attention: null pointer");
-    I2R_CHECK_ARG(a->heads > 0 && a->hp > 0 && a->hp % 16 == 0 && a->hp <= 256, "i2r_mh_attention: heads=%d hp=%d (hp: multiple of 16, <= 256)", a->heads, a->hp);
+    if (const int e = mh_check_heads("i2r_mh_attention", a->heads, a->hp)) return e;
     const int hs = a->heads * a->hp;
     I2R_CHECK_ARG(a->k_off >= hs && a->k_off % 4 == 0 && a->qk_cs >= a->k_off + hs && a->v_cs >= hs && a->out_cs >= hs && a->qk_cs % 4 == 0 &&
                       a->v_cs % 4 == 0 && a->out_cs % 4 == 0,
@@ -758,20 +679,12 @@ extern "C" int i2r_mh_attention(const i2r_mh_attn_args* a, void* stream) {
 
 extern "C" int i2r_attn_weights(const i2r_attn_weights_args* a, void* stream) {
     I2R_CHECK_ARG(a && a->qk && a->out && a->grp_off && a->out_off && a->ws, "i2r_attn_weights: null pointer");
-    I2R_CHECK_ARG(a->heads > 0 && a->hp > 0 && a->hp % 16 == 0 && a->hp <= 256, "i2r_attn_weights: heads=%d hp=%d (hp: multiple of 16, <= 256)", a->heads, a->hp);
-    const int hs = a->heads * a->hp;
-    I2R_CHECK_ARG(a->k_off >= hs && a->k_off % 4 == 0 && a->qk_cs >= a->k_off + hs && a->qk_cs % 4 == 0,
-                  "i2r_attn_weights: row stride qk=%d (k at %d) for %d heads x %d", a->qk_cs, a->k_off, a->heads, a->hp);
-    I2R_CHECK_ARG(a->n_grp > 0 && a->n_tiles > 0 && a->ws_stride >= 2 * a->heads && a->ws_stride % 2 == 0,
-                  "i2r_attn_weights: n_grp=%d n_tiles=%d ws_stride=%d", a->n_grp, a->n_tiles, a->ws_stride);
-    I2R_CHECK_ARG(reinterpret_cast<uintptr_t>(a->qk) % 16 == 0 && reinterpret_cast<uintptr_t>(a->ws) % 8 == 0, "i2r_attn_weights: alignment");
-    AwK k{a->qk, a->out, a->grp_off, reinterpret_cast<const long long*>(a->out_off), reinterpret_cast<float2*>(a->ws), a->n_grp, a->heads, a->hp,
-          a->k_off, a->qk_cs, a->n_tiles, a->ws_stride};
+    if (const int e = aw_check("i2r_attn_weights", a)) return e;
+    I2R_CHECK_ARG(a->n_tiles > 0, "i2r_attn_weights: n_tiles=%d", a->n_tiles);
+    const AwK k = aw_args(a, a->out, a->out_off);
     typedef void (*fn_t)(const AwK);
-#define I2R_AW_TABLE(K) {K<1>, K<2>, K<3>, K<4>, K<5>, K<6>, K<7>, K<8>, K<9>, K<10>, K<11>, K<12>, K<13>, K<14>, K<15>, K<16>}
     static const fn_t stats[16] = I2R_AW_TABLE(aw_stats_k);
     static const fn_t probs[16] = I2R_AW_TABLE(aw_probs_k);
-#undef I2R_AW_TABLE
     const dim3 grid((unsigned)((a->n_tiles + 3) / 4));
     i2r_launch(stats[a->hp / 16 - 1], grid, dim3(256), 0, (hipStream_t)stream, k);
     I2R_CHECK_LAUNCH("i2r_attn_weights (statistics)");
@@ -785,14 +698,9 @@ extern "C" int i2r_attn_query_maps(const i2r_attn_query_args* a, void* stream) {
     I2R_CHECK_ARG(a->mode == 0 || a->mode == 1, "i2r_attn_query_maps: mode=%d (0: dependency rows, 1: affect columns)", a->mode);
     I2R_CHECK_ARG(a->scale >= 1 && a->scale <= 64, "i2r_attn_query_maps: scale=%d (1 .. 64)", a->scale);
     I2R_CHECK_ARG(a->K >= 1 && a->K < (1 << 20), "i2r_attn_query_maps: K=%d", a->K);
-    I2R_CHECK_ARG(a->heads > 0 && a->hp > 0 && a->hp % 16 == 0 && a->hp <= 256, "i2r_attn_query_maps: heads=%d hp=%d (hp: multiple of 16, <= 256)", a->heads, a->hp);
-    const int hs = a->heads * a->hp;
-    I2R_CHECK_ARG(a->k_off >= hs && a->k_off % 4 == 0 && a->qk_cs >= a->k_off + hs && a->qk_cs % 4 == 0,
-                  "i2r_attn_query_maps: row stride qk=%d (k at %d) for %d heads x %d", a->qk_cs, a->k_off, a->heads, a->hp);
-    I2R_CHECK_ARG(a->n_grp > 0 && a->n_grp < 65536 && a->n_tiles > 0 && a->ws_stride >= 2 * a->heads && a->ws_stride % 2 == 0 &&
-                      (a->mode == 0 || a->n_col_tiles > 0),
-                  "i2r_attn_query_maps: n_grp=%d n_tiles=%d n_col_tiles=%d ws_stride=%d", a->n_grp, a->n_tiles, a->n_col_tiles, a->ws_stride);
-    I2R_CHECK_ARG(reinterpret_cast<uintptr_t>(a->qk) % 16 == 0 && reinterpret_cast<uintptr_t>(a->ws) % 8 == 0, "i2r_attn_query_maps: alignment");
+    if (const int e = aw_check("i2r_attn_query_maps", a)) return e;
+    I2R_CHECK_ARG(a->n_grp < 65536 && a->n_tiles > 0 && (a->mode == 0 || a->n_col_tiles > 0), "i2r_attn_query_maps: n_grp=%d n_tiles=%d n_col_tiles=%d",
+                  a->n_grp, a->n_tiles, a->n_col_tiles);
     int max_len = 0;
     if (a->scale > 1) {
         I2R_CHECK_ARG(a->rows && a->grp_off_host, "i2r_attn_query_maps: null pointer (scale > 1 needs rows and grp_off_host)");
@@ -803,17 +711,13 @@ extern "C" int i2r_attn_query_maps(const i2r_attn_query_args* a, void* stream) {
             max_len = len > max_len ? len : max_len;
         }
     }
-    AqK k{{a->qk, a->out, a->grp_off, reinterpret_cast<const long long*>(a->out_off), reinterpret_cast<float2*>(a->ws), a->n_grp, a->heads, a->hp,
-           a->k_off, a->qk_cs, a->n_tiles, a->ws_stride},
-          a->q_tok, a->q_cnt, a->rows, a->K, a->scale, a->h, a->w, 0};
+    const AqK k{aw_args(a, a->out, a->out_off), a->q_tok, a->q_cnt, a->rows, a->K, a->scale, a->h, a->w, 0};
     typedef void (*aw_t)(const AwK);
     typedef void (*aq_t)(const AqK);
-#define I2R_AW_TABLE(K) {K<1>, K<2>, K<3>, K<4>, K<5>, K<6>, K<7>, K<8>, K<9>, K<10>, K<11>, K<12>, K<13>, K<14>, K<15>, K<16>}
     static const aw_t stats[16] = I2R_AW_TABLE(aw_stats_k);
     static const aq_t row_stats[16] = I2R_AW_TABLE(aq_row_stats_k);
     static const aq_t rows[16] = I2R_AW_TABLE(aq_rows_k);
     static const aq_t cols[16] = I2R_AW_TABLE(aq_cols_k);
-#undef I2R_AW_TABLE
     const int hb = a->hp / 16 - 1;
     const dim3 grid((unsigned)((a->n_tiles + 3) / 4));
     if (a->mode == 0) {
@@ -843,13 +747,8 @@ extern "C" int i2r_attn_person_maps(const i2r_attn_person_args* a, void* stream)
     I2R_CHECK_ARG(a->mode == 0 || (a->maps && a->maps_off), "i2r_attn_person_maps: null pointer (modes 1 and 2 need maps and maps_off)");
     I2R_CHECK_ARG(a->scale >= 1 && a->scale <= 64, "i2r_attn_person_maps: scale=%d (1 .. 64)", a->scale);
     I2R_CHECK_ARG(a->seg >= 1 && a->seg < (1 << 24), "i2r_attn_person_maps: seg=%d", a->seg);
-    I2R_CHECK_ARG(a->heads > 0 && a->hp > 0 && a->hp % 16 == 0 && a->hp <= 256, "i2r_attn_person_maps: heads=%d hp=%d (hp: multiple of 16, <= 256)", a->heads, a->hp);
-    const int hs = a->heads * a->hp;
-    I2R_CHECK_ARG(a->k_off >= hs && a->k_off % 4 == 0 && a->qk_cs >= a->k_off + hs && a->qk_cs % 4 == 0,
-                  "i2r_attn_person_maps: row stride qk=%d (k at %d) for %d heads x %d", a->qk_cs, a->k_off, a->heads, a->hp);
-    I2R_CHECK_ARG(a->n_grp > 0 && a->n_grp < 65536 && a->ws_stride >= 2 * a->heads && a->ws_stride % 2 == 0,
-                  "i2r_attn_person_maps: n_grp=%d ws_stride=%d", a->n_grp, a->ws_stride);
-    I2R_CHECK_ARG(reinterpret_cast<uintptr_t>(a->qk) % 16 == 0 && reinterpret_cast<uintptr_t>(a->ws) % 8 == 0, "i2r_attn_person_maps: alignment");
+    if (const int e = aw_check("i2r_attn_person_maps", a)) return e;
+    I2R_CHECK_ARG(a->n_grp < 65536, "i2r_attn_person_maps: n_grp=%d", a->n_grp);
     if (a->scale > 1)
         I2R_CHECK_ARG(a->h > 0 && a->w > 0 && (long long)a->h * a->w == a->seg, "i2r_attn_person_maps: seg=%d is not h w = %d x %d", a->seg, a->h, a->w);
     long long n_stats = 0, n_pass[3] = {0, 0, 0};
@@ -858,12 +757,12 @@ extern "C" int i2r_attn_person_maps(const i2r_attn_person_args* a, void* stream)
         const int len = a->grp_off_host[g + 1] - a->grp_off_host[g];
         I2R_CHECK_ARG(len >= 0 && len % a->seg == 0, /* (an empty group is skipped) */ "i2r_attn_person_maps: group %d has %d tokens, not a multiple of seg = %d", g, len, a->seg);
         if (len == 0) continue;
-        n_stats += (long long)((len + 15) / 16) * ((len + kAwKeys - 1) / kAwKeys);
+        n_stats += (long long)((len + 15) / 16) * aw_key_blocks(len);
         for (int pass = 0; pass < 3; ++pass) n_pass[pass] += ap_items(pass, len, len / a->seg);
         max_len = len > max_len ? len : max_len;
     }
     const int pmax = max_len / a->seg;
-    I2R_CHECK_ARG(a->ws_stride >= 2 * a->heads * ((max_len + kAwKeys - 1) / kAwKeys), "i2r_attn_person_maps: ws_stride=%d for %d heads and groups of up to %d tokens",
+    I2R_CHECK_ARG(a->ws_stride >= 2 * a->heads * aw_key_blocks(max_len), "i2r_attn_person_maps: ws_stride=%d for %d heads and groups of up to %d tokens",
                   a->ws_stride, a->heads, max_len);
     I2R_CHECK_ARG(n_stats < (1ll << 31) && n_pass[0] < (1ll << 31) && n_pass[1] < (1ll << 31) && n_pass[2] < (1ll << 31), "i2r_attn_person_maps: grid");
     const long long n4 = ((long long)pmax * max_len * a->scale * a->scale + 3) / 4;
@@ -871,16 +770,12 @@ extern "C" int i2r_attn_person_maps(const i2r_attn_person_args* a, void* stream)
     if (max_len == 0) return I2R_OK;  // (every group is empty)
     const bool up = a->mode != 0 && a->scale > 1;
     const long long total = (long long)pmax * a->grp_off_host[a->n_grp];
-    ApK k{{a->qk, a->maps, a->grp_off, reinterpret_cast<const long long*>(a->maps_off), reinterpret_cast<float2*>(a->ws), a->n_grp, a->heads, a->hp,
-           a->k_off, a->qk_cs, (int)n_stats, a->ws_stride},
-          a->rel, reinterpret_cast<const long long*>(a->rel_off), a->rows, total, a->seg, a->mode, up ? a->scale : 1, pmax};
+    const ApK k{aw_args(a, a->maps, a->maps_off), a->rel, reinterpret_cast<const long long*>(a->rel_off), a->rows, total, a->seg, a->mode, up ? a->scale : 1, pmax};
     typedef void (*aw_t)(const AwK);
     typedef void (*ap_t)(const ApK);
-#define I2R_AW_TABLE(K) {K<1>, K<2>, K<3>, K<4>, K<5>, K<6>, K<7>, K<8>, K<9>, K<10>, K<11>, K<12>, K<13>, K<14>, K<15>, K<16>}
     static const aw_t stats[16] = I2R_AW_TABLE(aw_stats_k);
     static const ap_t affect[16] = I2R_AW_TABLE(ap_affect_k);
     static const ap_t depend[16] = I2R_AW_TABLE(ap_depend_k);
-#undef I2R_AW_TABLE
     const int hb = a->hp / 16 - 1;
     const hipStream_t st = (hipStream_t)stream;
     i2r_launch(stats[hb], dim3((unsigned)((n_stats + 3) / 4)), dim3(256), 0, st, k.a);

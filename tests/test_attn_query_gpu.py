@@ -158,6 +158,50 @@ def test_raw_upsampling_matches_float64_interpolate(P, h, w, scale):
         _check_canaries(out, out_off, sizes)
 
 
+def _run_full(qk, heads, hp, k_off, qk_cs, lens, first=7, gap=5):
+    """one i2r_attn_weights call over the groups into [L, L] blocks separated by canary gaps -> (out, block offsets, block sizes)"""
+    offs = [0]
+    for n in lens:
+        offs.append(offs[-1] + n)
+    out_off, sizes, pos = [], [], first
+    for n in lens:
+        out_off.append(pos)
+        sizes.append(n * n)
+        pos += n * n + gap
+    out = torch.full((pos + 64,), CANARY, device="cuda")
+    goff = torch.tensor(offs, dtype=torch.int32, device="cuda")
+    ooff = torch.tensor(out_off, dtype=torch.int64, device="cuda")
+    stride = 2 * heads * max(-(-n // 128) for n in lens)
+    ws = torch.empty(stride * offs[-1], device="cuda")
+    a = cabi.AttnWeightsArgs(qk.data_ptr(), out.data_ptr(), goff.data_ptr(), ooff.data_ptr(), ws.data_ptr(), len(lens), heads, hp, k_off, qk_cs,
+                             sum(-(-n // 16) * -(-n // 128) for n in lens), stride)
+    cabi.check(cabi.lib().i2r_attn_weights(ctypes.byref(a), _stream()), "i2r_attn_weights")
+    torch.cuda.synchronize()
+    return out, out_off, sizes
+
+
+@pytest.mark.parametrize("heads,hp", [(1, 96), (2, 48), (8, 16)])
+def test_identity_rows_equal_the_full_capture_bitwise(heads, hp):
+    """Mode 0 with the identity token table IS the full capture: both forms run the same block statistics, combine, block probabilities
+    and store tail of csrc/i2r_encoder_mh.hip, so their blocks are torch.equal, not merely close.  Group lengths: one lane, a ragged
+    16-tile, an exact tile, a tile plus one, a second key block holding one key, three key blocks with a ragged end.  (The two outputs
+    start at 7 and at 8 floats: every block takes the other store form in the other call.)"""
+    lens = [1, 5, 16, 17, 129, 260]
+    qk, k_off, qk_cs = _make_qk(heads, hp, lens, 31 * heads + hp)
+    tab = np.zeros((len(lens), max(lens)), dtype=np.int32)
+    for gi, n in enumerate(lens):
+        tab[gi, :n] = np.arange(n)
+    got, got_off, sizes = _run_query(qk, heads, hp, k_off, qk_cs, lens, len(lens), tab, 0, counts=lens, first=7)
+    full, full_off, full_sizes = _run_full(qk, heads, hp, k_off, qk_cs, lens, first=8)
+    assert sizes == full_sizes == [n * n for n in lens]
+    _check_canaries(got, got_off, sizes)
+    _check_canaries(full, full_off, sizes)
+    for gi, n in enumerate(lens):
+        a, b = got[got_off[gi]:got_off[gi] + n * n], full[full_off[gi]:full_off[gi] + n * n]
+        assert not (b == CANARY).any(), "L=%d: an entry of the full capture was not written" % n
+        assert torch.equal(a, b), "L=%d heads=%d hp=%d: %d entries differ, max-abs %.2e" % (n, heads, hp, int((a != b).sum()), (a - b).abs().max().item())
+
+
 def test_raw_rejects_bad_arguments():
     L = cabi.lib()
     a = cabi.AttnQueryArgs()
