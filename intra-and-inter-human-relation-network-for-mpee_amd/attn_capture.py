@@ -1,0 +1,241 @@
+"""The forms of an attention-map capture (Engine.forward(..., capture=, queries=, persons=)): full [L, L] maps, their rows / columns at
+query points, their reductions per person.  A form knows its program key, the launch a captured layer emits, the layout of one call
+(plan: integers only -- sizes, offsets and tile counts as include/i2r_hip.h specifies them), the per-call fields of a launch (patch) and
+the shape of what the caller gets back.  Nothing here touches a device or the library: Program.bind_capture (engine.py) does, for all three.
+"""
+import collections
+import dataclasses
+import math
+
+import torch
+
+from . import cabi
+
+AW_KEYS = 128  # key block of the attention-map kernels (csrc/i2r_encoder_mh.hip kAwKeys)
+
+
+class AttnQueries:
+    """The query form of an attention-map capture (Engine.forward(..., capture=, queries=)).
+    tokens: {stack: int32 [groups, K]} token indices inside each group of that stack (intra-human: the crop's y * w + x; inter-human: the
+            image's (person * h + y) * w + x), -1 = skip (an all-zero row); counts: optionally {stack: entries used per group};
+    mode: 0 / "dependency" (rows: what the query token attends to) or 1 / "affect" (columns: who attends to it);
+    upsample: integer bilinear scale of the returned maps (1 = raw), or {stack: scale} when the stacks differ (each stack's down_rate);
+    capacity: the K a program is keyed by (default: the widest table) -- calls that differ only in points or grouping share a program."""
+    MODES = {"dependency": 0, "affect": 1, 0: 0, 1: 1}
+
+    def __init__(self, tokens, mode="dependency", upsample=1, counts=None, capacity=None):
+        if mode not in self.MODES:
+            raise ValueError("mode %r: 'dependency' or 'affect'" % (mode,))
+        self.tokens, self.mode, self.counts = dict(tokens), self.MODES[mode], counts
+        self.upsample = {st: int(r) for st, r in upsample.items()} if isinstance(upsample, dict) else int(upsample)
+        self.capacity = int(capacity) if capacity is not None else max(int(torch.as_tensor(t).shape[-1]) for t in self.tokens.values())
+
+
+class PersonMaps:
+    """The per-person form of an attention-map capture (Engine.forward(..., capture=, persons=)): of every captured layer of the
+    inter-human stack the relation matrix R[i, j] (how much of person i's attention lands on person j) per image, and with
+    mode: 0 / None nothing else, 1 / "dependency" the maps D[i] (where person i looks, averaged over its tokens), 2 / "affect" the maps
+    F[j] (the share of every token's attention that lands on person j); upsample: integer bilinear scale of those maps (1 = raw)."""
+    MODES = {None: 0, "dependency": 1, "affect": 2, 0: 0, 1: 1, 2: 2}
+
+    def __init__(self, mode=None, upsample=1):
+        if isinstance(mode, bool) or mode not in self.MODES:
+            raise ValueError("mode %r: None, 'dependency' or 'affect'" % (mode,))
+        self.mode, self.upsample = self.MODES[mode], int(upsample)
+        if not 1 <= self.upsample <= 64:
+            raise ValueError("upsample %r (1 .. 64)" % (upsample,))
+
+
+# One set of blocks of a layer's part of the per-call buffer: group g's block starts offs[g] floats behind the set, the set `base` floats
+# behind the layer; shapes: the view of every group's block, None for a set nobody reads (person maps in mode 0).
+Block = collections.namedtuple("Block", "offs base shapes")
+
+
+@dataclasses.dataclass
+class Plan:
+    """what one capture (the captured layers of one stack) needs for one call"""
+    n_grp: int
+    ws_stride: int     # floats per workspace row: 2 * heads * ceil(max L / 128)
+    ws_floats: int
+    rows_floats: int   # the raw rows before up-sampling / the per-person rows (0: the form has none)
+    blocks: list       # [Block]: full and query maps one set, person maps two (relations, maps)
+    layer_floats: int  # every set and every layer starts on a 16-byte boundary
+    n_tiles: int = 0
+    n_col_tiles: int = 0
+    K: int = 1
+    tables: tuple = ()  # host int32 tensors the launches read on the device (query maps: tokens [groups, K], counts [groups])
+
+
+def _layer(*sets):
+    """per block set the view shape of every group (None: a block of no floats) -> ([Block], floats per layer)"""
+    blocks, base = [], 0
+    for shapes in sets:
+        offs = [0]
+        for s in shapes:
+            offs.append(offs[-1] + (math.prod(s) if s else 0))
+        blocks.append(Block(offs, base, shapes if shapes[0] else None))
+        base += -(-offs[-1] // 4) * 4
+    return blocks, base
+
+
+def _stride(heads, lens):
+    return 2 * heads * -(-max(lens) // AW_KEYS)
+
+
+def _tiles(rows, keys, key_tile=AW_KEYS):
+    """one wave per (16-row tile, key block) of every group"""
+    return sum(-(-r // 16) * -(-k // key_tile) for r, k in zip(rows, keys))
+
+
+class Form:
+    """what the three forms share; a form is made per call (resolve), and a program keeps the one it was built with"""
+    N_BLOCKS = 1  # block sets per layer = device offset tables per capture
+    call = None   # what bind_capture hands to plan() per call
+
+    def __init__(self, capture, suffix=()):
+        self.capture, self.key = capture, ("capture", capture) + suffix  # (key: the part of the program key behind the shape)
+
+    share = staticmethod(lambda plans: None)  # what the plans of all captures of a call must agree on, once they are made: nothing
+
+    @staticmethod
+    def result(views, inputs):
+        """views: per block set {(stack, layer): per group a view}; inputs(): {(stack, "input"): features} -> what the caller gets"""
+        return {**views[0], **inputs()}
+
+
+class FullForm(Form):
+    """[L, L] maps (i2r_attn_weights)"""
+
+    def launch(self, cap, qk, L, goff):
+        """-> (op kind, args) of one captured layer: cap the capture record, qk its q|k activation, L its pack; patch() fills in the rest"""
+        return cabi.CAPTURE_OP_ATTN_WEIGHTS, cabi.AttnWeightsArgs(qk.ptr, 0, goff.data_ptr(), cap["off"][0].data_ptr(), 0, 0, L["heads"], L["hp"],
+                                                                  L["hs"], qk.cs, 0, 0)
+
+    def plan(self, stack, hw, lens, heads, call=None):
+        """hw: the stack's token map (h, w); lens: tokens of every group to compute; heads: the widest head count among the launches"""
+        blocks, n_layer = _layer([(n, n) for n in lens])
+        stride = _stride(heads, lens)
+        return Plan(len(lens), stride, stride * sum(lens), 0, blocks, n_layer, n_tiles=_tiles(lens, lens))
+
+    @staticmethod
+    def share(plans):
+        """the i2r_attn_weights launches of all captures read ONE stride, the widest, and the workspace has the most rows of any at it"""
+        stride, rows = max(p.ws_stride for p in plans), max(p.ws_floats // p.ws_stride for p in plans)
+        for p in plans:
+            p.ws_stride, p.ws_floats = stride, rows * stride
+
+    @staticmethod
+    def patch(a, p, out, ws, rows, tables, host_off):
+        """the per-call fields of a launch: p its capture's plan, out its layer in the buffer, ws / rows / p.tables on the device, the host's group offsets"""
+        a.out, a.ws = out, ws
+        a.n_grp, a.n_tiles, a.ws_stride = p.n_grp, p.n_tiles, p.ws_stride
+
+
+class QueryForm(Form):
+    """rows (mode 0) / columns (mode 1) of the maps at query points, up-sampled by the stack's scale (i2r_attn_query_maps): no [L, L]
+    block exists, the workspaces are O(K L)"""
+
+    def __init__(self, capture, queries):
+        mode, stacks = int(queries.mode), sorted({st for st, _ in capture})
+        missing = set(stacks) - set(queries.tokens)
+        if missing:
+            raise ValueError("queries.tokens has no table for %s" % sorted(missing))
+        up = queries.upsample
+        try:
+            scales = tuple((st, int(up[st] if isinstance(up, dict) else up)) for st in stacks)
+        except KeyError as e:
+            raise ValueError("queries.upsample has no scale for stack %s" % e)
+        if mode not in (0, 1) or not all(1 <= r <= 64 for _, r in scales):
+            raise ValueError("queries: mode %r (0 dependency, 1 affect), upsample %r (1 .. 64)" % (queries.mode, up))
+        Form.__init__(self, capture, ("query", mode, int(queries.capacity), scales))
+        self.call, self.mode, self.scales = queries, mode, dict(scales)
+
+    def launch(self, cap, qk, L, goff):
+        return cabi.CAPTURE_OP_ATTN_QUERY, cabi.AttnQueryArgs(
+            qk=qk.ptr, grp_off=goff.data_ptr(), out_off=cap["off"][0].data_ptr(), heads=L["heads"], hp=L["hp"], k_off=L["hs"], qk_cs=qk.cs,
+            mode=self.mode, K=1, scale=self.scales[cap["stack"]], h=cap["x"].h, w=cap["x"].w)
+
+    def plan(self, stack, hw, lens, heads, call=None):
+        """call: the AttnQueries of this call -- tokens[stack] int32 [groups, K] (-1 = skip), optionally counts[stack] (entries per group)"""
+        mode, scale, (h, w) = self.mode, self.scales[stack], hw
+        tok = torch.as_tensor(call.tokens[stack]).to("cpu", torch.int32).contiguous()
+        if tok.dim() != 2 or tok.shape[0] != len(lens) or tok.shape[1] < 1:
+            raise ValueError("query tokens of %r: shape %s, expected [%d groups, K]" % (stack, tuple(tok.shape), len(lens)))
+        K = tok.shape[1]
+        cnt = getattr(call, "counts", None)
+        cnt = [int(c) for c in cnt[stack]] if cnt and cnt.get(stack) is not None else [K] * len(lens)
+        if len(cnt) != len(lens) or not all(1 <= c <= K for c in cnt):
+            raise ValueError("query counts of %r: %s for %d groups of up to %d entries" % (stack, cnt, len(lens), K))
+        for g, (n, c) in enumerate(zip(lens, cnt)):
+            if int(tok[g, :c].max()) >= n:
+                raise ValueError("query token %d of group %d of %r is outside its %d tokens" % (int(tok[g, :c].max()), g, stack, n))
+        assert all(n % (h * w) == 0 for n in lens)
+        blocks, n_layer = _layer([(c, n // (h * w), h * scale, w * scale) for n, c in zip(lens, cnt)])
+        stride = _stride(heads, lens)
+        tiles = (_tiles(cnt, lens), 0) if mode == 0 else (_tiles(lens, lens), _tiles(lens, cnt, 16))
+        return Plan(len(lens), stride, stride * (len(lens) * K if mode == 0 else sum(lens)), K * sum(lens) if scale > 1 else 1, blocks, n_layer,
+                    *tiles, K=K, tables=(tok, torch.tensor(cnt, dtype=torch.int32)))
+
+    @staticmethod
+    def patch(a, p, out, ws, rows, tables, host_off):
+        a.out, a.ws, a.rows, (a.q_tok, a.q_cnt), a.grp_off_host = out, ws, rows, tables, host_off
+        a.n_grp, a.n_tiles, a.n_col_tiles, a.ws_stride, a.K = p.n_grp, p.n_tiles, p.n_col_tiles, p.ws_stride, p.K
+
+
+class PersonForm(Form):
+    """the maps reduced per person (i2r_attn_person_maps): every group is an image of P_g persons of h w tokens; per layer the [P, P]
+    relation blocks, then (mode 1: dependency, 2: affect) the [P, P, h r, w r] map blocks.  The workspaces are O(P L)."""
+    N_BLOCKS = 2
+
+    def __init__(self, capture, persons):
+        self.mode, self.scale = int(persons.mode), int(persons.upsample)
+        Form.__init__(self, capture, ("persons", self.mode, self.scale))
+
+    def launch(self, cap, qk, L, goff):
+        rel_off, maps_off = cap["off"]
+        return cabi.CAPTURE_OP_ATTN_PERSON, cabi.AttnPersonArgs(
+            qk=qk.ptr, grp_off=goff.data_ptr(), rel_off=rel_off.data_ptr(), maps_off=maps_off.data_ptr(), heads=L["heads"], hp=L["hp"],
+            k_off=L["hs"], qk_cs=qk.cs, seg=cap["x"].h * cap["x"].w, mode=self.mode, scale=self.scale, h=cap["x"].h, w=cap["x"].w)
+
+    def plan(self, stack, hw, lens, heads, call=None):
+        mode, scale, (h, w) = self.mode, self.scale, hw
+        assert all(n % (h * w) == 0 for n in lens)
+        pers = [n // (h * w) for n in lens]
+        blocks, n_layer = _layer([(p, p) for p in pers], [(p, p, h * scale, w * scale) if mode else None for p in pers])
+        stride = _stride(heads, lens)
+        return Plan(len(lens), stride, stride * sum(lens), (2 if mode == 1 and scale > 1 else 1) * max(pers) * sum(lens), blocks, n_layer)
+
+    @staticmethod
+    def patch(a, p, out, ws, rows, tables, host_off):
+        a.rel, a.maps, a.ws, a.rows, a.grp_off_host = out, out + 4 * p.blocks[1].base, ws, rows, host_off
+        a.n_grp, a.ws_stride = p.n_grp, p.ws_stride
+
+    @staticmethod
+    def result(views, inputs):
+        return tuple(views)  # (relation, maps)
+
+
+def resolve(capture, queries, persons, flip_joint_map, stacks, inter_stack, window):
+    """What Engine.forward / forward_single were asked for -> the form of the call, None without a capture.  stacks: the engine's
+    capture_stacks(); inter_stack: the prefix of its inter-human stack; window: the inter-human block is the window type."""
+    if persons is not None:
+        if window:
+            raise ValueError("persons=: ATTENTION_TYPE window has no encoder stack to capture")
+        if flip_joint_map is not None or queries is not None:
+            raise ValueError("persons=: not with the flip test, not with queries=")
+        if not capture:
+            raise ValueError("persons= needs capture=: the (stack, layer) set of the inter-human stack to reduce")
+        other = sorted({str(st) for st, _ in capture} - {inter_stack})
+        if other or inter_stack not in stacks:
+            raise ValueError("persons=: %s is not this model's inter-human stack %r (an intra-human stack has one person per group)"
+                             % (other or "a capture", inter_stack if inter_stack in stacks else None))
+    if not capture:
+        if queries is not None:
+            raise ValueError("queries= needs capture=: the (stack, layer) set whose maps to query")
+        return None
+    capture = frozenset((str(st), int(i)) for st, i in capture)
+    for st, i in capture:
+        if st not in stacks or not 0 <= i < stacks[st]:
+            raise ValueError("capture (%r, %d): this model's encoder stacks are %s" % (st, i, stacks))
+    assert flip_joint_map is None and not window, "attention maps: no flip test, no window-type block"
+    return PersonForm(capture, persons) if persons is not None else QueryForm(capture, queries) if queries is not None else FullForm(capture)

@@ -10,7 +10,8 @@ import os
 
 import torch
 
-from . import cabi
+from . import attn_capture, cabi
+from .attn_capture import AttnQueries, PersonMaps  # noqa: F401 (the capture forms' public classes stay importable from here)
 from .pack import (PRECISIONS, PackedConv, Packer, _m16, _r16, fold_bn, pack_frag, pack_frag32, pack_k4, pack_k8,  # noqa: F401 (the packing names stay importable from here)
                    winograd_weights)
 
@@ -180,8 +181,7 @@ class Program:
         self.enc_stacks = []
         self.split_counters = []  # hand-off counters of the encoder stacks (zero between launches; re-zeroed when a run fails)
         self.captures = []   # encoder stacks whose attention maps this program computes (_capture_begin)
-        self.query = None    # (mode, {stack: scale}): the captured layers emit i2r_attn_query_maps instead of i2r_attn_weights (set_query_capture)
-        self.persons = None  # (mode, scale): the captured layers emit i2r_attn_person_maps instead (set_person_capture)
+        self.form = None     # the capture form the program was built with (attn_capture): the launch its captured layers emit, the layout of a call
         self.store_dt = 0    # storage type the conv TOWER keeps its maps in (set by the engine in the 16-bit modes: 1 bf16, 2 f16)
         self.in_fork = False
         self.nbytes = 0
@@ -194,7 +194,7 @@ class Program:
         self._flags = None      # flag buffer of the device-side sync form (_lane_flags)
         self._events = None     # the program's own fork / join / record events (_own_events)
         self._tev = None        # timing events of _run_timed
-        self._capture_ws = None  # per-call workspaces of set_capture / set_query_capture, held until the next call
+        self._capture_ws = None  # per-call tensors of bind_capture, held until the next call
 
     # ---- buffers ----
     def alloc(self, n, h, w, c, dt=0):
@@ -665,7 +665,7 @@ class Program:
         regroupable: the grouping (persons per image) may be changed later with set_groups() without rebuilding the program:
         the offset table gets capacity for one group per crop.
         capture: dict(stack=state-dict prefix, layers={i: fp32 Packer.encoder_layer_mh pack of layer i}) -- the attention maps of those
-        layers are computed too (i2r_attn_weights, emitted before the layer's input is released); see set_capture."""
+        layers are computed too (the launch of the program's capture form, emitted before the layer's input is released); see bind_capture."""
         assert x.dt == 0, "the encoder kernels read fp32 token rows"
         if layers and layers[0].get("mh"):
             return self.encoder_mh(x, layers, grp_off_host, pos=pos, pos_period=pos_period, lane=lane, regroupable=regroupable, pre_norm=pre_norm,
@@ -799,196 +799,56 @@ class Program:
         return _RawAct(pos, x)
 
     # ---- attention maps (capture programs) ----
-    # A capture program computes, next to its usual outputs, the head-averaged attention maps of the requested encoder layers
-    # (i2r_attn_weights) into ONE per-call buffer.  The launch list is fixed at build time; set_capture() patches the per-call part --
-    # output pointer, workspace, group count, tile count -- and uploads the group offsets of the blocks, like set_groups() does.
+    # A capture program computes, next to its usual outputs, the attention maps of the requested encoder layers in the form it was built
+    # with (attn_capture: full [L, L] maps, rows / columns at query points, reductions per person) into ONE per-call buffer.  The launch list
+    # is fixed at build time; bind_capture() patches the per-call part and uploads the offsets of the groups' blocks, like set_groups() does.
     def _capture_begin(self, capture, x):
         if not capture:
             return None
-        cap = dict(stack=capture["stack"], x=x, ops=[], out_off=torch.zeros(x.n, dtype=torch.int64, device=self.device))
-        self.keep.append(cap["out_off"])
+        cap = dict(stack=capture["stack"], x=x, ops=[], off=[torch.zeros(x.n, dtype=torch.int64, device=self.device) for _ in range(self.form.N_BLOCKS)])
+        self.keep += cap["off"]
         self.captures.append(cap)
         return cap
 
     def _capture_layer(self, cap, i, qk, L, goff, lane):
         assert qk.dt == 0 and qk.cs >= 2 * L["hs"]
         self.keep.append(L)
-        if self.query is not None:  # rows / columns at query points: tokens, counts, workspaces and outputs are patched per call
-            mode, scale = self.query[0], self.query[1][cap["stack"]]
-            a = cabi.AttnQueryArgs(qk=qk.ptr, grp_off=goff.data_ptr(), out_off=cap["out_off"].data_ptr(), heads=L["heads"], hp=L["hp"], k_off=L["hs"],
-                                   qk_cs=qk.cs, mode=mode, K=1, scale=scale, h=cap["x"].h, w=cap["x"].w)
-            self.ops.append((cabi.CAPTURE_OP_ATTN_QUERY, lane, a))
-            cap["ops"].append((i, a))
-            return
-        if self.persons is not None:  # relation matrices and per-person maps: outputs, workspaces and the host group table are patched per call
-            mode, scale = self.persons
-            if "rel_off" not in cap:
-                cap["rel_off"] = torch.zeros_like(cap["out_off"])
-                self.keep.append(cap["rel_off"])
-            a = cabi.AttnPersonArgs(qk=qk.ptr, grp_off=goff.data_ptr(), rel_off=cap["rel_off"].data_ptr(), maps_off=cap["out_off"].data_ptr(),
-                                    heads=L["heads"], hp=L["hp"], k_off=L["hs"], qk_cs=qk.cs, seg=cap["x"].h * cap["x"].w, mode=mode, scale=scale,
-                                    h=cap["x"].h, w=cap["x"].w)
-            self.ops.append((cabi.CAPTURE_OP_ATTN_PERSON, lane, a))
-            cap["ops"].append((i, a))
-            return
-        a = cabi.AttnWeightsArgs(qk.ptr, 0, goff.data_ptr(), cap["out_off"].data_ptr(), 0, 0, L["heads"], L["hp"], L["hs"], qk.cs, 0, 0)
-        self.ops.append((cabi.CAPTURE_OP_ATTN_WEIGHTS, lane, a))
+        kind, a = self.form.launch(cap, qk, L, goff)
+        self.ops.append((kind, lane, a))
         cap["ops"].append((i, a))
 
-    AW_KEYS = 128  # key block of i2r_attn_weights (csrc/i2r_encoder_mh.hip kAwKeys)
-
-    # The front that set_capture and set_query_capture share, per capture: the groups asked for are checked against the stack's current
-    # grouping, every group's block gets its offset inside a layer's part of the output buffer, and those offsets go to the device.
-    @staticmethod
-    def _capture_groups(cap, lens):
-        """lens must be the first groups of the stack as it is grouped now -> the widest head count among the capture's launches"""
-        cur = cap["grouping"]["current"]
-        assert len(lens) >= 1 and list(lens) == [cur[g + 1] - cur[g] for g in range(len(lens))]
-        return max(a.heads for _, a in cap["ops"]) if cap["ops"] else 1
-
-    @staticmethod
-    def _capture_blocks(sizes):
-        """floats of every group's block -> (block offsets inside a layer [groups + 1], floats per layer: layer blocks start on 16-byte boundaries)"""
-        offs = [0]
-        for n in sizes:
-            offs.append(offs[-1] + n)
-        return offs, -(-offs[-1] // 4) * 4
-
-    @staticmethod
-    def _upload_out_off(cap, offs):
-        cap["out_off"][:len(offs) - 1].copy_(torch.tensor(offs[:-1], dtype=torch.int64).pin_memory(), non_blocking=True)
-
-    def set_capture(self, glens):
+    def bind_capture(self, glens, call=None):
         """glens: per capture (program order) the token count of every group to compute (the real images / crops of this call, a prefix of
-        the stack's groups).  -> (buffer, {(stack, layer): [L_g x L_g views]}, {stack: input Act})."""
-        sizes, per_layer, need_ws, rows = [], [], 2, 0
-        for cap, lens in zip(self.captures, glens):
-            heads = self._capture_groups(cap, lens)
-            need_ws = max(need_ws, 2 * heads * -(-max(lens) // self.AW_KEYS))
-            rows = max(rows, sum(lens))
-            offs, n_layer = self._capture_blocks([n * n for n in lens])
-            sizes.append(offs)
-            per_layer.append(n_layer)
-        total = sum(n * len(cap["ops"]) for n, cap in zip(per_layer, self.captures))
-        buf = torch.empty(max(total, 1), dtype=torch.float32, device=self.device)
-        ws = torch.empty(rows * need_ws, dtype=torch.float32, device=self.device)
-        self._capture_ws = ws  # (kept until the next call: the launches read it asynchronously; torch's allocator orders reuse by stream)
-        maps, base = {}, 0
-        for cap, lens, offs, n_layer in zip(self.captures, glens, sizes, per_layer):
-            self._upload_out_off(cap, offs)
-            tiles = sum(-(-n // 16) * -(-n // self.AW_KEYS) for n in lens)
-            for i, a in cap["ops"]:
-                a.out, a.ws = buf.data_ptr() + 4 * base, ws.data_ptr()
-                a.n_grp, a.n_tiles, a.ws_stride = len(lens), tiles, need_ws
-                maps[(cap["stack"], i)] = [buf[base + o:base + o + n * n].view(n, n) for o, n in zip(offs, lens)]
-                base += n_layer
-        return buf, maps, {cap["stack"]: cap["x"] for cap in self.captures}
-
-    def set_query_capture(self, glens, queries):
-        """The query form of set_capture (a program built with `query`): per capture the token table queries.tokens[stack] (int32
-        [groups, K], -1 = skip) and optionally queries.counts[stack] (entries used per group).  -> (buffer, {(stack, layer): per group a
-        [K_g, P_g, h r, w r] view}, {stack: input Act}), r the stack's scale; the buffer holds exactly sum over layers and groups of K_g L_g r^2 floats (+ at most
-        3 floats between layers whose size is no multiple of 4).  No [L, L] block exists: the workspaces are O(K L)."""
-        mode, scales = self.query
-        plan, per_layer, n_ws, n_rows = [], [], 2, 1
-        for cap, lens in zip(self.captures, glens):
-            scale = scales[cap["stack"]]
-            heads = self._capture_groups(cap, lens)
-            tok = torch.as_tensor(queries.tokens[cap["stack"]]).to("cpu", torch.int32).contiguous()
-            if tok.dim() != 2 or tok.shape[0] != len(lens) or tok.shape[1] < 1:
-                raise ValueError("query tokens of %r: shape %s, expected [%d groups, K]" % (cap["stack"], tuple(tok.shape), len(lens)))
-            K = tok.shape[1]
-            cnt = getattr(queries, "counts", None)
-            cnt = [int(c) for c in cnt[cap["stack"]]] if cnt and cnt.get(cap["stack"]) is not None else [K] * len(lens)
-            if len(cnt) != len(lens) or not all(1 <= c <= K for c in cnt):
-                raise ValueError("query counts of %r: %s for %d groups of up to %d entries" % (cap["stack"], cnt, len(lens), K))
-            for g, (n, c) in enumerate(zip(lens, cnt)):
-                if int(tok[g, :c].max()) >= n:
-                    raise ValueError("query token %d of group %d of %r is outside its %d tokens" % (int(tok[g, :c].max()), g, cap["stack"], n))
-            hw = cap["x"].h * cap["x"].w
-            assert all(n % hw == 0 for n in lens)
-            stride = 2 * heads * -(-max(lens) // self.AW_KEYS)
-            n_ws = max(n_ws, stride * (len(lens) * K if mode == 0 else sum(lens)))
-            if scale > 1:
-                n_rows = max(n_rows, K * sum(lens))
-            offs, n_layer = self._capture_blocks([c * n * scale * scale for n, c in zip(lens, cnt)])
-            plan.append((tok, cnt, K, stride, offs, scale))
-            per_layer.append(n_layer)
-        starts, base = [], 0
-        for n, cap in zip(per_layer, self.captures):
-            starts.append([base + j * n for j in range(len(cap["ops"]))])
-            base += n * len(cap["ops"])
-        total = max((st[-1] + p[4][-1] for st, p in zip(starts, plan) if st), default=1)
-        buf = torch.empty(total, dtype=torch.float32, device=self.device)
-        ws = torch.empty(n_ws, dtype=torch.float32, device=self.device)
-        rows = torch.empty(n_rows, dtype=torch.float32, device=self.device)
-        held = [ws, rows]  # (kept until the next call: the launches read them asynchronously; torch's allocator orders reuse by stream)
-        maps = {}
-        for cap, lens, (tok, cnt, K, stride, offs, scale), st in zip(self.captures, glens, plan, starts):
-            self._upload_out_off(cap, offs)
-            d_tok = tok.pin_memory().to(self.device, non_blocking=True)
-            d_cnt = torch.tensor(cnt, dtype=torch.int32).pin_memory().to(self.device, non_blocking=True)
+        the stack's groups); call: the per-call data of the form (AttnQueries: token tables and counts).  -> per block set of the form
+        {(stack, layer): per group a view}, all views of one buffer: capture after capture, layer after layer, each as the form's plan
+        lays it out."""
+        form, plans = self.form, []
+        for cap, lens in zip(self.captures, glens):  # the groups asked for are the first groups of the stack as it is grouped now
             cur = cap["grouping"]["current"]
-            host_off = (C.c_int32 * (len(lens) + 1))(*cur[:len(lens) + 1])
-            held += [d_tok, d_cnt, host_off]
-            h, w = cap["x"].h, cap["x"].w
-            if mode == 0:
-                tiles, col_tiles = sum(-(-c // 16) * -(-n // self.AW_KEYS) for n, c in zip(lens, cnt)), 0
-            else:
-                tiles = sum(-(-n // 16) * -(-n // self.AW_KEYS) for n in lens)
-                col_tiles = sum(-(-n // 16) * -(-c // 16) for n, c in zip(lens, cnt))
-            for (i, a), b0 in zip(cap["ops"], st):
-                a.out, a.ws, a.rows = buf.data_ptr() + 4 * b0, ws.data_ptr(), rows.data_ptr()
-                a.q_tok, a.q_cnt, a.grp_off_host = d_tok.data_ptr(), d_cnt.data_ptr(), C.cast(host_off, C.c_void_p)
-                a.n_grp, a.n_tiles, a.n_col_tiles, a.ws_stride, a.K = len(lens), tiles, col_tiles, stride, K
-                maps[(cap["stack"], i)] = [buf[b0 + o:b0 + o + c * n * scale * scale].view(c, n // (h * w), h * scale, w * scale)
-                                           for o, n, c in zip(offs, lens, cnt)]
-        self._capture_ws = held
-        return buf, maps, {cap["stack"]: cap["x"] for cap in self.captures}
-
-    def set_person_capture(self, glens):
-        """The per-person form of set_capture (a program built with `persons`): every group is an image of P_g persons of h w tokens.
-        -> (buffer, {(stack, layer): per group a [P_g, P_g] relation matrix}, {(stack, layer): per group a [P_g, P_g, h r, w r] view, mode 0:
-        nothing}, {stack: input Act}), all views of the one buffer: per layer the relation blocks, then the map blocks.  No [L, L] block
-        exists: the workspaces are O(P L)."""
-        mode, scale = self.persons
-        plan, per_layer, n_ws, n_rows = [], [], 2, 1
-        for cap, lens in zip(self.captures, glens):
-            heads = self._capture_groups(cap, lens)
-            hw = cap["x"].h * cap["x"].w
-            assert all(n % hw == 0 for n in lens)
-            pers = [n // hw for n in lens]
-            stride = 2 * heads * -(-max(lens) // self.AW_KEYS)
-            n_ws = max(n_ws, stride * sum(lens))
-            n_rows = max(n_rows, (2 if mode == 1 and scale > 1 else 1) * max(pers) * sum(lens))
-            r_offs, n_rel = self._capture_blocks([p * p for p in pers])
-            m_offs, n_maps = self._capture_blocks([p * n * scale * scale if mode else 0 for p, n in zip(pers, lens)])
-            plan.append((pers, stride, r_offs, m_offs, n_rel))
-            per_layer.append(n_rel + n_maps)
-        total = sum(n * len(cap["ops"]) for n, cap in zip(per_layer, self.captures))
-        buf = torch.empty(max(total, 1), dtype=torch.float32, device=self.device)
-        ws = torch.empty(n_ws, dtype=torch.float32, device=self.device)
-        rows = torch.empty(n_rows, dtype=torch.float32, device=self.device)
+            assert len(lens) >= 1 and list(lens) == [cur[g + 1] - cur[g] for g in range(len(lens))]
+            plans.append(form.plan(cap["stack"], (cap["x"].h, cap["x"].w), lens, max(a.heads for _, a in cap["ops"]), call))
+        form.share(plans)
+        buf = torch.empty(sum(p.layer_floats * len(cap["ops"]) for p, cap in zip(plans, self.captures)), dtype=torch.float32, device=self.device)
+        ws = torch.empty(max(p.ws_floats for p in plans), dtype=torch.float32, device=self.device)
+        rows = torch.empty(max(p.rows_floats for p in plans), dtype=torch.float32, device=self.device)
         held = [ws, rows]  # (kept until the next call: the launches read them asynchronously; torch's allocator orders reuse by stream)
-        rel, maps, base = {}, {}, 0
-        for cap, lens, (pers, stride, r_offs, m_offs, n_rel), n_layer in zip(self.captures, glens, plan, per_layer):
-            self._upload_out_off(cap, m_offs)
-            cap["rel_off"][:len(pers)].copy_(torch.tensor(r_offs[:-1], dtype=torch.int64).pin_memory(), non_blocking=True)
-            cur = cap["grouping"]["current"]
-            host_off = (C.c_int32 * (len(lens) + 1))(*cur[:len(lens) + 1])
-            held.append(host_off)
-            h, w = cap["x"].h, cap["x"].w
+        views, base = [{} for _ in range(form.N_BLOCKS)], 0
+        for cap, lens, p in zip(self.captures, glens, plans):
+            for off, blk in zip(cap["off"], p.blocks):
+                off[:len(lens)].copy_(torch.tensor(blk.offs[:-1], dtype=torch.int64).pin_memory(), non_blocking=True)
+            tables = [t.pin_memory().to(self.device, non_blocking=True) for t in p.tables]
+            host_off = (C.c_int32 * (len(lens) + 1))(*cap["grouping"]["current"][:len(lens) + 1])  # (the query and person launches read it)
+            held += tables + [host_off]
+            ptrs = (ws.data_ptr(), rows.data_ptr(), [t.data_ptr() for t in tables], C.cast(host_off, C.c_void_p))
             for i, a in cap["ops"]:
-                a.rel, a.maps = buf.data_ptr() + 4 * base, buf.data_ptr() + 4 * (base + n_rel)
-                a.ws, a.rows, a.grp_off_host = ws.data_ptr(), rows.data_ptr(), C.cast(host_off, C.c_void_p)
-                a.n_grp, a.ws_stride = len(lens), stride
-                rel[(cap["stack"], i)] = [buf[base + o:base + o + p * p].view(p, p) for o, p in zip(r_offs, pers)]
-                if mode:
-                    maps[(cap["stack"], i)] = [buf[base + n_rel + o:base + n_rel + o + p * n * scale * scale].view(p, p, h * scale, w * scale)
-                                               for o, p, n in zip(m_offs, pers, lens)]
-                base += n_layer
+                form.patch(a, p, buf.data_ptr() + 4 * base, *ptrs)
+                for out, blk in zip(views, p.blocks):
+                    if blk.shapes:
+                        b = base + blk.base
+                        out[(cap["stack"], i)] = [buf[b + o:b + e].view(s) for o, e, s in zip(blk.offs, blk.offs[1:], blk.shapes)]
+                base += p.layer_floats
         self._capture_ws = held
-        return buf, rel, maps, {cap["stack"]: cap["x"] for cap in self.captures}
+        return views
 
     def set_groups(self, grouping, grp_off_host):
         """(Re)define the token groups of an encoder stack: uploads the offset table and patches the per-layer descriptors."""
@@ -1732,38 +1592,6 @@ def lane_report(device):
             "profiler_attached": PROFILER_ATTACHED}
 
 
-class AttnQueries:
-    """The query form of an attention-map capture (Engine.forward(..., capture=, queries=)).
-    tokens: {stack: int32 [groups, K]} token indices inside each group of that stack (intra-human: the crop's y * w + x; inter-human: the
-            image's (person * h + y) * w + x), -1 = skip (an all-zero row); counts: optionally {stack: entries used per group};
-    mode: 0 / "dependency" (rows: what the query token attends to) or 1 / "affect" (columns: who attends to it);
-    upsample: integer bilinear scale of the returned maps (1 = raw), or {stack: scale} when the stacks differ (each stack's down_rate);
-    capacity: the K a program is keyed by (default: the widest table) -- calls that differ only in points or grouping share a program."""
-    MODES = {"dependency": 0, "affect": 1, 0: 0, 1: 1}
-
-    def __init__(self, tokens, mode="dependency", upsample=1, counts=None, capacity=None):
-        if mode not in self.MODES:
-            raise ValueError("mode %r: 'dependency' or 'affect'" % (mode,))
-        self.tokens, self.mode, self.counts = dict(tokens), self.MODES[mode], counts
-        self.upsample = {st: int(r) for st, r in upsample.items()} if isinstance(upsample, dict) else int(upsample)
-        self.capacity = int(capacity) if capacity is not None else max(int(torch.as_tensor(t).shape[-1]) for t in self.tokens.values())
-
-
-class PersonMaps:
-    """The per-person form of an attention-map capture (Engine.forward(..., capture=, persons=)): of every captured layer of the
-    inter-human stack the relation matrix R[i, j] (how much of person i's attention lands on person j) per image, and with
-    mode: 0 / None nothing else, 1 / "dependency" the maps D[i] (where person i looks, averaged over its tokens), 2 / "affect" the maps
-    F[j] (the share of every token's attention that lands on person j); upsample: integer bilinear scale of those maps (1 = raw)."""
-    MODES = {None: 0, "dependency": 1, "affect": 2, 0: 0, 1: 1, 2: 2}
-
-    def __init__(self, mode=None, upsample=1):
-        if isinstance(mode, bool) or mode not in self.MODES:
-            raise ValueError("mode %r: None, 'dependency' or 'affect'" % (mode,))
-        self.mode, self.upsample = self.MODES[mode], int(upsample)
-        if not 1 <= self.upsample <= 64:
-            raise ValueError("upsample %r (1 .. 64)" % (upsample,))
-
-
 def _multi(y):
     """the 'multi' heat maps of what a forward returned (a dict where the model supervises its first stage too)"""
     return y["multi"] if isinstance(y, dict) else y
@@ -1938,14 +1766,6 @@ class Engine:
             packs[i] = L
         return dict(stack=stack, layers=packs)
 
-    def _check_capture(self, capture):
-        stacks = self.capture_stacks()
-        capture = frozenset((str(st), int(i)) for st, i in capture)
-        for st, i in capture:
-            if st not in stacks or not 0 <= i < stacks[st]:
-                raise ValueError("capture (%r, %d): this model's encoder stacks are %s" % (st, i, stacks))
-        return capture
-
     def _pack_single(self, pk, sf, p):
         """first (intra-human) stage under key prefix p: transpose_h.TransPoseH (:418-480) or hrformer.HRFormer (:2470-2476)"""
         M = self.cfg["MODEL"]
@@ -1964,7 +1784,7 @@ class Engine:
             self.tower = HRFormerB(pk, p)
             self.single_head = pk.head(p + "keypoint_head.final_layer")
 
-    def _emit_single(self, P, S, H, W, n_src, capture=()):  # (a query capture: P.query is set by the caller)
+    def _emit_single(self, P, S, H, W, n_src, capture=()):
         """-> (first-stage feature Act [S, H/4, W/4, d], stem args): tower (+ reduce + per-crop encoder for TransPose-H, :649-655)"""
         if self.singleformer == "hrformer":
             xs, stem_args = self.tower.emit(P, S, H, W, n_src=n_src)
@@ -2093,25 +1913,22 @@ class Engine:
             f = c
         return f
 
-    def _new_program(self, query=None, persons=None):
-        """an empty Program of this engine's storage type; query / persons: the program-key suffix of _check_queries / _check_persons, or None"""
+    def _new_program(self, form=None):
+        """an empty Program of this engine's storage type; form: the capture form of the call it is built for (attn_capture.resolve), or None"""
         P = Program(self.device)
-        P.store_dt = self.store_dt
-        P.query = (query[1], dict(query[3])) if query else None
-        P.persons = (persons[1], persons[2]) if persons else None
+        P.store_dt, P.form = self.store_dt, form
         return P
 
-    def _build(self, S, H, W, length, flip=False, part=None, capture=(), query=None, persons=None):
+    def _build(self, S, H, W, length, flip=False, part=None, form=None):
         """flip: the flip test of validate() (lib/core/function.py:142-162) batched into the same forward -- crops S..2S-1 are
         the mirrored copies (mirroring happens inside the stem kernels), every image appears twice as a token group.
         part (models whose first stage is the bare HRNet tower): "tower" = the per-crop tower + reduce only -> (P, patch, features Act);
         "tail" = everything behind it (position branch, inter-human encoder, deconvs, head) reading a feature buffer that tower
         programs fill (patch["feat"]) -- the two halves of a part-batch forward (_forward_split).
-        capture: frozenset of (stack, layer) whose attention maps the program computes too (Program.set_capture); query: the key suffix
-        of _check_queries -- their rows / columns at query points instead (Program.set_query_capture); persons: that of _check_persons
-        -- their per-person reductions instead (Program.set_person_capture)."""
+        form: the capture form (attn_capture.resolve) -- the program computes the attention maps of form.capture too (Program.bind_capture)."""
         M = self.cfg["MODEL"]
-        P = self._new_program(query, persons)
+        P = self._new_program(form)
+        capture = form.capture if form else ()
         patch = {}
         n_src = S
         if flip:
@@ -2255,13 +2072,12 @@ class Engine:
         assert self.name in ("transpose_h", "hrformer") and x.dim() == 4 and x.shape[1] == 3 and x.dtype == torch.float32
         S, _, H, W = x.shape
         x = x.to(self.device).contiguous()
-        capture = self._check_capture(capture) if capture else frozenset()
-        query = self._check_queries(queries, capture)
-        key = (S, H, W, "single") + (("capture", capture) if capture else ()) + (query or ())
+        form = attn_capture.resolve(capture, queries, None, None, self.capture_stacks(), self.inter_stack, self.window_attn)
+        key = (S, H, W, "single") + (form.key if form else ())
         with torch.cuda.device(self.device):
             def build():
-                P = self._new_program(query)
-                g, px = self._emit_single(P, S, H, W, S, capture)
+                P = self._new_program(form)
+                g, px = self._emit_single(P, S, H, W, S, form.capture if form else ())
                 hd = P.head(g, self.single_head)
                 P.finalize()
                 return (P, px, g, hd)
@@ -2270,68 +2086,30 @@ class Engine:
             J = self.cfg["MODEL"]["NUM_JOINTS"]
             hm = torch.empty(S, J, g.h, g.w, dtype=torch.float32, device=self.device)
             hd.out = hm.data_ptr()
-            if query:
-                self._check_map_sizes(P, H, W)
-                _, maps, inputs = P.set_query_capture([[g.h * g.w] * S], queries)
-            elif capture:
-                _, maps, inputs = P.set_capture([[g.h * g.w] * S])
+            views = self._bind_capture(P, form, S, [], H, W) if form else None
             P.run(self.side_streams if P.uses_lanes else None)
             # (NHWC arena buffer -> the reference's NCHW feature tensor: a torch view + copy, boundary plumbing only)
             feat = g.t.view(S, g.h, g.w, g.cs)[..., :g.c].permute(0, 3, 1, 2).contiguous()
-            if capture:
-                return (feat, hm), self._capture_result(maps, inputs, S)
+            if form:
+                return (feat, hm), form.result(views, lambda: self._capture_inputs(P, S))
         return feat, hm
 
-    def _check_queries(self, queries, capture):
-        """queries (AttnQueries) -> the program-key suffix ("query", mode, K capacity, scale), or None without queries"""
-        if queries is None:
-            return None
-        if not capture:
-            raise ValueError("queries= needs capture=: the (stack, layer) set whose maps to query")
-        mode, stacks = int(queries.mode), sorted({st for st, _ in capture})
-        missing = set(stacks) - set(queries.tokens)
-        if missing:
-            raise ValueError("queries.tokens has no table for %s" % sorted(missing))
-        up = queries.upsample
-        try:
-            scales = tuple((st, int(up[st] if isinstance(up, dict) else up)) for st in stacks)
-        except KeyError as e:
-            raise ValueError("queries.upsample has no scale for stack %s" % e)
-        if mode not in (0, 1) or not all(1 <= r <= 64 for _, r in scales):
-            raise ValueError("queries: mode %r (0 dependency, 1 affect), upsample %r (1 .. 64)" % (queries.mode, up))
-        return ("query", mode, int(queries.capacity), scales)
-
-    def _check_persons(self, persons, capture, flip_joint_map=None, queries=None):
-        """persons (PersonMaps) -> the program-key suffix ("persons", mode, scale), or None without persons"""
-        if persons is None:
-            return None
-        if self.window_attn:
-            raise ValueError("persons=: ATTENTION_TYPE window has no encoder stack to capture")
-        if flip_joint_map is not None or queries is not None:
-            raise ValueError("persons=: not with the flip test, not with queries=")
-        if not capture:
-            raise ValueError("persons= needs capture=: the (stack, layer) set of the inter-human stack to reduce")
-        other = sorted({str(st) for st, _ in capture} - {self.inter_stack})
-        if other or not self.layers:
-            raise ValueError("persons=: %s is not this model's inter-human stack %r (an intra-human stack has one person per group)"
-                             % (other or "a capture", self.inter_stack if self.layers else None))
-        return ("persons", int(persons.mode), int(persons.upsample))
-
-    def _check_map_sizes(self, P, H, W):
-        """the token maps attention_at mapped its points onto (capture_map_sizes) are the ones the program was built with"""
-        sizes = self.capture_map_sizes(H, W)
-        for cap in P.captures:
-            if sizes.get(cap["stack"]) != (cap["x"].h, cap["x"].w):
+    def _bind_capture(self, P, form, S, length, H, W):
+        """the capture part of a call: the real crops / images of this call (the capacity slots behind them cost nothing) on the token maps
+        capture_map_sizes promises (attention_at mapped its points onto them) -> the views of Program.bind_capture"""
+        sizes, glens = self.capture_map_sizes(H, W), []
+        for c in P.captures:
+            h, w = c["x"].h, c["x"].w
+            if sizes.get(c["stack"]) != (h, w):
                 raise RuntimeError("capture_map_sizes(%d, %d)[%r] = %s, but the program's stack input is %d x %d"
-                                   % (H, W, cap["stack"], sizes.get(cap["stack"]), cap["x"].h, cap["x"].w))
+                                   % (H, W, c["stack"], sizes.get(c["stack"]), h, w))
+            glens.append([h * w] * S if c["stack"] == self.single_stack else [n * h * w for n in length])
+        return P.bind_capture(glens, form.call)
 
     @staticmethod
-    def _capture_result(maps, inputs, S):
-        """maps + per captured stack its input features [S, c, h, w] (NCHW copies: the `reduce` output for the stacks fed by one)"""
-        out = dict(maps)
-        for st, a in inputs.items():
-            out[(st, "input")] = a.view()[:S, :, :, :a.c].permute(0, 3, 1, 2).contiguous()
-        return out
+    def _capture_inputs(P, S):
+        """per captured stack its input features [S, c, h, w] (NCHW copies: the `reduce` output for the stacks fed by one)"""
+        return {(c["stack"], "input"): c["x"].view()[:S, :, :, :c["x"].c].permute(0, 3, 1, 2).contiguous() for c in P.captures}
 
     @staticmethod
     def capacity(S):
@@ -2372,15 +2150,10 @@ class Engine:
         assert S == sum(length), "sum(length)=%d != number of crops %d" % (sum(length), S)
         assert all(n >= 1 for n in length), "every image needs at least one person"
         sine_n = max(length)  # (MULTI_POS_EMBEDDING sine: the canvas is max(length) persons wide, for every part of this batch)
-        pkey = self._check_persons(persons, capture, flip_joint_map, queries)
-        if capture:
-            capture = self._check_capture(capture)
-            assert flip_joint_map is None and not self.window_attn, "attention maps: no flip test, no window-type block"
-            query = self._check_queries(queries, capture)
+        form = attn_capture.resolve(capture, queries, persons, flip_joint_map, self.capture_stacks(), self.inter_stack, self.window_attn)
+        if form:
             with torch.cuda.device(self.device):
-                return self._forward_part(x, pos_mask, list(length), None, S, H, W, sine_n, capture=capture, queries=queries, query=query, persons=pkey)
-        if queries is not None:
-            self._check_queries(queries, capture)
+                return self._forward_part(x, pos_mask, list(length), None, S, H, W, sine_n, form=form)
         if self.window_attn and flip_joint_map is not None:
             # the window type mixes the rows of ALL images of a call (attention.py:1025-1029): the mirrored batch must be a call of its
             # own, as in validate() (function.py:142-162), not extra token groups of this one
@@ -2715,7 +2488,7 @@ class Engine:
         self._bind_groups(Pt, group_len, capG - G, flip)
         return self._run_bound(Pt, patch, capN, N, flip_joint_map, H, W)[0]
 
-    def _forward_part(self, x, pos_mask, length, flip_joint_map, S, H, W, sine_n, slot=0, capture=frozenset(), queries=None, query=None, persons=None):
+    def _forward_part(self, x, pos_mask, length, flip_joint_map, S, H, W, sine_n, slot=0, form=None):
         x = x.to(self.device).contiguous()
         flip = flip_joint_map is not None
         # one program per (capacity, H, W, flip): the launch list and every buffer depend on the crop capacity only; the
@@ -2724,15 +2497,14 @@ class Engine:
         key = (cap, H, W, flip) if slot == 0 else (cap, H, W, flip, slot)  # (a Program owns its arena: the concurrent half needs its own)
         if self.window_attn:  # the padded person layout IS the program: no capacity slots, one program per `length`
             cap, key = S, (S, H, W, flip, "window", tuple(length))
-        if capture:
-            key = key + ("capture", capture) + (query or ()) + (persons or ())
-        P, patch = self._program(key, lambda: self._build(cap, H, W, list(length) + [1] * (cap - S), flip, capture=capture, query=query, persons=persons))
+        if form:
+            key = key + form.key
+        P, patch = self._program(key, lambda: self._build(cap, H, W, list(length) + [1] * (cap - S), flip, form=form))
         self.last_concurrent = []
         self.last_programs = [P]  # (_forward merges the parts')
-        return self._run_program(P, patch, x, pos_mask, length, flip_joint_map, S, cap, H, W, sine_n, capture, queries, query, persons)
+        return self._run_program(P, patch, x, pos_mask, length, flip_joint_map, S, cap, H, W, sine_n, form)
 
-    def _run_program(self, P, patch, x, pos_mask, length, flip_joint_map, S, cap, H, W, sine_n, capture=frozenset(), queries=None, query=None,
-                     persons=None):
+    def _run_program(self, P, patch, x, pos_mask, length, flip_joint_map, S, cap, H, W, sine_n, form=None):
         """Bind one call into a built program of capacity `cap` and run it on the current stream: the token groups of `length` (capacity
         slots as one-person groups), the sine rows, the inputs (x None: tower programs filled patch["feat"]), fresh outputs, the capture
         buffers; then the flip merge and the slice to the S real crops.  -> what forward() returns."""
@@ -2745,24 +2517,10 @@ class Engine:
             if self.window_attn:  # one more crop: the zero mask of the padded persons (_emit_window_block)
                 pm = torch.cat([pm, pm.new_zeros(1, 1, H, W)], 0)
         self._bind_inputs(patch, x, pm, S)
-        if capture:  # the real images / crops of this call: the capacity slots behind them cost nothing
-            glens = []
-            for c in P.captures:
-                tok = c["x"].h * c["x"].w
-                glens.append([tok] * S if c["stack"] == self.single_stack else [n * tok for n in length])
-            if query:
-                self._check_map_sizes(P, H, W)
-            if persons:
-                _, rel, maps, _ = P.set_person_capture(glens)
-            else:
-                _, maps, inputs = P.set_query_capture(glens, queries) if query else P.set_capture(glens)
+        views = self._bind_capture(P, form, S, length, H, W) if form else None
         multi, single = self._run_bound(P, patch, cap, S, flip_joint_map, H, W)
         res = {"single": single, "multi": multi} if single is not None else multi
-        if persons:
-            return res, (rel, maps)
-        if capture:
-            return res, self._capture_result(maps, inputs, S)
-        return res
+        return (res, form.result(views, lambda: self._capture_inputs(P, S))) if form else res
 
     # the per-call steps every bound forward shares (_run_program, _forward_groups_shared)
     def _bind_groups(self, P, length, pad, flip):

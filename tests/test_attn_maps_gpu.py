@@ -286,3 +286,41 @@ def test_16bit_maps(tag, precision):
         print("   layer-0 input max-abs err %.3e; maps vs the restatement on the layer's own input %.2e; worst |dp| / softmax bound %.3f"
               % (in_err, worst_own, worst_ratio))
         assert worst_own < 1e-4 and worst_ratio <= 1.0
+
+
+def _flat(res):
+    """every tensor of what a capture call returned (output, maps; PersonRelations), cloned, in a fixed order"""
+    if torch.is_tensor(res):
+        return [res.clone()]
+    if isinstance(res, dict):
+        return [t for k in sorted(res, key=str) for t in _flat(res[k])]
+    if isinstance(res, (list, tuple)):
+        return [t for r in res for t in _flat(r)]
+    return _flat(res.relation) + _flat(res.maps)
+
+
+def test_one_engine_serves_all_three_forms():
+    """full capture, attention_at, person_relations and full capture again on ONE engine: every call gives the bits of the same call on a
+    fresh engine, the heat maps stay the default forward's, and the four calls build exactly three programs"""
+    cfg, sd, x, m, length, _ = setup("w48_l31")
+    x, m = x.cuda(), m.cuda()
+    pts = torch.tensor([[10.0, 20.0], [100.0, 200.0], [191.0, 255.0]]).repeat(x.shape[0], 1, 1)
+
+    def calls(net):
+        cap = {(net.engine().inter_stack, 0)}
+        return [lambda: net.engine().forward(x, m, length, capture=cap),
+                lambda: net.attention_at(x, m, length, pts, mode="affect", layers=cap),
+                lambda: net.person_relations(x, m, length, layers=cap, maps="dependency", upsample=2),
+                lambda: net.engine().forward(x, m, length, capture=cap)]
+
+    net = _net(cfg, sd)
+    y0 = net(x, m, length).clone()
+    eng = net.engine()
+    builds = eng.n_builds
+    got = [_flat(fn()) for fn in calls(net)]
+    assert eng.n_builds == builds + 3, "four calls in three forms: %d programs built" % (eng.n_builds - builds)
+    for i, res in enumerate(got):
+        assert torch.equal(res[0], y0), "call %d: heat maps differ from the default forward's" % i
+        fresh = _flat(calls(_net(cfg, sd))[i]())
+        assert len(res) == len(fresh) > 1 and all(torch.equal(a, b) for a, b in zip(res, fresh)), "call %d differs from a fresh engine's" % i
+    assert all(torch.equal(a, b) for a, b in zip(got[0], got[3]))
