@@ -764,6 +764,144 @@ __device__ __forceinline__ f32x4 load_xblk(const float* row, const float* prow, 
     return pack8<DT>(a0, a1);
 }
 
+// ---- the pieces the 16-bit kernels share (enc_kv_lp_k, enc_layer_lp_k, enc_layer_lp4_k) ----
+// They take EncK BY VALUE: inlined, that is the kernel's own argument block.  By reference enc_layer_lp4_k, which sits on the register
+// limit, got another allocation and a slower tail (profiles/enc_lp_core_resources.md).
+// Work item b of a launch whose items are runs of ITEM tokens of ONE group: the group's token range, the index of its first 32-key block
+// (blocks are numbered group by group) and the item's index j inside the group.
+struct LpItem {
+    int gs, ge, base32, j;
+};
+template <int ITEM>
+__device__ __forceinline__ LpItem lp_locate(const EncK p, int b) {
+    int gs = 0, ge = 0, base32 = 0;
+    for (int grp = 0; grp < p.n_grp; ++grp) {
+        gs = p.grp_off[grp];
+        ge = p.grp_off[grp + 1];
+        const int n = (int)((unsigned)(ge - gs + ITEM - 1) / ITEM);  // (groups are not empty: unsigned, a shift for ITEM = 16 / 64)
+        if (b < n) break;
+        b -= n;
+        base32 += (ge - gs + 31) >> 5;
+    }
+    return {gs, ge, base32, b};
+}
+
+// q projection of QF query fragments (token rows qrow[]): B operand = packed (src + pos); q is scaled by qscale * log2(e) (softmax in base 2)
+template <int DC, int QF, int DT, int CSR>
+__device__ __forceinline__ void lp_project_q(const EncK p, const int (&qrow)[QF], int li, int g, f32x4 (&qB)[QF][DC / 2]) {
+    constexpr int cs = CSR * 16, csp = DC * 16, KC = DC / 2;
+    f32x4 xB[QF][KC];
+#pragma unroll
+    for (int qf = 0; qf < QF; ++qf) {
+        const int prow = p.pos_period > 0 ? qrow[qf] % p.pos_period : qrow[qf];
+#pragma unroll
+        for (int c = 0; c < KC; ++c)
+            xB[qf][c] = load_xblk<CSR, DT>(p.src + (size_t)qrow[qf] * cs, p.pos ? p.pos + (size_t)prow * cs : nullptr, c, g);
+    }
+    f32x4 q32[QF][DC];
+    gemm_T_lp<DC, KC, QF, DT>(p.w_in_lp, p.vec_lp /* LpVec::BIN = 0 */, csp, xB, li, g, [&](int nt, int qf, f32x4 a) { q32[qf][nt] = a * (p.qscale * 1.4426950408889634f); });
+#pragma unroll
+    for (int qf = 0; qf < QF; ++qf)
+#pragma unroll
+        for (int c = 0; c < KC; ++c) qB[qf][c] = pack8<DT>(q32[qf][2 * c], q32[qf][2 * c + 1]);
+}
+
+// Softmax step of one 32-key block for QF query fragments.  st[qf][kf] = S^T[key 16kf + 4g + r][query li] - m: the running reference m is
+// folded into the S accumulator (it starts at negm = -m instead of 0: no subtraction per score).  Online softmax in base 2 with a lazy
+// reference: m (kept as -m in every lane of a query's column) is raised -- and O, l rescaled -- only when a score exceeds it by more than
+// 2^10; the group's first block always sets it (scores far below 0 must not underflow).  The common path has no cross-lane traffic and no
+// O rescale.  The step is three pieces, which the kernels place among their matrix instructions: lp_mask (a ragged block's keys >= ge),
+// lp_reference, lp_weights.  A block that is neither a group's first (`first`, a constant false there) nor ragged is ONE basic block with
+// one rarely taken branch for all fragments.
+__device__ __forceinline__ void lp_mask(f32x4& s, int key0, int ge) {  // s: scores of the keys key0 .. key0 + 3
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+        if (key0 + r >= ge) s[r] = -__builtin_inff();
+}
+template <int DC, int QF>
+__device__ __forceinline__ void lp_reference(f32x4 (*st)[2], f32x4* negm, f32x4 (*o)[DC], f32x4* ol, const bool first) {
+    // (plain fmaxf: an inline-asm v_max3 on MFMA results gets no hazard wait states from the compiler -- NaNs under -amdgpu-mfma-vgpr-form)
+    auto max3 = [](float x, float y, float z) { return fmaxf(fmaxf(x, y), z); };
+    float mx[QF], mxa = -__builtin_inff();
+#pragma unroll
+    for (int qf = 0; qf < QF; ++qf) {
+        mx[qf] = max3(max3(max3(st[qf][0][0], st[qf][0][1], st[qf][0][2]), st[qf][0][3], st[qf][1][0]), max3(st[qf][1][1], st[qf][1][2], st[qf][1][3]), st[qf][1][1]);
+        mxa = QF == 1 ? mx[qf] : fmaxf(mxa, mx[qf]);
+    }
+    if (first || __any(mxa > 10.f)) {
+#pragma unroll
+        for (int qf = 0; qf < QF; ++qf) {
+            if (QF > 1 && !first && !__any(mx[qf] > 10.f)) continue;  // (exactly the fragments a step of their own would touch)
+            float d = xmax(mx[qf]);          // how far the block's maximum lies above the reference
+            if (!first) {
+                d = fmaxf(d, 0.f);           // (the reference only rises afterwards)
+                const float alpha = __builtin_amdgcn_exp2f(-d);
+                ol[qf] *= alpha;
+#pragma unroll
+                for (int nt = 0; nt < DC; ++nt) o[qf][nt] *= alpha;
+            }
+            negm[qf] -= d;
+            st[qf][0] -= d;
+            st[qf][1] -= d;
+        }
+    }
+}
+// the weights 2^(S - m) of one fragment as the B operand of O += V^T P (keys {4g + r} U {16 + 4g + r}: the order V^T blocks are stored in)
+template <int DT>
+__device__ __forceinline__ f32x4 lp_weights(f32x4 (&st)[2]) {
+#pragma unroll
+    for (int kf = 0; kf < 2; ++kf)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) st[kf][r] = __builtin_amdgcn_exp2f(st[kf][r]);
+    return pack8<DT>(st[0], st[1]);
+}
+
+// Layer tail of NQ query fragments (token rows qrow[], the first fragment's first token tok0, stores below ge): O / l -> out-proj +
+// residual + LN1, FFN, + residual + LN2 -> out.  The weights are fetched once for all NQ fragments.
+template <int DC, int FC, int NQ, int DT, int CSR>
+__device__ __forceinline__ void lp_tail(const EncK p, const f32x4 (*o)[DC], const f32x4* ol, const int* qrow, int tok0, int ge, int li, int g) {
+    constexpr int cs = CSR * 16, csp = DC * 16, dff = FC * 16, KC = DC / 2, FKC = FC / 2;
+    typedef LpVec<DC, FC> V;
+    const float* vec = p.vec_lp;
+    f32x4 oB[NQ][KC];
+#pragma unroll
+    for (int qf = 0; qf < NQ; ++qf) {
+        const float inv = 1.f / xsum(ol[qf][0]);  // l sits in row 0 of the ones tile (lane g = 0, register 0); rows 4g of g > 0 are zero
+#pragma unroll
+        for (int c = 0; c < KC; ++c) oB[qf][c] = pack8<DT>(o[qf][2 * c] * inv, o[qf][2 * c + 1] * inv);
+    }
+    f32x4 x1[NQ][DC];
+    gemm_T_lp<DC, KC, NQ, DT>(p.w_out_lp, vec + V::BOUT, csp, oB, li, g, [&](int nt, int qf, f32x4 a) {
+        x1[qf][nt] = nt < CSR ? ld4(p.src + (size_t)qrow[qf] * cs + 16 * nt + 4 * g) + a : a;  // (features >= cs: zero weights -> a = 0)
+    });
+    f32x4 x1B[NQ][KC];
+#pragma unroll
+    for (int qf = 0; qf < NQ; ++qf) {
+        layer_norm<DC>(x1[qf], vec + V::LN1W, vec + V::LN1B, p.d, p.ln_eps, g);
+#pragma unroll
+        for (int c = 0; c < KC; ++c) x1B[qf][c] = pack8<DT>(x1[qf][2 * c], x1[qf][2 * c + 1]);
+    }
+    f32x4 hB[NQ][FKC];
+    {
+        f32x4 hprev[NQ];
+        gemm_T_lp<FC, KC, NQ, DT>(p.w1_lp, vec + V::B1, csp, x1B, li, g, [&](int ft, int qf, f32x4 a) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) a[r] = fmaxf(a[r], 0.f);
+            if (ft & 1) hB[qf][ft >> 1] = pack8<DT>(hprev[qf], a); else hprev[qf] = a;
+        });
+    }
+    gemm_T_lp<DC, FKC, NQ, DT>(p.w2_lp, vec + V::B2, dff, hB, li, g, [&](int nt, int qf, f32x4 a) { x1[qf][nt] += a; });
+#pragma unroll
+    for (int qf = 0; qf < NQ; ++qf) {
+        layer_norm<DC>(x1[qf], vec + V::LN2W, vec + V::LN2B, p.d, p.ln_eps, g);
+        const int qtok = tok0 + qf * 16 + li;
+        if (qtok < ge) {
+#pragma unroll
+            for (int nt = 0; nt < CSR; ++nt) *reinterpret_cast<f32x4*>(p.out + (size_t)qtok * cs + 16 * nt + 4 * g) = x1[qf][nt];
+        }
+    }
+}
+
 // K / V projection, TB consecutive 32-token blocks of ONE group per workgroup (blocks are numbered group by group, like the 16-key
 // fragments of the fp32 kernels: block b of group g sits at index sum_{g' < g} ceil(len_g' / 32) + b, so group offsets need no
 // alignment).  TB = 2 (round 4): the 36 KB of K / V projection rows stream from L2 once per 64 tokens instead of once per 32 -- every
@@ -776,16 +914,9 @@ template <int DC, int CSR, int DT, int TB>
 __global__ __launch_bounds__(64) void enc_kv_lp_k(const EncK p) {
     constexpr int KC = DC / 2, cs = CSR * 16, csp = DC * 16, TF = 2 * TB;
     const int lane = threadIdx.x, li = lane & 15, g = lane >> 4;
-    int b = blockIdx.x, gs = 0, ge = 0, base32 = 0;
-    for (int grp = 0; grp < p.n_grp; ++grp) {
-        gs = p.grp_off[grp];
-        ge = p.grp_off[grp + 1];
-        const int nb = (ge - gs + 31) >> 5, nw = (nb + TB - 1) / TB;
-        if (b < nw) break;
-        b -= nw;
-        base32 += nb;
-    }
-    const int t0 = gs + b * 32 * TB;
+    const LpItem it = lp_locate<32 * TB>(p, blockIdx.x);  // (ceil(ceil(len / 32) / TB) = ceil(len / (32 TB)) work items per group)
+    const int ge = it.ge, base32 = it.base32, b = it.j;
+    const int t0 = it.gs + b * 32 * TB;
     // B operands of the 16-token fragments: src + pos (keys) and src (values), packed to 16 bit like every GEMM input here
     f32x4 xq[TF][KC], xs[TF][KC];
     bool valid[TF];
@@ -848,52 +979,26 @@ __global__ __launch_bounds__(64) void enc_kv_lp_k(const EncK p) {
 
 template <int DC, int FC, int QF, int DT, int CSR>
 __global__ __launch_bounds__(64) void enc_layer_lp_k(const EncK p) {
-    constexpr int cs = CSR * 16, csp = DC * 16, dff = FC * 16, KC = DC / 2, FKC = FC / 2;
-    typedef LpVec<DC, FC> V;
+    constexpr int KC = DC / 2;
     const int lane = threadIdx.x, li = lane & 15, g = lane >> 4;
     constexpr int QT = QF * 16;
     // XCD x (= workgroup index % 8, MI355X_MICROARCH.md) takes a CONTIGUOUS eighth of the work items: the waves of a group then stream its
     // K / V through ONE 4 MB L2.  In launch order every XCD touched every group -- 57 crops x 1.2 MB of K / V per layer, all L2 misses.
-    int b = xcd_band_item(blockIdx.x, p.n_qblk), gs = 0, ge = 0, base32 = 0;
-    if (b < 0) return;
-    for (int grp = 0; grp < p.n_grp; ++grp) {
-        gs = p.grp_off[grp];
-        ge = p.grp_off[grp + 1];
-        const int nq = (ge - gs + QT - 1) / QT;
-        if (b < nq) break;
-        b -= nq;
-        base32 += (ge - gs + 31) >> 5;
-    }
-    const int q0 = gs + b * QT;
+    const int item = xcd_band_item(blockIdx.x, p.n_qblk);
+    if (item < 0) return;
+    const LpItem it = lp_locate<QT>(p, item);
+    const int gs = it.gs, ge = it.ge, base32 = it.base32;
+    const int q0 = gs + it.j * QT;
     int qrow[QF];
 #pragma unroll
     for (int qf = 0; qf < QF; ++qf) qrow[qf] = min(q0 + qf * 16 + li, ge - 1);
-    const float* vec = p.vec_lp;
-
-    // ---- q projection: B operand = packed (src + pos) ----
     f32x4 qB[QF][KC];
-    {
-        f32x4 xB[QF][KC];
-#pragma unroll
-        for (int qf = 0; qf < QF; ++qf) {
-            const int prow = p.pos_period > 0 ? qrow[qf] % p.pos_period : qrow[qf];
-#pragma unroll
-            for (int c = 0; c < KC; ++c)
-                xB[qf][c] = load_xblk<CSR, DT>(p.src + (size_t)qrow[qf] * cs, p.pos ? p.pos + (size_t)prow * cs : nullptr, c, g);
-        }
-        f32x4 q32[QF][DC];
-        gemm_T_lp<DC, KC, QF, DT>(p.w_in_lp, vec + V::BIN, csp, xB, li, g, [&](int nt, int qf, f32x4 a) { q32[qf][nt] = a * (p.qscale * 1.4426950408889634f); });
-#pragma unroll
-        for (int qf = 0; qf < QF; ++qf)
-#pragma unroll
-            for (int c = 0; c < KC; ++c) qB[qf][c] = pack8<DT>(q32[qf][2 * c], q32[qf][2 * c + 1]);
-    }
+    lp_project_q<DC, QF, DT, CSR>(p, qrow, li, g, qB);
 
     // ---- flash attention over the group's 32-key blocks; K rows / V^T blocks stream from L2 into registers, one block ahead ----
     // The loop is bound by the vector ALU, not by the matrix pipe (the 16-bit MFMA is 16x the fp32 rate; round 2: ~50 VALU instructions
-    // per 12 MFMAs), so the softmax is arranged to need as few VALU instructions per score as possible:
-    //  * the running reference m is folded into the S accumulator (acc starts at -m instead of 0): no subtraction per score;
-    //  * the row sums l come out of the matrix pipe: one extra A fragment whose row 0 is all ones makes  ol = 1^T P  next to O = V^T P;
+    // per 12 MFMAs), so the softmax (lp_reference) is arranged to need as few VALU instructions per score as possible; the row sums l come
+    // out of the matrix pipe: one extra A fragment whose row 0 is all ones makes  ol = 1^T P  next to O = V^T P.
     f32x4 o[QF][DC], ol[QF], negm[QF];
 #pragma unroll
     for (int qf = 0; qf < QF; ++qf) {
@@ -903,8 +1008,6 @@ __global__ __launch_bounds__(64) void enc_layer_lp_k(const EncK p) {
     }
     const f32x4 one4 = (f32x4){1.f, 1.f, 1.f, 1.f};
     const f32x4 onesA = li == 0 ? pack8<DT>(one4, one4) : (f32x4){0.f, 0.f, 0.f, 0.f};  // A fragment: row 0 = ones over the block's 32 keys
-    // (plain fmaxf: an inline-asm v_max3 on MFMA results gets no hazard wait states from the compiler -- NaNs under -amdgpu-mfma-vgpr-form)
-    auto max3 = [](float x, float y, float z) { return fmaxf(fmaxf(x, y), z); };
     auto fetch_kv = [&](int k0, f32x4(&ka)[2][KC], f32x4(&va)[DC]) {  // fragment-packed images of the group's block (k0 - gs) / 32
         const size_t blk = (size_t)(base32 + ((k0 - gs) >> 5));
 #pragma unroll
@@ -914,100 +1017,43 @@ __global__ __launch_bounds__(64) void enc_layer_lp_k(const EncK p) {
 #pragma unroll
         for (int nt = 0; nt < DC; ++nt) va[nt] = ld16(p.vbuf, ((blk * DC + nt) * 64 + lane) * 8);
     };
-    // online softmax in base 2 with a lazy reference: m (kept as -m in every lane of a query's column) is raised -- and O, l rescaled --
-    // only when a score exceeds it by more than 2^10; the first block always sets it (scores far below 0 must not underflow).  The
-    // common path has no cross-lane traffic and no O rescale.
-    auto attend = [&](int k0, const f32x4(&ka)[2][KC], const f32x4(&va)[DC]) {
-        const bool ragged = k0 + 32 > ge;  // (wave-uniform)
-        const bool first = k0 == gs;
+    auto scores = [&](int qf, const f32x4(&ka)[2][KC], f32x4(&st)[2]) {
 #pragma unroll
-        for (int qf = 0; qf < QF; ++qf) {
-            f32x4 st[2];
+        for (int kf = 0; kf < 2; ++kf) {
+            f32x4 a = negm[qf];
 #pragma unroll
-            for (int kf = 0; kf < 2; ++kf) {
-                f32x4 a = negm[qf];
-#pragma unroll
-                for (int c = 0; c < KC; ++c) a = mfma32_lp<DT>(ka[kf][c], qB[qf][c], a);  // S^T[key 16kf+4g+r][query li] - m
-                if (ragged) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        if (k0 + 16 * kf + 4 * g + r >= ge) a[r] = -__builtin_inff();
-                }
-                st[kf] = a;
-            }
-            const float mx = max3(max3(max3(st[0][0], st[0][1], st[0][2]), st[0][3], st[1][0]), max3(st[1][1], st[1][2], st[1][3]), st[1][1]);
-            if (first || __any(mx > 10.f)) {
-                float d = xmax(mx);             // how far the block's maximum lies above the reference
-                if (!first) d = fmaxf(d, 0.f);  // (the reference only rises afterwards)
-                if (!first) {
-                    const float alpha = __builtin_amdgcn_exp2f(-d);
-                    ol[qf] *= alpha;
-#pragma unroll
-                    for (int nt = 0; nt < DC; ++nt) o[qf][nt] *= alpha;
-                }
-                negm[qf] -= d;
-                st[0] -= d;
-                st[1] -= d;
-            }
-#pragma unroll
-            for (int kf = 0; kf < 2; ++kf)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) st[kf][r] = __builtin_amdgcn_exp2f(st[kf][r]);
-            const f32x4 pB = pack8<DT>(st[0], st[1]);  // keys {4g+r} U {16+4g+r} of the block: the order V^T blocks are stored in
-#pragma unroll
-            for (int nt = 0; nt < DC; ++nt) o[qf][nt] = mfma32_lp<DT>(va[nt], pB, o[qf][nt]);
-            ol[qf] = mfma32_lp<DT>(onesA, pB, ol[qf]);  // row 0: l[query li] += sum of the block's (16-bit rounded) weights
+            for (int c = 0; c < KC; ++c) a = mfma32_lp<DT>(ka[kf][c], qB[qf][c], a);  // S^T[key 16kf+4g+r][query li] - m
+            st[kf] = a;
         }
     };
-    // The same for a block that is neither a group's first nor ragged -- every block of the main loop -- as ONE basic block: the scores of
-    // all QF fragments first, ONE (rarely taken) branch for the reference update of all of them, then exp / pack / O = V^T P.  With a
-    // branch per fragment (attend above) the scheduler cannot place a fragment's softmax beside the next fragment's MFMAs, and the wave is
-    // alone on its SIMD: whatever it does not overlap itself is idle matrix-pipe time (same box: 1.57 -> 1.45 ms per 6-layer stack).
-    auto attend_fast = [&](const f32x4(&ka)[2][KC], const f32x4(&va)[DC]) {
+    auto weigh = [&](int qf, const f32x4(&va)[DC], f32x4(&st)[2]) {
+        const f32x4 pB = lp_weights<DT>(st);
+#pragma unroll
+        for (int nt = 0; nt < DC; ++nt) o[qf][nt] = mfma32_lp<DT>(va[nt], pB, o[qf][nt]);
+        ol[qf] = mfma32_lp<DT>(onesA, pB, ol[qf]);  // row 0: l[query li] += sum of the block's (16-bit rounded) weights
+    };
+    // One block.  A block of the main loop is neither a group's first nor ragged and runs as ONE basic block: the scores of all QF
+    // fragments first, ONE (rarely taken) branch for the reference update of all of them, then exp / pack / O += V^T P.  With a branch
+    // per fragment the scheduler cannot place a fragment's softmax beside the next fragment's MFMAs, and the wave is alone on its SIMD:
+    // whatever it does not overlap itself is idle matrix-pipe time (same box: 1.57 -> 1.45 ms per 6-layer stack).  general_c: the block
+    // may be the group's first or ragged (at most three such blocks per wave).
+    auto attend = [&](int k0, const f32x4(&ka)[2][KC], const f32x4(&va)[DC], auto general_c) {
+        constexpr bool general = decltype(general_c)::value;
         f32x4 st[QF][2];
-        float mx[QF];
 #pragma unroll
-        for (int qf = 0; qf < QF; ++qf) {
+        for (int qf = 0; qf < QF; ++qf) scores(qf, ka, st[qf]);
+        if (general && k0 + 32 > ge) {  // (wave-uniform)
 #pragma unroll
-            for (int kf = 0; kf < 2; ++kf) {
-                f32x4 a = negm[qf];
+            for (int qf = 0; qf < QF; ++qf)
 #pragma unroll
-                for (int c = 0; c < KC; ++c) a = mfma32_lp<DT>(ka[kf][c], qB[qf][c], a);
-                st[qf][kf] = a;
-            }
+                for (int kf = 0; kf < 2; ++kf) lp_mask(st[qf][kf], k0 + 16 * kf + 4 * g, ge);
         }
-        float mxa = -__builtin_inff();
+        lp_reference<DC, QF>(st, negm, o, ol, general && k0 == gs);
 #pragma unroll
-        for (int qf = 0; qf < QF; ++qf) {
-            mx[qf] = max3(max3(max3(st[qf][0][0], st[qf][0][1], st[qf][0][2]), st[qf][0][3], st[qf][1][0]), max3(st[qf][1][1], st[qf][1][2], st[qf][1][3]), st[qf][1][1]);
-            mxa = fmaxf(mxa, mx[qf]);
-        }
-        if (__any(mxa > 10.f)) {
-#pragma unroll
-            for (int qf = 0; qf < QF; ++qf) {
-                if (!__any(mx[qf] > 10.f)) continue;  // (exactly the fragments attend would have touched)
-                const float d = fmaxf(xmax(mx[qf]), 0.f);
-                const float alpha = __builtin_amdgcn_exp2f(-d);
-                ol[qf] *= alpha;
-#pragma unroll
-                for (int nt = 0; nt < DC; ++nt) o[qf][nt] *= alpha;
-                negm[qf] -= d;
-                st[qf][0] -= d;
-                st[qf][1] -= d;
-            }
-        }
-#pragma unroll
-        for (int qf = 0; qf < QF; ++qf) {
-#pragma unroll
-            for (int kf = 0; kf < 2; ++kf)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) st[qf][kf][r] = __builtin_amdgcn_exp2f(st[qf][kf][r]);
-            const f32x4 pB = pack8<DT>(st[qf][0], st[qf][1]);
-#pragma unroll
-            for (int nt = 0; nt < DC; ++nt) o[qf][nt] = mfma32_lp<DT>(va[nt], pB, o[qf][nt]);
-            ol[qf] = mfma32_lp<DT>(onesA, pB, ol[qf]);
-        }
+        for (int qf = 0; qf < QF; ++qf) weigh(qf, va, st[qf]);
     };
+    constexpr std::true_type general{};
+    constexpr std::false_type inner{};
     {
         f32x4 ka0[2][KC], va0[DC], ka1[2][KC], va1[DC];
         fetch_kv(gs, ka0, va0);
@@ -1015,62 +1061,24 @@ __global__ __launch_bounds__(64) void enc_layer_lp_k(const EncK p) {
         int k0 = gs;
         if (k0 + 64 <= ge) {  // the group's first block sets the reference: general path
             fetch_kv(k0 + 32, ka1, va1);
-            attend(k0, ka0, va0);
+            attend(k0, ka0, va0, general);
             fetch_kv(min(k0 + 64, last), ka0, va0);
-            attend_fast(ka1, va1);
+            attend(k0 + 32, ka1, va1, inner);
             k0 += 64;
         }
         for (; k0 + 64 <= ge; k0 += 64) {
             fetch_kv(k0 + 32, ka1, va1);
-            attend_fast(ka0, va0);
+            attend(k0, ka0, va0, inner);
             fetch_kv(min(k0 + 64, last), ka0, va0);  // (look-ahead past the end re-reads the last block, unused)
-            attend_fast(ka1, va1);
+            attend(k0 + 32, ka1, va1, inner);
         }
         if (k0 < ge) {
             if (k0 + 32 < ge) fetch_kv(k0 + 32, ka1, va1);
-            attend(k0, ka0, va0);
-            if (k0 + 32 < ge) attend(k0 + 32, ka1, va1);
+            attend(k0, ka0, va0, general);
+            if (k0 + 32 < ge) attend(k0 + 32, ka1, va1, general);
         }
     }
-
-    // ---- out-proj + residual + LN1, FFN, + residual + LN2 (per query fragment; weights shared across fragments) ----
-    f32x4 oB[QF][KC];
-#pragma unroll
-    for (int qf = 0; qf < QF; ++qf) {
-        const float inv = 1.f / xsum(ol[qf][0]);  // l sits in row 0 of the ones tile (lane g = 0, register 0); rows 4g of g > 0 are zero
-#pragma unroll
-        for (int c = 0; c < KC; ++c) oB[qf][c] = pack8<DT>(o[qf][2 * c] * inv, o[qf][2 * c + 1] * inv);
-    }
-    f32x4 x1[QF][DC];
-    gemm_T_lp<DC, KC, QF, DT>(p.w_out_lp, vec + V::BOUT, csp, oB, li, g, [&](int nt, int qf, f32x4 a) {
-        x1[qf][nt] = nt < CSR ? ld4(p.src + (size_t)qrow[qf] * cs + 16 * nt + 4 * g) + a : a;  // (features >= cs: zero weights -> a = 0)
-    });
-    f32x4 x1B[QF][KC];
-#pragma unroll
-    for (int qf = 0; qf < QF; ++qf) {
-        layer_norm<DC>(x1[qf], vec + V::LN1W, vec + V::LN1B, p.d, p.ln_eps, g);
-#pragma unroll
-        for (int c = 0; c < KC; ++c) x1B[qf][c] = pack8<DT>(x1[qf][2 * c], x1[qf][2 * c + 1]);
-    }
-    f32x4 hB[QF][FKC];
-    {
-        f32x4 hprev[QF];
-        gemm_T_lp<FC, KC, QF, DT>(p.w1_lp, vec + V::B1, csp, x1B, li, g, [&](int ft, int qf, f32x4 a) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) a[r] = fmaxf(a[r], 0.f);
-            if (ft & 1) hB[qf][ft >> 1] = pack8<DT>(hprev[qf], a); else hprev[qf] = a;
-        });
-    }
-    gemm_T_lp<DC, FKC, QF, DT>(p.w2_lp, vec + V::B2, dff, hB, li, g, [&](int nt, int qf, f32x4 a) { x1[qf][nt] += a; });
-#pragma unroll
-    for (int qf = 0; qf < QF; ++qf) {
-        layer_norm<DC>(x1[qf], vec + V::LN2W, vec + V::LN2B, p.d, p.ln_eps, g);
-        const int qtok = q0 + qf * 16 + li;
-        if (qtok < ge) {
-#pragma unroll
-            for (int nt = 0; nt < CSR; ++nt) *reinterpret_cast<f32x4*>(p.out + (size_t)qtok * cs + 16 * nt + 4 * g) = x1[qf][nt];
-        }
-    }
+    lp_tail<DC, FC, QF, DT, CSR>(p, o, ol, qrow, q0, ge, li, g);  // (all QF fragments side by side: the weights are fetched once)
 }
 
 // =====================================================================================================================
@@ -1085,34 +1093,28 @@ __global__ __launch_bounds__(64) void enc_layer_lp_k(const EncK p) {
 //     read their A operands from LDS -- a fragment crosses the vector-memory path once per 156 matrix instructions;
 //   * without the register-resident K / V blocks a wave needs < 256 registers: TWO workgroups per CU = two waves per SIMD, one
 //     wave's softmax beside the other's matrix instructions;
-//   * everything else (q projection, lazy-reference online softmax in base 2, row sums from the matrix pipe, out-proj / LN / FFN tail)
-//     is the code of enc_layer_lp_k, per wave.
+//   * everything else is shared with enc_layer_lp_k, per wave: the group walk (lp_locate), the q projection (lp_project_q), the
+//     lazy-reference online softmax in base 2 (lp_mask, lp_reference, lp_weights) and the out-proj / LN / FFN tail (lp_tail, here one fragment at a time).
+//     This kernel keeps where the A fragments come from -- the LDS ring and the register pipeline with its fences -- and the order
+//     in which the matrix instructions are issued around the softmax step.
 template <int DC, int FC, int DT, int CSR>
 __global__ __launch_bounds__(256, 2) void enc_layer_lp4_k(const EncK p) {
-    constexpr int QF = 3, cs = CSR * 16, csp = DC * 16, dff = FC * 16, KC = DC / 2, FKC = FC / 2, NFR = 2 * KC + DC;  // fragments of a 32-key block
+    constexpr int QF = 3, KC = DC / 2, NFR = 2 * KC + DC;  // fragments of a 32-key block
     static_assert(NFR == 12, "three fragments per wave");
-    typedef LpVec<DC, FC> V;
     constexpr int NS = 4, PD = 3;  // LDS ring slots (12 KB each) / prefetch distance in blocks
     static_assert(PD <= NS - 1 && PD >= 2, "ring");
     __shared__ __attribute__((aligned(16))) f32x4 kvs[NS][NFR * 64];
     const int tid = threadIdx.x, lane = tid & 63, li = lane & 15, g = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     constexpr int QW = QF * 16, QT = 4 * QW;  // queries per wave / per workgroup
-    int b = xcd_band_item(blockIdx.x, p.n_qblk), gs = 0, ge = 0, base32 = 0;  // (XCD-banded like enc_layer_lp_k; workgroup-uniform)
-    if (b < 0) return;
-    for (int grp = 0; grp < p.n_grp; ++grp) {
-        gs = p.grp_off[grp];
-        ge = p.grp_off[grp + 1];
-        const int nq = (ge - gs + QT - 1) / QT;
-        if (b < nq) break;
-        b -= nq;
-        base32 += (ge - gs + 31) >> 5;
-    }
-    const int q0 = gs + b * QT + wave * QW;
+    const int item = xcd_band_item(blockIdx.x, p.n_qblk);  // (XCD-banded like enc_layer_lp_k; workgroup-uniform)
+    if (item < 0) return;
+    const LpItem it = lp_locate<QT>(p, item);
+    const int gs = it.gs, ge = it.ge, base32 = it.base32;
+    const int q0 = gs + it.j * QT + wave * QW;
     int qrow[QF];
 #pragma unroll
     for (int qf = 0; qf < QF; ++qf) qrow[qf] = min(q0 + qf * 16 + li, ge - 1);
-    const float* vec = p.vec_lp;
 
     // ---- this wave's share of a block: fragments 3 wave .. 3 wave + 2 of [K (kf, c) | V^T nt] go from global memory STRAIGHT into an LDS
     //      slot (global_load_lds_dwordx4: 16 bytes per lane to M0 + 16 lane, i.e. the 1 KB fragment image as it is; no staging
@@ -1134,24 +1136,8 @@ __global__ __launch_bounds__(256, 2) void enc_layer_lp4_k(const EncK p) {
     for (int jb = 0; jb < PD; ++jb)
         if (jb < nblk) gload(jb, jb);
 
-    // ---- q projection: B operand = packed (src + pos) ----
     f32x4 qB[QF][KC];
-    {
-        f32x4 xB[QF][KC];
-#pragma unroll
-        for (int qf = 0; qf < QF; ++qf) {
-            const int prow = p.pos_period > 0 ? qrow[qf] % p.pos_period : qrow[qf];
-#pragma unroll
-            for (int c = 0; c < KC; ++c)
-                xB[qf][c] = load_xblk<CSR, DT>(p.src + (size_t)qrow[qf] * cs, p.pos ? p.pos + (size_t)prow * cs : nullptr, c, g);
-        }
-        f32x4 q32[QF][DC];
-        gemm_T_lp<DC, KC, QF, DT>(p.w_in_lp, vec + V::BIN, csp, xB, li, g, [&](int nt, int qf, f32x4 a) { q32[qf][nt] = a * (p.qscale * 1.4426950408889634f); });
-#pragma unroll
-        for (int qf = 0; qf < QF; ++qf)
-#pragma unroll
-            for (int c = 0; c < KC; ++c) qB[qf][c] = pack8<DT>(q32[qf][2 * c], q32[qf][2 * c + 1]);
-    }
+    lp_project_q<DC, QF, DT, CSR>(p, qrow, li, g, qB);
     landed();
     __syncthreads();
 
@@ -1164,9 +1150,8 @@ __global__ __launch_bounds__(256, 2) void enc_layer_lp4_k(const EncK p) {
     }
     const f32x4 one4 = (f32x4){1.f, 1.f, 1.f, 1.f};
     const f32x4 onesA = li == 0 ? pack8<DT>(one4, one4) : (f32x4){0.f, 0.f, 0.f, 0.f};  // A fragment: row 0 = ones over the block's 32 keys
-    auto max3 = [](float x, float y, float z) { return fmaxf(fmaxf(x, y), z); };
-    // one 32-key block out of LDS slot `sl`; general = the group's first block (sets the reference) or its ragged last one
-    auto attend = [&](const int sl, const int k0, const bool general) {
+    // one 32-key block out of LDS slot `sl`; general_c = the group's first block (sets the reference) or its ragged last one
+    auto attend = [&](const int sl, const int k0, auto general_c) {
         const f32x4* ks = kvs[sl];
         f32x4 st[QF][2];
 #pragma unroll
@@ -1190,48 +1175,17 @@ __global__ __launch_bounds__(256, 2) void enc_layer_lp4_k(const EncK p) {
             for (int qf = 0; qf < QF; ++qf) st[qf][kf] = mfma32_lp<DT>(fr[i % (LA + 1)], qB[qf][c], st[qf][kf]);  // S^T[key 16kf+4g+r][query li] - m
             __builtin_amdgcn_sched_barrier(0);
         }
-        const bool first = general && k0 == gs;
+        constexpr bool general = decltype(general_c)::value;
         if (general && k0 + 32 > ge) {  // (wave-uniform)
 #pragma unroll
             for (int qf = 0; qf < QF; ++qf)
 #pragma unroll
-                for (int kf = 0; kf < 2; ++kf)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        if (k0 + 16 * kf + 4 * g + r >= ge) st[qf][kf][r] = -__builtin_inff();
+                for (int kf = 0; kf < 2; ++kf) lp_mask(st[qf][kf], k0 + 16 * kf + 4 * g, ge);
         }
-        float mx[QF], mxa = -__builtin_inff();
-#pragma unroll
-        for (int qf = 0; qf < QF; ++qf) {
-            mx[qf] = max3(max3(max3(st[qf][0][0], st[qf][0][1], st[qf][0][2]), st[qf][0][3], st[qf][1][0]), max3(st[qf][1][1], st[qf][1][2], st[qf][1][3]), st[qf][1][1]);
-            mxa = fmaxf(mxa, mx[qf]);
-        }
-        if (first || __any(mxa > 10.f)) {
-#pragma unroll
-            for (int qf = 0; qf < QF; ++qf) {
-                if (!first && !__any(mx[qf] > 10.f)) continue;
-                float d = xmax(mx[qf]);          // how far the block's maximum lies above the reference
-                if (!first) {
-                    d = fmaxf(d, 0.f);           // (the reference only rises afterwards)
-                    const float alpha = __builtin_amdgcn_exp2f(-d);
-                    ol[qf] *= alpha;
-#pragma unroll
-                    for (int nt = 0; nt < DC; ++nt) o[qf][nt] *= alpha;
-                }
-                negm[qf] -= d;
-                st[qf][0] -= d;
-                st[qf][1] -= d;
-            }
-        }
+        lp_reference<DC, QF>(st, negm, o, ol, general && k0 == gs);
         f32x4 pB[QF];
 #pragma unroll
-        for (int qf = 0; qf < QF; ++qf) {
-#pragma unroll
-            for (int kf = 0; kf < 2; ++kf)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) st[qf][kf][r] = __builtin_amdgcn_exp2f(st[qf][kf][r]);
-            pB[qf] = pack8<DT>(st[qf][0], st[qf][1]);  // keys {4g+r} U {16+4g+r} of the block: the order V^T blocks are stored in
-        }
+        for (int qf = 0; qf < QF; ++qf) pB[qf] = lp_weights<DT>(st[qf]);
 #pragma unroll
         for (int nt = 0; nt < DC; ++nt) {
             const int i = 2 * KC + nt;
@@ -1251,7 +1205,7 @@ __global__ __launch_bounds__(256, 2) void enc_layer_lp4_k(const EncK p) {
     //      that the loop body is one straight path ----
     auto step = [&](const int j, auto general_c) {
         if (j + PD < nblk) gload(j + PD, (j + PD) % NS);
-        attend(j % NS, gs + 32 * j, decltype(general_c)::value);
+        attend(j % NS, gs + 32 * j, general_c);
         // block j + 1 must have landed: the fetches of blocks j + 2 .. j + PD issued behind it may still be in flight (3 loads each)
         const int rem = nblk - 1 - j;
         if (rem >= PD) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * (PD - 1)) : "memory");
@@ -1268,36 +1222,7 @@ __global__ __launch_bounds__(256, 2) void enc_layer_lp4_k(const EncK p) {
     //      its four) need 316 registers; the weights (90 KB) are re-read per fragment, 1 % of what the key loop streams ----
 #pragma unroll
     for (int qf = 0; qf < QF; ++qf) {
-        f32x4 oB[1][KC];
-        {
-            const float inv = 1.f / xsum(ol[qf][0]);  // l sits in row 0 of the ones tile (lane g = 0, register 0); rows 4g of g > 0 are zero
-#pragma unroll
-            for (int c = 0; c < KC; ++c) oB[0][c] = pack8<DT>(o[qf][2 * c] * inv, o[qf][2 * c + 1] * inv);
-        }
-        f32x4 x1[DC];
-        gemm_T_lp<DC, KC, 1, DT>(p.w_out_lp, vec + V::BOUT, csp, oB, li, g, [&](int nt, int, f32x4 a) {
-            x1[nt] = nt < CSR ? ld4(p.src + (size_t)qrow[qf] * cs + 16 * nt + 4 * g) + a : a;  // (features >= cs: zero weights -> a = 0)
-        });
-        f32x4 x1B[1][KC];
-        layer_norm<DC>(x1, vec + V::LN1W, vec + V::LN1B, p.d, p.ln_eps, g);
-#pragma unroll
-        for (int c = 0; c < KC; ++c) x1B[0][c] = pack8<DT>(x1[2 * c], x1[2 * c + 1]);
-        f32x4 hB[1][FKC];
-        {
-            f32x4 hprev;
-            gemm_T_lp<FC, KC, 1, DT>(p.w1_lp, vec + V::B1, csp, x1B, li, g, [&](int ft, int, f32x4 a) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) a[r] = fmaxf(a[r], 0.f);
-                if (ft & 1) hB[0][ft >> 1] = pack8<DT>(hprev, a); else hprev = a;
-            });
-        }
-        gemm_T_lp<DC, FKC, 1, DT>(p.w2_lp, vec + V::B2, dff, hB, li, g, [&](int nt, int, f32x4 a) { x1[nt] += a; });
-        layer_norm<DC>(x1, vec + V::LN2W, vec + V::LN2B, p.d, p.ln_eps, g);
-        const int qtok = q0 + qf * 16 + li;
-        if (qtok < ge) {
-#pragma unroll
-            for (int nt = 0; nt < CSR; ++nt) *reinterpret_cast<f32x4*>(p.out + (size_t)qtok * cs + 16 * nt + 4 * g) = x1[nt];
-        }
+        lp_tail<DC, FC, 1, DT, CSR>(p, o + qf, ol + qf, qrow + qf, q0 + qf * 16, ge, li, g);
         __builtin_amdgcn_sched_barrier(0);
     }
 }
@@ -1336,6 +1261,19 @@ int fill(const i2r_encoder_desc* d, EncK& k) {
     return I2R_OK;
 }
 
+// the (dtype, cs) choice of the 16-bit kernels as compile-time constants: f(DT, CSR) with DT = 1 bf16 | 2 f16, CSR = cs / 16 = 6 | 5
+template <typename F>
+void lp_form(int dtype, int cs, F f) {
+    using std::integral_constant;
+    if (dtype == 1) {
+        if (cs == 96) f(integral_constant<int, 1>{}, integral_constant<int, 6>{});
+        else f(integral_constant<int, 1>{}, integral_constant<int, 5>{});
+    } else {
+        if (cs == 96) f(integral_constant<int, 2>{}, integral_constant<int, 6>{});
+        else f(integral_constant<int, 2>{}, integral_constant<int, 5>{});
+    }
+}
+
 }  // namespace
 
 extern "C" int i2r_encoder_kv(const i2r_encoder_desc* d, void* stream) {
@@ -1347,14 +1285,9 @@ extern "C" int i2r_encoder_kv(const i2r_encoder_desc* d, void* stream) {
         constexpr int TB = I2R_KV_TB;
         const unsigned nblk = (unsigned)(TB == 2 ? d->n_qtiles64 : d->n_qtiles32);
         I2R_CHECK_ARG(nblk > 0, "i2r_encoder_kv: n_qtiles%d", TB == 2 ? 64 : 32);
-        const bool c6 = d->cs == 96;
-        if (d->dtype == 1) {
-            if (c6) i2r_launch((enc_kv_lp_k<6, 6, 1, TB>), dim3(nblk), dim3(64), 0, (hipStream_t)stream, k);
-            else i2r_launch((enc_kv_lp_k<6, 5, 1, TB>), dim3(nblk), dim3(64), 0, (hipStream_t)stream, k);
-        } else {
-            if (c6) i2r_launch((enc_kv_lp_k<6, 6, 2, TB>), dim3(nblk), dim3(64), 0, (hipStream_t)stream, k);
-            else i2r_launch((enc_kv_lp_k<6, 5, 2, TB>), dim3(nblk), dim3(64), 0, (hipStream_t)stream, k);
-        }
+        lp_form(d->dtype, d->cs, [&](auto DT, auto CSR) {
+            i2r_launch((enc_kv_lp_k<6, decltype(CSR)::value, decltype(DT)::value, TB>), dim3(nblk), dim3(64), 0, (hipStream_t)stream, k);
+        });
     } else {
         I2R_CHECK_ARG(d->n_qtiles16 > 0, "i2r_encoder_kv: n_qtiles16");
         if (d->cs == 96)
@@ -1366,14 +1299,6 @@ extern "C" int i2r_encoder_kv(const i2r_encoder_desc* d, void* stream) {
     return I2R_OK;
 }
 
-namespace {
-template <int QF, int DT>
-void launch_lp(const EncK& k, bool c6, unsigned grid, hipStream_t st) {
-    if (c6) i2r_launch((enc_layer_lp_k<6, 12, QF, DT, 6>), dim3(grid), dim3(64), 0, st, k);
-    else i2r_launch((enc_layer_lp_k<6, 12, QF, DT, 5>), dim3(grid), dim3(64), 0, st, k);
-}
-}  // namespace
-
 extern "C" int i2r_encoder_layer(const i2r_encoder_desc* d, void* stream) {
     EncK k;
     int rc = fill(d, k);
@@ -1381,34 +1306,28 @@ extern "C" int i2r_encoder_layer(const i2r_encoder_desc* d, void* stream) {
     if (d->dtype != 0) {
         // 64 queries per wave when that still gives >= 2 waves per SIMD-pair of the chip, else 16 (more, shorter waves)
         const bool big = d->n_qtiles64 >= 512;
-        k.n_qblk = big ? d->n_qtiles64 : d->n_qtiles16;
-        const unsigned grid = (unsigned)((k.n_qblk + 7) / 8 * 8);  // (XCD-banded work items inside the kernel)
-        const bool c6 = d->cs == 96;
 #ifdef I2R_TUNING
         static const int qf_env = getenv("I2R_ENC_QF") ? atoi(getenv("I2R_ENC_QF")) : 0;  // tuning switch: 2 = 32 queries per wave
-        if (qf_env == 2 && big) {
-            k.n_qblk = d->n_qtiles32;
-            const unsigned g2 = (unsigned)((d->n_qtiles32 + 7) / 8 * 8);
-            if (d->dtype == 1) launch_lp<2, 1>(k, c6, g2, (hipStream_t)stream); else launch_lp<2, 2>(k, c6, g2, (hipStream_t)stream);
-            I2R_CHECK_LAUNCH("i2r_encoder_layer");
-            return I2R_OK;
-        }
 #endif
-        if (big && d->n_qtiles192 > 0) {  // long groups: four waves per workgroup share the K / V stream through LDS (two workgroups per CU)
-            k.n_qblk = d->n_qtiles192;
-            const unsigned g4 = (unsigned)((d->n_qtiles192 + 7) / 8 * 8);
-            if (d->dtype == 1) {
-                if (c6) i2r_launch((enc_layer_lp4_k<6, 12, 1, 6>), dim3(g4), dim3(256), 0, (hipStream_t)stream, k);
-                else i2r_launch((enc_layer_lp4_k<6, 12, 1, 5>), dim3(g4), dim3(256), 0, (hipStream_t)stream, k);
+        lp_form(d->dtype, d->cs, [&](auto DT, auto CSR) {
+            constexpr int dt = decltype(DT)::value, csr = decltype(CSR)::value;
+            // work items are XCD-banded inside the kernels: a multiple of 8 workgroups
+            auto one_wave = [&](auto QF, int items) {
+                k.n_qblk = items;
+                i2r_launch((enc_layer_lp_k<6, 12, decltype(QF)::value, dt, csr>), dim3((unsigned)((items + 7) / 8 * 8)), dim3(64), 0, (hipStream_t)stream, k);
+            };
+#ifdef I2R_TUNING
+            if (qf_env == 2 && big) return one_wave(std::integral_constant<int, 2>{}, d->n_qtiles32);
+#endif
+            if (big && d->n_qtiles192 > 0) {  // long groups: four waves per workgroup share the K / V stream through LDS (two workgroups per CU)
+                k.n_qblk = d->n_qtiles192;
+                i2r_launch((enc_layer_lp4_k<6, 12, dt, csr>), dim3((unsigned)((d->n_qtiles192 + 7) / 8 * 8)), dim3(256), 0, (hipStream_t)stream, k);
+            } else if (big) {
+                one_wave(std::integral_constant<int, 4>{}, d->n_qtiles64);
             } else {
-                if (c6) i2r_launch((enc_layer_lp4_k<6, 12, 2, 6>), dim3(g4), dim3(256), 0, (hipStream_t)stream, k);
-                else i2r_launch((enc_layer_lp4_k<6, 12, 2, 5>), dim3(g4), dim3(256), 0, (hipStream_t)stream, k);
+                one_wave(std::integral_constant<int, 1>{}, d->n_qtiles16);
             }
-        } else if (d->dtype == 1) {
-            if (big) launch_lp<4, 1>(k, c6, grid, (hipStream_t)stream); else launch_lp<1, 1>(k, c6, grid, (hipStream_t)stream);
-        } else {
-            if (big) launch_lp<4, 2>(k, c6, grid, (hipStream_t)stream); else launch_lp<1, 2>(k, c6, grid, (hipStream_t)stream);
-        }
+        });
         I2R_CHECK_LAUNCH("i2r_encoder_layer");
         return I2R_OK;
     }

@@ -1257,6 +1257,81 @@ def test_encoder_layer_low_precision(precision, d, length, hw, period):
         assert out.t.view(-1, out.cs)[:, 78:].abs().max().item() == 0.0  # pad channels stay exactly zero
 
 
+# Token groups that reach the long-group branch of i2r_encoder_layer (n_qtiles64 >= 512) with a few dozen tokens per group, and every
+# special case of its key loop: hw, crops per group.
+_LONG_GROUP_CASES = {
+    # 16-token groups: one block that is both first and ragged; 32-token groups: one full block (nblk = 1 either way); three of the four
+    # waves of a workgroup have no query
+    "A": ((4, 4), [1] * 300 + [2] * 212),
+    # 35-token groups: nblk = 2 with 3 ragged keys; 420 / 245 / 210 tokens: 14 / 8 / 7 blocks (the four-slot ring wraps), ragged ends of
+    # 4 / 21 / 18 keys, groups of 3 and 2 workgroups whose last one has 36 and 53 queries; a long group first, in the middle and last
+    "B": ((5, 7), [12] + [1] * 250 + [7] + [1] * 250 + [6]),
+    # 192 tokens: exactly one workgroup, no ragged block; 96: nblk = the prefetch distance; 48: the last block exactly half masked
+    "C": ((6, 8), [4] + [2] * 100 + [1] * 310),
+}
+_long_group_inputs = {}
+
+
+def _long_group_case(case, d):
+    """state dict, features, per-token pos and the fp32 oracle of one (case, d), computed once: the oracle runs per class of group length
+    (padding 500+ groups to the longest one would make a [525, 420, 420] score tensor for nothing)"""
+    if (case, d) not in _long_group_inputs:
+        (h, w), length = _LONG_GROUP_CASES[case]
+        S = sum(length)
+        tag = "lg%s_%d" % (case, d)
+        sd = _encoder_sd(d, 192, tag)
+        feat = _rand((S, d, h, w), "f" + tag)
+        pos = _rand((S, d, h, w), "p" + tag, 0.5)
+        sd2 = {k.replace("L.", "E.layers.0."): v for k, v in sd.items()}
+        first, ref = [0], torch.empty_like(feat)
+        for n in length:
+            first.append(first[-1] + n)
+        for n in sorted(set(length)):
+            idx = torch.tensor([c for g, m in enumerate(length) if m == n for c in range(first[g], first[g + 1])])
+            ref[idx] = i2r_cpu.inter_human_encoder(sd2, "E", 1, feat[idx], pos[idx], [n] * (len(idx) // n))
+        _long_group_inputs[case, d] = (sd, feat, pos, ref)
+    return _long_group_inputs[case, d]
+
+
+@pytest.mark.parametrize("precision", ["bf16", "fp16"])
+@pytest.mark.parametrize("d", [96, 78])
+@pytest.mark.parametrize("case", sorted(_LONG_GROUP_CASES))
+def test_encoder_layer_low_precision_long_groups(precision, d, case):
+    """The two long-group forms of the 16-bit layer (n_qtiles64 >= 512) on short and ragged groups, vs the fp32 oracle at the bounds of
+    test_encoder_layer_low_precision: the engine's default -- four waves per 192 queries, K / V through the LDS ring -- and, with
+    n_qtiles192 = 0 on the same descriptors, one wave per 64 queries (QF = 4), which the engine itself never selects.  Both cut a group
+    into the fragments gs + 16k and run the same per-fragment arithmetic in the same order, so they agree bit for bit: torch.equal held
+    for all twelve cases before the kernels shared their code, and is what is asserted."""
+    (h, w), length = _LONG_GROUP_CASES[case]
+    sd, feat, pos, ref = _long_group_case(case, d)
+    P = engine.Program(torch.device(DEV))
+    L = engine.Packer(sd, torch.device(DEV), precision).encoder_layer("L", d, 192)
+    offs = [0]
+    for n in length:
+        offs.append(offs[-1] + n * h * w)
+    fa, pa = to_act(P, feat), to_act(P, pos)
+    outs = []
+    for four_waves in (True, False):
+        out = P.encoder(fa, [L], offs, pos=pa.ptr)
+        desc = P.ops[-1][2]
+        assert desc.dtype != 0 and desc.n_qtiles64 >= 512 and desc.n_qtiles192 > 0
+        if not four_waves:
+            desc.n_qtiles192 = 0  # (one descriptor serves the K/V launch and the layer launch; the K/V kernel does not read the field)
+        outs.append(out)
+    run(P)
+    tol_max, tol_mean = (0.12, 0.012) if precision == "bf16" else (0.02, 0.002)
+    got = [from_act(o) for o in outs]
+    errs = [(g - ref).abs() for g in got]
+    print("long groups %s d=%d %s: four-wave max %.4f mean %.5f, one-wave max %.4f mean %.5f, equal %s, rms(a-b) %.3e rms(a-ref) %.3e" % (
+        case, d, precision, errs[0].max().item(), errs[0].mean().item(), errs[1].max().item(), errs[1].mean().item(), torch.equal(*got),
+        (got[0] - got[1]).pow(2).mean().sqrt().item(), errs[0].pow(2).mean().sqrt().item()))
+    for o, err in zip(outs, errs):
+        assert err.max().item() < tol_max and err.mean().item() < tol_mean, (err.max().item(), err.mean().item())
+        if d == 78:
+            assert o.t.view(-1, o.cs)[:, 78:].abs().max().item() == 0.0  # pad channels stay exactly zero
+    assert torch.equal(outs[0].view(), outs[1].view())
+
+
 def test_run_program_timed_same_results_and_positive_durations():
     """i2r_run_program_timed (include/i2r_hip.h): the replay whose launches carry timing events -- bench.py's in-situ measurement hook --
     writes exactly what i2r_run_program writes, every launch's elapsed(start, stop) is positive and below the replay's wall time, and the
