@@ -208,6 +208,35 @@ I2R_API int i2r_flip_merge(const float* y, const float* y_flipped, const int32_t
 I2R_API int i2r_decode(const float* heatmaps, const float* center, const float* scale, float* preds, float* maxvals, int32_t n,
                int32_t joints, int32_t h, int32_t w, int32_t blur_kernel, int32_t transform_back, void* stream);
 
+/* i2r_joint_tokens -- heat maps to the query tables of i2r_attn_query_maps, on the device (additive: I2R_ABI_VERSION unchanged): the
+ * literal get_max_preds (lib/core/inference.py:20-48) of every map, with the arg-max of i2r_decode (first index wins a tie; a map whose
+ * maximum is not > 0 gives the point (0, 0): pred_mask), scaled to the crop's network input and mapped onto the token map of up to
+ * I2R_MAX_TOKEN_TABLES encoder stacks the way visualize.py:194-196 does.  With (px, py) the arg-max pixel of map (s, j):
+ *   points[s, j]  = (px * in_stride, py * in_stride)    fp32 [n_crops, joints, 2], optional (NULL)
+ *   maxvals[s, j] = the map's maximum                   fp32 [n_crops, joints],    optional (NULL)
+ *   table t:  tokens[crop_group[s] * K + crop_slot[s] * joints + j] = crop_slot[s] * fh * fw + row * fw + col,
+ *             row = min(py * in_stride / down, fh - 1), col = min(px * in_stride / down, fw - 1)   (integer division)
+ *   heatmaps  device fp32 [n_crops, joints, hh, hw] (NCHW, dense: what i2r_head and i2r_flip_merge write); in_stride: input pixels
+ *             per heat-map pixel
+ *   tokens    device int32 [n_grp, K], K >= joints the row stride: the q_tok of the stack's i2r_attn_query_maps launches.  The WHOLE
+ *             table is set to -1 (a skipped entry) ahead of the kernel, so every entry no crop writes reads -1 afterwards
+ *   crop_group, crop_slot  device int32 [n_crops]: the group of crop s in that stack and its place among the group's persons (an
+ *             intra-human stack: (s, 0); the inter-human stack: (image, person)).  The host entry point cannot check a device
+ *             table: the kernel skips the write of a crop whose group is outside [0, n_grp) or whose slot is negative or does not
+ *             fit the row ((slot + 1) * joints > K) -- it forms no address from an entry it has not checked
+ *   fh, fw, down  the stack's token map and its down rate (input pixels per token)
+ * One wave per map, a 64-lane butterfly, no LDS, no atomics, vector stores only: deterministic.  n_tables == 0 writes points / maxvals
+ * only.  I2R_E_ARG (nothing is launched or set): null a / heatmaps / table pointers, no output at all, n_crops, joints, hh, hw or
+ * in_stride < 1, hh * hw or max(hh, hw) * in_stride beyond 2^31 - 1, n_tables outside 0 .. 2, a table with n_grp, fh, fw or down < 1,
+ * K < joints or n_grp * K or (K / joints) * fh * fw beyond 2^31 - 1, n_crops * joints beyond 2^31 - 1 (the grid). */
+#define I2R_MAX_TOKEN_TABLES 2
+typedef struct i2r_token_table { int32_t* tokens; const int32_t* crop_group; const int32_t* crop_slot; int32_t n_grp, K, fh, fw, down, reserved; } i2r_token_table;
+typedef struct i2r_joint_tokens_args {
+    const float* heatmaps; float* points; float* maxvals; i2r_token_table table[I2R_MAX_TOKEN_TABLES /* 2 */];
+    int32_t n_crops, joints, hh, hw, in_stride, n_tables;
+} i2r_joint_tokens_args;
+I2R_API int i2r_joint_tokens(const i2r_joint_tokens_args* a, void* stream);
+
 /* i2r_pose_nms -- what every dataset class of the reference does with the decoded key points before it writes a result: the per-person
  * rescoring (lib/dataset/coco.py:384-396, same block in crowdpose.py / ochuman.py / coco_ochuman.py) and the per-image OKS-NMS or
  * soft-OKS-NMS (lib/nms/nms.py:75-181).  One workgroup per image.

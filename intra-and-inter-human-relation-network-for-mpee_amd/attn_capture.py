@@ -46,6 +46,21 @@ class PersonMaps:
             raise ValueError("upsample %r (1 .. 64)" % (upsample,))
 
 
+class JointQueries:
+    """The joint form of an attention-map capture (Engine.forward(..., capture=, joints=)): the query form whose points are the joints
+    the SAME forward predicts.  The token tables are made on the device from the call's own (flip-merged) heat maps -- arg-max of every
+    map as i2r_decode takes it, x 4, (int(y / down_rate), int(x / down_rate)) -- by i2r_joint_tokens, and the i2r_attn_query_maps
+    launches run behind the head instead of inside their layers: no second forward, no copy to the host.  K = the model's joints; the
+    inter-human stack gets all joints of all persons of the image as queries (entry person * J + j), as AttnQueries does with points.
+    mode, upsample: as AttnQueries.  Cost: every captured layer keeps its fp32 q|k activation [tokens, 2 hs] until the program ends."""
+
+    def __init__(self, mode="dependency", upsample=1):
+        if mode not in AttnQueries.MODES:
+            raise ValueError("mode %r: 'dependency' or 'affect'" % (mode,))
+        self.mode = AttnQueries.MODES[mode]
+        self.upsample = {st: int(r) for st, r in upsample.items()} if isinstance(upsample, dict) else int(upsample)
+
+
 # One set of blocks of a layer's part of the per-call buffer: group g's block starts offs[g] floats behind the set, the set `base` floats
 # behind the layer; shapes: the view of every group's block, None for a set nobody reads (person maps in mode 0).
 Block = collections.namedtuple("Block", "offs base shapes")
@@ -63,7 +78,9 @@ class Plan:
     n_tiles: int = 0
     n_col_tiles: int = 0
     K: int = 1
-    tables: tuple = ()  # host int32 tensors the launches read on the device (query maps: tokens [groups, K], counts [groups])
+    # host int32 tensors the launches read on the device (query maps: tokens [groups, K], counts [groups]); a shape instead of a tensor:
+    # an int32 table of that shape which the device fills itself (joint form: the tokens; its third table maps crops to entries)
+    tables: tuple = ()
 
 
 def _layer(*sets):
@@ -91,6 +108,7 @@ class Form:
     """what the three forms share; a form is made per call (resolve), and a program keeps the one it was built with"""
     N_BLOCKS = 1  # block sets per layer = device offset tables per capture
     call = None   # what bind_capture hands to plan() per call
+    deferred = False  # True: a captured layer keeps its q|k and emits nothing; the engine runs the form's launches behind the program
 
     def __init__(self, capture, suffix=()):
         self.capture, self.key = capture, ("capture", capture) + suffix  # (key: the part of the program key behind the shape)
@@ -157,7 +175,7 @@ class QueryForm(Form):
 
     def plan(self, stack, hw, lens, heads, call=None):
         """call: the AttnQueries of this call -- tokens[stack] int32 [groups, K] (-1 = skip), optionally counts[stack] (entries per group)"""
-        mode, scale, (h, w) = self.mode, self.scales[stack], hw
+        scale = self.scales[stack]
         tok = torch.as_tensor(call.tokens[stack]).to("cpu", torch.int32).contiguous()
         if tok.dim() != 2 or tok.shape[0] != len(lens) or tok.shape[1] < 1:
             raise ValueError("query tokens of %r: shape %s, expected [%d groups, K]" % (stack, tuple(tok.shape), len(lens)))
@@ -169,17 +187,47 @@ class QueryForm(Form):
         for g, (n, c) in enumerate(zip(lens, cnt)):
             if int(tok[g, :c].max()) >= n:
                 raise ValueError("query token %d of group %d of %r is outside its %d tokens" % (int(tok[g, :c].max()), g, stack, n))
+        return self._layout(scale, hw, lens, heads, K, cnt, (tok, torch.tensor(cnt, dtype=torch.int32)))
+
+    def _layout(self, scale, hw, lens, heads, K, cnt, tables):
+        """the plan of groups of lens tokens that use cnt of the K entries of their table rows"""
+        mode, (h, w) = self.mode, hw
         assert all(n % (h * w) == 0 for n in lens)
         blocks, n_layer = _layer([(c, n // (h * w), h * scale, w * scale) for n, c in zip(lens, cnt)])
         stride = _stride(heads, lens)
         tiles = (_tiles(cnt, lens), 0) if mode == 0 else (_tiles(lens, lens), _tiles(lens, cnt, 16))
         return Plan(len(lens), stride, stride * (len(lens) * K if mode == 0 else sum(lens)), K * sum(lens) if scale > 1 else 1, blocks, n_layer,
-                    *tiles, K=K, tables=(tok, torch.tensor(cnt, dtype=torch.int32)))
+                    *tiles, K=K, tables=tables)
 
     @staticmethod
     def patch(a, p, out, ws, rows, tables, host_off):
-        a.out, a.ws, a.rows, (a.q_tok, a.q_cnt), a.grp_off_host = out, ws, rows, tables, host_off
+        a.out, a.ws, a.rows, (a.q_tok, a.q_cnt), a.grp_off_host = out, ws, rows, tables[:2], host_off
         a.n_grp, a.n_tiles, a.n_col_tiles, a.ws_stride, a.K = p.n_grp, p.n_tiles, p.n_col_tiles, p.ws_stride, p.K
+
+
+class JointForm(QueryForm):
+    """the query form at the joints the same forward predicts (JointQueries): the tables are made on the device behind the head
+    (i2r_joint_tokens), so the launches of the captured layers run there too -- a captured layer keeps its q|k activation and emits
+    nothing.  Key: the query form's with K = the model's joints, plus a marker."""
+    deferred = True
+
+    def __init__(self, capture, joints, n_joints):
+        QueryForm.__init__(self, capture, AttnQueries({st: () for st, _ in capture}, joints.mode, joints.upsample, capacity=n_joints))
+        self.key, self.call, self.J = self.key + ("joints",), joints, int(n_joints)
+
+    def plan(self, stack, hw, lens, heads, call=None):
+        """every group holds n / (h w) persons of J joints: counts and table width are known without the tokens, which are not validated
+        here (the kernels clamp a device table's entries).  tables: the token table's shape (the device fills it), the counts, and
+        [2, crops] = (group, slot in the group) of every crop for i2r_joint_tokens"""
+        J, pers = self.J, [n // (hw[0] * hw[1]) for n in lens]
+        crops = [(g, p) for g, n in enumerate(pers) for p in range(n)]
+        K = max(pers) * J
+        tables = ((len(lens), K), torch.tensor([n * J for n in pers], dtype=torch.int32), torch.tensor(crops, dtype=torch.int32).t().contiguous())
+        return self._layout(self.scales[stack], hw, lens, heads, K, [n * J for n in pers], tables)
+
+    @staticmethod
+    def result(views, inputs):
+        return views[0]  # (no copy of the stacks' inputs: nobody asks this form for them)
 
 
 class PersonForm(Form):
@@ -215,9 +263,19 @@ class PersonForm(Form):
         return tuple(views)  # (relation, maps)
 
 
-def resolve(capture, queries, persons, flip_joint_map, stacks, inter_stack, window):
+def resolve(capture, queries, persons, flip_joint_map, stacks, inter_stack, window, joints=None, n_joints=None):
     """What Engine.forward / forward_single were asked for -> the form of the call, None without a capture.  stacks: the engine's
-    capture_stacks(); inter_stack: the prefix of its inter-human stack; window: the inter-human block is the window type."""
+    capture_stacks(); inter_stack: the prefix of its inter-human stack; window: the inter-human block is the window type; joints: a
+    JointQueries of a model of n_joints joints -- the one form that goes with the flip test (its launches run behind the merge)."""
+    if joints is not None:
+        if window:
+            raise ValueError("joints=: ATTENTION_TYPE window has no encoder stack to capture")
+        if queries is not None or persons is not None:
+            raise ValueError("joints=: not with queries= or persons= (the joint form makes its own tables)")
+        if not stacks:
+            raise ValueError("joints=: this model has no encoder stack to capture")
+        if not capture:
+            raise ValueError("joints= needs capture=: the (stack, layer) set whose maps to query")
     if persons is not None:
         if window:
             raise ValueError("persons=: ATTENTION_TYPE window has no encoder stack to capture")
@@ -237,5 +295,7 @@ def resolve(capture, queries, persons, flip_joint_map, stacks, inter_stack, wind
     for st, i in capture:
         if st not in stacks or not 0 <= i < stacks[st]:
             raise ValueError("capture (%r, %d): this model's encoder stacks are %s" % (st, i, stacks))
+    if joints is not None:
+        return JointForm(capture, joints, n_joints)
     assert flip_joint_map is None and not window, "attention maps: no flip test, no window-type block"
     return PersonForm(capture, persons) if persons is not None else QueryForm(capture, queries) if queries is not None else FullForm(capture)

@@ -1,7 +1,8 @@
-// The two steps that follow the forward in the reference's validate() loop (NEXT #1/#2), on device:
+// The steps that follow the forward in the reference's validate() loop (NEXT #1/#2), on device:
 //   i2r_flip_merge  flip-test merge: (y + flip_back(y_flipped)) * 0.5        lib/core/function.py:142-162, utils/transforms.py:16-30
 //   i2r_decode      heatmap -> keypoints (DarkPose decode)                   lib/core/inference.py:20-112, utils/transforms.py:50-101
-// Both are tiny, HBM/LDS-bound kernels; they remove the D2H copy of every heatmap and a Python double loop over S x J.
+//   i2r_joint_tokens  heatmap -> arg-max points and the query-token tables of i2r_attn_query_maps   lib/core/inference.py:20-48, visualize.py:194-196
+// All are tiny, HBM/LDS-bound kernels; they remove the D2H copy of every heatmap and a Python double loop over S x J.
 #include "i2r_common.h"
 
 namespace {
@@ -131,7 +132,81 @@ __global__ __launch_bounds__(256) void decode_k(const float* __restrict__ hm, co
     maxvals[sj] = origin_max;
 }
 
+// get_max_preds (inference.py:20-48) of every map -> points, maxvals and the query-token tables of the encoder stacks.  One wave per
+// (crop, joint) map, four maps per workgroup; the arg-max is decode_k's (amax2, the same butterfly), so the two agree on every tie.
+struct TokenTables {
+    i2r_token_table t[I2R_MAX_TOKEN_TABLES];
+    int n;
+};
+__global__ __launch_bounds__(256) void joint_tokens_k(const float* __restrict__ hm, float* __restrict__ points, float* __restrict__ maxvals,
+                                                      TokenTables tabs, int n_maps, int J, int hw, int w, int in_stride) {
+    const int lane = threadIdx.x & 63;
+    const long long map = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (map >= n_maps) return;  // (wave-uniform)
+    const float* src = hm + (size_t)map * hw;
+    ArgMax am = {-__builtin_inff(), 0x7fffffff};
+    for (int i = lane; i < hw; i += 64) am = amax2(am, ArgMax{src[i], i});
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) am = amax2(am, ArgMax{__shfl_xor(am.v, o), __shfl_xor(am.i, o)});
+    if (lane != 0) return;
+    int px = 0, py = 0;
+    if (am.v > 0.f) { px = am.i % w; py = am.i / w; }  // pred_mask (inference.py:42-45); a map of NaNs keeps the sentinel index: (0, 0) too
+    px *= in_stride;
+    py *= in_stride;
+    if (points) {
+        points[(size_t)map * 2] = (float)px;
+        points[(size_t)map * 2 + 1] = (float)py;
+    }
+    if (maxvals) maxvals[map] = am.v;
+    const int s = (int)(map / J), j = (int)(map - (long long)s * J);
+    for (int t = 0; t < tabs.n; ++t) {
+        const i2r_token_table& T = tabs.t[t];
+        const int g = T.crop_group[s], slot = T.crop_slot[s];
+        if (g < 0 || g >= T.n_grp || slot < 0 || ((long long)slot + 1) * J > T.K) continue;  // (a wrong device table costs entries, never a store outside)
+        const int row = min(py / T.down, T.fh - 1), col = min(px / T.down, T.fw - 1);
+        T.tokens[(size_t)g * T.K + slot * J + j] = slot * T.fh * T.fw + row * T.fw + col;
+    }
+}
+
 }  // namespace
+
+extern "C" int i2r_joint_tokens(const i2r_joint_tokens_args* a, void* stream) {
+    I2R_CHECK_ARG(a && a->heatmaps, "i2r_joint_tokens: null pointer");
+    I2R_CHECK_ARG(a->n_crops >= 1 && a->joints >= 1 && a->hh >= 1 && a->hw >= 1 && a->in_stride >= 1,
+                  "i2r_joint_tokens: n_crops=%d joints=%d heatmap %dx%d in_stride=%d", a->n_crops, a->joints, a->hh, a->hw, a->in_stride);
+    I2R_CHECK_ARG(a->n_tables >= 0 && a->n_tables <= I2R_MAX_TOKEN_TABLES, "i2r_joint_tokens: n_tables=%d (0 .. %d)", a->n_tables,
+                  I2R_MAX_TOKEN_TABLES);
+    I2R_CHECK_ARG(a->n_tables > 0 || a->points || a->maxvals, "i2r_joint_tokens: null pointer (no output)");
+    const long long n_maps = (long long)a->n_crops * a->joints, pix = (long long)a->hh * a->hw;
+    I2R_CHECK_ARG(pix <= 0x7fffffffLL && (long long)(a->hh > a->hw ? a->hh : a->hw) * a->in_stride <= 0x7fffffffLL,
+                  "i2r_joint_tokens: heatmap %dx%d at in_stride=%d exceeds the index range", a->hh, a->hw, a->in_stride);
+    I2R_CHECK_ARG(n_maps <= 0x7fffffffLL, "i2r_joint_tokens: %lld maps exceed the grid limit", n_maps);
+    TokenTables tabs;
+    tabs.n = a->n_tables;
+    for (int t = 0; t < I2R_MAX_TOKEN_TABLES; ++t) {
+        tabs.t[t] = t < a->n_tables ? a->table[t] : i2r_token_table{};
+        if (t >= a->n_tables) continue;
+        const i2r_token_table& T = a->table[t];
+        I2R_CHECK_ARG(T.tokens && T.crop_group && T.crop_slot, "i2r_joint_tokens: null pointer (table %d)", t);
+        I2R_CHECK_ARG(T.n_grp >= 1 && T.fh >= 1 && T.fw >= 1 && T.down >= 1, "i2r_joint_tokens: table %d: n_grp=%d token map %dx%d down=%d", t,
+                      T.n_grp, T.fh, T.fw, T.down);
+        I2R_CHECK_ARG(T.K >= a->joints, "i2r_joint_tokens: table %d: K=%d < joints=%d", t, T.K, a->joints);
+        I2R_CHECK_ARG((long long)T.n_grp * T.K <= 0x7fffffffLL && (long long)(T.K / a->joints) * T.fh * T.fw <= 0x7fffffffLL,
+                      "i2r_joint_tokens: table %d: n_grp=%d K=%d, %d persons of %dx%d tokens exceed the index range", t, T.n_grp, T.K,
+                      T.K / a->joints, T.fh, T.fw);
+    }
+    for (int t = 0; t < a->n_tables; ++t) {  // -1 = skip: what no crop writes
+        const hipError_t e = hipMemsetAsync(a->table[t].tokens, 0xFF, (size_t)a->table[t].n_grp * a->table[t].K * sizeof(int32_t), (hipStream_t)stream);
+        if (e != hipSuccess) {
+            i2r_set_error("i2r_joint_tokens: memset of table %d: %s", t, hipGetErrorString(e));
+            return I2R_E_LAUNCH;
+        }
+    }
+    i2r_launch(joint_tokens_k, dim3((unsigned)((n_maps + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a->heatmaps, a->points, a->maxvals, tabs,
+               (int)n_maps, a->joints, (int)pix, a->hw, a->in_stride);
+    I2R_CHECK_LAUNCH("i2r_joint_tokens");
+    return I2R_OK;
+}
 
 extern "C" int i2r_flip_merge(const float* y, const float* y_flipped, const int32_t* joint_map, float* out, int32_t n, int32_t joints,
                               int32_t h, int32_t w, void* stream) {

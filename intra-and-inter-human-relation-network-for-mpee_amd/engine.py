@@ -11,7 +11,7 @@ import os
 import torch
 
 from . import attn_capture, cabi
-from .attn_capture import AttnQueries, PersonMaps  # noqa: F401 (the capture forms' public classes stay importable from here)
+from .attn_capture import AttnQueries, JointQueries, PersonMaps  # noqa: F401 (the capture forms' public classes stay importable from here)
 from .pack import (PRECISIONS, PackedConv, Packer, _m16, _r16, fold_bn, pack_frag, pack_frag32, pack_k4, pack_k8,  # noqa: F401 (the packing names stay importable from here)
                    winograd_weights)
 
@@ -700,8 +700,8 @@ class Program:
             if cap is not None and i in capture["layers"]:  # q|k of the fused layer's input, projected again in fp32 (the fused kernels keep it on chip)
                 mh = capture["layers"][i]
                 qk = self.conv(cur, mh["qk"], in2=pos_act, lane=lane)
-                self._capture_layer(cap, i, qk, mh, goff, lane)
-                self.release(qk)
+                if not self._capture_layer(cap, i, qk, mh, goff, lane):
+                    self.release(qk)
             out = self.alloc(x.n, x.h, x.w, x.c)
             d = cabi.EncoderDesc()
             d.src, d.pos = cur.ptr, (pos if pos else None)
@@ -744,8 +744,7 @@ class Program:
             assert L["cs"] == x.cs
             qk_in = self.layernorm(cur, L["ln1"], eps=1e-5, lane=lane) if pre_norm else cur
             qk = self.conv(qk_in, L["qk"], in2=pos_act, lane=lane)
-            if cap is not None and i in capture["layers"]:
-                self._capture_layer(cap, i, qk, L, goff, lane)
+            held = cap is not None and i in capture["layers"] and self._capture_layer(cap, i, qk, L, goff, lane)
             v = self.conv(cur, L["v"], lane=lane)
             if pre_norm:
                 self.release(qk_in)
@@ -753,7 +752,7 @@ class Program:
             a = cabi.MhAttnArgs(qk.ptr, v.ptr, att.ptr, goff.data_ptr(), 0, L["heads"], L["hp"], L["hs"], qk.cs, v.cs, att.cs, 0, 0, 0)
             self.ops.append((cabi.OP_MH_ATTN, lane, a))
             mh_args.append(a)
-            self.release(qk, v)
+            self.release(*((v,) if held else (qk, v)))
             x1 = self.conv(att, L["o"], res1=cur, lane=lane)  # src + attention
             self.release(att)
             if cur is not x:
@@ -802,6 +801,8 @@ class Program:
     # A capture program computes, next to its usual outputs, the attention maps of the requested encoder layers in the form it was built
     # with (attn_capture: full [L, L] maps, rows / columns at query points, reductions per person) into ONE per-call buffer.  The launch list
     # is fixed at build time; bind_capture() patches the per-call part and uploads the offsets of the groups' blocks, like set_groups() does.
+    # A deferred form (the joint form) keeps its launches out of the list: they need the heat maps of the same call, so the engine issues
+    # them behind the run (Engine._joint_queries) on the q|k the captured layers kept.
     def _capture_begin(self, capture, x):
         if not capture:
             return None
@@ -811,11 +812,15 @@ class Program:
         return cap
 
     def _capture_layer(self, cap, i, qk, L, goff, lane):
+        """the launch of captured layer i on its q|k activation -> True when q|k must be held (a deferred form), else the caller releases it"""
         assert qk.dt == 0 and qk.cs >= 2 * L["hs"]
         self.keep.append(L)
         kind, a = self.form.launch(cap, qk, L, goff)
-        self.ops.append((kind, lane, a))
         cap["ops"].append((i, a))
+        if self.form.deferred:  # the engine runs the launch behind the program: q|k stays out of the pool until the program ends
+            return True
+        self.ops.append((kind, lane, a))
+        return False
 
     def bind_capture(self, glens, call=None):
         """glens: per capture (program order) the token count of every group to compute (the real images / crops of this call, a prefix of
@@ -836,7 +841,8 @@ class Program:
         for cap, lens, p in zip(self.captures, glens, plans):
             for off, blk in zip(cap["off"], p.blocks):
                 off[:len(lens)].copy_(torch.tensor(blk.offs[:-1], dtype=torch.int64).pin_memory(), non_blocking=True)
-            tables = [t.pin_memory().to(self.device, non_blocking=True) for t in p.tables]
+            tables = cap["tables"] = [t.pin_memory().to(self.device, non_blocking=True) if torch.is_tensor(t) else
+                                      torch.empty(t, dtype=torch.int32, device=self.device) for t in p.tables]
             host_off = (C.c_int32 * (len(lens) + 1))(*cap["grouping"]["current"][:len(lens) + 1])  # (the query and person launches read it)
             held += tables + [host_off]
             ptrs = (ws.data_ptr(), rows.data_ptr(), [t.data_ptr() for t in tables], C.cast(host_off, C.c_void_p))
@@ -2129,7 +2135,7 @@ class Engine:
     MAX_PROGRAMS = 48
     MAX_PROGRAM_BYTES = 32 << 30
 
-    def forward(self, x, pos_mask, length, flip_joint_map=None, capture=None, queries=None, persons=None):
+    def forward(self, x, pos_mask, length, flip_joint_map=None, capture=None, queries=None, persons=None, joints=None):
         """flip_joint_map (device int32 [J], see caller.joint_map): run the flip test in the same forward and return the merged
         'multi' heatmaps (the reference merges only outputs['multi'], function.py:137-162).
         capture: a set of (stack, layer) -- stack a state-dict prefix of capture_stacks() -- whose attention maps to return as well:
@@ -2144,16 +2150,25 @@ class Engine:
         persons (PersonMaps, with capture of layers of the inter-human stack only): instead of the [L, L] maps, their reduction per person
         -> (output, (relation, maps)): relation[(stack, layer)] = per image the [P, P] matrix, maps[(stack, layer)] = per image a
         [P, P, h r, w r] view (persons.mode 1: dependency maps, 2: affect maps, 0: no entry).  One program per (capture set, mode, scale);
-        another grouping at the same capacity reuses it.  ValueError: another stack, the window-type block, the flip test, queries."""
+        another grouping at the same capacity reuses it.  ValueError: another stack, the window-type block, the flip test, queries.
+        joints (JointQueries, with capture): the query form at the joints THIS forward predicts -> (output, (joints, maxvals, maps)):
+        joints [S, J, 2] = 4 x the arg-max (x, y) of every 'multi' heat map (i2r_decode's arg-max: first index, (0, 0) for a map without a
+        positive value), maxvals [S, J], both on the device; maps as for queries with K = J (the inter-human stack: entry person * J + j).
+        i2r_joint_tokens makes the token tables from the heat maps and the i2r_attn_query_maps launches of the captured layers run behind
+        the head, on the current stream, with no copy to the host in between.  It is the one form that goes with flip_joint_map: the
+        program is the flip program, the tables come from the MERGED maps, the launches cover the plain half (the first groups of each
+        stack); the mirrored pass's maps are not computed.  Every captured layer holds its fp32 q|k [tokens, 2 hs] until the program ends.
+        One program per (capture set, mode, J, scales).  ValueError: the window-type block, queries= or persons= too, no encoder stack."""
         assert x.dim() == 4 and x.shape[1] == 3 and x.dtype == torch.float32
         S, _, H, W = x.shape
         assert S == sum(length), "sum(length)=%d != number of crops %d" % (sum(length), S)
         assert all(n >= 1 for n in length), "every image needs at least one person"
         sine_n = max(length)  # (MULTI_POS_EMBEDDING sine: the canvas is max(length) persons wide, for every part of this batch)
-        form = attn_capture.resolve(capture, queries, persons, flip_joint_map, self.capture_stacks(), self.inter_stack, self.window_attn)
+        form = attn_capture.resolve(capture, queries, persons, flip_joint_map, self.capture_stacks(), self.inter_stack, self.window_attn,
+                                    joints, self.cfg["MODEL"]["NUM_JOINTS"])
         if form:
             with torch.cuda.device(self.device):
-                return self._forward_part(x, pos_mask, list(length), None, S, H, W, sine_n, form=form)
+                return self._forward_part(x, pos_mask, list(length), flip_joint_map if form.deferred else None, S, H, W, sine_n, form=form)
         if self.window_attn and flip_joint_map is not None:
             # the window type mixes the rows of ALL images of a call (attention.py:1025-1029): the mirrored batch must be a call of its
             # own, as in validate() (function.py:142-162), not extra token groups of this one
@@ -2520,7 +2535,31 @@ class Engine:
         views = self._bind_capture(P, form, S, length, H, W) if form else None
         multi, single = self._run_bound(P, patch, cap, S, flip_joint_map, H, W)
         res = {"single": single, "multi": multi} if single is not None else multi
+        if form and form.deferred:
+            return res, self._joint_queries(P, multi, S, H) + (form.result(views, None),)
         return (res, form.result(views, lambda: self._capture_inputs(P, S))) if form else res
+
+    def _joint_queries(self, P, multi, S, H):
+        """the launches of a joint-form program (attn_capture.JointForm) behind its head, on the current stream: i2r_joint_tokens on the
+        (merged) heat maps multi [S, J, H/4, W/4] fills the token tables bind_capture made, then the i2r_attn_query_maps launch of every
+        captured layer reads them and the q|k the layer kept.  -> (joints [S, J, 2], maxvals [S, J]) on the device"""
+        L, stream = cabi.lib(), torch.cuda.current_stream(self.device).cuda_stream
+        assert multi.is_contiguous() and multi.shape[0] == S and 1 <= len(P.captures) <= cabi.MAX_TOKEN_TABLES
+        J, hh, hw = multi.shape[1:]
+        joints = torch.empty(S, J, 2, dtype=torch.float32, device=self.device)
+        maxvals = torch.empty(S, J, dtype=torch.float32, device=self.device)
+        a = cabi.JointTokensArgs(heatmaps=multi.data_ptr(), points=joints.data_ptr(), maxvals=maxvals.data_ptr(), n_crops=S, joints=J, hh=hh, hw=hw,
+                                 in_stride=H // hh, n_tables=len(P.captures))
+        for t, cap in zip(a.table, P.captures):
+            tok, _, crops = cap["tables"]
+            assert crops.shape == (2, S)
+            t.tokens, t.crop_group, t.crop_slot = tok.data_ptr(), crops[0].data_ptr(), crops[1].data_ptr()
+            (t.n_grp, t.K), t.fh, t.fw, t.down = tok.shape, cap["x"].h, cap["x"].w, H // cap["x"].h
+        cabi.check(L.i2r_joint_tokens(C.byref(a), stream), "i2r_joint_tokens")
+        for cap in P.captures:
+            for _, q in cap["ops"]:
+                cabi.check(L.i2r_attn_query_maps(C.byref(q), stream), "i2r_attn_query_maps")
+        return joints, maxvals
 
     # the per-call steps every bound forward shares (_run_program, _forward_groups_shared)
     def _bind_groups(self, P, length, pad, flip):

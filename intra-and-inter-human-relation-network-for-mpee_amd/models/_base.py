@@ -329,6 +329,42 @@ class I2RModule(nn.Module):
             out, maps = eng.forward(x, pos_mask, length, capture=capture, queries=queries)
         return out, self._query_result(maps, lambda st: st.startswith("singleformer."))
 
+    def attention_at_joints(self, x, pos_mask, length, mode="dependency", layers=None, upsample=True, flip_pairs=None):
+        """The attention maps at the joints this very forward predicts, in ONE forward and without a trip to the host -- the flow the
+        reference's visualize.py is written for (its columns are labelled keypoint_name[p_id]: the query locations are a pose).  The
+        same as `out = model(x, ...)`, `joints = 4 * argmax(out)`, `attention_at(x, ..., points=joints.cpu())`, but the second forward and
+        the copy are gone: i2r_joint_tokens turns the heat maps into the token tables on the device (the arg-max of i2r_decode: first
+        index on a tie, the point (0, 0) for a map without a positive value -- get_max_preds, lib/core/inference.py:20-48) and the query
+        launches of the captured layers run behind the head.
+        mode, layers, upsample: as attention_at.  flip_pairs: the flip test as forward_flip runs it -- the joints come from the MERGED
+        heat maps, the attention maps from the plain pass (the mirrored pass's maps are not computed).
+        -> (output, joints, maxvals, maps): output exactly what forward (forward_flip with flip_pairs) returns; joints [S, J, 2] holding
+          (x, y) in the frame of each crop's network input and maxvals [S, J], device tensors, of output['multi'] when it is a dict; maps
+          as attention_at returns them with K = J (inter-human stack: entry person * J + joint).
+        Cost: every captured layer keeps its fp32 q|k activation [tokens, 2 * heads * head size] until the program ends.
+        ValueError: a model without encoder stacks, ATTENTION_TYPE window.  Not served: the stand-alone first stages, the grouped
+        forward, the per-person form.  Forward hooks keep working as before; this call serves none."""
+        from ..engine import JointQueries
+        name = self._engine_name() or self.cfg["MODEL"]["NAME"]
+        if name in ("transpose_h", "hrformer", "hrnet"):
+            raise ValueError("attention_at_joints: the stand-alone stage %s is not served" % name)
+        if torch.is_tensor(length):
+            length = length.tolist()
+        length = [int(n) for n in length]
+        eng = self.engine()
+        stacks = eng.capture_stacks()
+        capture = {(st, i) for st, n in stacks.items() for i in range(n)} if layers is None else {(str(st), int(i)) for st, i in layers}
+        H, W = x.shape[2], x.shape[3]
+        sizes = eng.capture_map_sizes(H, W)
+        scales = {st: (H // sizes[st][0] if upsample is True else max(int(upsample), 1)) for st in {st for st, _ in capture} if st in sizes}
+        jm = None
+        if flip_pairs is not None:
+            from ..caller import joint_map
+            jm = joint_map(flip_pairs, self.cfg["MODEL"]["NUM_JOINTS"]).to(eng.device)
+        with torch.no_grad():
+            out, (joints, maxvals, maps) = eng.forward(x, pos_mask, length, flip_joint_map=jm, capture=capture, joints=JointQueries(mode, scales))
+        return out, joints, maxvals, self._query_result(maps, lambda st: st.startswith("singleformer."))
+
     def person_relations(self, x, pos_mask, length, layers=None, maps=None, upsample=False):
         """The inter-human attention per person, computed on the device without ever building an [L, L] map: how much person i attends to
         person j, and where on j it looks.  With P the head-averaged softmax(q k^T) of a layer of the inter-human stack over the image's
