@@ -771,6 +771,33 @@ typedef struct i2r_attn_person_args {
 } i2r_attn_person_args;
 I2R_API int i2r_attn_person_maps(const i2r_attn_person_args* a, void* stream);
 
+/* The maps above under the flip test (additive: I2R_ABI_VERSION unchanged).  A stack group has tokens (p, y, x), t = p h w + y w + x; the
+ * mirror is mu(p, y, x) = (p, y, w - 1 - x), mu(t) = t - 2 (t mod w) + w - 1.  With P the map of a group in the plain pass and P' the map of
+ * the same group in the mirrored pass, the merged map is M[q, k] = (P[q, k] + P'[mu(q), mu(k)]) / 2.  The caller runs i2r_attn_query_maps /
+ * i2r_attn_person_maps at scale 1 twice -- on the plain groups, and on the mirrored groups with the table i2r_token_mirror made -- and
+ * i2r_attn_flip_merge un-mirrors the remaining (map) axis of the second set, merges and up-samples:
+ *   a, b     the raw row blocks of the plain / the mirrored pass: group g's block [rows_g, L_g] row-major at a + src_off[g] and b + src_off[g]
+ *            (the scale-1 layout of the two entry points above), L_g = P_g h w
+ *   rows_g   seg > 0: L_g / seg (the per-person maps); seg == 0: q_cnt[g] clamped to [0, K], K without q_cnt (the query maps)
+ *   out      group g's block [rows_g, P_g, h scale, w scale] at out + out_off[g]: the bilinear up-sampling of i2r_attn_query_maps applied to
+ *            m[r, p, y, x] = (a[r, p, y, x] + b[r, p, y, w - 1 - x]) / 2 (one rounded add, an exact halving); scale == 1: m itself
+ *   grp_off  device int32 [n_grp + 1]; src_off, out_off device int64 [n_grp]; q_cnt optional device int32 [n_grp]
+ *   grp_off_host  HOST copy of grp_off[0 .. n_grp], always: it is checked here and sizes the grid
+ * One thread per 4 consecutive outputs, no LDS, no atomics: deterministic.  An empty group is skipped; nothing outside the computed groups'
+ * blocks is written.  w == 1 and odd w are served (the centre column maps to itself).  I2R_E_ARG (nothing is launched): null pointers,
+ * scale outside 1 .. 64, h or w < 1, seg < 0, seg == 0 with K < 1 or >= 2^20, n_grp outside 1 .. 65535, a group length that h w (or seg)
+ * does not divide. */
+typedef struct i2r_attn_flip_merge_args {
+    const float* a; const float* b; float* out; const int32_t* grp_off; const int64_t* src_off; const int64_t* out_off; const int32_t* q_cnt;
+    const int32_t* grp_off_host;
+    int32_t n_grp, K, seg, scale, h, w;
+} i2r_attn_flip_merge_args;
+I2R_API int i2r_attn_flip_merge(const i2r_attn_flip_merge_args* a, void* stream);
+
+/* i2r_token_mirror -- dst[i] = mu(src[i]) for the n entries of a device int32 token table whose token maps are w wide; a negative entry
+ * (a skip) is kept.  src and dst are two tables.  n == 0 returns I2R_OK without a launch.  I2R_E_ARG: a null pointer, n < 0, w < 1. */
+I2R_API int i2r_token_mirror(const int32_t* src, int32_t* dst, int64_t n, int32_t w, void* stream);
+
 /* MODEL.ATTENTION_TYPE != 'default' (MODEL.NAME interformer: attention.py:991-1031,1046-1062) -- the inter-human "encoder" is ONE
  * GeneralTransformerBlock: a multi-head attention (q / k / v / out projections with bias, MHA_ :494-835; the relative position bias is
  * gathered but its addition is commented out, :780-786) over the (person, y, x) tokens of an image INCLUDING the padded persons' rows

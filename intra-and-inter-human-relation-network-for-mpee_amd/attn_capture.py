@@ -81,6 +81,10 @@ class Plan:
     # host int32 tensors the launches read on the device (query maps: tokens [groups, K], counts [groups]); a shape instead of a tensor:
     # an int32 table of that shape which the device fills itself (joint form: the tokens; its third table maps crops to entries)
     tables: tuple = ()
+    # a merged form (Form.merge) only: the scale-1 layout of the maps both passes write before i2r_attn_flip_merge -- group g's raw
+    # [rows_g, L_g] block starts raw_offs[g] floats behind either workspace of raw_floats floats
+    raw_offs: tuple = ()
+    raw_floats: int = 0
 
 
 def _layer(*sets):
@@ -109,11 +113,28 @@ class Form:
     N_BLOCKS = 1  # block sets per layer = device offset tables per capture
     call = None   # what bind_capture hands to plan() per call
     deferred = False  # True: a captured layer keeps its q|k and emits nothing; the engine runs the form's launches behind the program
+    merged = False    # True (merge()): the maps of the flip test, M = (P + un-mirrored P') / 2 (i2r_attn_flip_merge)
 
     def __init__(self, capture, suffix=()):
         self.capture, self.key = capture, ("capture", capture) + suffix  # (key: the part of the program key behind the shape)
 
     share = staticmethod(lambda plans: None)  # what the plans of all captures of a call must agree on, once they are made: nothing
+
+    def merge(self):
+        """This form under the flip test with flip_maps="merged": the program is the flip program, whose stacks run the mirrored crops as
+        a second half of doubled groups.  Every captured layer keeps its q|k; behind the program the form's launch runs at scale 1 on the
+        plain half and, with the mirrored token table, on the mirrored half, both into workspaces laid out by Plan.raw_offs, and
+        i2r_attn_flip_merge writes the merged, up-sampled maps into the capture buffer.  The key gains a marker."""
+        self.merged = self.deferred = True
+        self.key = self.key + ("flip-merged",)
+        return self
+
+    def _raw(self, p, rows, lens):
+        """fills in the scale-1 layout of a merged form's plan p: rows[g] x lens[g] floats per group"""
+        if self.merged:
+            (blk,), p.raw_floats = _layer([(r, n) for r, n in zip(rows, lens)])
+            p.raw_offs = tuple(blk.offs[:-1])
+        return p
 
     @staticmethod
     def result(views, inputs):
@@ -171,7 +192,7 @@ class QueryForm(Form):
     def launch(self, cap, qk, L, goff):
         return cabi.CAPTURE_OP_ATTN_QUERY, cabi.AttnQueryArgs(
             qk=qk.ptr, grp_off=goff.data_ptr(), out_off=cap["off"][0].data_ptr(), heads=L["heads"], hp=L["hp"], k_off=L["hs"], qk_cs=qk.cs,
-            mode=self.mode, K=1, scale=self.scales[cap["stack"]], h=cap["x"].h, w=cap["x"].w)
+            mode=self.mode, K=1, scale=1 if self.merged else self.scales[cap["stack"]], h=cap["x"].h, w=cap["x"].w)
 
     def plan(self, stack, hw, lens, heads, call=None):
         """call: the AttnQueries of this call -- tokens[stack] int32 [groups, K] (-1 = skip), optionally counts[stack] (entries per group)"""
@@ -196,13 +217,22 @@ class QueryForm(Form):
         blocks, n_layer = _layer([(c, n // (h * w), h * scale, w * scale) for n, c in zip(lens, cnt)])
         stride = _stride(heads, lens)
         tiles = (_tiles(cnt, lens), 0) if mode == 0 else (_tiles(lens, lens), _tiles(lens, cnt, 16))
-        return Plan(len(lens), stride, stride * (len(lens) * K if mode == 0 else sum(lens)), K * sum(lens) if scale > 1 else 1, blocks, n_layer,
-                    *tiles, K=K, tables=tables)
+        rows = K * sum(lens) if scale > 1 and not self.merged else 1  # (a merged form's launches run at scale 1: no rows workspace)
+        return self._raw(Plan(len(lens), stride, stride * (len(lens) * K if mode == 0 else sum(lens)), rows, blocks, n_layer, *tiles, K=K,
+                              tables=tables), cnt, lens)
 
     @staticmethod
     def patch(a, p, out, ws, rows, tables, host_off):
         a.out, a.ws, a.rows, (a.q_tok, a.q_cnt), a.grp_off_host = out, ws, rows, tables[:2], host_off
         a.n_grp, a.n_tiles, a.n_col_tiles, a.ws_stride, a.K = p.n_grp, p.n_tiles, p.n_col_tiles, p.ws_stride, p.K
+
+    def scale_of(self, stack):
+        return self.scales[stack]
+
+    @staticmethod
+    def aim(a, qk, tok, maps, raw_off, rel=None):
+        """a merged form's launch on one half of the flip program: that half's q|k rows and token table, the workspace its raw maps go to"""
+        a.qk, a.q_tok, a.out, a.out_off = qk, tok, maps, raw_off
 
 
 class JointForm(QueryForm):
@@ -243,7 +273,8 @@ class PersonForm(Form):
         rel_off, maps_off = cap["off"]
         return cabi.CAPTURE_OP_ATTN_PERSON, cabi.AttnPersonArgs(
             qk=qk.ptr, grp_off=goff.data_ptr(), rel_off=rel_off.data_ptr(), maps_off=maps_off.data_ptr(), heads=L["heads"], hp=L["hp"],
-            k_off=L["hs"], qk_cs=qk.cs, seg=cap["x"].h * cap["x"].w, mode=self.mode, scale=self.scale, h=cap["x"].h, w=cap["x"].w)
+            k_off=L["hs"], qk_cs=qk.cs, seg=cap["x"].h * cap["x"].w, mode=self.mode, scale=1 if self.merged else self.scale, h=cap["x"].h,
+            w=cap["x"].w)
 
     def plan(self, stack, hw, lens, heads, call=None):
         mode, scale, (h, w) = self.mode, self.scale, hw
@@ -251,22 +282,46 @@ class PersonForm(Form):
         pers = [n // (h * w) for n in lens]
         blocks, n_layer = _layer([(p, p) for p in pers], [(p, p, h * scale, w * scale) if mode else None for p in pers])
         stride = _stride(heads, lens)
-        return Plan(len(lens), stride, stride * sum(lens), (2 if mode == 1 and scale > 1 else 1) * max(pers) * sum(lens), blocks, n_layer)
+        twice = mode == 1 and scale > 1 and not self.merged  # (the raw D rows behind F; a merged form's launches run at scale 1)
+        p = Plan(len(lens), stride, stride * sum(lens), (2 if twice else 1) * max(pers) * sum(lens), blocks, n_layer)
+        return self._raw(p, pers, lens) if mode else p
 
     @staticmethod
     def patch(a, p, out, ws, rows, tables, host_off):
         a.rel, a.maps, a.ws, a.rows, a.grp_off_host = out, out + 4 * p.blocks[1].base, ws, rows, host_off
         a.n_grp, a.ws_stride = p.n_grp, p.ws_stride
 
+    def scale_of(self, stack):
+        return self.scale
+
+    @staticmethod
+    def aim(a, qk, tok, maps, raw_off, rel=None):
+        a.qk, a.rel, a.maps, a.maps_off = qk, rel, maps, raw_off
+
     @staticmethod
     def result(views, inputs):
         return tuple(views)  # (relation, maps)
 
 
-def resolve(capture, queries, persons, flip_joint_map, stacks, inter_stack, window, joints=None, n_joints=None):
+FLIP_MAPS = ("plain", "merged")
+
+
+def resolve(capture, queries, persons, flip_joint_map, stacks, inter_stack, window, joints=None, n_joints=None, flip_maps="plain"):
     """What Engine.forward / forward_single were asked for -> the form of the call, None without a capture.  stacks: the engine's
     capture_stacks(); inter_stack: the prefix of its inter-human stack; window: the inter-human block is the window type; joints: a
-    JointQueries of a model of n_joints joints -- the one form that goes with the flip test (its launches run behind the merge)."""
+    JointQueries of a model of n_joints joints -- with flip_maps "plain" the one form that goes with the flip test (its launches run
+    behind the merge, on the plain half); flip_maps "merged": the flip test's merged maps (Form.merge) of the query, per-person or joint
+    form -- never of the full [L, L] form, whose buffer it would double."""
+    if flip_maps not in FLIP_MAPS:
+        raise ValueError("flip_maps %r: 'plain' or 'merged'" % (flip_maps,))
+    if flip_maps == "merged":
+        if flip_joint_map is None:
+            raise ValueError("flip_maps='merged' needs the flip test (flip_joint_map)")
+        if window:
+            raise ValueError("flip_maps='merged': ATTENTION_TYPE window has no encoder stack to capture")
+        if sum(f is not None for f in (queries, persons, joints)) != 1:
+            raise ValueError("flip_maps='merged' goes with exactly one of queries=, persons=, joints= (the full [L, L] maps are not merged)")
+        return resolve(capture, queries, persons, None, stacks, inter_stack, window, joints, n_joints).merge()
     if joints is not None:
         if window:
             raise ValueError("joints=: ATTENTION_TYPE window has no encoder stack to capture")

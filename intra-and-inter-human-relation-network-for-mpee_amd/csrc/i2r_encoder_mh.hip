@@ -482,6 +482,71 @@ __global__ __launch_bounds__(256) void aq_upsample_k(const AqK p) {
     }
 }
 
+// ---- the flip test's maps: the mirrored pass's raw rows brought back into the plain frame, merged, up-sampled ------------------------------
+// aq_upsample_k with two sources: M[r, p, y, x] = (a[r, p, y, x] + b[r, p, y, w - 1 - x]) / 2 (one rounded add, an exact halving), then the
+// same align_corners=False arithmetic on M.  The rows of b were computed at the mirrored tokens (token_mirror_k), so only the map axis is
+// left to un-mirror here.  scale 1 stores M itself.  No LDS, no atomics; nothing outside a computed block is written.
+struct AfK {
+    const float* a;
+    const float* b;
+    float* out;
+    const int* grp_off;
+    const long long* src_off;  // group g's raw [rows_g, L_g] block, the same offset in a and in b
+    const long long* out_off;
+    const int* q_cnt;
+    int K, seg, scale, h, w;
+};
+
+// blockIdx.y = group; 4 consecutive floats of its [rows_g, P_g, h scale, w scale] block per thread
+__global__ __launch_bounds__(256) void aq_flip_merge_k(const AfK p) {
+    const int gi = blockIdx.y;
+    const int g0 = p.grp_off[gi], len = p.grp_off[gi + 1] - g0, hw = p.h * p.w;
+    if (len <= 0 || len % hw != 0 || (p.seg > 0 && len % p.seg != 0)) return;  // (the entry point checks the host's copy of the table)
+    const int kq = p.seg > 0 ? len / p.seg : (p.q_cnt ? min(max(p.q_cnt[gi], 0), p.K) : p.K);
+    const int H = p.h * p.scale, W = p.w * p.scale;
+    const long long n = (long long)kq * len * p.scale * p.scale;
+    const long long e0 = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (e0 >= n) return;
+    const float* sa = p.a + p.src_off[gi];  // [rows_g * P_g][h][w]
+    const float* sb = p.b + p.src_off[gi];
+    float* dst = p.out + p.out_off[gi];
+    const float rs = 1.f / (float)p.scale;
+    const int wm = p.w - 1;
+    float v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const long long e = min(e0 + j, n - 1);
+        const int ox = (int)(e % W), oy = (int)(e / W % H);
+        const long long m0 = e / ((long long)W * H) * hw;
+        const float* ma = sa + m0;
+        const float* mb = sb + m0;
+        const auto mg = [&](int y, int x) { return (ma[y * p.w + x] + mb[y * p.w + wm - x]) * 0.5f; };
+        if (p.scale == 1) {
+            v[j] = mg(oy, ox);
+            continue;
+        }
+        const float sy = fmaxf(((float)oy + 0.5f) * rs - 0.5f, 0.f), sx = fmaxf(((float)ox + 0.5f) * rs - 0.5f, 0.f);
+        const int y0 = (int)sy, x0 = (int)sx, y1 = min(y0 + 1, p.h - 1), x1 = min(x0 + 1, p.w - 1);
+        const float ly = sy - (float)y0, lx = sx - (float)x0;
+        v[j] = (1.f - ly) * ((1.f - lx) * mg(y0, x0) + lx * mg(y0, x1)) + ly * ((1.f - lx) * mg(y1, x0) + lx * mg(y1, x1));
+    }
+    if (e0 + 4 <= n && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
+        *reinterpret_cast<f32x4*>(dst + e0) = (f32x4){v[0], v[1], v[2], v[3]};
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (e0 + j < n) dst[e0 + j] = v[j];
+    }
+}
+
+// mu(t) = t - 2 (t mod w) + w - 1 for every entry of an int32 token table; a negative entry (a skip) stays as it is
+__global__ __launch_bounds__(256) void token_mirror_k(const int* __restrict__ src, int* __restrict__ dst, long long n, int w) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int t = src[i];
+    dst[i] = t < 0 ? t : t - 2 * (t % w) + w - 1;
+}
+
 // ---- attention per person: P reduced over the persons of an inter-human group (L_g = P_g seg tokens, person p = tokens [p seg, (p + 1) seg)) ----
 //   F[j, q] = sum_{k in j} P[q, k]          ap_affect_k, behind aw_stats_k: work item (group, 16-query tile, person j), S^T = K Q^T as above;
 //                                             aw_row_stats, then a sum of its own over j's keys (normalised once per head)
@@ -793,5 +858,39 @@ extern "C" int i2r_attn_person_maps(const i2r_attn_person_args* a, void* stream)
         i2r_launch(aq_upsample_k, dim3((unsigned)((n4 + 255) / 256), (unsigned)a->n_grp), dim3(256), 0, st, u);
         I2R_CHECK_LAUNCH("i2r_attn_person_maps (up-sampling)");
     }
+    return I2R_OK;
+}
+
+extern "C" int i2r_attn_flip_merge(const i2r_attn_flip_merge_args* a, void* stream) {
+    I2R_CHECK_ARG(a && a->a && a->b && a->out && a->grp_off && a->src_off && a->out_off && a->grp_off_host, "i2r_attn_flip_merge: null pointer");
+    I2R_CHECK_ARG(a->scale >= 1 && a->scale <= 64, "i2r_attn_flip_merge: scale=%d (1 .. 64)", a->scale);
+    I2R_CHECK_ARG(a->h > 0 && a->w > 0 && (long long)a->h * a->w < (1 << 24), "i2r_attn_flip_merge: h=%d w=%d", a->h, a->w);
+    I2R_CHECK_ARG(a->seg >= 0 && a->seg < (1 << 24) && (a->seg > 0 || (a->K >= 1 && a->K < (1 << 20))), "i2r_attn_flip_merge: seg=%d K=%d", a->seg, a->K);
+    I2R_CHECK_ARG(a->n_grp > 0 && a->n_grp < 65536, "i2r_attn_flip_merge: n_grp=%d", a->n_grp);
+    int max_len = 0, max_rows = 0;
+    for (int g = 0; g < a->n_grp; ++g) {
+        const int len = a->grp_off_host[g + 1] - a->grp_off_host[g];
+        I2R_CHECK_ARG(len >= 0 && len % (a->h * a->w) == 0 && (a->seg == 0 || len % a->seg == 0), /* (an empty group is skipped) */
+                      "i2r_attn_flip_merge: group %d has %d tokens, not a multiple of h w = %d x %d (seg = %d)", g, len, a->h, a->w, a->seg);
+        max_len = len > max_len ? len : max_len;
+        const int rows = a->seg > 0 ? len / a->seg : a->K;
+        max_rows = rows > max_rows ? rows : max_rows;
+    }
+    const long long n4 = ((long long)max_rows * max_len * a->scale * a->scale + 3) / 4;
+    I2R_CHECK_ARG((n4 + 255) / 256 < (1ll << 31), "i2r_attn_flip_merge: grid");
+    if (n4 == 0) return I2R_OK;  // (every group is empty)
+    const AfK k{a->a, a->b, a->out, a->grp_off, reinterpret_cast<const long long*>(a->src_off), reinterpret_cast<const long long*>(a->out_off),
+                a->q_cnt, a->K, a->seg, a->scale, a->h, a->w};
+    i2r_launch(aq_flip_merge_k, dim3((unsigned)((n4 + 255) / 256), (unsigned)a->n_grp), dim3(256), 0, (hipStream_t)stream, k);
+    I2R_CHECK_LAUNCH("i2r_attn_flip_merge");
+    return I2R_OK;
+}
+
+extern "C" int i2r_token_mirror(const int32_t* src, int32_t* dst, int64_t n, int32_t w, void* stream) {
+    I2R_CHECK_ARG(src && dst, "i2r_token_mirror: null pointer");
+    I2R_CHECK_ARG(n >= 0 && (n + 255) / 256 < (1ll << 31) && w >= 1, "i2r_token_mirror: n=%lld w=%d", (long long)n, w);
+    if (n == 0) return I2R_OK;
+    i2r_launch(token_mirror_k, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src, dst, (long long)n, w);
+    I2R_CHECK_LAUNCH("i2r_token_mirror");
     return I2R_OK;
 }

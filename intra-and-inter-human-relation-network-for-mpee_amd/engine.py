@@ -801,8 +801,8 @@ class Program:
     # A capture program computes, next to its usual outputs, the attention maps of the requested encoder layers in the form it was built
     # with (attn_capture: full [L, L] maps, rows / columns at query points, reductions per person) into ONE per-call buffer.  The launch list
     # is fixed at build time; bind_capture() patches the per-call part and uploads the offsets of the groups' blocks, like set_groups() does.
-    # A deferred form (the joint form) keeps its launches out of the list: they need the heat maps of the same call, so the engine issues
-    # them behind the run (Engine._joint_queries) on the q|k the captured layers kept.
+    # A deferred form keeps its launches out of the list: the joint form needs the heat maps of the same call, a merged form (the flip
+    # test's maps) the q|k of both halves, so the engine issues them behind the run (Engine._deferred_maps) on the q|k the captured layers kept.
     def _capture_begin(self, capture, x):
         if not capture:
             return None
@@ -853,8 +853,45 @@ class Program:
                         b = base + blk.base
                         out[(cap["stack"], i)] = [buf[b + o:b + e].view(s) for o, e, s in zip(blk.offs, blk.offs[1:], blk.shapes)]
                 base += p.layer_floats
+        if form.merged:
+            self._bind_merge(plans, glens, buf, held)
         self._capture_ws = held
         return views
+
+    def _bind_merge(self, plans, glens, buf, held):
+        """the per-call part of a merged form (attn_capture.Form.merge) behind bind_capture: per capture a record cap["merge"] of what
+        Engine._deferred_maps launches -- the q|k rows of either half of every captured layer (the mirrored groups repeat the plain ones
+        half the stack's rows further on, so ONE offset table serves both), the mirrored token table, the two raw workspaces (shared by
+        all layers: the launches are ordered on the stream), the relation workspaces of the per-person form, and the i2r_attn_flip_merge
+        args of every layer, whose out is the layer's maps block in buf."""
+        raw = [torch.empty(max(p.raw_floats for p in plans), dtype=torch.float32, device=self.device) for _ in range(2)]
+        held += raw
+        base = 0
+        for cap, lens, p in zip(self.captures, glens, plans):
+            cur, n = cap["grouping"]["current"], len(lens)
+            half = (len(cur) - 1) // 2
+            assert len(cur) == 2 * half + 1 and n <= half and all(cur[half + g] - cur[half] == cur[g] for g in range(n + 1)), "not a flip program's groups"
+            qk0 = cap.setdefault("qk0", [a.qk for _, a in cap["ops"]])  # (the launches' q|k as built: aim() moves a.qk between the halves)
+            maps = p.blocks[-1]  # (the per-person form: the set behind the relation blocks)
+            tok = cap["tables"][0] if cap["tables"] else None
+            rel = [torch.empty(p.blocks[0].offs[-1], dtype=torch.float32, device=self.device) for _ in range(2)] if self.form.N_BLOCKS == 2 else None
+            m = dict(qk=[(q, q + 4 * cur[half] * a.qk_cs) for q, (_, a) in zip(qk0, cap["ops"])], tok=(tok, torch.empty_like(tok) if tok is not None else None),
+                     raw=raw, rel=rel, raw_off=None, rel_out=[], layers=[])
+            if p.raw_floats:
+                m["raw_off"] = torch.tensor(p.raw_offs, dtype=torch.int64).pin_memory().to(self.device, non_blocking=True)
+            host_off = (C.c_int32 * (n + 1))(*cur[:n + 1])
+            held += [m, host_off]
+            for _, a in cap["ops"]:
+                if rel:
+                    m["rel_out"].append(buf[base:base + p.blocks[0].offs[-1]])
+                if p.raw_floats:
+                    seg = a.seg if rel else 0
+                    m["layers"].append(cabi.AttnFlipMergeArgs(
+                        a=raw[0].data_ptr(), b=raw[1].data_ptr(), out=buf.data_ptr() + 4 * (base + maps.base), grp_off=a.grp_off, src_off=m["raw_off"].data_ptr(),
+                        out_off=cap["off"][-1].data_ptr(), q_cnt=0 if rel else cap["tables"][1].data_ptr(), grp_off_host=C.cast(host_off, C.c_void_p),
+                        n_grp=n, K=p.K, seg=seg, scale=self.form.scale_of(cap["stack"]), h=cap["x"].h, w=cap["x"].w))
+                base += p.layer_floats
+            cap["merge"] = m
 
     def set_groups(self, grouping, grp_off_host):
         """(Re)define the token groups of an encoder stack: uploads the offset table and patches the per-layer descriptors."""
@@ -2135,7 +2172,7 @@ class Engine:
     MAX_PROGRAMS = 48
     MAX_PROGRAM_BYTES = 32 << 30
 
-    def forward(self, x, pos_mask, length, flip_joint_map=None, capture=None, queries=None, persons=None, joints=None):
+    def forward(self, x, pos_mask, length, flip_joint_map=None, capture=None, queries=None, persons=None, joints=None, flip_maps="plain"):
         """flip_joint_map (device int32 [J], see caller.joint_map): run the flip test in the same forward and return the merged
         'multi' heatmaps (the reference merges only outputs['multi'], function.py:137-162).
         capture: a set of (stack, layer) -- stack a state-dict prefix of capture_stacks() -- whose attention maps to return as well:
@@ -2158,14 +2195,19 @@ class Engine:
         the head, on the current stream, with no copy to the host in between.  It is the one form that goes with flip_joint_map: the
         program is the flip program, the tables come from the MERGED maps, the launches cover the plain half (the first groups of each
         stack); the mirrored pass's maps are not computed.  Every captured layer holds its fp32 q|k [tokens, 2 hs] until the program ends.
-        One program per (capture set, mode, J, scales).  ValueError: the window-type block, queries= or persons= too, no encoder stack."""
+        One program per (capture set, mode, J, scales).  ValueError: the window-type block, queries= or persons= too, no encoder stack.
+        flip_maps: "plain" (all of the above) or "merged" -- with flip_joint_map and ONE of queries, persons, joints: the maps of the flip
+        test, M = (P + P~) / 2 with P~[q, k] = P'[mu(q), mu(k)] the mirrored pass's map brought back into the plain frame (DESIGN.md
+        'i2r_attn_flip_merge'), in the layouts of the un-flipped calls; output is the merged heat maps.  The program is the flip program
+        with a marker in its key; every captured layer holds its fp32 q|k of BOTH halves until the program ends, and the launches run
+        behind the head (_deferred_maps).  ValueError: without the flip test, with the full [L, L] form, the window-type block."""
         assert x.dim() == 4 and x.shape[1] == 3 and x.dtype == torch.float32
         S, _, H, W = x.shape
         assert S == sum(length), "sum(length)=%d != number of crops %d" % (sum(length), S)
         assert all(n >= 1 for n in length), "every image needs at least one person"
         sine_n = max(length)  # (MULTI_POS_EMBEDDING sine: the canvas is max(length) persons wide, for every part of this batch)
         form = attn_capture.resolve(capture, queries, persons, flip_joint_map, self.capture_stacks(), self.inter_stack, self.window_attn,
-                                    joints, self.cfg["MODEL"]["NUM_JOINTS"])
+                                    joints, self.cfg["MODEL"]["NUM_JOINTS"], flip_maps)
         if form:
             with torch.cuda.device(self.device):
                 return self._forward_part(x, pos_mask, list(length), flip_joint_map if form.deferred else None, S, H, W, sine_n, form=form)
@@ -2536,13 +2578,46 @@ class Engine:
         multi, single = self._run_bound(P, patch, cap, S, flip_joint_map, H, W)
         res = {"single": single, "multi": multi} if single is not None else multi
         if form and form.deferred:
-            return res, self._joint_queries(P, multi, S, H) + (form.result(views, None),)
+            if isinstance(form, attn_capture.JointForm):
+                jt = self._joint_tokens(P, multi, S, H)
+                self._deferred_maps(P)
+                return res, jt + (form.result(views, None),)
+            self._deferred_maps(P)
         return (res, form.result(views, lambda: self._capture_inputs(P, S))) if form else res
 
-    def _joint_queries(self, P, multi, S, H):
-        """the launches of a joint-form program (attn_capture.JointForm) behind its head, on the current stream: i2r_joint_tokens on the
-        (merged) heat maps multi [S, J, H/4, W/4] fills the token tables bind_capture made, then the i2r_attn_query_maps launch of every
-        captured layer reads them and the q|k the layer kept.  -> (joints [S, J, 2], maxvals [S, J]) on the device"""
+    def _deferred_maps(self, P):
+        """the launches of a deferred form behind the program's head, on the current stream, on the q|k the captured layers kept.  The
+        plain joint form: the i2r_attn_query_maps launch of every captured layer.  A merged form (attn_capture.Form.merge; the records of
+        Program._bind_merge): i2r_token_mirror makes the mirrored pass's token table, then per captured layer the form's launch at scale 1
+        on the plain half and, at the mirrored tokens, on the mirrored half, and ONE i2r_attn_flip_merge into the capture buffer; the
+        relation matrices of the per-person form, mirror-invariant sums over whole persons, are merged by one torch expression on the
+        same stream: R_m = (R + R') / 2.  Nothing here reads the device."""
+        L, stream, form = cabi.lib(), torch.cuda.current_stream(self.device).cuda_stream, P.form
+        name = "i2r_attn_person_maps" if form.N_BLOCKS == 2 else "i2r_attn_query_maps"
+        launch = getattr(L, name)
+        for cap in P.captures:
+            if not form.merged:
+                for _, q in cap["ops"]:
+                    cabi.check(launch(C.byref(q), stream), name)
+                continue
+            m = cap["merge"]
+            tok, raw, rel = m["tok"], m["raw"], m["rel"] or (None, None)
+            if tok[0] is not None:
+                cabi.check(L.i2r_token_mirror(tok[0].data_ptr(), tok[1].data_ptr(), tok[0].numel(), cap["x"].w, stream), "i2r_token_mirror")
+            for j, (_, a) in enumerate(cap["ops"]):
+                for half in (0, 1):
+                    form.aim(a, m["qk"][j][half], tok[half].data_ptr() if tok[half] is not None else None, raw[half].data_ptr(),
+                             m["raw_off"].data_ptr() if m["raw_off"] is not None else None, rel[half].data_ptr() if rel[half] is not None else None)
+                    cabi.check(launch(C.byref(a), stream), name)
+                if m["layers"]:
+                    cabi.check(L.i2r_attn_flip_merge(C.byref(m["layers"][j]), stream), "i2r_attn_flip_merge")
+                if m["rel_out"]:
+                    torch.add(rel[0], rel[1], out=m["rel_out"][j]).mul_(0.5)
+
+    def _joint_tokens(self, P, multi, S, H):
+        """the tables of a joint-form program (attn_capture.JointForm) behind its head, on the current stream: i2r_joint_tokens on the
+        (merged) heat maps multi [S, J, H/4, W/4] fills the token tables bind_capture made; the launches that read them follow
+        (_deferred_maps).  -> (joints [S, J, 2], maxvals [S, J]) on the device"""
         L, stream = cabi.lib(), torch.cuda.current_stream(self.device).cuda_stream
         assert multi.is_contiguous() and multi.shape[0] == S and 1 <= len(P.captures) <= cabi.MAX_TOKEN_TABLES
         J, hh, hw = multi.shape[1:]
@@ -2556,9 +2631,6 @@ class Engine:
             t.tokens, t.crop_group, t.crop_slot = tok.data_ptr(), crops[0].data_ptr(), crops[1].data_ptr()
             (t.n_grp, t.K), t.fh, t.fw, t.down = tok.shape, cap["x"].h, cap["x"].w, H // cap["x"].h
         cabi.check(L.i2r_joint_tokens(C.byref(a), stream), "i2r_joint_tokens")
-        for cap in P.captures:
-            for _, q in cap["ops"]:
-                cabi.check(L.i2r_attn_query_maps(C.byref(q), stream), "i2r_attn_query_maps")
         return joints, maxvals
 
     # the per-call steps every bound forward shares (_run_program, _forward_groups_shared)

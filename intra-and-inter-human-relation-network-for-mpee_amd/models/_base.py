@@ -307,7 +307,18 @@ class I2RModule(nn.Module):
                 out[key] = views
         return out
 
-    def attention_at(self, x, pos_mask, length, points, mode="dependency", layers=None, upsample=True):
+    def _flip_map(self, eng, flip_pairs, flip_maps, who, default):
+        """flip_pairs / flip_maps of an attention call -> (the engine's flip_joint_map or None, its flip_maps)"""
+        if flip_maps not in ("plain", "merged"):
+            raise ValueError("%s: flip_maps %r ('plain' or 'merged')" % (who, flip_maps))
+        if flip_pairs is None:
+            return None, "plain"
+        if flip_maps == "plain" and default != "plain":
+            raise ValueError("%s: with flip_pairs only flip_maps='merged' is served (the plain pass's maps: call without flip_pairs)" % who)
+        from ..caller import joint_map
+        return joint_map(flip_pairs, self.cfg["MODEL"]["NUM_JOINTS"]).to(eng.device), flip_maps
+
+    def attention_at(self, x, pos_mask, length, points, mode="dependency", layers=None, upsample=True, flip_pairs=None, flip_maps="merged"):
         """The attention maps at query points, computed on the device without ever building an [L, L] map (the reference's
         visualize.py:186-233 / :333-388 reads exactly this of its hooks' output).
         points: [S, K, 2] holding (x, y) in the frame of each crop's network input (what visualize.py builds from preds); NaN = skip (a
@@ -319,17 +330,21 @@ class I2RModule(nn.Module):
           scale for every stack, False / 1 = the raw token maps.
         -> (model output, {(stack, layer): maps}): intra-human stack (the group is the crop) [S, K, 1, h r, w r]; inter-human stack (the
           group is the image, all its persons' points are queries, entry person * K + k) a list with one [P_img K, P_img, h r, w r] per image.
+        flip_pairs: the flip test as forward_flip runs it -- the output is forward_flip's, and the maps are those of the flip test,
+          M = (P + P~) / 2 with P~ the mirrored pass's map brought back into the plain frame (flip_maps="merged", the only choice here), in
+          the same layout.  The points stay in the frame of the un-mirrored crop.
         Forward hooks keep working as before; this call serves none."""
         if torch.is_tensor(length):
             length = length.tolist()
         length = [int(n) for n in length]
         eng = self.engine()
         capture, queries = self._query_plan(eng, x, points, mode, layers, upsample, length)
+        jm, flip_maps = self._flip_map(eng, flip_pairs, flip_maps, "attention_at", "merged")
         with torch.no_grad():
-            out, maps = eng.forward(x, pos_mask, length, capture=capture, queries=queries)
+            out, maps = eng.forward(x, pos_mask, length, flip_joint_map=jm, capture=capture, queries=queries, flip_maps=flip_maps)
         return out, self._query_result(maps, lambda st: st.startswith("singleformer."))
 
-    def attention_at_joints(self, x, pos_mask, length, mode="dependency", layers=None, upsample=True, flip_pairs=None):
+    def attention_at_joints(self, x, pos_mask, length, mode="dependency", layers=None, upsample=True, flip_pairs=None, flip_maps="plain"):
         """The attention maps at the joints this very forward predicts, in ONE forward and without a trip to the host -- the flow the
         reference's visualize.py is written for (its columns are labelled keypoint_name[p_id]: the query locations are a pose).  The
         same as `out = model(x, ...)`, `joints = 4 * argmax(out)`, `attention_at(x, ..., points=joints.cpu())`, but the second forward and
@@ -337,7 +352,8 @@ class I2RModule(nn.Module):
         index on a tie, the point (0, 0) for a map without a positive value -- get_max_preds, lib/core/inference.py:20-48) and the query
         launches of the captured layers run behind the head.
         mode, layers, upsample: as attention_at.  flip_pairs: the flip test as forward_flip runs it -- the joints come from the MERGED
-        heat maps, the attention maps from the plain pass (the mirrored pass's maps are not computed).
+        heat maps; the attention maps with flip_maps="plain" from the plain pass alone (the mirrored pass's maps are not computed), with
+        flip_maps="merged" from both passes, M = (P + P~) / 2 as attention_at defines it, queried at the same joints.
         -> (output, joints, maxvals, maps): output exactly what forward (forward_flip with flip_pairs) returns; joints [S, J, 2] holding
           (x, y) in the frame of each crop's network input and maxvals [S, J], device tensors, of output['multi'] when it is a dict; maps
           as attention_at returns them with K = J (inter-human stack: entry person * J + joint).
@@ -357,15 +373,13 @@ class I2RModule(nn.Module):
         H, W = x.shape[2], x.shape[3]
         sizes = eng.capture_map_sizes(H, W)
         scales = {st: (H // sizes[st][0] if upsample is True else max(int(upsample), 1)) for st in {st for st, _ in capture} if st in sizes}
-        jm = None
-        if flip_pairs is not None:
-            from ..caller import joint_map
-            jm = joint_map(flip_pairs, self.cfg["MODEL"]["NUM_JOINTS"]).to(eng.device)
+        jm, flip_maps = self._flip_map(eng, flip_pairs, flip_maps, "attention_at_joints", "plain")
         with torch.no_grad():
-            out, (joints, maxvals, maps) = eng.forward(x, pos_mask, length, flip_joint_map=jm, capture=capture, joints=JointQueries(mode, scales))
+            out, (joints, maxvals, maps) = eng.forward(x, pos_mask, length, flip_joint_map=jm, capture=capture, joints=JointQueries(mode, scales),
+                                                       flip_maps=flip_maps)
         return out, joints, maxvals, self._query_result(maps, lambda st: st.startswith("singleformer."))
 
-    def person_relations(self, x, pos_mask, length, layers=None, maps=None, upsample=False):
+    def person_relations(self, x, pos_mask, length, layers=None, maps=None, upsample=False, flip_pairs=None, flip_maps="merged"):
         """The inter-human attention per person, computed on the device without ever building an [L, L] map: how much person i attends to
         person j, and where on j it looks.  With P the head-averaged softmax(q k^T) of a layer of the inter-human stack over the image's
         persons * h * w tokens (what the forward hooks get):
@@ -377,6 +391,9 @@ class I2RModule(nn.Module):
         -> (model output, result): result.relation[(stack, layer)] = a list with one [P_img, P_img] tensor per image;
           result.maps[(stack, layer)] = a list with one [P_img, P_img, h r, w r] tensor per image -- first index i (dependency) or j
           (affect), second index the person whose token map it is; empty without maps.  All are views of one buffer.
+        flip_pairs: the flip test as forward_flip runs it -- the output is forward_flip's, and with P' the mirrored pass's map and mu the
+          mirror of a token: R_m = (R + R') / 2, D_m[i, k] = (D[i, k] + D'[i, mu(k)]) / 2, F_m[j, q] = (F[j, q] + F'[j, mu(q)]) / 2 (sums over
+          whole persons are mirror-invariant; flip_maps="merged" is the only choice here); the identities above hold for them as well.
         ValueError: a stand-alone first stage (no inter-human stack), ATTENTION_TYPE window, a layer of another stack.
         Forward hooks keep working as before; this call serves none."""
         from ..engine import PersonMaps
@@ -395,8 +412,10 @@ class I2RModule(nn.Module):
         capture = {(st, i) for i in range(eng.capture_stacks().get(st, 0))} if layers is None else {(str(s), int(i)) for s, i in layers}
         if upsample is True:
             upsample = x.shape[2] // eng.capture_map_sizes(x.shape[2], x.shape[3])[st][0]
+        jm, flip_maps = self._flip_map(eng, flip_pairs, flip_maps, "person_relations", "merged")
         with torch.no_grad():
-            out, (rel, views) = eng.forward(x, pos_mask, length, capture=capture, persons=PersonMaps(maps, max(int(upsample), 1)))
+            out, (rel, views) = eng.forward(x, pos_mask, length, flip_joint_map=jm, capture=capture, persons=PersonMaps(maps, max(int(upsample), 1)),
+                                            flip_maps=flip_maps)
         return out, PersonRelations(rel, views)
 
     def forward(self, x, pos_mask, length):
