@@ -184,6 +184,16 @@ I2R_API int i2r_conv_wino_form(const i2r_conv_desc* const* descs, int32_t n, int
  * launch run the general epilogue.  Always I2R_OK. */
 I2R_API int i2r_conv_wino_forms(int32_t on);
 
+/* i2r_conv_direct_form -- what an fp32 algo 0 (grouped) launch of a double-buffered variant (conv_igemm_f32<MT, NT, CAP, PF> with PF > 0)
+ * resolves to (additive: I2R_ABI_VERSION unchanged).  *form: 1 = every member has one channel chunk (the single-chunk body), 2 = the
+ * pipelined body, 0 = the general body (PF 0, 16-bit operands, algo 1, and every launch while the forms are switched off).  *epi (may be
+ * null): the epilogue form under the rule of i2r_conv_wino_form plus rep == 1 -- 1 = bias + ReLU, 2 = bias + res1 + ReLU, 0 = the general
+ * epilogue (always 0 with form 0).  The results do not depend on either, bit for bit; kernel names do not report them.  No launch happens. */
+I2R_API int i2r_conv_direct_form(const i2r_conv_desc* const* descs, int32_t n, int32_t* form, int32_t* epi);
+/* i2r_conv_direct_forms -- process-wide switch (atomic): on != 0 (the default) lets such launches take the forms, 0 makes every launch
+ * run the general body and epilogue.  Always I2R_OK. */
+I2R_API int i2r_conv_direct_forms(int32_t on);
+
 /* ---- after the forward: flip-test merge and keypoint decode -------------------------------- */
 /* i2r_flip_merge -- out = (y + flip_back(y_flipped)) * 0.5  with flip_back = reverse W + swap left/right joints
  * (lib/core/function.py:142-162, lib/utils/transforms.py:16-30). joint_map: device int32[joints], the joint whose mirrored

@@ -320,14 +320,88 @@ __device__ __forceinline__ void conv_epilogue(const ConvK& p, f32x4 (&acc)[MT][N
     }
 }
 
+// Compile-time forms of the fp32 epilogue (conv_igemm_f32's EPI, chosen per launch by direct_form in i2r_conv_plan.h): 1 = bias + ReLU,
+// 2 = bias + res1 + ReLU, every pixel written once (rep 1), channel blocks exact in cout and out_cs -- the arithmetic of the rep == 1
+// branch above, operation for operation ((acc + (bias [+ res1])), max with 0), without its flag tests, tail handling and the two
+// descriptors it does not use.  Three steps, so that the body can place them: conv_epilogue_prep reads the member's fields, forms the
+// descriptors and the lanes' offsets (ahead of the K loop: no scalar load inside it); conv_epilogue_fetch issues the bias and residual
+// loads (the body calls it ahead of its last K steps, so the pieces arrive under MFMAs); conv_epilogue_form transposes, sums and stores.
+template <int MT, int NT, int EPI>
+struct ConvEpiPre {
+    __amdgpu_buffer_rsrc_t rs_out, rs_bias, rs_r1;
+    unsigned nb;       // byte offset of this lane's 16-byte piece of fragment 0 in the bias
+    unsigned off[MT];  // byte offset of (pixel, that piece) in out / res1, kOOB outside the map
+    f32x4 bias[NT];
+    f32x4 r1[EPI == 2 ? MT : 1][NT];
+};
 
+template <int MT, int NT, int EPI>
+__device__ __forceinline__ void conv_epilogue_prep(const ConvK& p, ConvEpiPre<MT, NT, EPI>& pre, int img, int oy0, int ox0, int wm, int n_base,
+                                                   int li, int g, int tile_px) {
+    const int pj = li >> 2, pq = li & 3;
+    float* out = p.out;
+    const float* bias = p.bias;
+    const float* res1 = p.res1;
+    unsigned out_bytes = p.out_bytes, bias_bytes = (unsigned)p.cout_pad * 4u;
+    asm volatile("" : "+s"(out), "+s"(bias), "+s"(res1), "+s"(out_bytes), "+s"(bias_bytes));  // (kept: not read again where they are used)
+    pre.rs_out = __builtin_amdgcn_make_buffer_rsrc(out, 0, out_bytes, 0x00020000);
+    pre.rs_bias = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(bias), 0, bias_bytes, 0x00020000);
+    if constexpr (EPI == 2) pre.rs_r1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(res1), 0, out_bytes, 0x00020000);
+    pre.nb = (unsigned)(n_base + pq * 4) * 4u;
+    const int conv_h = p.conv_h, conv_w = p.conv_w, out_h = p.out_h, out_w = p.out_w, out_cs = p.out_cs;
+    const int step = p.out_step, off_y = p.out_off_y, off_x = p.out_off_x;
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+        const int m = (wm * MT + mt) * 16 + g * 4 + pj;
+        const int ty = div_m(m, p.tile_w, p.m_tw), tx = m - ty * p.tile_w;
+        const int oy = oy0 + ty, ox = ox0 + tx;
+        const bool pv = m < tile_px && oy < conv_h && ox < conv_w;
+        pre.off[mt] = pv ? (unsigned)(((img * out_h + oy * step + off_y) * out_w + ox * step + off_x) * out_cs) * 4u + pre.nb : kOOB;
+        asm volatile("" : "+v"(pre.off[mt]));
+    }
+}
+
+template <int MT, int NT, int EPI>
+__device__ __forceinline__ void conv_epilogue_fetch(ConvEpiPre<MT, NT, EPI>& pre) {
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) pre.bias[nt] = buf_ld16(pre.rs_bias, pre.nb + nt * 64u, 0);
+    if constexpr (EPI == 2) {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) pre.r1[mt][nt] = buf_ld16(pre.rs_r1, pre.off[mt] + nt * 64u, 0);
+    }
+}
+
+template <int MT, int NT, int EPI>
+__device__ __forceinline__ void conv_epilogue_form(f32x4 (&acc)[MT][NT], const ConvEpiPre<MT, NT, EPI>& pre, int li, int g) {
+    const int j4 = li & 3;
+    const int pj = li >> 2, pq = li & 3;
+    const int perm_src = (g * 16 + pq * 4 + pj) * 4;
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            f32x4 v = quad_transpose(acc[mt][nt], j4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float x = v[e];
+                v[e] = __int_as_float(__builtin_amdgcn_ds_bpermute(perm_src, __float_as_int(x)));
+            }
+            f32x4 r = pre.bias[nt];
+            if constexpr (EPI == 2) r += pre.r1[mt][nt];
+            f32x4 t = v + r;
+            t[0] = fmaxf(t[0], 0.f); t[1] = fmaxf(t[1], 0.f); t[2] = fmaxf(t[2], 0.f); t[3] = fmaxf(t[3], 0.f);
+            buf_st16(pre.rs_out, pre.off[mt] + nt * 64u, 0, t);
+        }
+}
 
 typedef void (*conv_fn)(const ConvGroupK);
 
 }  // namespace
 
 // kernel pickers of the implicit-GEMM translation units (one per operand type, so the three conv files compile in parallel); null = no such variant
-void* i2r_pick_conv_f32(int nt, int mt, int cap, int pf);
+void* i2r_pick_conv_f32(int nt, int mt, int cap, int pf, int form, int epi);  // form / epi: i2r_conv.hip, conv_body_forms
 void* i2r_pick_conv_bf16(int nt, int mt, int cap, int pf);
 void* i2r_pick_conv_f16(int nt, int mt, int cap, int pf);
 // Winograd F(2x2, 3x3) fp32 kernels (i2r_conv_wino.hip): MT fragments x NT channel fragments per workgroup; LDS bytes of a workgroup

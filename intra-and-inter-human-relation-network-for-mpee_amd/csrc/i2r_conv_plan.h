@@ -48,6 +48,7 @@ struct ConvPlan {
     int algo, dtype;
     int nt, mt, cap, pf;    // the instantiation (cap, pf: implicit GEMM only)
     bool fused_in; int form;  // Winograd: a member has a fused input; epilogue form (wino_form), 0 otherwise
+    int dform, depi;        // fp32 implicit GEMM with pf > 0: body and epilogue form (direct_form), 0 / 0 otherwise
     size_t lds; long long total;  // LDS bytes of a workgroup; workgroups
     int seq[kMaxGroups];    // run length per member (1 for implicit GEMM)
     conv_fn fn;             // null: no such instantiation
@@ -339,6 +340,30 @@ int wino_form(const i2r_conv_desc* const* descs, int32_t n, const ConvGroupK& gr
     return descs[0]->res1 ? 2 : 1;
 }
 
+// Body and epilogue form of an fp32 implicit-GEMM launch of a double-buffered variant (conv_igemm_f32's FORM / EPI, i2r_conv.hip).
+// Body: 1 when every member has a single channel chunk, else 2 (which also runs one-chunk members).  Epilogue: the rule of wino_form,
+// and every pixel written once (rep 1; out_step / offsets are free: the deconv parities qualify).  The synchronous variant (pf 0), a tuning
+// build with ablation bits (the stamps and switches live in the general body), a member with a second input (in2), four M fragments per wave (no launch of the models has
+// them; the forms are not compiled for it) and every launch while the switch is off: 0 / 0.
+std::atomic<int> g_direct_forms{1};
+constexpr int kDirectFormMaxMT = 3;
+
+void direct_form(const i2r_conv_desc* const* descs, int32_t n, const ConvGroupK& grp, int pf, int mt, int& form, int& epi) {
+    form = epi = 0;
+    if (pf == 0 || mt > kDirectFormMaxMT || descs[0]->algo != 0 || descs[0]->dtype != 0 || !g_direct_forms.load(std::memory_order_relaxed)) return;
+    for (int i = 0; i < n; ++i)
+        if (I2R_DBG(grp.g[i]) != 0 || descs[i]->in2) return;  // (in2: conv_body's order, see conv_body_forms)
+    form = 1;
+    epi = descs[0]->res1 ? 2 : 1;
+    for (int i = 0; i < n; ++i) {
+        const i2r_conv_desc* d = descs[i];
+        if (grp.g[i].npass != 1) form = 2;
+        if (d->relu != 1 || d->res2 || d->res_post || d->rep != 1 || d->cout != d->cout_pad || d->cout_pad > d->out_cs ||
+            (d->res1 != nullptr) != (descs[0]->res1 != nullptr))
+            epi = 0;
+    }
+}
+
 // The plan of a launch.  with_table: the launch has a dispatch table (i2r_conv_grouped's block_map); without one a Winograd launch
 // numbers its items in XCD bands, which changes its grid.
 int resolve(const i2r_conv_desc* const* descs, int32_t n, bool with_table, ConvPlan& p) {
@@ -404,8 +429,9 @@ int resolve(const i2r_conv_desc* const* descs, int32_t n, bool with_table, ConvP
     I2R_CHECK_ARG(p.total < (1ll << 31), "i2r_conv_grouped: grid");
     p.fused_in = p.algo == 1 && any_fused_input(descs, n);
     p.form = p.algo == 1 ? wino_form(descs, n, grp) : 0;
+    direct_form(descs, n, grp, p.pf, p.mt, p.dform, p.depi);
     p.fn = reinterpret_cast<conv_fn>(p.algo == 1    ? i2r_pick_conv_wino(p.nt, p.mt, p.fused_in, p.form)
-                                     : p.dtype == 0 ? i2r_pick_conv_f32(p.nt, p.mt, p.cap, p.pf)
+                                     : p.dtype == 0 ? i2r_pick_conv_f32(p.nt, p.mt, p.cap, p.pf, p.dform, p.depi)
                                      : p.dtype == 1 ? i2r_pick_conv_bf16(p.nt, p.mt, p.cap, p.pf)
                                                     : i2r_pick_conv_f16(p.nt, p.mt, p.cap, p.pf));
     return I2R_OK;
@@ -423,6 +449,20 @@ extern "C" int i2r_conv_wino_form(const i2r_conv_desc* const* descs, int32_t n, 
     if (int rc = resolve(descs, n, true, p)) return rc;
     I2R_CHECK_ARG(form != nullptr, "i2r_conv_wino_form: form");
     *form = p.form;
+    return I2R_OK;
+}
+
+extern "C" int i2r_conv_direct_forms(int32_t on) {
+    g_direct_forms.store(on ? 1 : 0, std::memory_order_relaxed);
+    return I2R_OK;
+}
+
+extern "C" int i2r_conv_direct_form(const i2r_conv_desc* const* descs, int32_t n, int32_t* form, int32_t* epi) {
+    ConvPlan p;
+    if (int rc = resolve(descs, n, true, p)) return rc;
+    I2R_CHECK_ARG(form != nullptr, "i2r_conv_direct_form: form");
+    *form = p.dform;
+    if (epi) *epi = p.depi;
     return I2R_OK;
 }
 

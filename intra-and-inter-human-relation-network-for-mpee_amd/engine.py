@@ -42,6 +42,7 @@ PRUNE_FUSE = True  # the last HRNet module computes only the fuse outputs its ca
 WINOGRAD = True  # fp32 3x3 stride-1 convs on the Winograd F(2x2, 3x3) kernels
 WINO_SEQ = True  # ... whose workgroups run several fragments on one set-up, as many as the library chooses per launch (i2r_conv_desc.seq = 0; False: one)
 WINO_FORMS = True  # ... with the epilogue compiled per shape (bias + ReLU, bias + res1 + ReLU; i2r_conv_wino_forms); False: the general epilogue, same bits
+CONV_FORMS = True  # direct fp32 convs (conv_igemm_f32) on their single-chunk / pipelined bodies and epilogue forms (i2r_conv_direct_forms); False: the general body, same bits
 # fork / join / record / wait as device-side signal / wait kernels (csrc/i2r_api.hip) when the lanes are independent queues.  A wait kernel
 # spins until ANOTHER kernel signals it: under a tool that lets one kernel run at a time (rocprofv3 counter collection serialises dispatches)
 # it could only time out, so the event form is used whenever a profiler library is attached to the process.
@@ -166,6 +167,18 @@ def push_wino_forms():
     if _wino_forms_pushed != bool(WINO_FORMS):
         cabi.check(cabi.lib().i2r_conv_wino_forms(int(bool(WINO_FORMS))), "i2r_conv_wino_forms")
         _wino_forms_pushed = bool(WINO_FORMS)
+
+
+_conv_forms_pushed = None
+
+
+def push_conv_forms():
+    """CONV_FORMS -> the library's process-wide switch (i2r_conv_direct_forms); a launch resolves its form when it runs, so this is
+    called before a program runs, one comparison when nothing changed"""
+    global _conv_forms_pushed
+    if _conv_forms_pushed != bool(CONV_FORMS):
+        cabi.check(cabi.lib().i2r_conv_direct_forms(int(bool(CONV_FORMS))), "i2r_conv_direct_forms")
+        _conv_forms_pushed = bool(CONV_FORMS)
 
 
 class Program:
@@ -981,6 +994,7 @@ class Program:
         activation arena and hand-off counters: never replay one Program concurrently on two streams."""
         L = cabi.lib()
         push_wino_forms()
+        push_conv_forms()
         cur = torch.cuda.current_stream(self.device).cuda_stream
         if side_streams is None:
             streams = (C.c_void_p * 4)(cur, cur, cur, cur)
