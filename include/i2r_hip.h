@@ -804,6 +804,46 @@ typedef struct i2r_attn_flip_merge_args {
 } i2r_attn_flip_merge_args;
 I2R_API int i2r_attn_flip_merge(const i2r_attn_flip_merge_args* a, void* stream);
 
+/* Attention roll-out (Abnar & Zuidema 2020): a soft-max map APPLIED to a thin matrix, the one step the relations through all encoder
+ * layers are chained from, without ever building [L_g, L_g] (additive: I2R_ABI_VERSION unchanged).  Take a stack with captured layers
+ * lo .. hi, a contiguous range; P_l is the head-averaged softmax(q k^T) of layer l, exactly what i2r_attn_weights defines:
+ *   A_l = (1 - alpha) I + alpha P_l          alpha in [0, 1]
+ *   T   = A_hi A_hi-1 ... A_lo               (rows sum to 1)
+ * T[q, k] is how much output token q of layer hi draws on input token k of layer lo.  All working matrices are X [K_g, L_g], row-major,
+ * fp32, per group: the scale-1 layout of i2r_attn_query_maps.  One STEP (this call, on the q|k of one layer) is
+ *   side 0:  X' = (1 - alpha) X + alpha X P_l            side 1:  X' = (1 - alpha) X + alpha X P_l^T
+ *   result                                              seed X_0                                      side  layer order
+ *   dependency rows at query tokens, T[q, :]            one-hot row at q (negative token: zero row)    0     hi -> lo
+ *   affect columns at query tokens, T[:, q]             the same                                       1     lo -> hi
+ *   per person dependency D_T[i, k] = mean_{q in i} T[q, k]   row i = 1 / seg on person i's tokens     0     hi -> lo
+ *   per person affect F_T[j, q] = sum_{k in j} T[q, k]        row j = 1 on person j's tokens           1     lo -> hi
+ *   relation R_T[i, j] = sum_{k in j} D_T[i, k] = mean_{q in i} F_T[j, q] (from whichever chain ran)
+ *   qk, grp_off, ws, ws_stride, heads, hp, k_off, qk_cs, n_grp: exactly as i2r_attn_weights reads them (ws: ws_stride floats per token row)
+ *   in, out  group g's [K_g, L_g] block at in + x_off[g] and out + x_off[g]; x_off device int64 [n_grp]; in != out
+ *   K_g      seg > 0: L_g / seg; seg == 0: q_cnt[g] (optional device int32 [n_grp]) clamped to [0, K], K without q_cnt -- as
+ *            i2r_attn_flip_merge counts its rows
+ *   scale, h, w, rows: as in i2r_attn_query_maps -- scale > 1 (the LAST step of a chain): the raw rows go to the workspace rows
+ *            (K * grp_off[n_grp] floats; seg > 0: max K_g in place of K) and group g's [K_g, P_g, h scale, w scale] block, the bilinear
+ *            up-sampling of i2r_attn_query_maps, to out + out_off[g]; out_off device int64 [n_grp], NULL = x_off (scale 1 only)
+ *   grp_off_host  HOST copy of grp_off[0 .. n_grp], always: it is checked here and sizes the launches
+ * Passes: the statistics pass of i2r_attn_weights; one product pass, one workgroup of 8 waves per (16 output columns, 64 rows of X), which
+ * recomputes the map's entries on the fp32 matrix pipe and feeds each probability fragment straight back as an operand against the
+ * matching 4-wide slice of X (side 1: the S^T fragments of i2r_attn_weights; side 0: the S fragments of the column form); then the
+ * up-sampling pass.  Heads are summed in a fixed order; wave w walks every 8th piece of the reduction dimension in ascending order and
+ * the partial sums are added in wave order (a fixed-order combine through LDS), no atomics: deterministic.  An
+ * empty group is skipped; nothing outside the computed groups' blocks is written; a zero row of in gives a zero row of out; alpha == 0
+ * copies in bit for bit.  I2R_E_ARG (nothing is launched): null pointers, in == out, side outside {0, 1}, alpha outside [0, 1] (NaN too),
+ * scale outside 1 .. 64, seg < 0, seg == 0 with K < 1 or >= 2^20, n_grp outside 1 .. 65535, a group length that seg (or, at scale > 1,
+ * h w) does not divide, scale > 1 without rows / out_off or with h or w < 1, ws_stride < 2 heads ceil(max L_g / 128), and the heads / hp /
+ * stride / alignment conditions of i2r_attn_weights. */
+typedef struct i2r_attn_rollout_args {
+    const float* qk; const float* in; float* out; const int32_t* grp_off; const int64_t* x_off; const int64_t* out_off; float* ws;
+    const int32_t* q_cnt; float* rows; const int32_t* grp_off_host;
+    int32_t n_grp, heads, hp, k_off, qk_cs, ws_stride, K, seg, side, scale, h, w;
+    float alpha; int32_t reserved;
+} i2r_attn_rollout_args;
+I2R_API int i2r_attn_rollout_step(const i2r_attn_rollout_args* a, void* stream);
+
 /* i2r_token_mirror -- dst[i] = mu(src[i]) for the n entries of a device int32 token table whose token maps are w wide; a negative entry
  * (a skip) is kept.  src and dst are two tables.  n == 0 returns I2R_OK without a launch.  I2R_E_ARG: a null pointer, n < 0, w < 1. */
 I2R_API int i2r_token_mirror(const int32_t* src, int32_t* dst, int64_t n, int32_t w, void* stream);

@@ -1,7 +1,7 @@
 """The forms of an attention-map capture (Engine.forward(..., capture=, queries=, persons=)): full [L, L] maps, their rows / columns at
-query points, their reductions per person.  A form knows its program key, the launch a captured layer emits, the layout of one call
+query points, their reductions per person, and the roll-out through all captured layers of a stack (rollout=).  A form knows its program key, the launch a captured layer emits, the layout of one call
 (plan: integers only -- sizes, offsets and tile counts as include/i2r_hip.h specifies them), the per-call fields of a launch (patch) and
-the shape of what the caller gets back.  Nothing here touches a device or the library: Program.bind_capture (engine.py) does, for all three.
+the shape of what the caller gets back.  Nothing here touches a device or the library: Program.bind_capture (engine.py) does, for all of them.
 """
 import collections
 import dataclasses
@@ -61,6 +61,31 @@ class JointQueries:
         self.upsample = {st: int(r) for st, r in upsample.items()} if isinstance(upsample, dict) else int(upsample)
 
 
+class Rollout:
+    """The roll-out form of an attention-map capture (Engine.forward(..., capture=, rollout=)): the relations THROUGH the captured layers
+    lo .. hi of a stack (a contiguous range) instead of the maps of each.  With P_l the head-averaged softmax(q k^T) of layer l,
+      A_l = (1 - alpha) I + alpha P_l,  T = A_hi A_hi-1 ... A_lo  (rows sum to 1; Abnar & Zuidema 2020),
+    T[q, k] is how much output token q of layer hi draws on input token k of layer lo (include/i2r_hip.h: i2r_attn_rollout_step).
+    tokens given ({stack: int32 [groups, K]}, counts, capacity: as AttnQueries): rows T[q, :] (mode 0 / "dependency") or columns T[:, q]
+      (mode 1 / "affect") at the query tokens, up-sampled by `upsample` (an int, or {stack: scale});
+    tokens None: the per-person reductions of the inter-human stack -- the relation R_T [P, P] per image, and with mode 1 / "dependency"
+      the maps D_T[i, k] = mean_{q in i} T[q, k], 2 / "affect" F_T[j, q] = sum_{k in j} T[q, k] (mode 0 / None: none), as PersonMaps."""
+
+    def __init__(self, tokens=None, mode="dependency", alpha=0.5, upsample=1, counts=None, capacity=None):
+        self.points = tokens is not None
+        modes = AttnQueries.MODES if self.points else PersonMaps.MODES
+        if isinstance(mode, bool) or mode not in modes:
+            raise ValueError("mode %r: %s" % (mode, "'dependency' or 'affect'" if self.points else "None, 'dependency' or 'affect'"))
+        alpha = float(alpha)
+        if not 0.0 <= alpha <= 1.0:  # (NaN too)
+            raise ValueError("alpha %r (0 .. 1)" % (alpha,))
+        self.tokens, self.mode, self.alpha, self.counts = dict(tokens) if self.points else None, modes[mode], alpha, counts
+        self.upsample = {st: int(r) for st, r in upsample.items()} if isinstance(upsample, dict) else int(upsample)
+        self.capacity = 0
+        if self.points:
+            self.capacity = int(capacity) if capacity is not None else max(int(torch.as_tensor(t).shape[-1]) for t in self.tokens.values())
+
+
 # One set of blocks of a layer's part of the per-call buffer: group g's block starts offs[g] floats behind the set, the set `base` floats
 # behind the layer; shapes: the view of every group's block, None for a set nobody reads (person maps in mode 0).
 Block = collections.namedtuple("Block", "offs base shapes")
@@ -85,6 +110,10 @@ class Plan:
     # [rows_g, L_g] block starts raw_offs[g] floats behind either workspace of raw_floats floats
     raw_offs: tuple = ()
     raw_floats: int = 0
+    # the roll-out form only: floats behind the capture's block sets (its two working matrices), and the seed of the chain: (int64 flat
+    # indices into a working matrix, the value they get; everything else is 0)
+    extra_floats: int = 0
+    seed: tuple = ()
 
 
 def _layer(*sets):
@@ -108,12 +137,29 @@ def _tiles(rows, keys, key_tile=AW_KEYS):
     return sum(-(-r // 16) * -(-k // key_tile) for r, k in zip(rows, keys))
 
 
+def _query_tables(call, stack, lens):
+    """the validated tables of a call with query tokens (AttnQueries, Rollout) -> (tokens int32 [groups, K] on the host, K, entries per group)"""
+    tok = torch.as_tensor(call.tokens[stack]).to("cpu", torch.int32).contiguous()
+    if tok.dim() != 2 or tok.shape[0] != len(lens) or tok.shape[1] < 1:
+        raise ValueError("query tokens of %r: shape %s, expected [%d groups, K]" % (stack, tuple(tok.shape), len(lens)))
+    K = tok.shape[1]
+    cnt = getattr(call, "counts", None)
+    cnt = [int(c) for c in cnt[stack]] if cnt and cnt.get(stack) is not None else [K] * len(lens)
+    if len(cnt) != len(lens) or not all(1 <= c <= K for c in cnt):
+        raise ValueError("query counts of %r: %s for %d groups of up to %d entries" % (stack, cnt, len(lens), K))
+    for g, (n, c) in enumerate(zip(lens, cnt)):
+        if int(tok[g, :c].max()) >= n:
+            raise ValueError("query token %d of group %d of %r is outside its %d tokens" % (int(tok[g, :c].max()), g, stack, n))
+    return tok, K, cnt
+
+
 class Form:
-    """what the three forms share; a form is made per call (resolve), and a program keeps the one it was built with"""
+    """what the forms share; a form is made per call (resolve), and a program keeps the one it was built with"""
     N_BLOCKS = 1  # block sets per layer = device offset tables per capture
     call = None   # what bind_capture hands to plan() per call
     deferred = False  # True: a captured layer keeps its q|k and emits nothing; the engine runs the form's launches behind the program
     merged = False    # True (merge()): the maps of the flip test, M = (P + un-mirrored P') / 2 (i2r_attn_flip_merge)
+    per_stack = False  # True: the captured layers of a stack share ONE set of blocks (their product), not one each
 
     def __init__(self, capture, suffix=()):
         self.capture, self.key = capture, ("capture", capture) + suffix  # (key: the part of the program key behind the shape)
@@ -196,19 +242,8 @@ class QueryForm(Form):
 
     def plan(self, stack, hw, lens, heads, call=None):
         """call: the AttnQueries of this call -- tokens[stack] int32 [groups, K] (-1 = skip), optionally counts[stack] (entries per group)"""
-        scale = self.scales[stack]
-        tok = torch.as_tensor(call.tokens[stack]).to("cpu", torch.int32).contiguous()
-        if tok.dim() != 2 or tok.shape[0] != len(lens) or tok.shape[1] < 1:
-            raise ValueError("query tokens of %r: shape %s, expected [%d groups, K]" % (stack, tuple(tok.shape), len(lens)))
-        K = tok.shape[1]
-        cnt = getattr(call, "counts", None)
-        cnt = [int(c) for c in cnt[stack]] if cnt and cnt.get(stack) is not None else [K] * len(lens)
-        if len(cnt) != len(lens) or not all(1 <= c <= K for c in cnt):
-            raise ValueError("query counts of %r: %s for %d groups of up to %d entries" % (stack, cnt, len(lens), K))
-        for g, (n, c) in enumerate(zip(lens, cnt)):
-            if int(tok[g, :c].max()) >= n:
-                raise ValueError("query token %d of group %d of %r is outside its %d tokens" % (int(tok[g, :c].max()), g, stack, n))
-        return self._layout(scale, hw, lens, heads, K, cnt, (tok, torch.tensor(cnt, dtype=torch.int32)))
+        tok, K, cnt = _query_tables(call, stack, lens)
+        return self._layout(self.scales[stack], hw, lens, heads, K, cnt, (tok, torch.tensor(cnt, dtype=torch.int32)))
 
     def _layout(self, scale, hw, lens, heads, K, cnt, tables):
         """the plan of groups of lens tokens that use cnt of the K entries of their table rows"""
@@ -303,17 +338,117 @@ class PersonForm(Form):
         return tuple(views)  # (relation, maps)
 
 
+class RolloutForm(Form):
+    """the relations through the captured layers lo .. hi of every captured stack (Rollout; i2r_attn_rollout_step): a chain of thin
+    products X' = (1 - alpha) X + alpha X P_l (side 0, layers hi -> lo) or ... X P_l^T (side 1, lo -> hi) from a seed X_0, ping-pong
+    between two working matrices [K_g, L_g] per group behind the stack's blocks in the capture buffer; the last step writes (and
+    up-samples) into the blocks.  Deferred: a captured layer keeps its q|k and the engine runs the chain behind the head.  Per stack ONE
+    set of result blocks -- at query tokens the layout of the query form, per person that of the per-person form (relation, maps) --
+    and a last, view-less set: the scale-1 layout of the working matrices.  alpha is per call: it is not in the key."""
+    deferred = per_stack = True
+
+    def __init__(self, capture, rollout):
+        self.points, self.mode = bool(rollout.points), int(rollout.mode)
+        stacks = sorted({st for st, _ in capture})
+        self.range = {}
+        for st in stacks:
+            layers = sorted(i for s, i in capture if s == st)
+            if layers != list(range(layers[0], layers[-1] + 1)):
+                raise ValueError("rollout: the layers %s of %r are not a contiguous range" % (layers, st))
+            self.range[st] = (layers[0], layers[-1])
+        up = rollout.upsample
+        try:
+            scales = tuple((st, int(up[st] if isinstance(up, dict) else up)) for st in stacks)
+        except KeyError as e:
+            raise ValueError("rollout.upsample has no scale for stack %s" % e)
+        if not all(1 <= r <= 64 for _, r in scales):
+            raise ValueError("rollout: upsample %r (1 .. 64)" % (up,))
+        if self.points:
+            missing = set(stacks) - set(rollout.tokens)
+            if missing:
+                raise ValueError("rollout.tokens has no table for %s" % sorted(missing))
+            self.side = self.mode
+        else:
+            self.side = 1 if self.mode == 2 else 0  # (relation only: the dependency chain)
+        self.N_BLOCKS = 2 if self.points else 3
+        Form.__init__(self, capture, ("rollout", "points" if self.points else "persons", self.mode, int(rollout.capacity), scales))
+        self.call, self.scales = rollout, dict(scales)
+
+    def launch(self, cap, qk, L, goff):
+        return None, cabi.AttnRolloutArgs(qk=qk.ptr, grp_off=goff.data_ptr(), heads=L["heads"], hp=L["hp"], k_off=L["hs"], qk_cs=qk.cs, K=1, side=self.side,
+                                          seg=0 if self.points else cap["x"].h * cap["x"].w, scale=1, h=cap["x"].h, w=cap["x"].w)
+
+    def plan(self, stack, hw, lens, heads, call=None):
+        """call: the Rollout of this call (tokens, counts: as the query form; alpha)"""
+        scale, (h, w) = self.scales[stack], hw
+        assert all(n % (h * w) == 0 for n in lens)
+        pers = [n // (h * w) for n in lens]
+        if self.points:
+            tok, K, cnt = _query_tables(call, stack, lens)
+            tables = (torch.tensor(cnt, dtype=torch.int32),)
+            sets = [[(c, p, h * scale, w * scale) for c, p in zip(cnt, pers)]]
+        else:
+            K, cnt, tables = max(pers), pers, ()
+            sets = [[(p, p) for p in pers], [(p, p, h * scale, w * scale) if self.mode else None for p in pers]]
+        blocks, n_layer = _layer(*sets)
+        x_offs = [0]
+        for c, n in zip(cnt, lens):
+            x_offs.append(x_offs[-1] + c * n)
+        x_floats = -(-x_offs[-1] // 4) * 4
+        blocks.append(Block(x_offs, n_layer, None))  # (the two working matrices start behind the stack's blocks)
+        idx = []
+        for g, (c, n) in enumerate(zip(cnt, lens)):
+            if self.points:
+                k = torch.arange(c)[tok[g, :c] >= 0]
+                idx.append(x_offs[g] + k * n + tok[g, :c][tok[g, :c] >= 0].long())
+            else:  # row p: person p's tokens
+                t = torch.arange(n)
+                idx.append(x_offs[g] + (t // (h * w)) * n + t)
+        value = 1.0 if self.points or self.side == 1 else 1.0 / (h * w)
+        stride = _stride(heads, lens)
+        return Plan(len(lens), stride, stride * sum(lens), K * sum(lens) if scale > 1 else 1, blocks, n_layer, K=K, tables=tables,
+                    extra_floats=2 * x_floats, seed=(torch.cat(idx), value))
+
+    @staticmethod
+    def patch(a, p, out, ws, rows, tables, host_off):
+        a.ws, a.rows, a.q_cnt, a.grp_off_host = ws, rows, tables[0] if tables else None, host_off
+        a.n_grp, a.ws_stride, a.K = p.n_grp, p.ws_stride, p.K
+
+    def result(self, views, inputs):
+        """per stack (not per layer): at query tokens {stack: per group a view}; per person ({stack: relations}, {stack: maps})"""
+        strip = lambda d: {st: v for (st, _), v in d.items()}
+        return strip(views[0]) if self.points else (strip(views[0]), strip(views[1]))
+
+
 FLIP_MAPS = ("plain", "merged")
 
 
-def resolve(capture, queries, persons, flip_joint_map, stacks, inter_stack, window, joints=None, n_joints=None, flip_maps="plain"):
+def resolve(capture, queries, persons, flip_joint_map, stacks, inter_stack, window, joints=None, n_joints=None, flip_maps="plain", rollout=None):
     """What Engine.forward / forward_single were asked for -> the form of the call, None without a capture.  stacks: the engine's
     capture_stacks(); inter_stack: the prefix of its inter-human stack; window: the inter-human block is the window type; joints: a
     JointQueries of a model of n_joints joints -- with flip_maps "plain" the one form that goes with the flip test (its launches run
     behind the merge, on the plain half); flip_maps "merged": the flip test's merged maps (Form.merge) of the query, per-person or joint
-    form -- never of the full [L, L] form, whose buffer it would double."""
+    form -- never of the full [L, L] form, whose buffer it would double.  rollout: a Rollout -- the relations through the captured layers,
+    a form of its own: not with the flip test (a product of merged maps is not the merge of products), nor with another form."""
     if flip_maps not in FLIP_MAPS:
         raise ValueError("flip_maps %r: 'plain' or 'merged'" % (flip_maps,))
+    if rollout is not None:
+        if window:
+            raise ValueError("rollout=: ATTENTION_TYPE window has no encoder stack to capture")
+        if flip_joint_map is not None or flip_maps != "plain":
+            raise ValueError("rollout=: not with the flip test (a product of merged maps is not the merge of products)")
+        if queries is not None or persons is not None or joints is not None:
+            raise ValueError("rollout=: not with queries=, persons= or joints= (predicted-joint queries are not served)")
+        if not capture:
+            raise ValueError("rollout= needs capture=: the (stack, layer) range to roll out")
+        capture = frozenset((str(st), int(i)) for st, i in capture)
+        for st, i in capture:
+            if st not in stacks or not 0 <= i < stacks[st]:
+                raise ValueError("capture (%r, %d): this model's encoder stacks are %s" % (st, i, stacks))
+        other = sorted({st for st, _ in capture} - {inter_stack})
+        if not rollout.points and other:
+            raise ValueError("rollout= per person: %s is not this model's inter-human stack %r" % (other, inter_stack if inter_stack in stacks else None))
+        return RolloutForm(capture, rollout)
     if flip_maps == "merged":
         if flip_joint_map is None:
             raise ValueError("flip_maps='merged' needs the flip test (flip_joint_map)")

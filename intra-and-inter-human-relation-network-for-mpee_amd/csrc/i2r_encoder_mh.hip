@@ -187,6 +187,7 @@ __global__ __launch_bounds__(256) void view_scramble_k(const float* __restrict__
 //   aw_block_stats  pass 1 of a 16-query tile over one key block (the online-softmax loop)
 //   aw_row_stats    the combine: (M, 1 / L) of a row and head from its block statistics
 //   aw_block_probs  pass 2 of a 16-query tile over the key tiles of one block, added into the caller's accumulators over the heads
+//   aw_tile_probs   pass 2 of a 16-query tile against 16 key rows in the S = Q K^T form (the gathered columns, the roll-out's side 0)
 //   aw_store4       the store tail: 4 consecutive floats of a row, one 16-byte piece or guarded elements
 constexpr int kAwKeys = 128, kAwTiles = kAwKeys / 16;
 
@@ -312,6 +313,32 @@ __device__ __forceinline__ void aw_block_probs(const AwK& p, int li, int g, int 
     }
 }
 
+// Tile probabilities in the S = Q K^T form (A = the rows of 16 queries, B = 16 key rows): acc[r] += exp2(s - M) / L of query row
+// q0 + 4g + r (clamped to its group, which ends at g1) and the lane's key row krow, over the heads in order; lane (g, li) holds 4
+// consecutive entries of column li, each with its own row's statistics
+template <int HB>
+__device__ __forceinline__ void aw_tile_probs(const AwK& p, int li, int g, int q0, int g1, int krow, int nkb, f32x4& acc) {
+    const int hs2 = p.ws_stride / 2, qrow = min(q0 + li, g1 - 1);
+    for (int head = 0; head < p.heads; ++head) {
+        float mm[4], inv[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r)  // the statistics of the lane's 4 query rows
+            aw_row_stats(p.ws + (size_t)min(q0 + 4 * g + r, g1 - 1) * hs2, nkb, p.heads, head, mm[r], inv[r]);
+        f32x4 q[HB];
+        aw_load_q<HB>(p, qrow, head, g, q);
+        const float* kp = p.qk + (size_t)krow * p.qk_cs + p.k_off + head * p.hp + 4 * g;
+        f32x4 s = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int u = 0; u < HB; ++u) {
+            const f32x4 kk = *reinterpret_cast<const f32x4*>(kp + 16 * u);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) s = mfma16(q[u][c], kk[c], s);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[r] += __builtin_amdgcn_exp2f(s[r] - mm[r]) * inv[r];
+    }
+}
+
 // The store tail: v = 4 consecutive floats of row `row` of the [*, len] block blk, at offset k (a multiple of 4) -- one 16-byte piece when the
 // block is 16-byte aligned and 4 divides len (every piece then lies whole inside its row), guarded element stores otherwise: no store ever
 // straddles a row end or touches a byte outside the block
@@ -357,8 +384,8 @@ __global__ __launch_bounds__(256) void aw_probs_k(const AwK p) {
 //   mode 0  aq_row_stats_k / aq_rows_k: aw_block_stats / aw_block_probs with the QUERY side gathered -- work item (group, 16 gathered
 //           queries, block of kAwKeys keys); workspace row = gi * K + k (K = row stride of q_tok), (m, l) per (key block, head) as above
 //   mode 1  aw_stats_k unchanged (every row's statistics), then aq_cols_k: the KEY side gathered, S = Q K^T (A = query rows, B = gathered
-//           key rows): lane (g, li) holds S[query 4g + r][gathered key li], i.e. 4 consecutive entries of column li -> one aw_store4; the
-//           one kernel of the family with a score form of its own (its 4 rows' statistics come from aw_row_stats)
+//           key rows): lane (g, li) holds S[query 4g + r][gathered key li], i.e. 4 consecutive entries of column li -> one aw_store4
+//           (aw_tile_probs: the family's second score form, its 4 rows' statistics from aw_row_stats)
 //   aq_upsample_k: each [P_g, h, w] row -> [P_g, h scale, w scale], F.interpolate's bilinear align_corners=False arithmetic
 // A negative token gives a zero row; a token >= L_g is clamped (the host validates; a device table cannot be checked by the entry point).
 struct AqK {
@@ -424,27 +451,9 @@ __global__ __launch_bounds__(256) void aq_cols_k(const AqK p) {
     const int nkb = aw_key_blocks(g1 - g0), nkt = (kq + 15) / 16, q0 = g0 + item / nkt * 16, kt = item - item / nkt * nkt;
     const int kc = kt * 16 + li;  // the lane's column (as the B operand and as the owner of the results)
     const int tok = p.q_tok[(size_t)gi * p.K + min(kc, kq - 1)];
-    const int krow = g0 + min(max(tok, 0), g1 - g0 - 1), qrow = min(q0 + li, g1 - 1);
-    const int hs2 = p.a.ws_stride / 2;
+    const int krow = g0 + min(max(tok, 0), g1 - g0 - 1);
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    for (int head = 0; head < p.a.heads; ++head) {
-        float mm[4], inv[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r)  // the statistics of the lane's 4 query rows
-            aw_row_stats(p.a.ws + (size_t)min(q0 + 4 * g + r, g1 - 1) * hs2, nkb, p.a.heads, head, mm[r], inv[r]);
-        f32x4 q[HB];
-        aw_load_q<HB>(p.a, qrow, head, g, q);
-        const float* kp = p.a.qk + (size_t)krow * p.a.qk_cs + p.a.k_off + head * p.a.hp + 4 * g;
-        f32x4 s = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int u = 0; u < HB; ++u) {
-            const f32x4 kk = *reinterpret_cast<const f32x4*>(kp + 16 * u);
-#pragma unroll
-            for (int c = 0; c < 4; ++c) s = mfma16(q[u][c], kk[c], s);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[r] += __builtin_amdgcn_exp2f(s[r] - mm[r]) * inv[r];
-    }
+    aw_tile_probs<HB>(p.a, li, g, q0, g1, krow, nkb, acc);
     if (kc >= kq) return;
     const float rh = tok < 0 ? 0.f : 1.f / (float)p.a.heads;
     aw_store4(aq_block(p, gi, g0), kc, g1 - g0, q0 - g0 + 4 * g, acc * rh);  // column kc as a contiguous vector over the query rows
@@ -656,8 +665,115 @@ __global__ __launch_bounds__(256) void ap_relation_k(const ApK p) {
     if (lane == 0) p.rel[p.rel_off[gi] + (long long)i * np + j] = s / (float)p.seg;
 }
 
+// ---- attention roll-out: one step X' = (1 - alpha) X + alpha X P (side 0) or (1 - alpha) X + alpha X P^T (side 1) of a thin matrix -----------
+// X [K_g, L_g] per group, the scale-1 layout of the query maps.  Behind aw_stats_k (every row's statistics), one product pass, one workgroup
+// of kArWaves waves per (group, 16 output columns, chunk of kArRows rows of X): wave w walks every kArWaves-th piece of the reduction
+// dimension in ascending order, the partial sums meet in LDS and are added in wave order (a fixed-order combine: deterministic):
+//   side 1 (ar_step_k<HB, 1>)  out[k, q] = sum_j X[k, j] P[q, j]: aw_block_probs of the 16 queries q over pieces of kApKeys keys
+//                              (S^T form: lane (g, li) holds P[query li][key 4g + r]), and p[r] IS the B operand of step r against
+//                              A = X[row li][keys 4g .. 4g + 3] -- the way enc_mh_attn_k feeds P into P V
+//   side 0 (ar_step_k<HB, 0>)  out[k, j] = sum_q X[k, q] P[q, j]: aw_tile_probs of the 16 keys j against one 16-query tile after the
+//                              other (S form: lane (g, li) holds P[query 4g + r][key li]), B of step r against A = X[row li][queries 4g ..]
+// Either way lane (g, li) ends with out[row 4g + r][column li].  The probabilities are summed over the heads (fixed order) before the
+// product; 1 / heads goes into the closing scale.  A key / query past the group's end has a clamped, finite probability and meets a zero
+// of X (ar_load4 reads nothing outside the block).  LDS for the combine only (the operands stay in registers), no atomics.  The last step of a chain writes its raw rows into the `rows`
+// workspace and aq_upsample_k makes the maps.
+constexpr int kArRows = 64, kArTiles = kArRows / 16, kArWaves = 8;  // (kArWaves >= kArTiles: wave x closes row tile x)
+
+struct ArK {
+    AqK q;  // q.a.out / q.a.out_off: the output blocks; q.rows: the raw rows at scale > 1
+    const float* in;
+    const long long* x_off;
+    float alpha;
+};
+
+__device__ __forceinline__ int ar_count(const ArK& p, int gi, int len) {
+    return p.q.seg > 0 ? (len % p.q.seg == 0 ? len / p.q.seg : 0) : aq_count(p.q, gi);
+}
+
+// X[row][k .. k + 3] of the [rows, len] block blk as the A operand of 4 matrix steps; zeros past the block's rows or the row's end
+__device__ __forceinline__ f32x4 ar_load4(const float* blk, int row, int rows, int len, int k) {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (row >= rows || k >= len) return v;
+    const float* src = blk + (long long)row * len + k;
+    if ((len & 3) == 0 && (reinterpret_cast<uintptr_t>(blk) & 15) == 0) return *reinterpret_cast<const f32x4*>(src);
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+        if (k + r < len) v[r] = src[r];
+    return v;
+}
+
+template <int HB, int SIDE>
+__global__ __launch_bounds__(64 * kArWaves) void ar_step_k(const ArK p) {
+    __shared__ f32x4 part[kArWaves][kArTiles][64];
+    const int lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4, wave = threadIdx.x >> 6;
+    int item = blockIdx.x, gi, g0, g1, kq = 0;  // (one item per workgroup: every wave takes the same branches up to the barrier)
+    const auto items = [&](int grp, int len) { return (len + 15) / 16 * (((kq = ar_count(p, grp, len)) + kArRows - 1) / kArRows); };
+    if (!aw_group(p.q.a, item, gi, g0, g1, items)) return;
+    const int len = g1 - g0, nkb = aw_key_blocks(len), nch = (kq + kArRows - 1) / kArRows;
+    const int c0 = g0 + item / nch * 16, r0 = (item - item / nch * nch) * kArRows;  // the item's 16 output columns (tokens), its first row of X
+    const float* xin = p.in + p.x_off[gi];
+    f32x4 o[kArTiles] = {};
+    if (SIDE == 1) {
+        const int qrow = min(c0 + li, g1 - 1);
+        const float2* st = p.q.a.ws + (size_t)qrow * (p.q.a.ws_stride / 2);
+        for (int k_beg = g0 + wave * kApKeys; k_beg < g1; k_beg += kArWaves * kApKeys) {  // the wave's pieces of 32 keys, ascending
+            const int n_kt = (min(k_beg + kApKeys, g1) - k_beg + 15) / 16;
+            f32x4 acc[kApTiles] = {};
+            aw_block_probs<HB>(p.q.a, li, g, qrow, st, nkb, c0 + li < g1, g1, k_beg, n_kt, acc);
+#pragma unroll
+            for (int t = 0; t < kApTiles; ++t) {
+                if (t < n_kt) {
+#pragma unroll
+                    for (int x = 0; x < kArTiles; ++x) {
+                        if (r0 + 16 * x < kq) {
+                            const f32x4 xa = ar_load4(xin, r0 + 16 * x + li, kq, len, k_beg - g0 + 16 * t + 4 * g);
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) o[x] = mfma16(xa[r], acc[t][r], o[x]);
+                        }
+                    }
+                }
+            }
+        }
+    } else {
+        const int krow = min(c0 + li, g1 - 1);
+        for (int qt = g0 + wave * 16; qt < g1; qt += kArWaves * 16) {  // the wave's query tiles, ascending
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            aw_tile_probs<HB>(p.q.a, li, g, qt, g1, krow, nkb, acc);
+#pragma unroll
+            for (int x = 0; x < kArTiles; ++x) {
+                if (r0 + 16 * x < kq) {
+                    const f32x4 xa = ar_load4(xin, r0 + 16 * x + li, kq, len, qt - g0 + 4 * g);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) o[x] = mfma16(xa[r], acc[r], o[x]);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int x = 0; x < kArTiles; ++x) part[wave][x][lane] = o[x];
+    __syncthreads();
+    // the combine: wave x adds the kArWaves partial sums of row tile x in wave order and writes the tile
+    if (wave >= kArTiles || r0 + 16 * wave >= kq || c0 + li >= g1) return;
+    f32x4 sum = part[0][wave][lane];
+#pragma unroll
+    for (int w = 1; w < kArWaves; ++w) sum += part[w][wave][lane];
+    const float keep = 1.f - p.alpha, mix = p.alpha / (float)p.q.a.heads;
+    float* blk = aq_block(p.q, gi, g0);
+    const int col = c0 - g0 + li;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {  // 16 lanes: 16 consecutive floats of one row
+        const int row = r0 + 16 * wave + 4 * g + r;
+        if (row >= kq) continue;
+        const float xv = xin[(long long)row * len + col];
+        blk[(long long)row * len + col] = p.alpha == 0.f ? xv : keep * xv + mix * sum[r];
+    }
+}
+
 // ---- host side: what the entry points share ----
 #define I2R_AW_TABLE(K) {K<1>, K<2>, K<3>, K<4>, K<5>, K<6>, K<7>, K<8>, K<9>, K<10>, K<11>, K<12>, K<13>, K<14>, K<15>, K<16>}  // [hp / 16 - 1]
+
+#define I2R_AW_TABLE2(K, S) {K<1, S>, K<2, S>, K<3, S>, K<4, S>, K<5, S>, K<6, S>, K<7, S>, K<8, S>, K<9, S>, K<10, S>, K<11, S>, K<12, S>, K<13, S>, K<14, S>, K<15, S>, K<16, S>}
 
 int mh_check_heads(const char* who, int heads, int hp) {
     I2R_CHECK_ARG(heads > 0 && hp > 0 && hp % 16 == 0 && hp <= 256, "%s: heads=%d hp=%d (hp: multiple of 16, <= 256)", who, heads, hp);
@@ -857,6 +973,58 @@ extern "C" int i2r_attn_person_maps(const i2r_attn_person_args* a, void* stream)
         const AqK u{k.a, nullptr, nullptr, a->rows + (a->mode == 1 ? total : 0), pmax, a->scale, a->h, a->w, a->seg};
         i2r_launch(aq_upsample_k, dim3((unsigned)((n4 + 255) / 256), (unsigned)a->n_grp), dim3(256), 0, st, u);
         I2R_CHECK_LAUNCH("i2r_attn_person_maps (up-sampling)");
+    }
+    return I2R_OK;
+}
+
+extern "C" int i2r_attn_rollout_step(const i2r_attn_rollout_args* a, void* stream) {
+    I2R_CHECK_ARG(a && a->qk && a->in && a->out && a->grp_off && a->x_off && a->ws && a->grp_off_host, "i2r_attn_rollout_step: null pointer");
+    I2R_CHECK_ARG(a->in != a->out, "i2r_attn_rollout_step: in == out (a step reads every row of in for every entry of out)");
+    I2R_CHECK_ARG(a->side == 0 || a->side == 1, "i2r_attn_rollout_step: side=%d (0: X P, 1: X P^T)", a->side);
+    I2R_CHECK_ARG(a->alpha >= 0.f && a->alpha <= 1.f, "i2r_attn_rollout_step: alpha=%g (0 .. 1)", (double)a->alpha);
+    I2R_CHECK_ARG(a->scale >= 1 && a->scale <= 64, "i2r_attn_rollout_step: scale=%d (1 .. 64)", a->scale);
+    I2R_CHECK_ARG(a->seg >= 0 && a->seg < (1 << 24) && (a->seg > 0 || (a->K >= 1 && a->K < (1 << 20))), "i2r_attn_rollout_step: seg=%d K=%d", a->seg, a->K);
+    if (const int e = aw_check("i2r_attn_rollout_step", a)) return e;
+    I2R_CHECK_ARG(a->n_grp < 65536, "i2r_attn_rollout_step: n_grp=%d", a->n_grp);
+    if (a->scale > 1) {
+        I2R_CHECK_ARG(a->rows && a->out_off && a->rows != a->in && a->rows != a->out, "i2r_attn_rollout_step: scale > 1 needs out_off and a rows workspace of its own");
+        I2R_CHECK_ARG(a->h > 0 && a->w > 0 && (long long)a->h * a->w < (1 << 24), "i2r_attn_rollout_step: h=%d w=%d", a->h, a->w);
+    }
+    long long n_stats = 0, n_items = 0;
+    int max_len = 0, max_rows = 0;
+    for (int g = 0; g < a->n_grp; ++g) {
+        const int len = a->grp_off_host[g + 1] - a->grp_off_host[g];
+        I2R_CHECK_ARG(len >= 0 && (a->seg == 0 || len % a->seg == 0) && (a->scale == 1 || len % (a->h * a->w) == 0), /* (an empty group is skipped) */
+                      "i2r_attn_rollout_step: group %d has %d tokens, not a multiple of seg = %d / h w = %d x %d", g, len, a->seg, a->h, a->w);
+        if (len == 0) continue;
+        const int rows = a->seg > 0 ? len / a->seg : a->K;  // (q_cnt lives on the device: K bounds it, surplus waves find no item)
+        n_stats += (long long)((len + 15) / 16) * aw_key_blocks(len);
+        n_items += (long long)((len + 15) / 16) * ((rows + kArRows - 1) / kArRows);  // (one workgroup each)
+        max_len = len > max_len ? len : max_len;
+        max_rows = rows > max_rows ? rows : max_rows;
+    }
+    I2R_CHECK_ARG(a->ws_stride >= 2 * a->heads * aw_key_blocks(max_len), "i2r_attn_rollout_step: ws_stride=%d for %d heads and groups of up to %d tokens",
+                  a->ws_stride, a->heads, max_len);
+    const long long n4 = ((long long)max_rows * max_len * a->scale * a->scale + 3) / 4;
+    I2R_CHECK_ARG(n_stats < (1ll << 31) && n_items < (1ll << 31) && (n4 + 255) / 256 < (1ll << 31), "i2r_attn_rollout_step: grid");
+    if (max_len == 0) return I2R_OK;  // (every group is empty)
+    const int K = a->seg > 0 ? max_rows : a->K;  // the row stride of the rows workspace, as the up-sampling pass reads it
+    const ArK k{AqK{aw_args(a, a->out, a->out_off ? a->out_off : a->x_off), nullptr, a->seg > 0 ? nullptr : a->q_cnt, a->rows, K, a->scale, a->h, a->w, a->seg},
+                a->in, reinterpret_cast<const long long*>(a->x_off), a->alpha};
+    typedef void (*aw_t)(const AwK);
+    typedef void (*ar_t)(const ArK);
+    static const aw_t stats[16] = I2R_AW_TABLE(aw_stats_k);
+    static const ar_t step0[16] = I2R_AW_TABLE2(ar_step_k, 0);
+    static const ar_t step1[16] = I2R_AW_TABLE2(ar_step_k, 1);
+    const int hb = a->hp / 16 - 1;
+    const hipStream_t st = (hipStream_t)stream;
+    i2r_launch(stats[hb], dim3((unsigned)((n_stats + 3) / 4)), dim3(256), 0, st, k.q.a);
+    I2R_CHECK_LAUNCH("i2r_attn_rollout_step (statistics)");
+    i2r_launch((a->side ? step1 : step0)[hb], dim3((unsigned)n_items), dim3(64 * kArWaves), 0, st, k);
+    I2R_CHECK_LAUNCH("i2r_attn_rollout_step (product)");
+    if (a->scale > 1) {
+        i2r_launch(aq_upsample_k, dim3((unsigned)((n4 + 255) / 256), (unsigned)a->n_grp), dim3(256), 0, st, k.q);
+        I2R_CHECK_LAUNCH("i2r_attn_rollout_step (up-sampling)");
     }
     return I2R_OK;
 }

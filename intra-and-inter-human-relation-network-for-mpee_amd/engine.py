@@ -11,7 +11,7 @@ import os
 import torch
 
 from . import attn_capture, cabi
-from .attn_capture import AttnQueries, JointQueries, PersonMaps  # noqa: F401 (the capture forms' public classes stay importable from here)
+from .attn_capture import AttnQueries, JointQueries, PersonMaps, Rollout  # noqa: F401 (the capture forms' public classes stay importable from here)
 from .pack import (PRECISIONS, PackedConv, Packer, _m16, _r16, fold_bn, pack_frag, pack_frag32, pack_k4, pack_k8,  # noqa: F401 (the packing names stay importable from here)
                    winograd_weights)
 
@@ -846,7 +846,8 @@ class Program:
             assert len(lens) >= 1 and list(lens) == [cur[g + 1] - cur[g] for g in range(len(lens))]
             plans.append(form.plan(cap["stack"], (cap["x"].h, cap["x"].w), lens, max(a.heads for _, a in cap["ops"]), call))
         form.share(plans)
-        buf = torch.empty(sum(p.layer_floats * len(cap["ops"]) for p, cap in zip(plans, self.captures)), dtype=torch.float32, device=self.device)
+        slots = (lambda cap: 1) if form.per_stack else (lambda cap: len(cap["ops"]))  # (a roll-out: one set of blocks per stack)
+        buf = torch.empty(sum(p.layer_floats * slots(cap) + p.extra_floats for p, cap in zip(plans, self.captures)), dtype=torch.float32, device=self.device)
         ws = torch.empty(max(p.ws_floats for p in plans), dtype=torch.float32, device=self.device)
         rows = torch.empty(max(p.rows_floats for p in plans), dtype=torch.float32, device=self.device)
         held = [ws, rows]  # (kept until the next call: the launches read them asynchronously; torch's allocator orders reuse by stream)
@@ -859,15 +860,20 @@ class Program:
             host_off = (C.c_int32 * (len(lens) + 1))(*cap["grouping"]["current"][:len(lens) + 1])  # (the query and person launches read it)
             held += tables + [host_off]
             ptrs = (ws.data_ptr(), rows.data_ptr(), [t.data_ptr() for t in tables], C.cast(host_off, C.c_void_p))
-            for i, a in cap["ops"]:
+            cap["base"] = base
+            for n, (i, a) in enumerate(cap["ops"]):
                 form.patch(a, p, buf.data_ptr() + 4 * base, *ptrs)
-                for out, blk in zip(views, p.blocks):
-                    if blk.shapes:
-                        b = base + blk.base
-                        out[(cap["stack"], i)] = [buf[b + o:b + e].view(s) for o, e, s in zip(blk.offs, blk.offs[1:], blk.shapes)]
-                base += p.layer_floats
+                if n < slots(cap):
+                    for out, blk in zip(views, p.blocks):
+                        if blk.shapes:
+                            b = base + blk.base
+                            out[(cap["stack"], i)] = [buf[b + o:b + e].view(s) for o, e, s in zip(blk.offs, blk.offs[1:], blk.shapes)]
+                    base += p.layer_floats
+            base += p.extra_floats
         if form.merged:
             self._bind_merge(plans, glens, buf, held)
+        if form.per_stack:
+            self._bind_rollout(plans, glens, buf, rows, held, call.alpha)
         self._capture_ws = held
         return views
 
@@ -905,6 +911,43 @@ class Program:
                         n_grp=n, K=p.K, seg=seg, scale=self.form.scale_of(cap["stack"]), h=cap["x"].h, w=cap["x"].w))
                 base += p.layer_floats
             cap["merge"] = m
+
+    def _bind_rollout(self, plans, glens, buf, rows, held, alpha):
+        """the per-call part of the roll-out form (attn_capture.RolloutForm) behind bind_capture: per capture a record cap["rollout"] of what
+        Engine._deferred_maps runs -- the seed of the chain (flat indices into the first working matrix, uploaded here), the steps in
+        chain order (side 0: layers hi -> lo, side 1: lo -> hi), each reading the matrix the step before wrote, the last one writing (and
+        up-sampling) into the stack's blocks, and for the per-person form the views the [P, P] relations are reduced from and into.
+        alpha: this call's (the program is not keyed by it)."""
+        form = self.form
+        for cap, lens, p in zip(self.captures, glens, plans):
+            xl, res = p.blocks[-1], p.blocks[-2]  # the working matrices' layout; the set the last step writes (maps)
+            n_x = p.extra_floats // 2
+            x0 = cap["base"] + xl.base
+            X = [buf[x0:x0 + n_x], buf[x0 + n_x:x0 + 2 * n_x]]
+            idx, value = p.seed
+            seed = idx.pin_memory().to(self.device, non_blocking=True)
+            x_off, out_off = cap["off"][-1], cap["off"][-2]
+            scale = form.scales[cap["stack"]]
+            ops = sorted(cap["ops"], key=lambda o: o[0], reverse=form.side == 0)
+            to_blocks = res.shapes is not None  # (per person without maps: the chain ends in a working matrix)
+            for n, (_, a) in enumerate(ops):
+                last = n == len(ops) - 1
+                a.in_, a.out, a.x_off, a.out_off, a.scale, a.alpha = X[n % 2].data_ptr(), X[(n + 1) % 2].data_ptr(), x_off.data_ptr(), None, 1, alpha
+                if last and to_blocks:
+                    a.out, a.out_off, a.scale = buf.data_ptr() + 4 * (cap["base"] + res.base), out_off.data_ptr(), scale
+            r = dict(X0=X[0], seed=seed, value=value, steps=[a for _, a in ops], rel=None)
+            if not form.points:  # R_T from the raw rows of the last step: in the maps blocks at scale 1, else in the working matrix / rows
+                cur = cap["grouping"]["current"]
+                if to_blocks and scale > 1:
+                    raw = [rows[p.K * cur[g]:p.K * cur[g] + (n // a.seg) * n] for g, n in enumerate(lens)]
+                else:
+                    src, b0 = (buf, cap["base"] + res.base) if to_blocks else (X[len(ops) % 2], 0)
+                    raw = [src[b0 + o:b0 + e] for o, e in zip(xl.offs, xl.offs[1:])]
+                rb = cap["base"] + p.blocks[0].base
+                r["rel"] = [(v.view(n // a.seg, n // a.seg, a.seg), buf[rb + o:rb + e].view(n // a.seg, n // a.seg))
+                            for v, n, o, e in zip(raw, lens, p.blocks[0].offs, p.blocks[0].offs[1:])]
+            held += [seed, r]
+            cap["rollout"] = r
 
     def set_groups(self, grouping, grp_off_host):
         """(Re)define the token groups of an encoder stack: uploads the offset table and patches the per-layer descriptors."""
@@ -2186,7 +2229,7 @@ class Engine:
     MAX_PROGRAMS = 48
     MAX_PROGRAM_BYTES = 32 << 30
 
-    def forward(self, x, pos_mask, length, flip_joint_map=None, capture=None, queries=None, persons=None, joints=None, flip_maps="plain"):
+    def forward(self, x, pos_mask, length, flip_joint_map=None, capture=None, queries=None, persons=None, joints=None, flip_maps="plain", rollout=None):
         """flip_joint_map (device int32 [J], see caller.joint_map): run the flip test in the same forward and return the merged
         'multi' heatmaps (the reference merges only outputs['multi'], function.py:137-162).
         capture: a set of (stack, layer) -- stack a state-dict prefix of capture_stacks() -- whose attention maps to return as well:
@@ -2214,14 +2257,21 @@ class Engine:
         test, M = (P + P~) / 2 with P~[q, k] = P'[mu(q), mu(k)] the mirrored pass's map brought back into the plain frame (DESIGN.md
         'i2r_attn_flip_merge'), in the layouts of the un-flipped calls; output is the merged heat maps.  The program is the flip program
         with a marker in its key; every captured layer holds its fp32 q|k of BOTH halves until the program ends, and the launches run
-        behind the head (_deferred_maps).  ValueError: without the flip test, with the full [L, L] form, the window-type block."""
+        behind the head (_deferred_maps).  ValueError: without the flip test, with the full [L, L] form, the window-type block.
+        rollout (attn_capture.Rollout, with capture of a contiguous layer range lo .. hi per stack): the attention roll-out T = A_hi ... A_lo,
+        A_l = (1 - alpha) I + alpha P_l, THROUGH those layers instead of the maps of each (DESIGN.md 'i2r_attn_rollout_step') -- with tokens
+        -> (output, {stack: maps}), maps as for queries of ONE layer: rows T[q, :] (mode 0) or columns T[:, q] (mode 1); without tokens (the
+        inter-human stack only) -> (output, ({stack: relation}, {stack: maps})) as for persons.  Every captured layer holds its fp32 q|k
+        until the program ends; the chain of i2r_attn_rollout_step launches runs behind the head between two working matrices in the
+        capture buffer.  One program per (capture set, kind, mode, K capacity, scales); alpha, points and grouping are per call.
+        ValueError: the flip test, another form, the window-type block, a layer set with a hole."""
         assert x.dim() == 4 and x.shape[1] == 3 and x.dtype == torch.float32
         S, _, H, W = x.shape
         assert S == sum(length), "sum(length)=%d != number of crops %d" % (sum(length), S)
         assert all(n >= 1 for n in length), "every image needs at least one person"
         sine_n = max(length)  # (MULTI_POS_EMBEDDING sine: the canvas is max(length) persons wide, for every part of this batch)
         form = attn_capture.resolve(capture, queries, persons, flip_joint_map, self.capture_stacks(), self.inter_stack, self.window_attn,
-                                    joints, self.cfg["MODEL"]["NUM_JOINTS"], flip_maps)
+                                    joints, self.cfg["MODEL"]["NUM_JOINTS"], flip_maps, rollout)
         if form:
             with torch.cuda.device(self.device):
                 return self._forward_part(x, pos_mask, list(length), flip_joint_map if form.deferred else None, S, H, W, sine_n, form=form)
@@ -2435,7 +2485,7 @@ class Engine:
             r += n
         return out
 
-    def forward_groups(self, x, pos_mask, members, group_len, flip_joint_map=None, share_first_stage=None, persons=None):
+    def forward_groups(self, x, pos_mask, members, group_len, flip_joint_map=None, share_first_stage=None, persons=None, rollout=None):
         """x [S, 3, H, W], pos_mask [S, 1, H, W]: the DISTINCT crops of a batch; members: device int32 [sum(group_len)] of crop indices in
         [0, S), group after group (input.main_target_groups); group_len: host list of the groups' sizes.  -> the 'multi' heat maps of the
         FIRST member of every group, [len(group_len), J, H/4, W/4] -- what the reference's validate_main_target keeps of model(x[members],
@@ -2448,9 +2498,11 @@ class Engine:
         expanded forward.  Programs are keyed by capacities only: other groups of the same sizes build nothing.  On every shared path
         (the default one of the HRNet tower included) a member index outside [0, S) is never dereferenced: the hand-over gathers are
         bound to the S real crops of the call, so its rows -- features, mask -- are zeros, never what a capacity slot holds.
-        persons: ValueError when given -- the grouped forward has no attention-map capture (forward(..., capture=, persons=) has)."""
+        persons, rollout: ValueError when given -- the grouped forward has no attention-map capture (forward(..., capture=, persons=) has)."""
         if persons is not None:
             raise ValueError("forward_groups: persons= is not served (no attention-map capture on the grouped forward)")
+        if rollout is not None:
+            raise ValueError("forward_groups: rollout= is not served (no attention-map capture on the grouped forward)")
         assert x.dim() == 4 and x.shape[1] == 3 and x.dtype == torch.float32
         assert share_first_stage in (None, True, False)
         S, _, H, W = x.shape
@@ -2607,6 +2659,20 @@ class Engine:
         relation matrices of the per-person form, mirror-invariant sums over whole persons, are merged by one torch expression on the
         same stream: R_m = (R + R') / 2.  Nothing here reads the device."""
         L, stream, form = cabi.lib(), torch.cuda.current_stream(self.device).cuda_stream, P.form
+        if form.per_stack:
+            # The roll-out form (the records of Program._bind_rollout): the seed by two torch fills, the chain of i2r_attn_rollout_step
+            # launches, and for the per-person form R_T = sum_{k in j} D_T = mean_{q in i} F_T as one torch reduction per image.
+            for cap in P.captures:
+                r = cap["rollout"]
+                r["X0"].zero_().index_fill_(0, r["seed"], r["value"])
+                for a in r["steps"]:
+                    cabi.check(L.i2r_attn_rollout_step(C.byref(a), stream), "i2r_attn_rollout_step")
+                for rows, rel in r["rel"] or ():
+                    if form.side == 0:
+                        torch.sum(rows, 2, out=rel)
+                    else:
+                        rel.copy_(rows.mean(2).t())
+            return
         name = "i2r_attn_person_maps" if form.N_BLOCKS == 2 else "i2r_attn_query_maps"
         launch = getattr(L, name)
         for cap in P.captures:

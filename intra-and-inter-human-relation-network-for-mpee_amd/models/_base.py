@@ -225,7 +225,7 @@ class I2RModule(nn.Module):
         with torch.no_grad():
             return eng.forward(x, pos_mask, [int(n) for n in length], flip_joint_map=jm)
 
-    def forward_main_target(self, x, pos_mask, length, boxes, max_patch=None, flip_pairs=None, share_first_stage=None):
+    def forward_main_target(self, x, pos_mask, length, boxes, max_patch=None, flip_pairs=None, share_first_stage=None, rollout=None):
         """The model side of the reference's grouped test mode (PATCH_MODE main_target: collater.get_max_patch + validate_main_target,
         lib/dataset/collater.py:35-51, lib/core/function.py:289-468): every person is the target of a group of itself and its
         min(n, max_patch) - 1 nearest neighbours in the image (input.main_target_groups, by the boxes' top-left corners), the model runs
@@ -237,6 +237,8 @@ class I2RModule(nn.Module):
         -> [S, J, H/4, W/4], one row per person in input order, so decode / val_metrics / rescore_nms / oks_eval take it with the
         ordinary per-person centres and scales."""
         from ..input import main_target_groups
+        if rollout is not None:
+            raise ValueError("forward_main_target: rollout= is not served (no attention-map capture on the grouped forward)")
         if torch.is_tensor(length):
             length = length.tolist()
         length = [int(n) for n in length]
@@ -416,6 +418,91 @@ class I2RModule(nn.Module):
         with torch.no_grad():
             out, (rel, views) = eng.forward(x, pos_mask, length, flip_joint_map=jm, capture=capture, persons=PersonMaps(maps, max(int(upsample), 1)),
                                             flip_maps=flip_maps)
+        return out, PersonRelations(rel, views)
+
+    def _rollout_served(self, who, flip_pairs):
+        """the refusals of a roll-out call that need no engine"""
+        if flip_pairs is not None:
+            raise ValueError("%s: flip_pairs is not served (a product of merged maps is not the merge of products)" % who)
+        name = self._engine_name() or self.cfg["MODEL"]["NAME"]
+        if name in ("transpose_h", "hrformer", "hrnet"):
+            raise ValueError("%s: the stand-alone stage %s is not served" % (who, name))
+        if name == "interformer" and self.cfg["MODEL"]["ATTENTION_TYPE"] != "default":
+            raise ValueError("%s: ATTENTION_TYPE %r has no encoder stack to capture" % (who, self.cfg["MODEL"]["ATTENTION_TYPE"]))
+
+    @staticmethod
+    def _rollout_capture(have, who, stacks, layers):
+        """stacks / layers of a roll-out call, have = the engine's capture_stacks() -> the capture set: every layer lo .. hi of every chosen stack"""
+        chosen = sorted(have) if stacks is None else [str(st) for st in ([stacks] if isinstance(stacks, str) else stacks)]
+        for st in chosen:
+            if st not in have:
+                raise ValueError("%s: this model's encoder stacks are %s, not %r" % (who, sorted(have), st))
+        if layers is None:
+            layers = {st: (0, have[st] - 1) for st in chosen}
+        elif not isinstance(layers, dict):
+            if len(layers) == 2 and all(isinstance(i, int) for i in layers):
+                layers = {st: tuple(layers) for st in chosen}
+            else:  # a set of (stack, layer): it has to be a range per stack (attn_capture.RolloutForm checks)
+                return {(str(st), int(i)) for st, i in layers}
+        capture = set()
+        for st, (lo, hi) in layers.items():
+            if str(st) not in have or not 0 <= int(lo) <= int(hi) < have[str(st)]:
+                raise ValueError("%s: layers (%r, %r) of %r; this model's encoder stacks are %s" % (who, lo, hi, st, have))
+            capture |= {(str(st), i) for i in range(int(lo), int(hi) + 1)}
+        return capture
+
+    def rollout_at(self, x, pos_mask, length, points, mode="dependency", stacks=None, layers=None, alpha=0.5, upsample=True, flip_pairs=None):
+        """The attention roll-out (Abnar & Zuidema 2020) at query points: the relations THROUGH the encoder layers lo .. hi of a stack,
+        computed on the device without ever building an [L, L] map.  With P_l the head-averaged softmax(q k^T) of layer l (what the
+        forward hooks get),  A_l = (1 - alpha) I + alpha P_l  and  T = A_hi A_hi-1 ... A_lo  (rows sum to 1): T[q, k] is how much output
+        token q of layer hi draws on input token k of layer lo.
+        points, the token rule, NaN = skip, outside the crop = ValueError, mode, upsample: exactly as attention_at -- "dependency" gives
+          the row T[q, :] (where the query point's output comes from), "affect" the column T[:, q] (which outputs draw on it).
+        stacks: the encoder stacks to roll out, default all; layers: None = every layer of each, (lo, hi) for all of them or
+          {stack: (lo, hi)}; a set of (stack, layer) with a hole is a ValueError.  alpha in [0, 1]: the weight of the attention against the
+          residual path (0.5 is the paper's).  With lo == hi and alpha = 1 the result is attention_at's of that layer.
+        -> (model output, {stack: maps}), maps as attention_at returns them for ONE layer.
+        ValueError: flip_pairs (a product of merged maps is not the merge of products; the definition is left open), points that are not
+        given (predicted-joint queries), ATTENTION_TYPE window, the stand-alone first stages.  Forward hooks keep working; this call serves none."""
+        from ..engine import Rollout
+        self._rollout_served("rollout_at", flip_pairs)
+        if points is None or isinstance(points, str):
+            raise ValueError("rollout_at: points %r -- predicted-joint queries are not served; pass [S, K, 2] points" % (points,))
+        if torch.is_tensor(length):
+            length = length.tolist()
+        length = [int(n) for n in length]
+        eng = self.engine()
+        capture = self._rollout_capture(eng.capture_stacks(), "rollout_at", stacks, layers)
+        capture, q = self._query_plan(eng, x, points, mode, capture, upsample, length)
+        with torch.no_grad():
+            out, maps = eng.forward(x, pos_mask, length, capture=capture, rollout=Rollout(q.tokens, mode, alpha, q.upsample, q.counts, q.capacity))
+        maps = self._query_result({(st, 0): v for st, v in maps.items()}, lambda st: st.startswith("singleformer."))
+        return out, {st: v for (st, _), v in maps.items()}
+
+    def person_rollout(self, x, pos_mask, length, maps=None, layers=None, alpha=0.5, upsample=False, flip_pairs=None):
+        """The attention roll-out of the inter-human stack per person: person_relations' three reductions of T = A_hi ... A_lo (rollout_at)
+        instead of one layer's map --
+          relation   R_T[i, j] = mean over the tokens q of person i of the sum over the tokens k of person j of T[q, k]   (rows sum to 1)
+          dependency D_T[i, k] = mean over the tokens q of person i of T[q, k]                                          (rows sum to 1)
+          affect     F_T[j, q] = sum over the tokens k of person j of T[q, k]                                            (sum over j = 1)
+        i.e. how much person i's output, after the layers lo .. hi, draws on person j's input, and where.
+        maps, upsample: as person_relations; layers: None = all layers of the stack, or (lo, hi); alpha: as rollout_at.
+        -> (model output, result): result.relation[stack] = a list with one [P_img, P_img] tensor per image; result.maps[stack] = a list
+          with one [P_img, P_img, h r, w r] tensor per image (empty without maps).  All are views of one buffer.
+        ValueError: flip_pairs, ATTENTION_TYPE window, the stand-alone first stages, a layer of another stack."""
+        self._rollout_served("person_rollout", flip_pairs)
+        if maps not in (None, "dependency", "affect"):
+            raise ValueError("maps %r: None, 'dependency' or 'affect'" % (maps,))
+        from ..engine import Rollout
+        if torch.is_tensor(length):
+            length = length.tolist()
+        length = [int(n) for n in length]
+        eng = self.engine()
+        capture = self._rollout_capture(eng.capture_stacks(), "person_rollout", [eng.inter_stack], layers)
+        if upsample is True:
+            upsample = x.shape[2] // eng.capture_map_sizes(x.shape[2], x.shape[3])[eng.inter_stack][0]
+        with torch.no_grad():
+            out, (rel, views) = eng.forward(x, pos_mask, length, capture=capture, rollout=Rollout(None, maps, alpha, max(int(upsample), 1)))
         return out, PersonRelations(rel, views)
 
     def forward(self, x, pos_mask, length):
