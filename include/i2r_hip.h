@@ -684,6 +684,14 @@ typedef struct i2r_encoder_desc {
 
 I2R_API int i2r_encoder_kv(const i2r_encoder_desc* d, void* stream);
 I2R_API int i2r_encoder_layer(const i2r_encoder_desc* d, void* stream);
+/* i2r_encoder_layer_form -- what i2r_encoder_layer would launch for this descriptor (additive: I2R_ABI_VERSION unchanged); the launcher
+ * and this query share one selection.  The descriptor is validated exactly as for a launch.
+ * fp32 (dtype 0): *qt = 16-query tiles per workgroup, 2 once n_qtiles32 >= 512, else 1; *ks = 2 for the partial key split (qt 1, scratch
+ * given, 32 < ceil(n_qtiles16 / 8) < 64), else 1 -> enc_layer4_k<cs / 16, 12, qt, ks>.
+ * 16-bit (dtype 1 / 2): *qt = 16-query fragments per work item -- 12 (four waves share 192 queries: n_qtiles64 >= 512 and
+ * n_qtiles192 > 0), 4 (64 queries per wave: n_qtiles64 >= 512), else 1 (16 queries per wave); *ks = 1.
+ * *grid (may be null): the workgroup count.  qt and ks are required.  No launch happens. */
+I2R_API int i2r_encoder_layer_form(const i2r_encoder_desc* d, int32_t* qt, int32_t* ks, int32_t* grid);
 
 /* i2r_mh_attention -- softmax(q k^T) v of nn.MultiheadAttention with ANY head count over the same variable-length token groups
  * (MODEL.N_HEAD > 1: interformer_pureMulti.py:461,473, transpose_h.py:457,467, interformer_2stage.py:221,233, attention.py:1039; the yacs

@@ -1274,6 +1274,62 @@ void lp_form(int dtype, int cs, F f) {
     }
 }
 
+// ---- what i2r_encoder_layer launches for a descriptor that passed fill(): ONE rule, shared by the launcher and by the launch-nothing
+//      query i2r_encoder_layer_form (include/i2r_hip.h), so that what the query reports cannot drift from what runs ----
+struct EncForm {
+    int qt;         // 16-query fragments per work item: fp32 1 | 2 (QT); 16-bit 1 | 4 (one wave), 12 (four waves, 192 queries) [tuning build: 2]
+    int ks;         // 2 = the partial key split (fp32, one tile per workgroup), else 1
+    int items;      // work items (the kernel's n_qblk)
+    int t_x;        // ks == 2: tiles per XCD
+    unsigned grid;  // workgroups
+};
+
+int select_form(const i2r_encoder_desc* d, EncForm& f) {
+    f.ks = 1;
+    f.t_x = 0;
+    if (d->dtype != 0) {
+        // 64 queries per wave when that still gives >= 2 waves per SIMD-pair of the chip, else 16 (more, shorter waves)
+        const bool big = d->n_qtiles64 >= 512;
+#ifdef I2R_TUNING
+        static const int qf_env = getenv("I2R_ENC_QF") ? atoi(getenv("I2R_ENC_QF")) : 0;  // tuning switch: 2 = 32 queries per wave
+        if (qf_env == 2 && big) {
+            f.qt = 2;
+            f.items = d->n_qtiles32;
+        } else
+#endif
+        if (big && d->n_qtiles192 > 0) {  // long groups: four waves per workgroup share the K / V stream through LDS (two workgroups per CU)
+            f.qt = 12;
+            f.items = d->n_qtiles192;
+        } else if (big) {
+            f.qt = 4;
+            f.items = d->n_qtiles64;
+        } else {
+            f.qt = 1;
+            f.items = d->n_qtiles16;
+        }
+        f.grid = (unsigned)((f.items + 7) / 8 * 8);  // work items are XCD-banded inside the kernels: a multiple of 8 workgroups
+        return I2R_OK;
+    }
+    I2R_CHECK_ARG(d->n_qtiles16 > 0 && d->n_qtiles32 > 0, "i2r_encoder_layer: n_qtiles16 / n_qtiles32");
+    // two 16-query tiles per workgroup halve the K / V traffic per MFMA; worth it once there are enough workgroups for the chip
+#ifdef I2R_TUNING
+    static const int qt_env = getenv("I2R_ENC_QT") ? atoi(getenv("I2R_ENC_QT")) : 0;  // tuning switch: force 1 or 2
+#else
+    constexpr int qt_env = 0;
+#endif
+    f.qt = qt_env ? qt_env : (d->n_qtiles32 >= 512 ? 2 : 1);
+    f.items = f.qt == 2 ? d->n_qtiles32 : d->n_qtiles16;
+    f.grid = (unsigned)((f.items + 7) / 8 * 8);  // (XCD-major tile order inside the kernel)
+    // between one and two tiles per CU (256 CUs = 8 XCDs x 32): split just enough tiles by keys that every CU gets two workgroups
+    const int t_x = (d->n_qtiles16 + 7) / 8;
+    if (f.qt == 1 && d->split_ws && d->split_cnt && t_x > 32 && t_x < 64) {
+        f.ks = 2;
+        f.t_x = t_x;
+        f.grid = 512;
+    }
+    return I2R_OK;
+}
+
 }  // namespace
 
 extern "C" int i2r_encoder_kv(const i2r_encoder_desc* d, void* stream) {
@@ -1299,64 +1355,58 @@ extern "C" int i2r_encoder_kv(const i2r_encoder_desc* d, void* stream) {
     return I2R_OK;
 }
 
+extern "C" int i2r_encoder_layer_form(const i2r_encoder_desc* d, int32_t* qt, int32_t* ks, int32_t* grid) {
+    I2R_CHECK_ARG(qt && ks, "i2r_encoder_layer_form: null form pointer");
+    EncK k;
+    int rc = fill(d, k);
+    if (rc) return rc;
+    EncForm f;
+    rc = select_form(d, f);
+    if (rc) return rc;
+    *qt = f.qt;
+    *ks = f.ks;
+    if (grid) *grid = (int32_t)f.grid;
+    return I2R_OK;
+}
+
 extern "C" int i2r_encoder_layer(const i2r_encoder_desc* d, void* stream) {
     EncK k;
     int rc = fill(d, k);
     if (rc) return rc;
+    EncForm f;
+    rc = select_form(d, f);
+    if (rc) return rc;
+    k.n_qblk = f.items;
     if (d->dtype != 0) {
-        // 64 queries per wave when that still gives >= 2 waves per SIMD-pair of the chip, else 16 (more, shorter waves)
-        const bool big = d->n_qtiles64 >= 512;
-#ifdef I2R_TUNING
-        static const int qf_env = getenv("I2R_ENC_QF") ? atoi(getenv("I2R_ENC_QF")) : 0;  // tuning switch: 2 = 32 queries per wave
-#endif
         lp_form(d->dtype, d->cs, [&](auto DT, auto CSR) {
             constexpr int dt = decltype(DT)::value, csr = decltype(CSR)::value;
-            // work items are XCD-banded inside the kernels: a multiple of 8 workgroups
-            auto one_wave = [&](auto QF, int items) {
-                k.n_qblk = items;
-                i2r_launch((enc_layer_lp_k<6, 12, decltype(QF)::value, dt, csr>), dim3((unsigned)((items + 7) / 8 * 8)), dim3(64), 0, (hipStream_t)stream, k);
+            auto one_wave = [&](auto QF) {
+                i2r_launch((enc_layer_lp_k<6, 12, decltype(QF)::value, dt, csr>), dim3(f.grid), dim3(64), 0, (hipStream_t)stream, k);
             };
+            if (f.qt == 12) i2r_launch((enc_layer_lp4_k<6, 12, dt, csr>), dim3(f.grid), dim3(256), 0, (hipStream_t)stream, k);
+            else if (f.qt == 4) one_wave(std::integral_constant<int, 4>{});
 #ifdef I2R_TUNING
-            if (qf_env == 2 && big) return one_wave(std::integral_constant<int, 2>{}, d->n_qtiles32);
+            else if (f.qt == 2) one_wave(std::integral_constant<int, 2>{});
 #endif
-            if (big && d->n_qtiles192 > 0) {  // long groups: four waves per workgroup share the K / V stream through LDS (two workgroups per CU)
-                k.n_qblk = d->n_qtiles192;
-                i2r_launch((enc_layer_lp4_k<6, 12, dt, csr>), dim3((unsigned)((d->n_qtiles192 + 7) / 8 * 8)), dim3(256), 0, (hipStream_t)stream, k);
-            } else if (big) {
-                one_wave(std::integral_constant<int, 4>{}, d->n_qtiles64);
-            } else {
-                one_wave(std::integral_constant<int, 1>{}, d->n_qtiles16);
-            }
+            else one_wave(std::integral_constant<int, 1>{});
         });
         I2R_CHECK_LAUNCH("i2r_encoder_layer");
         return I2R_OK;
     }
-    I2R_CHECK_ARG(d->n_qtiles16 > 0 && d->n_qtiles32 > 0, "i2r_encoder_layer: n_qtiles16 / n_qtiles32");
-    // two 16-query tiles per workgroup halve the K / V traffic per MFMA; worth it once there are enough workgroups for the chip
-#ifdef I2R_TUNING
-    static const int qt_env = getenv("I2R_ENC_QT") ? atoi(getenv("I2R_ENC_QT")) : 0;  // tuning switch: force 1 or 2
-#else
-    constexpr int qt_env = 0;
-#endif
-    const int qt = qt_env ? qt_env : (d->n_qtiles32 >= 512 ? 2 : 1);
-    k.n_qblk = qt == 2 ? d->n_qtiles32 : d->n_qtiles16;
-    unsigned grid = (unsigned)((k.n_qblk + 7) / 8 * 8);  // (XCD-major tile order inside the kernel)
-    // between one and two tiles per CU (256 CUs = 8 XCDs x 32): split just enough tiles by keys that every CU gets two workgroups
-    const int t_x = (d->n_qtiles16 + 7) / 8;
-    const bool split = qt == 1 && d->split_ws && d->split_cnt && t_x > 32 && t_x < 64;
+    const bool split = f.ks == 2;
     if (split) {
-        k.tiles_per_xcd = t_x;
-        k.full_per_xcd = 2 * t_x - 64;
-        grid = 512;
+        k.tiles_per_xcd = f.t_x;
+        k.full_per_xcd = 2 * f.t_x - 64;
     }
+    const dim3 grid(f.grid);
     if (d->cs == 96) {
-        if (qt == 2) i2r_launch((enc_layer4_k<6, 12, 2>), dim3(grid), dim3(256), 0, (hipStream_t)stream, k);
-        else if (split) i2r_launch((enc_layer4_k<6, 12, 1, 2>), dim3(grid), dim3(256), 0, (hipStream_t)stream, k);
-        else i2r_launch((enc_layer4_k<6, 12, 1>), dim3(grid), dim3(256), 0, (hipStream_t)stream, k);
+        if (f.qt == 2) i2r_launch((enc_layer4_k<6, 12, 2>), grid, dim3(256), 0, (hipStream_t)stream, k);
+        else if (split) i2r_launch((enc_layer4_k<6, 12, 1, 2>), grid, dim3(256), 0, (hipStream_t)stream, k);
+        else i2r_launch((enc_layer4_k<6, 12, 1>), grid, dim3(256), 0, (hipStream_t)stream, k);
     } else {
-        if (qt == 2) i2r_launch((enc_layer4_k<5, 12, 2>), dim3(grid), dim3(256), 0, (hipStream_t)stream, k);
-        else if (split) i2r_launch((enc_layer4_k<5, 12, 1, 2>), dim3(grid), dim3(256), 0, (hipStream_t)stream, k);
-        else i2r_launch((enc_layer4_k<5, 12, 1>), dim3(grid), dim3(256), 0, (hipStream_t)stream, k);
+        if (f.qt == 2) i2r_launch((enc_layer4_k<5, 12, 2>), grid, dim3(256), 0, (hipStream_t)stream, k);
+        else if (split) i2r_launch((enc_layer4_k<5, 12, 1, 2>), grid, dim3(256), 0, (hipStream_t)stream, k);
+        else i2r_launch((enc_layer4_k<5, 12, 1>), grid, dim3(256), 0, (hipStream_t)stream, k);
     }
     I2R_CHECK_LAUNCH("i2r_encoder_layer");
     return I2R_OK;
