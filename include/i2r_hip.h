@@ -789,6 +789,37 @@ typedef struct i2r_attn_person_args {
 } i2r_attn_person_args;
 I2R_API int i2r_attn_person_maps(const i2r_attn_person_args* a, void* stream);
 
+/* The target form of the maps per person (additive: I2R_ABI_VERSION unchanged): what grouped inference (PATCH_MODE main_target) needs of
+ * them.  Group g holds m_g = L_g / seg members; member 0, tokens [0, seg), is the TARGET, the only member whose output is kept, so only
+ * its query rows are computed.  With P, F, D, R as i2r_attn_person_maps defines them:
+ *   affect      F_t[j, q] = sum_{k in member j} P[q, k], q < seg        [m_g, seg]: which of the target's tokens look at member j; sum_j = 1
+ *   dependency  D_t[k]    = (1 / seg) sum_{q < seg} P[q, k] = D[0, k]   [L_g] = m_g maps [h, w]: where the target looks; sums to 1
+ *   relation    r[j]      = (1 / seg) sum_{q < seg} F_t[j, q] = R[0, j] [m_g]: sums to 1
+ *   rel[rel_off[g] + j] = r[j], always; mode 1: the maps block of group g holds D_t, mode 2: F_t, mode 0: maps is not touched
+ *   scale == 1: maps[maps_off[g] + t] = D_t[t]  /  maps[maps_off[g] + j seg + q] = F_t[j, q]     (L_g floats either way)
+ *   scale  > 1: seg = h w; the block is m_g maps [h, w] -> [m_g, h scale, w scale], the bilinear up-sampling of i2r_attn_query_maps
+ *   qk, grp_off, heads, hp, k_off, qk_cs, ws, ws_stride, seg, scale, h, w, grp_off_host: exactly as i2r_attn_person_maps reads them
+ *            (ws: ws_stride floats per token row, rows up to grp_off[n_grp]; only the targets' rows are written and read)
+ *   rel_off, maps_off  device int64 [n_grp]: float offsets of the groups' blocks (m_g floats / L_g scale^2 floats; maps, maps_off: may
+ *            be NULL in mode 0)
+ *   rows     device workspace of grp_off[n_grp] floats: F_t of group g, [m_g, seg], at rows + grp_off[g] (r is reduced from it in every
+ *            mode; mode 2 at scale 1 writes F_t straight into maps and leaves rows alone); twice that for mode 1 at scale > 1 (the raw
+ *            D_t of group g at rows + grp_off[n_grp] + grp_off[g])
+ * Only the first n_grp groups are computed; an empty group is skipped; nothing outside the computed groups' blocks is written.  Passes,
+ * one wave per work item: statistics (target 16-query tile, 128-key block) -- ceil(seg / 16) ceil(L_g / 128) per group; F_t (target
+ * 16-query tile, member j) -- ceil(seg / 16) m_g; mode 1: D_t (32-key block) -- ceil(L_g / 32); r (member j) -- m_g; then the
+ * up-sampling pass.  These are the person-0 / q < seg work items of i2r_attn_person_maps through the same device functions in the same
+ * head, tile and lane orders: at scale 1 rel, D_t and F_t are bit-identical to R[0, :], D[0, :] and F[:, 0:seg] of that call.  fp32
+ * matrix pipe, no LDS, no atomics: deterministic.  I2R_E_ARG (nothing is launched): null pointers, mode outside {0, 1, 2}, scale < 1 or
+ * > 64, seg < 1, n_grp outside 1 .. 65535, a group length that seg does not divide, scale > 1 with seg != h w, ws_stride < 2 heads
+ * ceil(max L_g / 128), and the heads / hp / stride / alignment conditions of i2r_attn_weights. */
+typedef struct i2r_attn_target_args {
+    const float* qk; const int32_t* grp_off; float* ws; float* rel; const int64_t* rel_off; float* maps; const int64_t* maps_off;
+    float* rows; const int32_t* grp_off_host;
+    int32_t n_grp, heads, hp, k_off, qk_cs, ws_stride, seg, mode, scale, h, w, reserved;
+} i2r_attn_target_args;
+I2R_API int i2r_attn_target_maps(const i2r_attn_target_args* a, void* stream);
+
 /* The maps above under the flip test (additive: I2R_ABI_VERSION unchanged).  A stack group has tokens (p, y, x), t = p h w + y w + x; the
  * mirror is mu(p, y, x) = (p, y, w - 1 - x), mu(t) = t - 2 (t mod w) + w - 1.  With P the map of a group in the plain pass and P' the map of
  * the same group in the mirrored pass, the merged map is M[q, k] = (P[q, k] + P'[mu(q), mu(k)]) / 2.  The caller runs i2r_attn_query_maps /
@@ -919,7 +950,8 @@ enum {
     I2R_OP_RECORD = 26, I2R_OP_WAIT = 27, I2R_OP_LANE_FLAGS = 28, I2R_OP_ATTN_WEIGHTS = 29,
     I2R_OP_ATTN_QUERY = 30,
     I2R_OP_ROWS_GATHER_MULTI = 31, /* args: i2r_gather_multi_args (additive: I2R_ABI_VERSION unchanged) */
-    I2R_OP_ATTN_PERSON = 32 /* args: i2r_attn_person_args (additive as well) */
+    I2R_OP_ATTN_PERSON = 32, /* args: i2r_attn_person_args (additive as well) */
+    I2R_OP_ATTN_TARGET = 33 /* args: i2r_attn_target_args (additive as well) */
 };
 
 typedef struct i2r_stem_args {

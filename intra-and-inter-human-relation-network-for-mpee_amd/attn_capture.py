@@ -1,5 +1,6 @@
 """The forms of an attention-map capture (Engine.forward(..., capture=, queries=, persons=)): full [L, L] maps, their rows / columns at
-query points, their reductions per person, and the roll-out through all captured layers of a stack (rollout=).  A form knows its program key, the launch a captured layer emits, the layout of one call
+query points, their reductions per person, the roll-out through all captured layers of a stack (rollout=), and the target form of the
+grouped forward (Engine.forward_groups(..., capture=, relations=)).  A form knows its program key, the launch a captured layer emits, the layout of one call
 (plan: integers only -- sizes, offsets and tile counts as include/i2r_hip.h specifies them), the per-call fields of a launch (patch) and
 the shape of what the caller gets back.  Nothing here touches a device or the library: Program.bind_capture (engine.py) does, for all of them.
 """
@@ -44,6 +45,27 @@ class PersonMaps:
         self.mode, self.upsample = self.MODES[mode], int(upsample)
         if not 1 <= self.upsample <= 64:
             raise ValueError("upsample %r (1 .. 64)" % (upsample,))
+
+
+class TargetMaps:
+    """The target form of an attention-map capture (Engine.forward_groups(..., capture=, relations=)): of every captured layer of the
+    inter-human stack, per person group, the relations of the group's TARGET (its first member, the one grouped inference keeps) to the
+    group's members -- r[j], how much of the target's attention lands on member j -- and with
+    maps: None nothing else, "dependency" the maps D_t[j] (where on member j the target looks, averaged over the target's tokens),
+    "affect" the maps F_t[j] (which of the target's own tokens look at member j); scale: integer bilinear scale of those maps (1 = raw);
+    slots: members per group the call's buffer is laid out for (every group's blocks are `slots` entries apart, zeros behind its own
+    members: the layers' blocks are dense [groups, slots, ...] tensors); default: the largest group of the call."""
+    MODES = {None: 0, "dependency": 1, "affect": 2}
+
+    def __init__(self, maps=None, scale=1, slots=None):
+        if isinstance(maps, bool) or maps not in self.MODES:
+            raise ValueError("maps %r: None, 'dependency' or 'affect'" % (maps,))
+        self.maps, self.mode, self.scale = maps, self.MODES[maps], int(scale)
+        if not 1 <= self.scale <= 64:
+            raise ValueError("scale %r (1 .. 64)" % (scale,))
+        self.slots = int(slots) if slots is not None else None
+        if self.slots is not None and self.slots < 1:
+            raise ValueError("slots %r (>= 1)" % (slots,))
 
 
 class JointQueries:
@@ -160,6 +182,7 @@ class Form:
     deferred = False  # True: a captured layer keeps its q|k and emits nothing; the engine runs the form's launches behind the program
     merged = False    # True (merge()): the maps of the flip test, M = (P + un-mirrored P') / 2 (i2r_attn_flip_merge)
     per_stack = False  # True: the captured layers of a stack share ONE set of blocks (their product), not one each
+    zero_fill = False  # True: the blocks of a call are laid out with gaps the caller reads as zeros -- the per-call buffer starts zeroed
 
     def __init__(self, capture, suffix=()):
         self.capture, self.key = capture, ("capture", capture) + suffix  # (key: the part of the program key behind the shape)
@@ -338,6 +361,52 @@ class PersonForm(Form):
         return tuple(views)  # (relation, maps)
 
 
+class TargetForm(Form):
+    """the target's rows of the maps reduced per person (i2r_attn_target_maps; TargetMaps): every group is a person group of m_g members
+    of h w tokens whose first member is the target; per layer the relation blocks [m_g], then (mode 1: dependency, 2: affect) the map
+    blocks [m_g, h r, w r].  Group g's blocks start g * slots entries behind the set (slots >= every m_g), so a layer's set is a dense,
+    zero-padded [groups, slots (, h r, w r)] tensor.  The workspaces are O(L): `rows` holds F_t, sum L_g floats, and behind it the raw
+    D_t for mode 1 at scale > 1."""
+    N_BLOCKS = 2
+    zero_fill = True
+
+    def __init__(self, capture, targets):
+        self.mode, self.scale = int(targets.mode), int(targets.scale)
+        Form.__init__(self, capture, ("targets", self.mode, self.scale))
+        self.call = targets
+
+    def launch(self, cap, qk, L, goff):
+        rel_off, maps_off = cap["off"]
+        return cabi.CAPTURE_OP_ATTN_TARGET, cabi.AttnTargetArgs(
+            qk=qk.ptr, grp_off=goff.data_ptr(), rel_off=rel_off.data_ptr(), maps_off=maps_off.data_ptr(), heads=L["heads"], hp=L["hp"],
+            k_off=L["hs"], qk_cs=qk.cs, seg=cap["x"].h * cap["x"].w, mode=self.mode, scale=self.scale, h=cap["x"].h, w=cap["x"].w)
+
+    def plan(self, stack, hw, lens, heads, call=None):
+        """call: the TargetMaps of this call (its slots; None: the largest group's members)"""
+        mode, scale, (h, w) = self.mode, self.scale, hw
+        assert all(n % (h * w) == 0 for n in lens)
+        pers = [n // (h * w) for n in lens]
+        slots = getattr(call, "slots", None) or max(pers)
+        if slots < max(pers):
+            raise ValueError("relations: a group of %d members, the call is laid out for %d" % (max(pers), slots))
+        m_floats = h * scale * w * scale
+        rel = Block([g * slots for g in range(len(lens) + 1)], 0, [(p,) for p in pers])
+        base = -(-rel.offs[-1] // 4) * 4
+        maps = Block([g * slots * m_floats if mode else 0 for g in range(len(lens) + 1)], base, [(p, h * scale, w * scale) for p in pers] if mode else None)
+        twice = mode == 1 and scale > 1  # (the raw D_t rows behind F_t)
+        stride = _stride(heads, lens)
+        return Plan(len(lens), stride, stride * sum(lens), (2 if twice else 1) * sum(lens), [rel, maps], base + -(-maps.offs[-1] // 4) * 4, K=slots)
+
+    @staticmethod
+    def patch(a, p, out, ws, rows, tables, host_off):
+        a.rel, a.maps, a.ws, a.rows, a.grp_off_host = out, out + 4 * p.blocks[1].base, ws, rows, host_off
+        a.n_grp, a.ws_stride = p.n_grp, p.ws_stride
+
+    @staticmethod
+    def result(views, inputs):
+        return tuple(views)  # (relation, maps)
+
+
 class RolloutForm(Form):
     """the relations through the captured layers lo .. hi of every captured stack (Rollout; i2r_attn_rollout_step): a chain of thin
     products X' = (1 - alpha) X + alpha X P_l (side 0, layers hi -> lo) or ... X P_l^T (side 1, lo -> hi) from a seed X_0, ping-pong
@@ -423,15 +492,39 @@ class RolloutForm(Form):
 FLIP_MAPS = ("plain", "merged")
 
 
-def resolve(capture, queries, persons, flip_joint_map, stacks, inter_stack, window, joints=None, n_joints=None, flip_maps="plain", rollout=None):
+def resolve(capture, queries, persons, flip_joint_map, stacks, inter_stack, window, joints=None, n_joints=None, flip_maps="plain", rollout=None, *,
+            targets=None):
     """What Engine.forward / forward_single were asked for -> the form of the call, None without a capture.  stacks: the engine's
     capture_stacks(); inter_stack: the prefix of its inter-human stack; window: the inter-human block is the window type; joints: a
     JointQueries of a model of n_joints joints -- with flip_maps "plain" the one form that goes with the flip test (its launches run
     behind the merge, on the plain half); flip_maps "merged": the flip test's merged maps (Form.merge) of the query, per-person or joint
     form -- never of the full [L, L] form, whose buffer it would double.  rollout: a Rollout -- the relations through the captured layers,
-    a form of its own: not with the flip test (a product of merged maps is not the merge of products), nor with another form."""
+    a form of its own: not with the flip test (a product of merged maps is not the merge of products), nor with another form.
+    targets: a TargetMaps -- the target form of the grouped forward (Engine.forward_groups(..., relations=)), a form of its own as well:
+    layers of the inter-human stack only, not with the flip test, nor with another form."""
     if flip_maps not in FLIP_MAPS:
         raise ValueError("flip_maps %r: 'plain' or 'merged'" % (flip_maps,))
+    if targets is not None:
+        if not isinstance(targets, TargetMaps):
+            raise ValueError("relations=: a TargetMaps, not %r" % (type(targets).__name__,))
+        if queries is not None or persons is not None or joints is not None or rollout is not None:
+            raise ValueError("relations=: not with queries=, persons=, joints= or rollout= (roll-out and predicted-joint queries are not served "
+                             "on the grouped forward)")
+        if window:
+            raise ValueError("relations=: ATTENTION_TYPE window has no encoder stack to capture")
+        if flip_joint_map is not None or flip_maps != "plain":
+            raise ValueError("relations=: not with the flip test")
+        if not capture:
+            raise ValueError("relations= needs capture=: the (stack, layer) set of the inter-human stack to reduce")
+        capture = frozenset((str(st), int(i)) for st, i in capture)
+        other = sorted({st for st, _ in capture} - {inter_stack})
+        if other or inter_stack not in stacks:
+            raise ValueError("relations=: %s is not this model's inter-human stack %r (an intra-human stack has one person per group)"
+                             % (other or "a capture", inter_stack if inter_stack in stacks else None))
+        for st, i in capture:
+            if not 0 <= i < stacks[st]:
+                raise ValueError("capture (%r, %d): this model's encoder stacks are %s" % (st, i, stacks))
+        return TargetForm(capture, targets)
     if rollout is not None:
         if window:
             raise ValueError("rollout=: ATTENTION_TYPE window has no encoder stack to capture")

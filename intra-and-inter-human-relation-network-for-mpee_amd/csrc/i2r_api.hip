@@ -228,6 +228,7 @@ static int run_program(const i2r_op* ops, int32_t n_ops, void* const* streams, v
             case I2R_OP_ATTN_WEIGHTS: rc = i2r_attn_weights((const i2r_attn_weights_args*)op.args, st); break;
             case I2R_OP_ATTN_QUERY: rc = i2r_attn_query_maps((const i2r_attn_query_args*)op.args, st); break;
             case I2R_OP_ATTN_PERSON: rc = i2r_attn_person_maps((const i2r_attn_person_args*)op.args, st); break;
+            case I2R_OP_ATTN_TARGET: rc = i2r_attn_target_maps((const i2r_attn_target_args*)op.args, st); break;
             case I2R_OP_ENC_KV: rc = i2r_encoder_kv((const i2r_encoder_desc*)op.args, st); break;
             case I2R_OP_ENC_LAYER: rc = i2r_encoder_layer((const i2r_encoder_desc*)op.args, st); break;
             default: i2r_set_error("i2r_run_program: op %d unknown kind %d", i, op.kind); return I2R_E_ARG;

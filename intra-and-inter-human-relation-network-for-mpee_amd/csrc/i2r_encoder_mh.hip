@@ -594,23 +594,19 @@ __device__ __forceinline__ bool ap_item(const ApK& p, int pass, int& item, int& 
     return true;
 }
 
+// F of one 16-query tile and one person: the share of query row qrow's attention (statistics row st) on the keys [k_beg, k_end), heads in
+// order, each normalised once; the lane's part -- the caller adds the four key lanes (xor 16, 32) and divides by the heads
 template <int HB>
-__global__ __launch_bounds__(256) void ap_affect_k(const ApK p) {
-    const int lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4;
-    int item = blockIdx.x * 4 + (threadIdx.x >> 6), gi, g0, g1, np;
-    if (!ap_item(p, 0, item, gi, g0, g1, np)) return;
-    const int q0 = g0 + item / np * 16, j = item - item / np * np, len = g1 - g0, nkb = aw_key_blocks(len);
-    const int qrow = min(q0 + li, g1 - 1), k_beg = g0 + j * p.seg, k_end = k_beg + p.seg;
-    const float2* st = p.a.ws + (size_t)qrow * (p.a.ws_stride / 2);
+__device__ __forceinline__ float ap_affect_part(const AwK& a, int li, int g, int qrow, const float2* st, int nkb, int k_beg, int k_end) {
     float acc = 0.f;
-    for (int head = 0; head < p.a.heads; ++head) {
+    for (int head = 0; head < a.heads; ++head) {
         float mm, inv;
-        aw_row_stats(st, nkb, p.a.heads, head, mm, inv);
+        aw_row_stats(st, nkb, a.heads, head, mm, inv);
         f32x4 q[HB];
-        aw_load_q<HB>(p.a, qrow, head, g, q);
+        aw_load_q<HB>(a, qrow, head, g, q);
         float hsum = 0.f;
         for (int k0 = k_beg; k0 < k_end; k0 += 16) {
-            const f32x4 s = aw_scores<HB>(p.a, min(k0 + li, k_end - 1), head, g, q);
+            const f32x4 s = aw_scores<HB>(a, min(k0 + li, k_end - 1), head, g, q);
 #pragma unroll
             for (int r = 0; r < 4; ++r)
                 if (k0 + 4 * g + r < k_end) hsum += __builtin_amdgcn_exp2f(s[r] - mm);
@@ -619,24 +615,19 @@ __global__ __launch_bounds__(256) void ap_affect_k(const ApK p) {
     }
     acc += __shfl_xor(acc, 16);
     acc += __shfl_xor(acc, 32);
-    if (g == 0 && q0 + li < g1) ap_block(p, 2, gi, g0)[(long long)j * len + (q0 + li - g0)] = acc * (1.f / (float)p.a.heads);
+    return acc * (1.f / (float)a.heads);
 }
 
+// D of one person and one block of kApKeys keys: aw_block_probs of the queries [q_beg, q_end) over the keys [k_beg, k_end) of a group that
+// ends at g1, tile after tile into one set of accumulators, a butterfly over the 16 query lanes, times rs -> row[k - g0]
 template <int HB>
-__global__ __launch_bounds__(256) void ap_depend_k(const ApK p) {
-    const int lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4;
-    int item = blockIdx.x * 4 + (threadIdx.x >> 6), gi, g0, g1, np;
-    if (!ap_item(p, 1, item, gi, g0, g1, np)) return;
-    const int len = g1 - g0, nkb = aw_key_blocks(len), nb = (len + kApKeys - 1) / kApKeys, i = item / nb, kb = item - i * nb;
-    const int k_beg = g0 + kb * kApKeys, k_end = min(k_beg + kApKeys, g1), n_kt = (k_end - k_beg + 15) / 16;
-    const int q_beg = g0 + i * p.seg, q_end = q_beg + p.seg;
+__device__ __forceinline__ void ap_depend_block(const AwK& a, int li, int g, int q_beg, int q_end, int g0, int g1, int k_beg, int k_end, float rs, float* row) {
+    const int nkb = aw_key_blocks(g1 - g0), n_kt = (k_end - k_beg + 15) / 16;
     f32x4 acc[kApTiles] = {};
     for (int qt = q_beg; qt < q_end; qt += 16) {  // (a query lane past the person's end adds nothing)
         const int qrow = min(qt + li, q_end - 1);
-        aw_block_probs<HB>(p.a, li, g, qrow, p.a.ws + (size_t)qrow * (p.a.ws_stride / 2), nkb, qt + li < q_end, g1, k_beg, n_kt, acc);
+        aw_block_probs<HB>(a, li, g, qrow, a.ws + (size_t)qrow * (a.ws_stride / 2), nkb, qt + li < q_end, g1, k_beg, n_kt, acc);
     }
-    const float rs = 1.f / ((float)p.a.heads * (float)p.seg);
-    float* row = ap_block(p, 1, gi, g0) + (long long)i * len;
 #pragma unroll
     for (int t = 0; t < kApTiles; ++t) {
         f32x4 v = acc[t];
@@ -652,17 +643,112 @@ __global__ __launch_bounds__(256) void ap_depend_k(const ApK p) {
     }
 }
 
+// one person's share of a row of F: the mean of seg consecutive floats, lane-strided partial sums and a butterfly over the wave
+__device__ __forceinline__ float ap_mean(const float* f, int seg, int lane) {
+    float s = 0.f;
+    for (int t = lane; t < seg; t += 64) s += f[t];
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) s += __shfl_xor(s, m);
+    return s / (float)seg;
+}
+
+template <int HB>
+__global__ __launch_bounds__(256) void ap_affect_k(const ApK p) {
+    const int lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4;
+    int item = blockIdx.x * 4 + (threadIdx.x >> 6), gi, g0, g1, np;
+    if (!ap_item(p, 0, item, gi, g0, g1, np)) return;
+    const int q0 = g0 + item / np * 16, j = item - item / np * np, len = g1 - g0, nkb = aw_key_blocks(len);
+    const int qrow = min(q0 + li, g1 - 1), k_beg = g0 + j * p.seg;
+    const float f = ap_affect_part<HB>(p.a, li, g, qrow, p.a.ws + (size_t)qrow * (p.a.ws_stride / 2), nkb, k_beg, k_beg + p.seg);
+    if (g == 0 && q0 + li < g1) ap_block(p, 2, gi, g0)[(long long)j * len + (q0 + li - g0)] = f;
+}
+
+template <int HB>
+__global__ __launch_bounds__(256) void ap_depend_k(const ApK p) {
+    const int lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4;
+    int item = blockIdx.x * 4 + (threadIdx.x >> 6), gi, g0, g1, np;
+    if (!ap_item(p, 1, item, gi, g0, g1, np)) return;
+    const int len = g1 - g0, nb = (len + kApKeys - 1) / kApKeys, i = item / nb, kb = item - i * nb;
+    const int k_beg = g0 + kb * kApKeys, q_beg = g0 + i * p.seg;
+    ap_depend_block<HB>(p.a, li, g, q_beg, q_beg + p.seg, g0, g1, k_beg, min(k_beg + kApKeys, g1), 1.f / ((float)p.a.heads * (float)p.seg),
+                        ap_block(p, 1, gi, g0) + (long long)i * len);
+}
+
 __global__ __launch_bounds__(256) void ap_relation_k(const ApK p) {
     const int lane = threadIdx.x & 63;
     int item = blockIdx.x * 4 + (threadIdx.x >> 6), gi, g0, g1, np;
     if (!ap_item(p, 2, item, gi, g0, g1, np)) return;
     const int i = item / np, j = item - i * np;
-    const float* f = ap_block(p, 2, gi, g0) + (long long)j * (g1 - g0) + (long long)i * p.seg;
-    float s = 0.f;
-    for (int t = lane; t < p.seg; t += 64) s += f[t];
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) s += __shfl_xor(s, m);
-    if (lane == 0) p.rel[p.rel_off[gi] + (long long)i * np + j] = s / (float)p.seg;
+    const float r = ap_mean(ap_block(p, 2, gi, g0) + (long long)j * (g1 - g0) + (long long)i * p.seg, p.seg, lane);
+    if (lane == 0) p.rel[p.rel_off[gi] + (long long)i * np + j] = r;
+}
+
+// ---- the target form of the maps per person: the grouped test mode keeps only member 0 (the target) of a group, so only ITS query rows ----
+//   F_t[j, q] = F[j, q], q < seg      at_affect_k: work item (group, 16-query tile of the target, member j) -- ap_affect_part
+//   D_t[k]    = D[0, k]               at_depend_k: work item (group, block of kApKeys keys) -- ap_depend_block over the target's queries
+//   r[j]      = R[0, j]               at_relation_k: one wave per (group, j) -- ap_mean of F_t[j, :]
+// behind at_stats_k, aw_block_stats on the target's query tiles only (workspace rows [g0, g0 + seg) of a group).  These are the i = 0 /
+// q < seg work items of the person form through the same device functions in the same head, tile and lane orders: at scale 1 the outputs
+// are bit-identical to row 0 of the person form.  A query lane past the target's end reads the target's last row and stores nothing.
+// Compact workspace: F_t [m_g, seg] of group g at rows + grp_off[g]; the raw D_t [L_g] (mode 1, scale > 1) d_shift floats behind.
+struct AtK {
+    AwK a;  // a.out / a.out_off: the maps blocks (modes 1 and 2)
+    float* rel;
+    const long long* rel_off;
+    float* rows;
+    long long d_shift;
+    int seg, mode, scale;
+};
+
+__device__ __forceinline__ float* at_block(const AtK& p, int what, int gi, int g0) {
+    if (p.mode == what && p.scale == 1) return p.a.out + p.a.out_off[gi];
+    return p.rows + g0 + (what == 1 ? p.d_shift : 0);
+}
+
+// work items per group of the four passes (statistics, F_t, D_t, r); the host entry point counts with the same function
+__host__ __device__ __forceinline__ int at_items(int pass, int len, int seg) {
+    return pass == 0 ? (seg + 15) / 16 * aw_key_blocks(len) : pass == 1 ? (seg + 15) / 16 * (len / seg) : pass == 2 ? (len + kApKeys - 1) / kApKeys : len / seg;
+}
+
+__device__ __forceinline__ bool at_item(const AtK& p, int pass, int& item, int& gi, int& g0, int& g1) {
+    return aw_group(p.a, item, gi, g0, g1, [&](int, int len) { return len % p.seg != 0 ? 0 : at_items(pass, len, p.seg); });
+}
+
+template <int HB>
+__global__ __launch_bounds__(256) void at_stats_k(const AtK p) {
+    const int lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4;
+    int item = blockIdx.x * 4 + (threadIdx.x >> 6), gi, g0, g1;
+    if (!at_item(p, 0, item, gi, g0, g1)) return;
+    const int nkb = aw_key_blocks(g1 - g0), q0 = g0 + item / nkb * 16, kb = item - item / nkb * nkb, q_end = g0 + p.seg, k_beg = g0 + kb * kAwKeys;
+    aw_block_stats<HB>(p.a, li, g, min(q0 + li, q_end - 1), g1, k_beg, min(k_beg + kAwKeys, g1), q0 + li < q_end, q0 + li, kb);
+}
+
+template <int HB>
+__global__ __launch_bounds__(256) void at_affect_k(const AtK p) {
+    const int lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4;
+    int item = blockIdx.x * 4 + (threadIdx.x >> 6), gi, g0, g1;
+    if (!at_item(p, 1, item, gi, g0, g1)) return;
+    const int np = (g1 - g0) / p.seg, q0 = g0 + item / np * 16, j = item - item / np * np, nkb = aw_key_blocks(g1 - g0), q_end = g0 + p.seg;
+    const int qrow = min(q0 + li, q_end - 1), k_beg = g0 + j * p.seg;
+    const float f = ap_affect_part<HB>(p.a, li, g, qrow, p.a.ws + (size_t)qrow * (p.a.ws_stride / 2), nkb, k_beg, k_beg + p.seg);
+    if (g == 0 && q0 + li < q_end) at_block(p, 2, gi, g0)[(long long)j * p.seg + (q0 + li - g0)] = f;
+}
+
+template <int HB>
+__global__ __launch_bounds__(256) void at_depend_k(const AtK p) {
+    const int lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4;
+    int item = blockIdx.x * 4 + (threadIdx.x >> 6), gi, g0, g1;
+    if (!at_item(p, 2, item, gi, g0, g1)) return;
+    const int k_beg = g0 + item * kApKeys;
+    ap_depend_block<HB>(p.a, li, g, g0, g0 + p.seg, g0, g1, k_beg, min(k_beg + kApKeys, g1), 1.f / ((float)p.a.heads * (float)p.seg), at_block(p, 1, gi, g0));
+}
+
+__global__ __launch_bounds__(256) void at_relation_k(const AtK p) {
+    const int lane = threadIdx.x & 63;
+    int item = blockIdx.x * 4 + (threadIdx.x >> 6), gi, g0, g1;
+    if (!at_item(p, 3, item, gi, g0, g1)) return;
+    const float r = ap_mean(at_block(p, 2, gi, g0) + (long long)item * p.seg, p.seg, lane);
+    if (lane == 0) p.rel[p.rel_off[gi] + item] = r;
 }
 
 // ---- attention roll-out: one step X' = (1 - alpha) X + alpha X P (side 0) or (1 - alpha) X + alpha X P^T (side 1) of a thin matrix -----------
@@ -973,6 +1059,58 @@ extern "C" int i2r_attn_person_maps(const i2r_attn_person_args* a, void* stream)
         const AqK u{k.a, nullptr, nullptr, a->rows + (a->mode == 1 ? total : 0), pmax, a->scale, a->h, a->w, a->seg};
         i2r_launch(aq_upsample_k, dim3((unsigned)((n4 + 255) / 256), (unsigned)a->n_grp), dim3(256), 0, st, u);
         I2R_CHECK_LAUNCH("i2r_attn_person_maps (up-sampling)");
+    }
+    return I2R_OK;
+}
+
+extern "C" int i2r_attn_target_maps(const i2r_attn_target_args* a, void* stream) {
+    I2R_CHECK_ARG(a && a->qk && a->grp_off && a->ws && a->rel && a->rel_off && a->rows && a->grp_off_host, "i2r_attn_target_maps: null pointer");
+    I2R_CHECK_ARG(a->mode >= 0 && a->mode <= 2, "i2r_attn_target_maps: mode=%d (0: relation only, 1: + dependency maps, 2: + affect maps)", a->mode);
+    I2R_CHECK_ARG(a->mode == 0 || (a->maps && a->maps_off), "i2r_attn_target_maps: null pointer (modes 1 and 2 need maps and maps_off)");
+    I2R_CHECK_ARG(a->scale >= 1 && a->scale <= 64, "i2r_attn_target_maps: scale=%d (1 .. 64)", a->scale);
+    I2R_CHECK_ARG(a->seg >= 1 && a->seg < (1 << 24), "i2r_attn_target_maps: seg=%d", a->seg);
+    if (const int e = aw_check("i2r_attn_target_maps", a)) return e;
+    I2R_CHECK_ARG(a->n_grp < 65536, "i2r_attn_target_maps: n_grp=%d", a->n_grp);
+    if (a->scale > 1)
+        I2R_CHECK_ARG(a->h > 0 && a->w > 0 && (long long)a->h * a->w == a->seg, "i2r_attn_target_maps: seg=%d is not h w = %d x %d", a->seg, a->h, a->w);
+    long long n_pass[4] = {0, 0, 0, 0};
+    int max_len = 0;
+    for (int g = 0; g < a->n_grp; ++g) {
+        const int len = a->grp_off_host[g + 1] - a->grp_off_host[g];
+        I2R_CHECK_ARG(len >= 0 && len % a->seg == 0, /* (an empty group is skipped) */ "i2r_attn_target_maps: group %d has %d tokens, not a multiple of seg = %d", g, len, a->seg);
+        if (len == 0) continue;
+        for (int pass = 0; pass < 4; ++pass) n_pass[pass] += at_items(pass, len, a->seg);
+        max_len = len > max_len ? len : max_len;
+    }
+    I2R_CHECK_ARG(a->ws_stride >= 2 * a->heads * aw_key_blocks(max_len), "i2r_attn_target_maps: ws_stride=%d for %d heads and groups of up to %d tokens",
+                  a->ws_stride, a->heads, max_len);
+    I2R_CHECK_ARG(n_pass[0] < (1ll << 31) && n_pass[1] < (1ll << 31) && n_pass[2] < (1ll << 31) && n_pass[3] < (1ll << 31), "i2r_attn_target_maps: grid");
+    const long long n4 = ((long long)max_len * a->scale * a->scale + 3) / 4;
+    I2R_CHECK_ARG((n4 + 255) / 256 < (1ll << 31), "i2r_attn_target_maps: up-sampling grid");
+    if (max_len == 0) return I2R_OK;  // (every group is empty)
+    const bool up = a->mode != 0 && a->scale > 1;
+    const long long total = a->grp_off_host[a->n_grp];
+    const AtK k{aw_args(a, a->maps, a->maps_off), a->rel, reinterpret_cast<const long long*>(a->rel_off), a->rows, total, a->seg, a->mode, up ? a->scale : 1};
+    typedef void (*at_t)(const AtK);
+    static const at_t stats[16] = I2R_AW_TABLE(at_stats_k);
+    static const at_t affect[16] = I2R_AW_TABLE(at_affect_k);
+    static const at_t depend[16] = I2R_AW_TABLE(at_depend_k);
+    const int hb = a->hp / 16 - 1;
+    const hipStream_t st = (hipStream_t)stream;
+    i2r_launch(stats[hb], dim3((unsigned)((n_pass[0] + 3) / 4)), dim3(256), 0, st, k);
+    I2R_CHECK_LAUNCH("i2r_attn_target_maps (statistics)");
+    i2r_launch(affect[hb], dim3((unsigned)((n_pass[1] + 3) / 4)), dim3(256), 0, st, k);
+    I2R_CHECK_LAUNCH("i2r_attn_target_maps (affect)");
+    if (a->mode == 1) {
+        i2r_launch(depend[hb], dim3((unsigned)((n_pass[2] + 3) / 4)), dim3(256), 0, st, k);
+        I2R_CHECK_LAUNCH("i2r_attn_target_maps (dependency)");
+    }
+    i2r_launch(at_relation_k, dim3((unsigned)((n_pass[3] + 3) / 4)), dim3(256), 0, st, k);
+    I2R_CHECK_LAUNCH("i2r_attn_target_maps (relation)");
+    if (up) {  // the raw row of the mode's maps (D_t behind F_t in the workspace) -> maps: one row of the query maps per group, K = 1
+        const AqK u{k.a, nullptr, nullptr, a->rows + (a->mode == 1 ? total : 0), 1, a->scale, a->h, a->w, 0};
+        i2r_launch(aq_upsample_k, dim3((unsigned)((n4 + 255) / 256), (unsigned)a->n_grp), dim3(256), 0, st, u);
+        I2R_CHECK_LAUNCH("i2r_attn_target_maps (up-sampling)");
     }
     return I2R_OK;
 }

@@ -11,7 +11,7 @@ import os
 import torch
 
 from . import attn_capture, cabi
-from .attn_capture import AttnQueries, JointQueries, PersonMaps, Rollout  # noqa: F401 (the capture forms' public classes stay importable from here)
+from .attn_capture import AttnQueries, JointQueries, PersonMaps, Rollout, TargetMaps  # noqa: F401 (the capture forms' public classes stay importable from here)
 from .pack import (PRECISIONS, PackedConv, Packer, _m16, _r16, fold_bn, pack_frag, pack_frag32, pack_k4, pack_k8,  # noqa: F401 (the packing names stay importable from here)
                    winograd_weights)
 
@@ -847,7 +847,8 @@ class Program:
             plans.append(form.plan(cap["stack"], (cap["x"].h, cap["x"].w), lens, max(a.heads for _, a in cap["ops"]), call))
         form.share(plans)
         slots = (lambda cap: 1) if form.per_stack else (lambda cap: len(cap["ops"]))  # (a roll-out: one set of blocks per stack)
-        buf = torch.empty(sum(p.layer_floats * slots(cap) + p.extra_floats for p, cap in zip(plans, self.captures)), dtype=torch.float32, device=self.device)
+        buf = (torch.zeros if form.zero_fill else torch.empty)(sum(p.layer_floats * slots(cap) + p.extra_floats for p, cap in zip(plans, self.captures)),
+                                                               dtype=torch.float32, device=self.device)
         ws = torch.empty(max(p.ws_floats for p in plans), dtype=torch.float32, device=self.device)
         rows = torch.empty(max(p.rows_floats for p in plans), dtype=torch.float32, device=self.device)
         held = [ws, rows]  # (kept until the next call: the launches read them asynchronously; torch's allocator orders reuse by stream)
@@ -867,7 +868,7 @@ class Program:
                     for out, blk in zip(views, p.blocks):
                         if blk.shapes:
                             b = base + blk.base
-                            out[(cap["stack"], i)] = [buf[b + o:b + e].view(s) for o, e, s in zip(blk.offs, blk.offs[1:], blk.shapes)]
+                            out[(cap["stack"], i)] = [buf[b + o:b + o + math.prod(s)].view(s) for o, s in zip(blk.offs, blk.shapes)]
                     base += p.layer_floats
             base += p.extra_floats
         if form.merged:
@@ -2485,7 +2486,8 @@ class Engine:
             r += n
         return out
 
-    def forward_groups(self, x, pos_mask, members, group_len, flip_joint_map=None, share_first_stage=None, persons=None, rollout=None):
+    def forward_groups(self, x, pos_mask, members, group_len, flip_joint_map=None, share_first_stage=None, persons=None, rollout=None, relations=None,
+                       capture=None):
         """x [S, 3, H, W], pos_mask [S, 1, H, W]: the DISTINCT crops of a batch; members: device int32 [sum(group_len)] of crop indices in
         [0, S), group after group (input.main_target_groups); group_len: host list of the groups' sizes.  -> the 'multi' heat maps of the
         FIRST member of every group, [len(group_len), J, H/4, W/4] -- what the reference's validate_main_target keeps of model(x[members],
@@ -2498,11 +2500,25 @@ class Engine:
         expanded forward.  Programs are keyed by capacities only: other groups of the same sizes build nothing.  On every shared path
         (the default one of the HRNet tower included) a member index outside [0, S) is never dereferenced: the hand-over gathers are
         bound to the S real crops of the call, so its rows -- features, mask -- are zeros, never what a capacity slot holds.
-        persons, rollout: ValueError when given -- the grouped forward has no attention-map capture (forward(..., capture=, persons=) has)."""
+        persons, rollout: ValueError when given -- the grouped forward has no attention-map capture (forward(..., capture=, persons=) has)
+        but the target form:
+        relations (attn_capture.TargetMaps, with capture = a set of (stack, layer) of the inter-human stack): the relations of every
+        group's TARGET (its first member, the one whose heat maps are kept) to the group's members, of every captured layer, on whichever
+        of the three ways the call runs -> (heat maps, (relation, maps)): relation[(stack, layer)] = per group a [m_g] view (sums to 1),
+        maps[(stack, layer)] = per group a [m_g, h r, w r] view (relations.maps "dependency": where on member j the target looks,
+        "affect": which of the target's tokens look at member j; None: no entry); views of one zeroed buffer in which group g's blocks
+        start g * slots entries into their layer's set (include/i2r_hip.h: i2r_attn_target_maps).  One program per (capacities, capture
+        set, mode, scale); other groups at the same capacities build nothing, and the default grouped programs are not touched.
+        ValueError: the flip test, another stack's layer, the window-type block, persons= or rollout= too."""
         if persons is not None:
             raise ValueError("forward_groups: persons= is not served (no attention-map capture on the grouped forward)")
         if rollout is not None:
             raise ValueError("forward_groups: rollout= is not served (no attention-map capture on the grouped forward)")
+        form = None
+        if relations is not None:
+            form = attn_capture.resolve(capture, None, None, flip_joint_map, self.capture_stacks(), self.inter_stack, self.window_attn, targets=relations)
+        elif capture:
+            raise ValueError("forward_groups: capture= goes with relations= (the target form is the grouped forward's only capture)")
         assert x.dim() == 4 and x.shape[1] == 3 and x.dtype == torch.float32
         assert share_first_stage in (None, True, False)
         S, _, H, W = x.shape
@@ -2515,13 +2531,18 @@ class Engine:
             pm = pos_mask.to(self.device, torch.float32).contiguous() if pos_mask is not None else None
             mode = self._groups_shared(H, W, share_first_stage)
             if mode is not None:
-                return self._forward_groups_shared(mode, x, pm, members, group_len, flip_joint_map, S, H, W)
+                return self._forward_groups_shared(mode, x, pm, members, group_len, flip_joint_map, S, H, W, form)
             # not shared: the reference's own arithmetic on the gathered inputs (index plumbing in torch, every launch in forward())
             idx = members.long()
+            first = torch.tensor(self._first_rows(group_len), dtype=torch.long).to(self.device)
+            if form:  # (one capture program over the expanded batch, as forward(..., capture=) runs its forms)
+                y, res = self._forward_part(x.index_select(0, idx), pm.index_select(0, idx) if pm is not None else None, group_len, None, sum(group_len),
+                                            H, W, max(group_len), form=form)
+                return _multi(y).index_select(0, first), res
             y = _multi(self.forward(x.index_select(0, idx), pm.index_select(0, idx) if pm is not None else None, group_len, flip_joint_map))
-            return y.index_select(0, torch.tensor(self._first_rows(group_len), dtype=torch.long).to(self.device))
+            return y.index_select(0, first)
 
-    def _build_groups(self, mode, capS, capG, capN, H, W, flip):
+    def _build_groups(self, mode, capS, capG, capN, H, W, flip, form=None):
         """The program of a grouped forward behind the first stage: person-level features and position rows [capS] -> ONE rows_gather_multi
         (patch["hand_over"]) into group layout [capG] by the member table -> inter-human encoder -> one rows_gather_multi of the first row
         of every group [capN] -> _emit_tail.  With the flip test every buffer holds the mirrored half behind the plain one.
@@ -2529,8 +2550,9 @@ class Engine:
         gathered (a segment whose source is the call's pos_mask) and the position branch runs on them.
         mode "first": the program holds the first stage too (no `single` head), pooling to TRANS_SIZE and the position branch on the
         distinct crops, bound straight to the call's pos_mask; its rows are gathered like the features, and for the tail the
-        full-resolution first-stage features of every group's FIRST member [capN] by patch["first_member"]."""
-        P = self._new_program()
+        full-resolution first-stage features of every group's FIRST member [capN] by patch["first_member"].
+        form: the target form (attn_capture.TargetForm) -- the inter-human encoder captures form.capture too (Program.bind_capture)."""
+        P = self._new_program(form)
         patch, k, tw = {}, (2 if flip else 1), self.cfg["MODEL"]["TRANS_SIZE"][-1]
         g = pos = posg = sf = None
         if mode == "tower":
@@ -2573,17 +2595,18 @@ class Engine:
             pe.in_, pe.n_valid = gm.ptr, capG
             assert (posg.h, posg.w, posg.cs) == (fg.h, fg.w, fg.cs)
         e = P.encoder(fg, self.layers, self._token_offsets([1] * (k * capG), fg.h * fg.w), pos=posg.ptr if posg is not None else 0,
-                      regroupable=True, pre_norm=self.pre_norm)
+                      regroupable=True, pre_norm=self.pre_norm, capture=self._capture_spec(form.capture, self.inter_stack, self.layers, d=fg.c) if form else None)
         e1 = P.alloc(k * capN, e.h, e.w, e.c, e.dt)
         P.rows_gather_multi([(e, e1, ftab, capN, capG, half * capG, half * capN) for half in range(k)])
         P.release(e)
         return self._emit_tail(P, patch, e1, sf)
 
-    def _forward_groups_shared(self, mode, x, pm, members, group_len, flip_joint_map, S, H, W):
+    def _forward_groups_shared(self, mode, x, pm, members, group_len, flip_joint_map, S, H, W, form=None):
         flip = flip_joint_map is not None
         G, N = sum(group_len), len(group_len)
         capS, capG, capN = self.capacity(S), self.capacity(G), self.capacity(N)
-        Pt, patch = self._program((capG, capN, capS, H, W, flip, "groups", mode), lambda: self._build_groups(mode, capS, capG, capN, H, W, flip))
+        key = (capG, capN, capS, H, W, flip, "groups", mode)
+        Pt, patch = self._program(key + form.key if form else key, lambda: self._build_groups(mode, capS, capG, capN, H, W, flip, form))
         progs = []
         if mode == "tower":  # (the tower is per crop: any cut of the S crops serves)
             progs = self._run_towers(x, self._split_bounds([1] * S, H, W) or [0, S], H, W, flip, patch["pfeat"].view(), capS)
@@ -2609,6 +2632,9 @@ class Engine:
         if "first_member" in patch:
             torch.index_select(patch["members"], 0, patch["_first_idx"], out=patch["first_member"])  # (on the device: nothing is read back)
         self._bind_groups(Pt, group_len, capG - G, flip)
+        if form:  # (the call's real groups: the capacity slots behind them are never among the computed groups)
+            views = self._bind_capture(Pt, form, S, group_len, H, W)
+            return self._run_bound(Pt, patch, capN, N, flip_joint_map, H, W)[0], form.result(views, None)
         return self._run_bound(Pt, patch, capN, N, flip_joint_map, H, W)[0]
 
     def _forward_part(self, x, pos_mask, length, flip_joint_map, S, H, W, sine_n, slot=0, form=None):

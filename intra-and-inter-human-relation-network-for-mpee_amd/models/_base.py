@@ -71,6 +71,15 @@ class PersonRelations:
         self.relation, self.maps = relation, maps
 
 
+class TargetRelations:
+    """what I2RModule.main_target_relations returns, S = persons of the batch = groups, one per person in input order:
+    members int32 [S, max_patch] (batch crop indices of person i's group, target first, -1 behind group_len[i]), group_len int32 [S],
+    relation {(stack, layer): [S, max_patch]}, image_relation {(stack, layer): [per image [P, P]]}, maps {(stack, layer): [S, max_patch, h r, w r]}"""
+
+    def __init__(self, members, group_len, relation, image_relation, maps):
+        self.members, self.group_len, self.relation, self.image_relation, self.maps = members, group_len, relation, image_relation, maps
+
+
 def _call_forward_hooks(module, output):
     """the module's forward hooks, called as a forward of it would (inputs: none -- the fused forward has no per-module call)"""
     for hid, hook in list(module._forward_hooks.items()):
@@ -255,6 +264,73 @@ class I2RModule(nn.Module):
         with torch.no_grad():
             groups = main_target_groups(boxes, length, int(max_patch), eng.device)
             return eng.forward_groups(x, pos_mask, groups.members, groups.group_len, flip_joint_map=jm, share_first_stage=share_first_stage)
+
+    def main_target_relations(self, x, pos_mask, length, boxes, max_patch=None, layers=None, maps=None, upsample=False, share_first_stage=None,
+                              flip_pairs=None):
+        """person_relations for the grouped test mode: forward_main_target's heat maps and, from the SAME forward, how much every person
+        -- the target of its group -- attends to each member of the group, and where.  With P the head-averaged softmax(q k^T) of a layer
+        of the inter-human stack over the group's members * h * w tokens, the target's tokens first:
+          relation   r[j]    = mean over the target's tokens q of the sum over the tokens k of member j of P[q, k]      (sums to 1)
+          dependency D_t[k]  = mean over the target's tokens q of P[q, k]: where the target looks, one map per member   (sums to 1)
+          affect     F_t[j, q] = sum over the tokens k of member j of P[q, k]: the target's token q's share for member j (sum over j = 1)
+        -- row 0 of what person_relations gives on the expanded batch (x[members], pos_mask[members], group_len), at 1 / m of its work.
+        x, pos_mask, length, boxes, max_patch, share_first_stage: as forward_main_target; layers, maps, upsample: as person_relations.
+        -> (heat maps [S, J, H/4, W/4], result): result.members int32 [S, max_patch] (row i: the batch crop indices of person i's group,
+          target first, -1 behind result.group_len[i]); result.relation[(stack, layer)] [S, max_patch] (row i: r of person i's group, 0
+          behind its members); result.image_relation[(stack, layer)] = a list with one [P_img, P_img] tensor per image, R[i, j] = r_i at
+          j's slot where j is in i's group, 0 elsewhere (rows sum to 1; with max_patch >= P_img the grouped counterpart of
+          person_relations' R); result.maps[(stack, layer)] [S, max_patch, h r, w r], slot s = the map on member s (dependency) or the
+          target's own token map for member s (affect), zeros behind the group; empty without maps.  relation and maps are views of one
+          buffer; nothing is read back from the device.
+        ValueError: flip_pairs (the flip test is not served here), a stand-alone first stage, ATTENTION_TYPE window, a layer of another
+        stack, a bad maps, and wherever forward_groups refuses.  Forward hooks are not served by this call."""
+        from ..engine import TargetMaps
+        from ..input import main_target_groups
+        name = self._engine_name() or self.cfg["MODEL"]["NAME"]
+        if flip_pairs is not None:
+            raise ValueError("main_target_relations: flip_pairs is not served (no flip test on the grouped forward's relations)")
+        if name in ("transpose_h", "hrformer", "hrnet"):
+            raise ValueError("main_target_relations: %s has no inter-human stack" % name)
+        if name == "interformer" and self.cfg["MODEL"]["ATTENTION_TYPE"] != "default":
+            raise ValueError("main_target_relations: ATTENTION_TYPE %r has no encoder stack to capture" % (self.cfg["MODEL"]["ATTENTION_TYPE"],))
+        if isinstance(maps, bool) or maps not in (None, "dependency", "affect"):
+            raise ValueError("maps %r: None, 'dependency' or 'affect'" % (maps,))
+        if torch.is_tensor(length):
+            length = length.tolist()
+        length = [int(n) for n in length]
+        if max_patch is None:
+            max_patch = (self.cfg.get("DATASET") or {}).get("MAX_PATCH")
+            if max_patch is None:
+                raise ValueError("main_target_relations: max_patch is not given and the config has no DATASET.MAX_PATCH")
+        max_patch = int(max_patch)
+        eng = self.engine()
+        st = eng.inter_stack
+        capture = {(st, i) for i in range(eng.capture_stacks().get(st, 0))} if layers is None else {(str(s), int(i)) for s, i in layers}
+        other = sorted({s for s, _ in capture} - {st})
+        if other or not capture:
+            raise ValueError("main_target_relations: %s is not this model's inter-human stack %r" % (other or "an empty layer set", st))
+        fh, fw = eng.capture_map_sizes(x.shape[2], x.shape[3])[st]
+        scale = x.shape[2] // fh if upsample is True else max(int(upsample), 1)
+        S = x.shape[0]
+        assert S == sum(length), "sum(length)=%d != number of crops %d" % (sum(length), S)
+        with torch.no_grad():
+            groups = main_target_groups(boxes, length, max_patch, eng.device)
+            out, (rel, views) = eng.forward_groups(x, pos_mask, groups.members, groups.group_len, share_first_stage=share_first_stage,
+                                                   relations=TargetMaps(maps, scale, slots=max_patch), capture=capture)
+            mh, mw = fh * scale, fw * scale
+            relation = {k: v[0].as_strided((S, max_patch), (max_patch, 1)) for k, v in rel.items()}
+            dense = {k: v[0].as_strided((S, max_patch, mh, mw), (max_patch * mh * mw, mh * mw, mw, 1)) for k, v in views.items()}
+            # the tables, dense: slot s of group g at g * max_patch + s (index plumbing on the device, from host-made index tables)
+            dev, glen = eng.device, groups.group_len
+            slot = torch.tensor([g * max_patch + s for g, n in enumerate(glen) for s in range(n)], dtype=torch.long).to(dev)
+            members = torch.full((S * max_patch,), -1, dtype=torch.int32, device=dev).index_copy_(0, slot, groups.members).view(S, max_patch)
+            first = torch.tensor([o for b, n in enumerate(length) for o in [sum(length[:b])] * n], dtype=torch.long).to(dev)  # the image's first crop, per person
+            col = (members.long() - first.view(S, 1)).clamp_(min=0)
+            image_relation = {}
+            for k, r in relation.items():  # (a slot behind the group adds its 0 to column 0: every (i, j) of a group is written once)
+                big = torch.zeros(S, max(length), dtype=torch.float32, device=dev).scatter_add_(1, col, r * (members >= 0))
+                image_relation[k] = [big[o:o + n, :n] for o, n in zip([sum(length[:b]) for b in range(len(length))], length)]
+        return out, TargetRelations(members, torch.tensor(glen, dtype=torch.int32).to(dev), relation, image_relation, dense)
 
     def _hooked(self):
         """(stack, layer, self_attn module) of every layer with forward hooks on its self_attn (usually none)"""
