@@ -162,7 +162,9 @@ I2R_API int i2r_maxpool3x3s2(const float* in, float* out, int32_t n_img, int32_t
 
 /* i2r_head -- final 1x1 conv (with bias) NHWC -> boundary NCHW heatmaps
  * (final_layer, interformer_pureMulti.py:486-492,776; interformer.py:176-182,317).
- * w: float[cout][cin] (the nn.Conv2d weight as is), bias[cout]. out: [n_img, cout, h, w]. */
+ * w: float[cout][cin] (the nn.Conv2d weight as is), bias[cout]. out: [n_img, cout, h, w].
+ * cin % 4 == 0, 1 <= cout <= 32.  cin a multiple of 16 up to 128 runs on the matrix pipe; any other cin keeps its weights
+ * in 64 KB of LDS: cin <= 1024 (cout <= 16), 816 (cout <= 20), 512 (cout <= 32), beyond that I2R_E_ARG and no launch. */
 I2R_API int i2r_head(const float* in, const float* w, const float* bias, float* out_nchw, int32_t n_img, int32_t h,
              int32_t w_, int32_t cin, int32_t in_cs, int32_t cout, void* stream);
 

@@ -475,7 +475,11 @@ extern "C" int i2r_stem_conv(const float* in_nchw, const float* w, const float* 
     }
     typedef void (*stem_fn)(const float*, const float*, const float*, float*, int, int, int, int, int, int, int, int, int);
     static const stem_fn fns[2][3] = {{stem_conv_k<1, 0>, stem_conv_k<1, 1>, stem_conv_k<1, 2>}, {stem_conv_k<3, 0>, stem_conv_k<3, 1>, stem_conv_k<3, 2>}};
-    i2r_launch(fns[cin == 3][out_dt], dim3(nblk), dim3(256), (size_t)(9 * cin + 1) * cout * sizeof(float), (hipStream_t)stream, in_nchw, w,
+    // weights + bias are dynamic LDS (64 KB without raising the kernel's limit); the 16-bit form stores 8 values = 16 bytes at a time
+    const size_t lds = (size_t)(9 * cin + 1) * cout * sizeof(float);
+    I2R_CHECK_ARG(lds <= 64 * 1024, "i2r_stem_conv: cin=%d cout=%d needs %zu bytes of LDS (at most 65536)", cin, cout, lds);
+    I2R_CHECK_ARG(out_dt == 0 || out_cs % 8 == 0, "i2r_stem_conv: out_cs=%d of a 16-bit output must be a multiple of 8 (cout=%d)", out_cs, cout);
+    i2r_launch(fns[cin == 3][out_dt], dim3(nblk), dim3(256), lds, (hipStream_t)stream, in_nchw, w,
                        bias, out_nhwc, n_img, in_h, in_w, out_h, out_w, cout, out_cs, n_src, n_valid);
     I2R_CHECK_LAUNCH("i2r_stem_conv");
     return I2R_OK;
@@ -589,7 +593,10 @@ extern "C" int i2r_head(const float* in, const float* w, const float* bias, floa
     typedef void (*head_fn)(const float*, const float*, const float*, float*, int, int, int, int, int);
     const int jp = cout <= 16 ? 16 : cout <= 20 ? 20 : 32;
     const head_fn fn = jp == 16 ? head_k<16> : jp == 20 ? head_k<20> : head_k<32>;
-    i2r_launch(fn, dim3(nblk), dim3(256), (size_t)(cin / 4) * jp * sizeof(f32x4), (hipStream_t)stream, in, w, bias, out_nchw, n_img, h * w_,
+    // the [cin / 4][JP] weight image is dynamic LDS: 64 KB is what a launch gets without raising the kernel's limit (cin <= 1024 / 816 / 512)
+    const size_t lds = (size_t)(cin / 4) * jp * sizeof(f32x4);
+    I2R_CHECK_ARG(lds <= 64 * 1024,"i2r_head: cin=%d cout=%d needs %zu bytes of LDS (at most 65536)", cin, cout, lds);
+    i2r_launch(fn, dim3(nblk), dim3(256), lds, (hipStream_t)stream, in, w, bias, out_nchw, n_img, h * w_,
                        cin, in_cs, cout);
     I2R_CHECK_LAUNCH("i2r_head");
     return I2R_OK;
