@@ -2,7 +2,8 @@
 query points, their reductions per person, the roll-out through all captured layers of a stack (rollout=), and the target form of the
 grouped forward (Engine.forward_groups(..., capture=, relations=)).  A form knows its program key, the launch a captured layer emits, the layout of one call
 (plan: integers only -- sizes, offsets and tile counts as include/i2r_hip.h specifies them), the per-call fields of a launch (patch) and
-the shape of what the caller gets back.  Nothing here touches a device or the library: Program.bind_capture (engine.py) does, for all of them.
+the shape of what the caller gets back, and which pair of attn_bind.py does its work behind the program's head (behind).  Nothing here
+touches a device or the library: Program.bind_capture (engine.py) and attn_bind.py do, for all of them.
 """
 import collections
 import dataclasses
@@ -138,6 +139,39 @@ class Plan:
     seed: tuple = ()
 
 
+@dataclasses.dataclass
+class Capture:
+    """one captured encoder stack of a program (Program.captures): made when the stack is emitted, bound per call by Program.bind_capture"""
+    stack: str
+    x: object               # the stack's input activation: its token map is x.h x x.w, of x.n crops
+    off: list               # per block set of the form an int64 device table [x.n]: where every group's block starts
+    ops: list = dataclasses.field(default_factory=list)  # [(layer, args)]: the launch of every captured layer
+    grouping: dict = None   # the stack's grouping record (Program.set_groups)
+    tables: list = None     # this call's Plan.tables on the device
+    base: int = 0           # floats of this call's buffer in front of the capture's first block
+    call: object = None     # what the form's work behind the head needs of this call (attn_bind: Merge, Chain)
+
+
+@dataclasses.dataclass
+class Merge:
+    """a merged form's call on one capture (attn_bind.bind_merge)"""
+    tok: tuple      # the token table of the plain and of the mirrored half (None, None: the per-person form has none)
+    rel: list       # the per-person form: the relation workspace of either half, else None
+    # per captured layer (the plain half's launch args, the mirrored half's, its AttnFlipMergeArgs or 0: a form without maps, its relation
+    # blocks in the buffer or None)
+    layers: list = dataclasses.field(default_factory=list)
+
+
+@dataclasses.dataclass
+class Chain:
+    """the roll-out form's call on one capture (attn_bind.bind_rollout)"""
+    X0: object      # the first working matrix, seeded with `value` at the flat indices `seed`
+    seed: object
+    value: float
+    steps: list     # the AttnRolloutArgs in chain order
+    rel: list       # per person: per group (the raw rows [P, P, h w], the relation block [P, P] they reduce into), else None
+
+
 def _layer(*sets):
     """per block set the view shape of every group (None: a block of no floats) -> ([Block], floats per layer)"""
     blocks, base = [], 0
@@ -183,11 +217,21 @@ class Form:
     merged = False    # True (merge()): the maps of the flip test, M = (P + un-mirrored P') / 2 (i2r_attn_flip_merge)
     per_stack = False  # True: the captured layers of a stack share ONE set of blocks (their product), not one each
     zero_fill = False  # True: the blocks of a call are laid out with gaps the caller reads as zeros -- the per-call buffer starts zeroed
+    J = None           # the joint form: the model's joints -- its token tables are made on the device behind the head (i2r_joint_tokens)
+    # every form: entry, the C entry point of its launch; a form that can be merged: HALF, the fields of its launch args that differ between
+    # the halves of the flip program -- (q|k rows, token table, workspace of the raw maps, their offsets, relation workspace), None: no such field
 
     def __init__(self, capture, suffix=()):
         self.capture, self.key = capture, ("capture", capture) + suffix  # (key: the part of the program key behind the shape)
 
+    # the bind / run pair of attn_bind.py that does this form's work behind the program's head; None: every launch is in the program
+    behind = property(lambda self: "rollout" if self.per_stack else "merge" if self.merged else "launches" if self.deferred else None)
+
+    def begin(self, stack, x, table):  # -> the Capture of a stack a program emits; table() makes one device offset table
+        return Capture(stack, x, [table() for _ in range(self.N_BLOCKS)])
+
     share = staticmethod(lambda plans: None)  # what the plans of all captures of a call must agree on, once they are made: nothing
+    sets = staticmethod(lambda cap: len(cap.ops))  # the sets of blocks a capture has in the per-call buffer: one per captured layer
 
     def merge(self):
         """This form under the flip test with flip_maps="merged": the program is the flip program, whose stacks run the mirrored crops as
@@ -206,17 +250,27 @@ class Form:
         return p
 
     @staticmethod
-    def result(views, inputs):
-        """views: per block set {(stack, layer): per group a view}; inputs(): {(stack, "input"): features} -> what the caller gets"""
+    def result(views, inputs, behind=None):
+        """views: per block set {(stack, layer): per group a view}; inputs(): {(stack, "input"): features}; behind: what the run of the
+        form's pair returned -> what the caller gets"""
         return {**views[0], **inputs()}
+
+
+def _scales(who, up, stacks):
+    """upsample of a call (an int, or {stack: scale}) -> ((stack, scale), ...) of the captured stacks"""
+    try:
+        return tuple((st, int(up[st] if isinstance(up, dict) else up)) for st in stacks)
+    except KeyError as e:
+        raise ValueError("%s.upsample has no scale for stack %s" % (who, e))
 
 
 class FullForm(Form):
     """[L, L] maps (i2r_attn_weights)"""
+    entry = "i2r_attn_weights"
 
     def launch(self, cap, qk, L, goff):
-        """-> (op kind, args) of one captured layer: cap the capture record, qk its q|k activation, L its pack; patch() fills in the rest"""
-        return cabi.CAPTURE_OP_ATTN_WEIGHTS, cabi.AttnWeightsArgs(qk.ptr, 0, goff.data_ptr(), cap["off"][0].data_ptr(), 0, 0, L["heads"], L["hp"],
+        """-> (op kind, args) of one captured layer: cap its Capture, qk its q|k activation, L its pack; patch() fills in the rest"""
+        return cabi.CAPTURE_OP_ATTN_WEIGHTS, cabi.AttnWeightsArgs(qk.ptr, 0, goff.data_ptr(), cap.off[0].data_ptr(), 0, 0, L["heads"], L["hp"],
                                                                   L["hs"], qk.cs, 0, 0)
 
     def plan(self, stack, hw, lens, heads, call=None):
@@ -242,26 +296,23 @@ class FullForm(Form):
 class QueryForm(Form):
     """rows (mode 0) / columns (mode 1) of the maps at query points, up-sampled by the stack's scale (i2r_attn_query_maps): no [L, L]
     block exists, the workspaces are O(K L)"""
+    entry, HALF = "i2r_attn_query_maps", ("qk", "q_tok", "out", "out_off", None)
 
     def __init__(self, capture, queries):
         mode, stacks = int(queries.mode), sorted({st for st, _ in capture})
         missing = set(stacks) - set(queries.tokens)
         if missing:
             raise ValueError("queries.tokens has no table for %s" % sorted(missing))
-        up = queries.upsample
-        try:
-            scales = tuple((st, int(up[st] if isinstance(up, dict) else up)) for st in stacks)
-        except KeyError as e:
-            raise ValueError("queries.upsample has no scale for stack %s" % e)
+        scales = _scales("queries", queries.upsample, stacks)
         if mode not in (0, 1) or not all(1 <= r <= 64 for _, r in scales):
-            raise ValueError("queries: mode %r (0 dependency, 1 affect), upsample %r (1 .. 64)" % (queries.mode, up))
+            raise ValueError("queries: mode %r (0 dependency, 1 affect), upsample %r (1 .. 64)" % (queries.mode, queries.upsample))
         Form.__init__(self, capture, ("query", mode, int(queries.capacity), scales))
         self.call, self.mode, self.scales = queries, mode, dict(scales)
 
     def launch(self, cap, qk, L, goff):
         return cabi.CAPTURE_OP_ATTN_QUERY, cabi.AttnQueryArgs(
-            qk=qk.ptr, grp_off=goff.data_ptr(), out_off=cap["off"][0].data_ptr(), heads=L["heads"], hp=L["hp"], k_off=L["hs"], qk_cs=qk.cs,
-            mode=self.mode, K=1, scale=1 if self.merged else self.scales[cap["stack"]], h=cap["x"].h, w=cap["x"].w)
+            qk=qk.ptr, grp_off=goff.data_ptr(), out_off=cap.off[0].data_ptr(), heads=L["heads"], hp=L["hp"], k_off=L["hs"], qk_cs=qk.cs,
+            mode=self.mode, K=1, scale=1 if self.merged else self.scales[cap.stack], h=cap.x.h, w=cap.x.w)
 
     def plan(self, stack, hw, lens, heads, call=None):
         """call: the AttnQueries of this call -- tokens[stack] int32 [groups, K] (-1 = skip), optionally counts[stack] (entries per group)"""
@@ -283,14 +334,6 @@ class QueryForm(Form):
     def patch(a, p, out, ws, rows, tables, host_off):
         a.out, a.ws, a.rows, (a.q_tok, a.q_cnt), a.grp_off_host = out, ws, rows, tables[:2], host_off
         a.n_grp, a.n_tiles, a.n_col_tiles, a.ws_stride, a.K = p.n_grp, p.n_tiles, p.n_col_tiles, p.ws_stride, p.K
-
-    def scale_of(self, stack):
-        return self.scales[stack]
-
-    @staticmethod
-    def aim(a, qk, tok, maps, raw_off, rel=None):
-        """a merged form's launch on one half of the flip program: that half's q|k rows and token table, the workspace its raw maps go to"""
-        a.qk, a.q_tok, a.out, a.out_off = qk, tok, maps, raw_off
 
 
 class JointForm(QueryForm):
@@ -314,25 +357,39 @@ class JointForm(QueryForm):
         return self._layout(self.scales[stack], hw, lens, heads, K, [n * J for n in pers], tables)
 
     @staticmethod
-    def result(views, inputs):
-        return views[0]  # (no copy of the stacks' inputs: nobody asks this form for them)
+    def result(views, inputs, behind=None):  # behind: (joints, maxvals) of i2r_joint_tokens; no copy of the stacks' inputs: nobody asks for them
+        return tuple(behind) + (views[0],)  # (joints, maxvals, maps)
 
 
-class PersonForm(Form):
+class _PerPerson(Form):
+    """what the two forms that reduce the maps per person share: two block sets per layer, (relation, maps); OP: (op kind, args class)"""
+    N_BLOCKS = 2
+
+    def launch(self, cap, qk, L, goff):
+        rel_off, maps_off = cap.off
+        return self.OP[0], self.OP[1](
+            qk=qk.ptr, grp_off=goff.data_ptr(), rel_off=rel_off.data_ptr(), maps_off=maps_off.data_ptr(), heads=L["heads"], hp=L["hp"],
+            k_off=L["hs"], qk_cs=qk.cs, seg=cap.x.h * cap.x.w, mode=self.mode, scale=1 if self.merged else self.scale, h=cap.x.h, w=cap.x.w)
+
+    @staticmethod
+    def patch(a, p, out, ws, rows, tables, host_off):
+        a.rel, a.maps, a.ws, a.rows, a.grp_off_host = out, out + 4 * p.blocks[1].base, ws, rows, host_off
+        a.n_grp, a.ws_stride = p.n_grp, p.ws_stride
+
+    @staticmethod
+    def result(views, inputs, behind=None):
+        return tuple(views)  # (relation, maps)
+
+
+class PersonForm(_PerPerson):
     """the maps reduced per person (i2r_attn_person_maps): every group is an image of P_g persons of h w tokens; per layer the [P, P]
     relation blocks, then (mode 1: dependency, 2: affect) the [P, P, h r, w r] map blocks.  The workspaces are O(P L)."""
-    N_BLOCKS = 2
+    entry, HALF, OP = "i2r_attn_person_maps", ("qk", None, "maps", "maps_off", "rel"), (cabi.CAPTURE_OP_ATTN_PERSON, cabi.AttnPersonArgs)
 
     def __init__(self, capture, persons):
         self.mode, self.scale = int(persons.mode), int(persons.upsample)
         Form.__init__(self, capture, ("persons", self.mode, self.scale))
-
-    def launch(self, cap, qk, L, goff):
-        rel_off, maps_off = cap["off"]
-        return cabi.CAPTURE_OP_ATTN_PERSON, cabi.AttnPersonArgs(
-            qk=qk.ptr, grp_off=goff.data_ptr(), rel_off=rel_off.data_ptr(), maps_off=maps_off.data_ptr(), heads=L["heads"], hp=L["hp"],
-            k_off=L["hs"], qk_cs=qk.cs, seg=cap["x"].h * cap["x"].w, mode=self.mode, scale=1 if self.merged else self.scale, h=cap["x"].h,
-            w=cap["x"].w)
+        self.scales = {st: self.scale for st, _ in capture}  # (as the query form's: per stack)
 
     def plan(self, stack, hw, lens, heads, call=None):
         mode, scale, (h, w) = self.mode, self.scale, hw
@@ -344,42 +401,19 @@ class PersonForm(Form):
         p = Plan(len(lens), stride, stride * sum(lens), (2 if twice else 1) * max(pers) * sum(lens), blocks, n_layer)
         return self._raw(p, pers, lens) if mode else p
 
-    @staticmethod
-    def patch(a, p, out, ws, rows, tables, host_off):
-        a.rel, a.maps, a.ws, a.rows, a.grp_off_host = out, out + 4 * p.blocks[1].base, ws, rows, host_off
-        a.n_grp, a.ws_stride = p.n_grp, p.ws_stride
 
-    def scale_of(self, stack):
-        return self.scale
-
-    @staticmethod
-    def aim(a, qk, tok, maps, raw_off, rel=None):
-        a.qk, a.rel, a.maps, a.maps_off = qk, rel, maps, raw_off
-
-    @staticmethod
-    def result(views, inputs):
-        return tuple(views)  # (relation, maps)
-
-
-class TargetForm(Form):
+class TargetForm(_PerPerson):
     """the target's rows of the maps reduced per person (i2r_attn_target_maps; TargetMaps): every group is a person group of m_g members
     of h w tokens whose first member is the target; per layer the relation blocks [m_g], then (mode 1: dependency, 2: affect) the map
     blocks [m_g, h r, w r].  Group g's blocks start g * slots entries behind the set (slots >= every m_g), so a layer's set is a dense,
     zero-padded [groups, slots (, h r, w r)] tensor.  The workspaces are O(L): `rows` holds F_t, sum L_g floats, and behind it the raw
     D_t for mode 1 at scale > 1."""
-    N_BLOCKS = 2
-    zero_fill = True
+    entry, zero_fill, OP = "i2r_attn_target_maps", True, (cabi.CAPTURE_OP_ATTN_TARGET, cabi.AttnTargetArgs)
 
     def __init__(self, capture, targets):
         self.mode, self.scale = int(targets.mode), int(targets.scale)
         Form.__init__(self, capture, ("targets", self.mode, self.scale))
         self.call = targets
-
-    def launch(self, cap, qk, L, goff):
-        rel_off, maps_off = cap["off"]
-        return cabi.CAPTURE_OP_ATTN_TARGET, cabi.AttnTargetArgs(
-            qk=qk.ptr, grp_off=goff.data_ptr(), rel_off=rel_off.data_ptr(), maps_off=maps_off.data_ptr(), heads=L["heads"], hp=L["hp"],
-            k_off=L["hs"], qk_cs=qk.cs, seg=cap["x"].h * cap["x"].w, mode=self.mode, scale=self.scale, h=cap["x"].h, w=cap["x"].w)
 
     def plan(self, stack, hw, lens, heads, call=None):
         """call: the TargetMaps of this call (its slots; None: the largest group's members)"""
@@ -397,15 +431,6 @@ class TargetForm(Form):
         stride = _stride(heads, lens)
         return Plan(len(lens), stride, stride * sum(lens), (2 if twice else 1) * sum(lens), [rel, maps], base + -(-maps.offs[-1] // 4) * 4, K=slots)
 
-    @staticmethod
-    def patch(a, p, out, ws, rows, tables, host_off):
-        a.rel, a.maps, a.ws, a.rows, a.grp_off_host = out, out + 4 * p.blocks[1].base, ws, rows, host_off
-        a.n_grp, a.ws_stride = p.n_grp, p.ws_stride
-
-    @staticmethod
-    def result(views, inputs):
-        return tuple(views)  # (relation, maps)
-
 
 class RolloutForm(Form):
     """the relations through the captured layers lo .. hi of every captured stack (Rollout; i2r_attn_rollout_step): a chain of thin
@@ -415,6 +440,7 @@ class RolloutForm(Form):
     set of result blocks -- at query tokens the layout of the query form, per person that of the per-person form (relation, maps) --
     and a last, view-less set: the scale-1 layout of the working matrices.  alpha is per call: it is not in the key."""
     deferred = per_stack = True
+    entry, sets = "i2r_attn_rollout_step", staticmethod(lambda cap: 1)
 
     def __init__(self, capture, rollout):
         self.points, self.mode = bool(rollout.points), int(rollout.mode)
@@ -425,13 +451,9 @@ class RolloutForm(Form):
             if layers != list(range(layers[0], layers[-1] + 1)):
                 raise ValueError("rollout: the layers %s of %r are not a contiguous range" % (layers, st))
             self.range[st] = (layers[0], layers[-1])
-        up = rollout.upsample
-        try:
-            scales = tuple((st, int(up[st] if isinstance(up, dict) else up)) for st in stacks)
-        except KeyError as e:
-            raise ValueError("rollout.upsample has no scale for stack %s" % e)
+        scales = _scales("rollout", rollout.upsample, stacks)
         if not all(1 <= r <= 64 for _, r in scales):
-            raise ValueError("rollout: upsample %r (1 .. 64)" % (up,))
+            raise ValueError("rollout: upsample %r (1 .. 64)" % (rollout.upsample,))
         if self.points:
             missing = set(stacks) - set(rollout.tokens)
             if missing:
@@ -445,7 +467,7 @@ class RolloutForm(Form):
 
     def launch(self, cap, qk, L, goff):
         return None, cabi.AttnRolloutArgs(qk=qk.ptr, grp_off=goff.data_ptr(), heads=L["heads"], hp=L["hp"], k_off=L["hs"], qk_cs=qk.cs, K=1, side=self.side,
-                                          seg=0 if self.points else cap["x"].h * cap["x"].w, scale=1, h=cap["x"].h, w=cap["x"].w)
+                                          seg=0 if self.points else cap.x.h * cap.x.w, scale=1, h=cap.x.h, w=cap.x.w)
 
     def plan(self, stack, hw, lens, heads, call=None):
         """call: the Rollout of this call (tokens, counts: as the query form; alpha)"""
@@ -483,7 +505,7 @@ class RolloutForm(Form):
         a.ws, a.rows, a.q_cnt, a.grp_off_host = ws, rows, tables[0] if tables else None, host_off
         a.n_grp, a.ws_stride, a.K = p.n_grp, p.ws_stride, p.K
 
-    def result(self, views, inputs):
+    def result(self, views, inputs, behind=None):
         """per stack (not per layer): at query tokens {stack: per group a view}; per person ({stack: relations}, {stack: maps})"""
         strip = lambda d: {st: v for (st, _), v in d.items()}
         return strip(views[0]) if self.points else (strip(views[0]), strip(views[1]))
@@ -510,34 +532,21 @@ def resolve(capture, queries, persons, flip_joint_map, stacks, inter_stack, wind
         if queries is not None or persons is not None or joints is not None or rollout is not None:
             raise ValueError("relations=: not with queries=, persons=, joints= or rollout= (roll-out and predicted-joint queries are not served "
                              "on the grouped forward)")
-        if window:
-            raise ValueError("relations=: ATTENTION_TYPE window has no encoder stack to capture")
+        _no_window(window, "relations=")
         if flip_joint_map is not None or flip_maps != "plain":
             raise ValueError("relations=: not with the flip test")
         if not capture:
             raise ValueError("relations= needs capture=: the (stack, layer) set of the inter-human stack to reduce")
-        capture = frozenset((str(st), int(i)) for st, i in capture)
-        other = sorted({st for st, _ in capture} - {inter_stack})
-        if other or inter_stack not in stacks:
-            raise ValueError("relations=: %s is not this model's inter-human stack %r (an intra-human stack has one person per group)"
-                             % (other or "a capture", inter_stack if inter_stack in stacks else None))
-        for st, i in capture:
-            if not 0 <= i < stacks[st]:
-                raise ValueError("capture (%r, %d): this model's encoder stacks are %s" % (st, i, stacks))
-        return TargetForm(capture, targets)
+        return TargetForm(_capture_set(capture, stacks, inter_stack, "relations="), targets)
     if rollout is not None:
-        if window:
-            raise ValueError("rollout=: ATTENTION_TYPE window has no encoder stack to capture")
+        _no_window(window, "rollout=")
         if flip_joint_map is not None or flip_maps != "plain":
             raise ValueError("rollout=: not with the flip test (a product of merged maps is not the merge of products)")
         if queries is not None or persons is not None or joints is not None:
             raise ValueError("rollout=: not with queries=, persons= or joints= (predicted-joint queries are not served)")
         if not capture:
             raise ValueError("rollout= needs capture=: the (stack, layer) range to roll out")
-        capture = frozenset((str(st), int(i)) for st, i in capture)
-        for st, i in capture:
-            if st not in stacks or not 0 <= i < stacks[st]:
-                raise ValueError("capture (%r, %d): this model's encoder stacks are %s" % (st, i, stacks))
+        capture = _capture_set(capture, stacks)
         other = sorted({st for st, _ in capture} - {inter_stack})
         if not rollout.points and other:
             raise ValueError("rollout= per person: %s is not this model's inter-human stack %r" % (other, inter_stack if inter_stack in stacks else None))
@@ -545,40 +554,48 @@ def resolve(capture, queries, persons, flip_joint_map, stacks, inter_stack, wind
     if flip_maps == "merged":
         if flip_joint_map is None:
             raise ValueError("flip_maps='merged' needs the flip test (flip_joint_map)")
-        if window:
-            raise ValueError("flip_maps='merged': ATTENTION_TYPE window has no encoder stack to capture")
+        _no_window(window, "flip_maps='merged'")
         if sum(f is not None for f in (queries, persons, joints)) != 1:
             raise ValueError("flip_maps='merged' goes with exactly one of queries=, persons=, joints= (the full [L, L] maps are not merged)")
         return resolve(capture, queries, persons, None, stacks, inter_stack, window, joints, n_joints).merge()
     if joints is not None:
-        if window:
-            raise ValueError("joints=: ATTENTION_TYPE window has no encoder stack to capture")
+        _no_window(window, "joints=")
         if queries is not None or persons is not None:
             raise ValueError("joints=: not with queries= or persons= (the joint form makes its own tables)")
         if not stacks:
             raise ValueError("joints=: this model has no encoder stack to capture")
         if not capture:
             raise ValueError("joints= needs capture=: the (stack, layer) set whose maps to query")
+        return JointForm(_capture_set(capture, stacks), joints, n_joints)
     if persons is not None:
-        if window:
-            raise ValueError("persons=: ATTENTION_TYPE window has no encoder stack to capture")
+        _no_window(window, "persons=")
         if flip_joint_map is not None or queries is not None:
             raise ValueError("persons=: not with the flip test, not with queries=")
         if not capture:
             raise ValueError("persons= needs capture=: the (stack, layer) set of the inter-human stack to reduce")
-        other = sorted({str(st) for st, _ in capture} - {inter_stack})
-        if other or inter_stack not in stacks:
-            raise ValueError("persons=: %s is not this model's inter-human stack %r (an intra-human stack has one person per group)"
-                             % (other or "a capture", inter_stack if inter_stack in stacks else None))
+        return PersonForm(_capture_set(capture, stacks, inter_stack, "persons="), persons)
     if not capture:
         if queries is not None:
             raise ValueError("queries= needs capture=: the (stack, layer) set whose maps to query")
         return None
+    capture = _capture_set(capture, stacks)
+    assert flip_joint_map is None and not window, "attention maps: no flip test, no window-type block"
+    return QueryForm(capture, queries) if queries is not None else FullForm(capture)
+
+
+def _no_window(window, who):
+    if window:
+        raise ValueError("%s: ATTENTION_TYPE window has no encoder stack to capture" % who)
+
+
+def _capture_set(capture, stacks, inter_stack=None, who=None):
+    """-> a call's capture as a frozenset of (stack, layer) of this model's stacks; who: a form of the inter-human stack alone"""
     capture = frozenset((str(st), int(i)) for st, i in capture)
+    other = sorted({st for st, _ in capture} - {inter_stack})
+    if who and (other or inter_stack not in stacks):
+        raise ValueError("%s: %s is not this model's inter-human stack %r (an intra-human stack has one person per group)"
+                         % (who, other or "a capture", inter_stack if inter_stack in stacks else None))
     for st, i in capture:
         if st not in stacks or not 0 <= i < stacks[st]:
             raise ValueError("capture (%r, %d): this model's encoder stacks are %s" % (st, i, stacks))
-    if joints is not None:
-        return JointForm(capture, joints, n_joints)
-    assert flip_joint_map is None and not window, "attention maps: no flip test, no window-type block"
-    return PersonForm(capture, persons) if persons is not None else QueryForm(capture, queries) if queries is not None else FullForm(capture)
+    return capture

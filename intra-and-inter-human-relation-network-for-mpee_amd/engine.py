@@ -10,7 +10,7 @@ import os
 
 import torch
 
-from . import attn_capture, cabi
+from . import attn_bind, attn_capture, cabi
 from .attn_capture import AttnQueries, JointQueries, PersonMaps, Rollout, TargetMaps  # noqa: F401 (the capture forms' public classes stay importable from here)
 from .pack import (PRECISIONS, PackedConv, Packer, _m16, _r16, fold_bn, pack_frag, pack_frag32, pack_k4, pack_k8,  # noqa: F401 (the packing names stay importable from here)
                    winograd_weights)
@@ -792,7 +792,7 @@ class Program:
         per crop) the engine may regroup it per call (groupings)"""
         self.set_groups(grouping, grp_off_host)
         if cap is not None:
-            cap["grouping"] = grouping
+            cap.grouping = grouping
         self.enc_stacks.append(grouping)  # every encoder stack of the program (bench.py: algorithmic FLOPs of the attention blocks)
         if regroup_tok is not None:
             self.groupings.append((grouping, regroup_tok))
@@ -815,25 +815,23 @@ class Program:
     # with (attn_capture: full [L, L] maps, rows / columns at query points, reductions per person) into ONE per-call buffer.  The launch list
     # is fixed at build time; bind_capture() patches the per-call part and uploads the offsets of the groups' blocks, like set_groups() does.
     # A deferred form keeps its launches out of the list: the joint form needs the heat maps of the same call, a merged form (the flip
-    # test's maps) the q|k of both halves, so the engine issues them behind the run (Engine._deferred_maps) on the q|k the captured layers kept.
+    # test's maps) the q|k of both halves, so the engine issues them behind the run (the form's pair in attn_bind.py) on the q|k the captured layers kept.
     def _capture_begin(self, capture, x):
         if not capture:
             return None
-        cap = dict(stack=capture["stack"], x=x, ops=[], off=[torch.zeros(x.n, dtype=torch.int64, device=self.device) for _ in range(self.form.N_BLOCKS)])
-        self.keep += cap["off"]
-        self.captures.append(cap)
-        return cap
+        self.captures.append(self.form.begin(capture["stack"], x, lambda: torch.zeros(x.n, dtype=torch.int64, device=self.device)))
+        self.keep += self.captures[-1].off
+        return self.captures[-1]
 
     def _capture_layer(self, cap, i, qk, L, goff, lane):
         """the launch of captured layer i on its q|k activation -> True when q|k must be held (a deferred form), else the caller releases it"""
         assert qk.dt == 0 and qk.cs >= 2 * L["hs"]
         self.keep.append(L)
         kind, a = self.form.launch(cap, qk, L, goff)
-        cap["ops"].append((i, a))
-        if self.form.deferred:  # the engine runs the launch behind the program: q|k stays out of the pool until the program ends
-            return True
-        self.ops.append((kind, lane, a))
-        return False
+        cap.ops.append((i, a))
+        if not self.form.behind:  # (else the form's pair runs the launch behind the program: q|k stays out of the pool until the program ends)
+            self.ops.append((kind, lane, a))
+        return bool(self.form.behind)
 
     def bind_capture(self, glens, call=None):
         """glens: per capture (program order) the token count of every group to compute (the real images / crops of this call, a prefix of
@@ -842,113 +840,38 @@ class Program:
         lays it out."""
         form, plans = self.form, []
         for cap, lens in zip(self.captures, glens):  # the groups asked for are the first groups of the stack as it is grouped now
-            cur = cap["grouping"]["current"]
+            cur = cap.grouping["current"]
             assert len(lens) >= 1 and list(lens) == [cur[g + 1] - cur[g] for g in range(len(lens))]
-            plans.append(form.plan(cap["stack"], (cap["x"].h, cap["x"].w), lens, max(a.heads for _, a in cap["ops"]), call))
+            plans.append(form.plan(cap.stack, (cap.x.h, cap.x.w), lens, max(a.heads for _, a in cap.ops), call))
         form.share(plans)
-        slots = (lambda cap: 1) if form.per_stack else (lambda cap: len(cap["ops"]))  # (a roll-out: one set of blocks per stack)
-        buf = (torch.zeros if form.zero_fill else torch.empty)(sum(p.layer_floats * slots(cap) + p.extra_floats for p, cap in zip(plans, self.captures)),
+        buf = (torch.zeros if form.zero_fill else torch.empty)(sum(p.layer_floats * form.sets(cap) + p.extra_floats for p, cap in zip(plans, self.captures)),
                                                                dtype=torch.float32, device=self.device)
         ws = torch.empty(max(p.ws_floats for p in plans), dtype=torch.float32, device=self.device)
         rows = torch.empty(max(p.rows_floats for p in plans), dtype=torch.float32, device=self.device)
         held = [ws, rows]  # (kept until the next call: the launches read them asynchronously; torch's allocator orders reuse by stream)
-        views, base = [{} for _ in range(form.N_BLOCKS)], 0
+        views, base = [{} for _ in plans[0].blocks], 0
         for cap, lens, p in zip(self.captures, glens, plans):
-            for off, blk in zip(cap["off"], p.blocks):
+            for off, blk in zip(cap.off, p.blocks):
                 off[:len(lens)].copy_(torch.tensor(blk.offs[:-1], dtype=torch.int64).pin_memory(), non_blocking=True)
-            tables = cap["tables"] = [t.pin_memory().to(self.device, non_blocking=True) if torch.is_tensor(t) else
-                                      torch.empty(t, dtype=torch.int32, device=self.device) for t in p.tables]
-            host_off = (C.c_int32 * (len(lens) + 1))(*cap["grouping"]["current"][:len(lens) + 1])  # (the query and person launches read it)
+            tables = cap.tables = [t.pin_memory().to(self.device, non_blocking=True) if torch.is_tensor(t) else
+                                   torch.empty(t, dtype=torch.int32, device=self.device) for t in p.tables]
+            host_off = (C.c_int32 * (len(lens) + 1))(*cap.grouping["current"][:len(lens) + 1])  # (the query and person launches read it)
             held += tables + [host_off]
             ptrs = (ws.data_ptr(), rows.data_ptr(), [t.data_ptr() for t in tables], C.cast(host_off, C.c_void_p))
-            cap["base"] = base
-            for n, (i, a) in enumerate(cap["ops"]):
+            cap.base = base
+            for n, (i, a) in enumerate(cap.ops):
                 form.patch(a, p, buf.data_ptr() + 4 * base, *ptrs)
-                if n < slots(cap):
+                if n < form.sets(cap):  # (a roll-out: one set of blocks per stack)
                     for out, blk in zip(views, p.blocks):
                         if blk.shapes:
                             b = base + blk.base
-                            out[(cap["stack"], i)] = [buf[b + o:b + o + math.prod(s)].view(s) for o, s in zip(blk.offs, blk.shapes)]
+                            out[(cap.stack, i)] = [buf[b + o:b + o + math.prod(s)].view(s) for o, s in zip(blk.offs, blk.shapes)]
                     base += p.layer_floats
             base += p.extra_floats
-        if form.merged:
-            self._bind_merge(plans, glens, buf, held)
-        if form.per_stack:
-            self._bind_rollout(plans, glens, buf, rows, held, call.alpha)
+        if form.behind:  # (the call's part of the work behind the head)
+            attn_bind.PAIRS[form.behind][0](self, plans, glens, buf, rows, held, call)
         self._capture_ws = held
         return views
-
-    def _bind_merge(self, plans, glens, buf, held):
-        """the per-call part of a merged form (attn_capture.Form.merge) behind bind_capture: per capture a record cap["merge"] of what
-        Engine._deferred_maps launches -- the q|k rows of either half of every captured layer (the mirrored groups repeat the plain ones
-        half the stack's rows further on, so ONE offset table serves both), the mirrored token table, the two raw workspaces (shared by
-        all layers: the launches are ordered on the stream), the relation workspaces of the per-person form, and the i2r_attn_flip_merge
-        args of every layer, whose out is the layer's maps block in buf."""
-        raw = [torch.empty(max(p.raw_floats for p in plans), dtype=torch.float32, device=self.device) for _ in range(2)]
-        held += raw
-        base = 0
-        for cap, lens, p in zip(self.captures, glens, plans):
-            cur, n = cap["grouping"]["current"], len(lens)
-            half = (len(cur) - 1) // 2
-            assert len(cur) == 2 * half + 1 and n <= half and all(cur[half + g] - cur[half] == cur[g] for g in range(n + 1)), "not a flip program's groups"
-            qk0 = cap.setdefault("qk0", [a.qk for _, a in cap["ops"]])  # (the launches' q|k as built: aim() moves a.qk between the halves)
-            maps = p.blocks[-1]  # (the per-person form: the set behind the relation blocks)
-            tok = cap["tables"][0] if cap["tables"] else None
-            rel = [torch.empty(p.blocks[0].offs[-1], dtype=torch.float32, device=self.device) for _ in range(2)] if self.form.N_BLOCKS == 2 else None
-            m = dict(qk=[(q, q + 4 * cur[half] * a.qk_cs) for q, (_, a) in zip(qk0, cap["ops"])], tok=(tok, torch.empty_like(tok) if tok is not None else None),
-                     raw=raw, rel=rel, raw_off=None, rel_out=[], layers=[])
-            if p.raw_floats:
-                m["raw_off"] = torch.tensor(p.raw_offs, dtype=torch.int64).pin_memory().to(self.device, non_blocking=True)
-            host_off = (C.c_int32 * (n + 1))(*cur[:n + 1])
-            held += [m, host_off]
-            for _, a in cap["ops"]:
-                if rel:
-                    m["rel_out"].append(buf[base:base + p.blocks[0].offs[-1]])
-                if p.raw_floats:
-                    seg = a.seg if rel else 0
-                    m["layers"].append(cabi.AttnFlipMergeArgs(
-                        a=raw[0].data_ptr(), b=raw[1].data_ptr(), out=buf.data_ptr() + 4 * (base + maps.base), grp_off=a.grp_off, src_off=m["raw_off"].data_ptr(),
-                        out_off=cap["off"][-1].data_ptr(), q_cnt=0 if rel else cap["tables"][1].data_ptr(), grp_off_host=C.cast(host_off, C.c_void_p),
-                        n_grp=n, K=p.K, seg=seg, scale=self.form.scale_of(cap["stack"]), h=cap["x"].h, w=cap["x"].w))
-                base += p.layer_floats
-            cap["merge"] = m
-
-    def _bind_rollout(self, plans, glens, buf, rows, held, alpha):
-        """the per-call part of the roll-out form (attn_capture.RolloutForm) behind bind_capture: per capture a record cap["rollout"] of what
-        Engine._deferred_maps runs -- the seed of the chain (flat indices into the first working matrix, uploaded here), the steps in
-        chain order (side 0: layers hi -> lo, side 1: lo -> hi), each reading the matrix the step before wrote, the last one writing (and
-        up-sampling) into the stack's blocks, and for the per-person form the views the [P, P] relations are reduced from and into.
-        alpha: this call's (the program is not keyed by it)."""
-        form = self.form
-        for cap, lens, p in zip(self.captures, glens, plans):
-            xl, res = p.blocks[-1], p.blocks[-2]  # the working matrices' layout; the set the last step writes (maps)
-            n_x = p.extra_floats // 2
-            x0 = cap["base"] + xl.base
-            X = [buf[x0:x0 + n_x], buf[x0 + n_x:x0 + 2 * n_x]]
-            idx, value = p.seed
-            seed = idx.pin_memory().to(self.device, non_blocking=True)
-            x_off, out_off = cap["off"][-1], cap["off"][-2]
-            scale = form.scales[cap["stack"]]
-            ops = sorted(cap["ops"], key=lambda o: o[0], reverse=form.side == 0)
-            to_blocks = res.shapes is not None  # (per person without maps: the chain ends in a working matrix)
-            for n, (_, a) in enumerate(ops):
-                last = n == len(ops) - 1
-                a.in_, a.out, a.x_off, a.out_off, a.scale, a.alpha = X[n % 2].data_ptr(), X[(n + 1) % 2].data_ptr(), x_off.data_ptr(), None, 1, alpha
-                if last and to_blocks:
-                    a.out, a.out_off, a.scale = buf.data_ptr() + 4 * (cap["base"] + res.base), out_off.data_ptr(), scale
-            r = dict(X0=X[0], seed=seed, value=value, steps=[a for _, a in ops], rel=None)
-            if not form.points:  # R_T from the raw rows of the last step: in the maps blocks at scale 1, else in the working matrix / rows
-                cur = cap["grouping"]["current"]
-                if to_blocks and scale > 1:
-                    raw = [rows[p.K * cur[g]:p.K * cur[g] + (n // a.seg) * n] for g, n in enumerate(lens)]
-                else:
-                    src, b0 = (buf, cap["base"] + res.base) if to_blocks else (X[len(ops) % 2], 0)
-                    raw = [src[b0 + o:b0 + e] for o, e in zip(xl.offs, xl.offs[1:])]
-                rb = cap["base"] + p.blocks[0].base
-                r["rel"] = [(v.view(n // a.seg, n // a.seg, a.seg), buf[rb + o:rb + e].view(n // a.seg, n // a.seg))
-                            for v, n, o, e in zip(raw, lens, p.blocks[0].offs, p.blocks[0].offs[1:])]
-            held += [seed, r]
-            cap["rollout"] = r
 
     def set_groups(self, grouping, grp_off_host):
         """(Re)define the token groups of an encoder stack: uploads the offset table and patches the per-layer descriptors."""
@@ -2192,7 +2115,7 @@ class Engine:
             # (NHWC arena buffer -> the reference's NCHW feature tensor: a torch view + copy, boundary plumbing only)
             feat = g.t.view(S, g.h, g.w, g.cs)[..., :g.c].permute(0, 3, 1, 2).contiguous()
             if form:
-                return (feat, hm), form.result(views, lambda: self._capture_inputs(P, S))
+                return (feat, hm), self._finish_capture(P, views, S, H)
         return feat, hm
 
     def _bind_capture(self, P, form, S, length, H, W):
@@ -2200,17 +2123,17 @@ class Engine:
         capture_map_sizes promises (attention_at mapped its points onto them) -> the views of Program.bind_capture"""
         sizes, glens = self.capture_map_sizes(H, W), []
         for c in P.captures:
-            h, w = c["x"].h, c["x"].w
-            if sizes.get(c["stack"]) != (h, w):
+            h, w = c.x.h, c.x.w
+            if sizes.get(c.stack) != (h, w):
                 raise RuntimeError("capture_map_sizes(%d, %d)[%r] = %s, but the program's stack input is %d x %d"
-                                   % (H, W, c["stack"], sizes.get(c["stack"]), h, w))
-            glens.append([h * w] * S if c["stack"] == self.single_stack else [n * h * w for n in length])
+                                   % (H, W, c.stack, sizes.get(c.stack), h, w))
+            glens.append([h * w] * S if c.stack == self.single_stack else [n * h * w for n in length])
         return P.bind_capture(glens, form.call)
 
     @staticmethod
     def _capture_inputs(P, S):
         """per captured stack its input features [S, c, h, w] (NCHW copies: the `reduce` output for the stacks fed by one)"""
-        return {(c["stack"], "input"): c["x"].view()[:S, :, :, :c["x"].c].permute(0, 3, 1, 2).contiguous() for c in P.captures}
+        return {(c.stack, "input"): c.x.view()[:S, :, :, :c.x.c].permute(0, 3, 1, 2).contiguous() for c in P.captures}
 
     @staticmethod
     def capacity(S):
@@ -2258,7 +2181,7 @@ class Engine:
         test, M = (P + P~) / 2 with P~[q, k] = P'[mu(q), mu(k)] the mirrored pass's map brought back into the plain frame (DESIGN.md
         'i2r_attn_flip_merge'), in the layouts of the un-flipped calls; output is the merged heat maps.  The program is the flip program
         with a marker in its key; every captured layer holds its fp32 q|k of BOTH halves until the program ends, and the launches run
-        behind the head (_deferred_maps).  ValueError: without the flip test, with the full [L, L] form, the window-type block.
+        behind the head (attn_bind.run_merge).  ValueError: without the flip test, with the full [L, L] form, the window-type block.
         rollout (attn_capture.Rollout, with capture of a contiguous layer range lo .. hi per stack): the attention roll-out T = A_hi ... A_lo,
         A_l = (1 - alpha) I + alpha P_l, THROUGH those layers instead of the maps of each (DESIGN.md 'i2r_attn_rollout_step') -- with tokens
         -> (output, {stack: maps}), maps as for queries of ONE layer: rows T[q, :] (mode 0) or columns T[:, q] (mode 1); without tokens (the
@@ -2275,7 +2198,7 @@ class Engine:
                                     joints, self.cfg["MODEL"]["NUM_JOINTS"], flip_maps, rollout)
         if form:
             with torch.cuda.device(self.device):
-                return self._forward_part(x, pos_mask, list(length), flip_joint_map if form.deferred else None, S, H, W, sine_n, form=form)
+                return self._forward_part(x, pos_mask, list(length), flip_joint_map if form.behind else None, S, H, W, sine_n, form=form)
         if self.window_attn and flip_joint_map is not None:
             # the window type mixes the rows of ALL images of a call (attention.py:1025-1029): the mirrored batch must be a call of its
             # own, as in validate() (function.py:142-162), not extra token groups of this one
@@ -2632,10 +2555,10 @@ class Engine:
         if "first_member" in patch:
             torch.index_select(patch["members"], 0, patch["_first_idx"], out=patch["first_member"])  # (on the device: nothing is read back)
         self._bind_groups(Pt, group_len, capG - G, flip)
-        if form:  # (the call's real groups: the capacity slots behind them are never among the computed groups)
-            views = self._bind_capture(Pt, form, S, group_len, H, W)
-            return self._run_bound(Pt, patch, capN, N, flip_joint_map, H, W)[0], form.result(views, None)
-        return self._run_bound(Pt, patch, capN, N, flip_joint_map, H, W)[0]
+        # (a capture: the call's real groups -- the capacity slots behind them are never among the computed groups)
+        views = self._bind_capture(Pt, form, S, group_len, H, W) if form else None
+        out = self._run_bound(Pt, patch, capN, N, flip_joint_map, H, W)[0]
+        return (out, self._finish_capture(Pt, views, S, H)) if form else out
 
     def _forward_part(self, x, pos_mask, length, flip_joint_map, S, H, W, sine_n, slot=0, form=None):
         x = x.to(self.device).contiguous()
@@ -2669,75 +2592,13 @@ class Engine:
         views = self._bind_capture(P, form, S, length, H, W) if form else None
         multi, single = self._run_bound(P, patch, cap, S, flip_joint_map, H, W)
         res = {"single": single, "multi": multi} if single is not None else multi
-        if form and form.deferred:
-            if isinstance(form, attn_capture.JointForm):
-                jt = self._joint_tokens(P, multi, S, H)
-                self._deferred_maps(P)
-                return res, jt + (form.result(views, None),)
-            self._deferred_maps(P)
-        return (res, form.result(views, lambda: self._capture_inputs(P, S))) if form else res
+        return (res, self._finish_capture(P, views, S, H, multi)) if form else res
 
-    def _deferred_maps(self, P):
-        """the launches of a deferred form behind the program's head, on the current stream, on the q|k the captured layers kept.  The
-        plain joint form: the i2r_attn_query_maps launch of every captured layer.  A merged form (attn_capture.Form.merge; the records of
-        Program._bind_merge): i2r_token_mirror makes the mirrored pass's token table, then per captured layer the form's launch at scale 1
-        on the plain half and, at the mirrored tokens, on the mirrored half, and ONE i2r_attn_flip_merge into the capture buffer; the
-        relation matrices of the per-person form, mirror-invariant sums over whole persons, are merged by one torch expression on the
-        same stream: R_m = (R + R') / 2.  Nothing here reads the device."""
-        L, stream, form = cabi.lib(), torch.cuda.current_stream(self.device).cuda_stream, P.form
-        if form.per_stack:
-            # The roll-out form (the records of Program._bind_rollout): the seed by two torch fills, the chain of i2r_attn_rollout_step
-            # launches, and for the per-person form R_T = sum_{k in j} D_T = mean_{q in i} F_T as one torch reduction per image.
-            for cap in P.captures:
-                r = cap["rollout"]
-                r["X0"].zero_().index_fill_(0, r["seed"], r["value"])
-                for a in r["steps"]:
-                    cabi.check(L.i2r_attn_rollout_step(C.byref(a), stream), "i2r_attn_rollout_step")
-                for rows, rel in r["rel"] or ():
-                    if form.side == 0:
-                        torch.sum(rows, 2, out=rel)
-                    else:
-                        rel.copy_(rows.mean(2).t())
-            return
-        name = "i2r_attn_person_maps" if form.N_BLOCKS == 2 else "i2r_attn_query_maps"
-        launch = getattr(L, name)
-        for cap in P.captures:
-            if not form.merged:
-                for _, q in cap["ops"]:
-                    cabi.check(launch(C.byref(q), stream), name)
-                continue
-            m = cap["merge"]
-            tok, raw, rel = m["tok"], m["raw"], m["rel"] or (None, None)
-            if tok[0] is not None:
-                cabi.check(L.i2r_token_mirror(tok[0].data_ptr(), tok[1].data_ptr(), tok[0].numel(), cap["x"].w, stream), "i2r_token_mirror")
-            for j, (_, a) in enumerate(cap["ops"]):
-                for half in (0, 1):
-                    form.aim(a, m["qk"][j][half], tok[half].data_ptr() if tok[half] is not None else None, raw[half].data_ptr(),
-                             m["raw_off"].data_ptr() if m["raw_off"] is not None else None, rel[half].data_ptr() if rel[half] is not None else None)
-                    cabi.check(launch(C.byref(a), stream), name)
-                if m["layers"]:
-                    cabi.check(L.i2r_attn_flip_merge(C.byref(m["layers"][j]), stream), "i2r_attn_flip_merge")
-                if m["rel_out"]:
-                    torch.add(rel[0], rel[1], out=m["rel_out"][j]).mul_(0.5)
-
-    def _joint_tokens(self, P, multi, S, H):
-        """the tables of a joint-form program (attn_capture.JointForm) behind its head, on the current stream: i2r_joint_tokens on the
-        (merged) heat maps multi [S, J, H/4, W/4] fills the token tables bind_capture made; the launches that read them follow
-        (_deferred_maps).  -> (joints [S, J, 2], maxvals [S, J]) on the device"""
-        L, stream = cabi.lib(), torch.cuda.current_stream(self.device).cuda_stream
-        assert multi.is_contiguous() and multi.shape[0] == S and 1 <= len(P.captures) <= cabi.MAX_TOKEN_TABLES
-        J, hh, hw = multi.shape[1:]
-        joints = torch.empty(S, J, 2, dtype=torch.float32, device=self.device)
-        maxvals = torch.empty(S, J, dtype=torch.float32, device=self.device)
-        a = cabi.JointTokensArgs(heatmaps=multi.data_ptr(), points=joints.data_ptr(), maxvals=maxvals.data_ptr(), n_crops=S, joints=J, hh=hh, hw=hw,
-                                 in_stride=H // hh, n_tables=len(P.captures))
-        for t, cap in zip(a.table, P.captures):
-            tok, _, crops = cap["tables"]
-            assert crops.shape == (2, S)
-            t.tokens, t.crop_group, t.crop_slot = tok.data_ptr(), crops[0].data_ptr(), crops[1].data_ptr()
-            (t.n_grp, t.K), t.fh, t.fw, t.down = tok.shape, cap["x"].h, cap["x"].w, H // cap["x"].h
-        cabi.check(L.i2r_joint_tokens(C.byref(a), stream), "i2r_joint_tokens")
-        return joints, maxvals
+    def _finish_capture(self, P, views, S, H, multi=None):
+        """behind a capture program that has run: the work its form keeps behind the head (attn_bind: the joint form goes head ->
+        i2r_joint_tokens on `multi` -> query launches), on the current stream, then what the caller gets of the bound `views`"""
+        behind = attn_bind.PAIRS[P.form.behind][1](P, multi, S, H) if P.form.behind else None
+        return P.form.result(views, lambda: self._capture_inputs(P, S), behind)
 
     # the per-call steps every bound forward shares (_run_program, _forward_groups_shared)
     def _bind_groups(self, P, length, pad, flip):

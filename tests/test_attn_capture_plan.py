@@ -217,6 +217,44 @@ def test_forms_and_their_program_keys():
         resolve(cap, None, None, "flip", *args)
 
 
+def test_every_form_names_its_work_behind_the_head_and_its_entry_point():
+    """every form resolve() can return: `behind` is one of the four values and attn_bind has a bind / run pair for it, `entry` is an
+    exported C entry point, and the flags the other tests read keep their values (deferred, merged, per_stack, N_BLOCKS)"""
+    from i2r_amd import attn_bind, cabi
+    from i2r_amd.attn_capture import JointQueries, Rollout, TargetMaps
+    stacks = {"single": 4, "inter": 6}
+    cap, inter = {("inter", 0), ("inter", 1), ("single", 3)}, {("inter", 2), ("inter", 3)}
+    tok = {"inter": torch.zeros(2, 7, dtype=torch.int32), "single": torch.zeros(4, 3, dtype=torch.int32)}
+    q, j = AttnQueries(tok, "affect", 4), JointQueries()
+    res = lambda capture, queries=None, persons=None, flip=None, **kw: resolve(capture, queries, persons, flip, stacks, "inter", False, **kw)  # noqa: E731
+    cases = [  # (the call, its form's class name, behind, entry, deferred, merged, per_stack, N_BLOCKS)
+        (res(cap), "FullForm", None, "i2r_attn_weights", False, False, False, 1),
+        (res(cap, q), "QueryForm", None, "i2r_attn_query_maps", False, False, False, 1),
+        (res(inter, persons=PersonMaps("affect", 2)), "PersonForm", None, "i2r_attn_person_maps", False, False, False, 2),
+        (res(cap, joints=j, n_joints=17), "JointForm", "launches", "i2r_attn_query_maps", True, False, False, 1),
+        (res(cap, flip="flip", joints=j, n_joints=17), "JointForm", "launches", "i2r_attn_query_maps", True, False, False, 1),
+        (res(inter, targets=TargetMaps("dependency")), "TargetForm", None, "i2r_attn_target_maps", False, False, False, 2),
+        (res(cap, rollout=Rollout(tok)), "RolloutForm", "rollout", "i2r_attn_rollout_step", True, False, True, 2),
+        (res(inter, rollout=Rollout(None, "affect")), "RolloutForm", "rollout", "i2r_attn_rollout_step", True, False, True, 3),
+        (res(cap, q, flip="flip", flip_maps="merged"), "QueryForm", "merge", "i2r_attn_query_maps", True, True, False, 1),
+        (res(inter, persons=PersonMaps("affect", 2), flip="flip", flip_maps="merged"), "PersonForm", "merge", "i2r_attn_person_maps", True, True, False, 2),
+        (res(cap, flip="flip", joints=j, n_joints=17, flip_maps="merged"), "JointForm", "merge", "i2r_attn_query_maps", True, True, False, 1),
+    ]
+    assert set(attn_bind.PAIRS) == {"launches", "merge", "rollout"}
+    for f, name, behind, entry, deferred, merged, per_stack, n_blocks in cases:
+        assert type(f).__name__ == name
+        assert f.behind == behind and f.behind in (None, "launches", "merge", "rollout"), name
+        if f.behind is not None:
+            bind, run = attn_bind.PAIRS[f.behind]
+            assert callable(bind) and callable(run)
+        assert f.entry == entry and f.entry in cabi.EXPORTS, name
+        assert (f.deferred, f.merged, f.per_stack, f.N_BLOCKS) == (deferred, merged, per_stack, n_blocks), name
+        assert (f.J == 17) == (name == "JointForm") and bool(f.behind) == f.deferred
+        if f.merged:  # (the fields a merged form's second launch is aimed through are fields of its launch args)
+            args = {"i2r_attn_query_maps": cabi.AttnQueryArgs, "i2r_attn_person_maps": cabi.AttnPersonArgs}[f.entry]
+            assert len(f.HALF) == 5 and {n for n in f.HALF if n} <= {n for n, _ in args._fields_}
+
+
 CHILD = """
 import sys
 sys.path[:0] = [%r, %r]

@@ -1,4 +1,4 @@
-"""GPU aid for changes to the HOST side of the attention-map capture (attn_capture.py, Program.bind_capture): for a fixed list of calls
+"""GPU aid for changes to the HOST side of the attention-map capture (attn_capture.py, attn_bind.py, Program.bind_capture): for a fixed list of calls
 it dumps what the device is handed and what comes back, so that two trees can be compared bit for bit.
     python tools/attn_capture_host_ab.py dump out.json      (uses only Engine / model API plus the program's op list: copy the tool alone
                                                              into a checkout of the other tree and run it there too)
@@ -7,7 +7,12 @@ it dumps what the device is handed and what comes back, so that two trees can be
 Per call: the program's op list (kind, lane), every capture launch's args after binding -- non-pointer fields by value, pointer fields
 as (the buffer they point into, byte offset) --, shape and buffer offset of every returned view, a checksum of every returned tensor.
 Calls: w48_pure_en6 and tph_192_p6_b4 (both stacks): full capture of every layer, attention_at in both modes with upsample on and off;
-w48_pure_en6 also person_relations in all three modes at two groupings of one capacity."""
+w48_pure_en6 also person_relations in all three modes at two groupings of one capacity.
+The forms whose launches run behind the program's head or are not among CAPTURE_KINDS (their launches are not in the op list, and their
+per-call records are the host's own business) are compared by what no tree can lay out differently -- op list, program key, whether the
+call built a program, shape and buffer offset of every returned view, sha256 of every returned tensor: attention_at_joints plain,
+under the flip test and flip-merged; attention_at and person_relations flip-merged; rollout_at in both modes; person_rollout with maps
+None and "affect"; main_target_relations in the shared mode the model takes (else the expanded one)."""
 import ctypes as C
 import hashlib
 import json
@@ -30,9 +35,10 @@ def _tensors(obj, path=""):
     elif isinstance(obj, (list, tuple)):
         for i, v in enumerate(obj):
             yield from _tensors(v, "%s.%d" % (path, i))
-    elif hasattr(obj, "relation"):  # models._base.PersonRelations
-        yield from _tensors(obj.relation, path + ".relation")
-        yield from _tensors(obj.maps, path + ".maps")
+    elif hasattr(obj, "relation"):  # models._base.PersonRelations, TargetRelations
+        for field in ("relation", "maps", "members", "group_len", "image_relation"):
+            if hasattr(obj, field):
+                yield from _tensors(getattr(obj, field), "%s.%s" % (path, field))
 
 
 def _plain(key):
@@ -42,7 +48,7 @@ def _plain(key):
     return [_plain(k) for k in key] if isinstance(key, (tuple, list)) else key
 
 
-def _describe(P, result):
+def _describe(P, result, launches=True):
     import torch
     from i2r_amd import cabi
     spans = []  # (first byte, bytes, label) of every buffer a capture launch may point into
@@ -60,8 +66,8 @@ def _describe(P, result):
             elif isinstance(t, C.Array):
                 spans.append((C.addressof(t), C.sizeof(t), "%s host int32[%d]" % (group, len(t))))
     per_call = {n: v["storage_floats"] for n, v in views.items() if n.startswith(".1") and "input" not in n}  # (.0: the model output)
-    launches = []
-    for kind, lane, a in P.ops:
+    records = []
+    for kind, lane, a in P.ops if launches else ():
         if kind not in CAPTURE_KINDS:
             continue
         rec = dict(kind=kind, lane=lane)
@@ -75,16 +81,16 @@ def _describe(P, result):
             if hit and hit[0][0].startswith("result["):  # (the one buffer whose total size may differ between trees: named without it)
                 hit = [("capture buffer", hit[0][1])]
             rec[f] = list(hit[0]) if hit else ("null" if not v else "unknown")
-        launches.append(rec)
+        records.append(rec)
     for v in views.values():
         del v["storage_floats"]
-    return dict(ops=[[k, lane] for k, lane, _ in P.ops], launches=launches, views=views, capture_buffer_floats=sorted(set(per_call.values())))
+    return dict(ops=[[k, lane] for k, lane, _ in P.ops], launches=records, views=views, capture_buffer_floats=sorted(set(per_call.values())))
 
 
 def dump(path):
     import torch
     import i2r_amd  # noqa: F401
-    from i2r_amd import arch, config, models, synth
+    from i2r_amd import arch, caller, config, models, synth
     out = {}
     for name, factory in (("w48_pure_en6", models.interformer_pureMulti), ("tph_192_p6_b4", models.interformer)):
         cfg = config.load_config(name)
@@ -109,12 +115,35 @@ def dump(path):
                     calls.append(("person_relations %s %s" % (maps, list(g)),
                                   lambda maps=maps, xg=xg, mg=mg, lg=lg: net.person_relations(xg.cuda(), mg.cuda(), lg, maps=maps, upsample=True)))
         calls.append(("full again", calls[0][1]))
-        for label, fn in calls:
+        n_bound = len(calls)  # (the calls above: every capture launch is in the op list; the ones below: see the module docstring)
+        pairs = caller.FLIP_PAIRS["crowdpose" if cfg.MODEL.NUM_JOINTS == 14 else "coco"]
+        for label, kw in (("plain", {}), ("flip test", dict(flip_pairs=pairs)), ("flip merged", dict(flip_pairs=pairs, flip_maps="merged"))):
+            calls.append(("attention_at_joints %s" % label, lambda kw=kw: net.attention_at_joints(x, m, length, **kw)))
+        for mode in ("dependency", "affect"):
+            calls.append(("attention_at %s flip merged" % mode, lambda mode=mode: net.attention_at(x, m, length, pts, mode=mode, flip_pairs=pairs, flip_maps="merged")))
+            calls.append(("rollout_at %s" % mode, lambda mode=mode: net.rollout_at(x, m, length, pts, mode=mode)))
+        if name == "w48_pure_en6":
+            for g in groupings:
+                xg, mg, lg = data[tuple(g)]
+                calls.append(("person_relations dependency flip merged %s" % list(g),
+                              lambda xg=xg, mg=mg, lg=lg: net.person_relations(xg.cuda(), mg.cuda(), lg, maps="dependency", upsample=True, flip_pairs=pairs, flip_maps="merged")))
+                for maps in (None, "affect"):
+                    calls.append(("person_rollout %s %s" % (maps, list(g)),
+                                  lambda maps=maps, xg=xg, mg=mg, lg=lg: net.person_rollout(xg.cuda(), mg.cuda(), lg, maps=maps, upsample=True)))
+        try:
+            share = True if eng._groups_shared(256, 192, True) else None
+        except ValueError:
+            share = None
+        boxes = (torch.rand(x.shape[0], 4, generator=torch.Generator().manual_seed(0), dtype=torch.float64) * 200).numpy()
+        calls.append(("main_target_relations affect share=%s" % share,
+                      lambda: net.main_target_relations(x, m, length, boxes, max_patch=2, maps="affect", upsample=True, share_first_stage=share)))
+        for n, (label, fn) in enumerate(calls):
             builds = eng.n_builds
             res = fn()
             torch.cuda.synchronize()
-            rec = _describe(eng.last_programs[0], res)
-            rec["program_key"] = _plain(next(k for k, v in eng.programs.items() if v[0] is eng.last_programs[0]))
+            P = next(P for P in eng.last_programs if P.captures)
+            rec = _describe(P, res, launches=n < n_bound)
+            rec["program_key"] = _plain(next(k for k, v in eng.programs.items() if v[0] is P))
             rec["built"] = eng.n_builds - builds
             out["%s: %s" % (name, label)] = rec
             print(name, label, "launches", len(rec["launches"]), "views", len(rec["views"]), flush=True)

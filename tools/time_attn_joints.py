@@ -62,7 +62,7 @@ def main():
                 samples[k].append(_sample(flows[k], calls))
         eng = net.engine()
         prog = next(v[0] for k, v in eng.programs.items() if "joints" in k and k[k.index("query") + 1] == ("dependency", "affect").index(mode))
-        held = sum(c["x"].n * c["x"].h * c["x"].w * 4 * next(q.qk_cs for _, q in c["ops"]) * len(c["ops"]) for c in prog.captures)
+        held = sum(c.x.n * c.x.h * c.x.w * 4 * next(q.qk_cs for _, q in c.ops) * len(c.ops) for c in prog.captures)
         row = dict(config="1", model="w48_pure_en6", crops=S, length=length, mode=mode, layers=cfg.MODEL.ENCODER_LAYERS, rounds=rounds, calls_per_sample=calls,
                    maps_equal=bool(same), held_qk_bytes=int(held))
         for k, v in samples.items():
