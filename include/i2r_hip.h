@@ -447,6 +447,49 @@ typedef struct i2r_val_combine_args {
 } i2r_val_combine_args;
 I2R_API int i2r_val_combine(const i2r_val_combine_args* a, void* stream);
 
+/* ---- head re-fit: the gradient of the validation loss with respect to final_layer, on frozen features ---------------------------
+ * i2r_head_grad -- JointsMSELoss.forward (lib/core/loss.py:15-41) behind a 1x1 final_layer with bias, differentiated with respect to
+ * that layer's weight and bias, in one pass over the layer's INPUT (additive: I2R_ABI_VERSION unchanged).  No heat map, target map or
+ * gradient map is stored.  Write N = n_crops * h * w_, J = joints:
+ *   o[s,j,p] = sum_c w[j,c] feat[s,p,c] + bias[j]             (the fp32 matrix pipe: an fmaf chain over c that starts at the bias)
+ *   t, tw     what i2r_val_metrics uses in the same form -- tensor: target fp32 [n_crops, joints, h, w_] (NCHW) + target_weight fp32
+ *             [n_crops, joints] (may be null when use_target_weight == 0); analytic: joints_hm, joints_vis, joints_weight, sigma as
+ *             i2r_joint_targets takes them (the adjusted weight, the draw decision at > 0.5, joints_weight after it, the Gaussian's
+ *             argument in fp64).  Both forms or neither: I2R_E_ARG
+ *   sse[j]  = sum_{s,p} (tw o - tw t)^2, the four fp32 operations of a term rounded separately, added up in fp64;
+ *             use_target_weight == 0: (o - t)^2
+ *   loss    = sum_j 0.5 * sse[j] / N / J
+ *   g[s,j,p]= tw[s,j]^2 (o - t); use_target_weight == 0: o - t
+ *   dw[j,c] = (sum_{s,p} g feat[s,p,c]) / (N J);  db[j] = (sum_{s,p} g) / (N J)
+ * Inputs (device): feat fp32 NHWC, [n_crops, h, w_] rows of in_cs floats of which channels [0, cin) are read; w fp32 [joints] rows of
+ * w_cs floats (the nn.Conv2d weight as is when w_cs == cin); bias fp32 [joints].
+ * Results (device, all required): dw fp32 [joints][cin] dense, db fp32 [joints], loss float64 [1], sse float64 [joints].
+ * Two launches.  Tile: one wave owns a run of 16-pixel fragments of ONE crop, runs both products on the fp32 matrix pipe and writes its
+ * partial dw (fp32), db and sse (fp64) to the workspace.  Finish: every output is the fp64 sum of its partials in a fixed order, divided
+ * once by N J in fp64 and rounded once to fp32.  No floating-point atomics: two runs give the same bits, whatever the workspace held.
+ * No fp32 accumulator ever sums more than one crop's pixels: with u = 2^-24 the result is within
+ *   ((cin + 1) u (sum_c |w||f| + |b|) tw^2 + 4 u |g|) per gradient element (+ 2.5e-7 tw^2 for a drawn analytic target), and
+ *   (h w_ + 4) u sum |g||f| / (N J) + u |dw| on top for the sums, of the same expressions evaluated in float64.
+ * ws: workspace of i2r_head_grad_ws_bytes bytes, 8-byte aligned, contents irrelevant before and after.
+ * Limits: 1 <= joints <= 32; cin a multiple of 16 in [16, 128] (the matrix-pipe range of i2r_head), cin <= in_cs, cin <= w_cs; feat
+ * 16-byte aligned, in_cs % 4 == 0; h, w_ >= 1.  A violation returns I2R_E_ARG without a launch.  n_crops == 0 returns I2R_OK, launches
+ * nothing and writes nothing. */
+typedef struct i2r_head_grad_args {
+    const float* feat;
+    const float* w; const float* bias;
+    const float* target; const float* target_weight;                                  /* tensor form */
+    const double* joints_hm; const float* joints_vis; const float* joints_weight;     /* analytic form */
+    void* ws;
+    float* dw; float* db;
+    double* loss; double* sse;
+    double sigma;
+    int32_t n_crops, h, w_, cin, in_cs, w_cs, joints, use_target_weight;
+} i2r_head_grad_args;
+I2R_API int i2r_head_grad(const i2r_head_grad_args* a, void* stream);
+/* *bytes = the workspace size i2r_head_grad needs for this shape (a function of the shape alone; 0 for n_crops == 0).  A shape outside
+ * the limits above, or a null bytes: I2R_E_ARG.  (A status return like every entry of this header; the size comes back through bytes.) */
+I2R_API int i2r_head_grad_ws_bytes(int32_t n_crops, int32_t h, int32_t w_, int32_t cin, int32_t joints, int64_t* bytes);
+
 /* ---- input side (reference lib/dataset/JointsDataset.py:296-333) ------------------------
  * i2r_crop_affine -- cv2.warpAffine(image, trans, IMAGE_SIZE, INTER_LINEAR) + ToTensor + Normalize for the n persons of ONE
  * image: out[p][c][y][x] = (bilinear(img, M_p (x, y, 1)^T) / 255 - mean[c]) * inv_std[c], taps outside the image = 0.

@@ -21,7 +21,15 @@ lib/core/evaluate.py:41-71), from the joint positions alone -- the target heat m
 and of both across the ranks of a data-parallel run: the raw sums of every rank's batch combined into the numbers of the whole batch
 (val_sums_row / val_combine; dist.val_metrics_all is the gather in front of them), and the rows of dist.gather_poses collected over the
 steps of an epoch on the device for one oks_eval at its end (PoseTable).
+
+and of the one training step the project serves, the re-fit of final_layer on frozen features (the criterion + backward of train(),
+function.py:30, restricted to that layer): the loss and its gradient in one fused kernel, the optimizer step in torch:
+
+    hi   = model.head_input(x, pos_mask, length)                                   # the tensor final_layer reads, copied out
+    fit  = HeadFit.from_model(model)                                               # or HeadFit(hi.cin, new_joint_count, cfg=cfg)
+    loss = fit.step(hi.feat, joints_hm=jhm, joints_vis=vis)                        # head_grad + optimizer.step(), no host copy
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -354,6 +362,180 @@ def val_combine(parts, h, w, meter=None):
     with torch.cuda.device(dev):
         cabi.check(cabi.lib().i2r_val_combine(ctypes.byref(a), torch.cuda.current_stream(dev).cuda_stream), "i2r_val_combine")
     return r
+
+
+# ---- head re-fit: final_layer trained on frozen features (the one gradient of the project; DESIGN.md 'i2r_head_grad') -----------------
+HeadGrad = collections.namedtuple("HeadGrad", "loss dw db sse")   # device tensors: float64 [1], fp32 [J, cin], fp32 [J], float64 [J]
+
+
+def _head_inputs(feat, weight, bias):
+    """feat [S, h, w, cs] fp32 NHWC cuda (I2RModule.head_input; any NHWC tensor with cs % 4 == 0), weight [J, cin(, 1, 1)], bias [J]
+    -> (feat, weight [J, cin], bias, S, h, w, cs, J, cin), contiguous on feat's device"""
+    assert feat.is_cuda and feat.dtype == torch.float32 and feat.dim() == 4, "feat: fp32 NHWC [S, h, w, cs] on the device"
+    feat = feat.contiguous()
+    S, h, w, cs = feat.shape
+    wt = weight.detach()
+    J = wt.shape[0]
+    wt = _dev(wt.reshape(J, -1), torch.float32, feat.device, (J, wt.numel() // J))
+    b = _dev(bias.detach(), torch.float32, feat.device, (J,))
+    cin = wt.shape[1]
+    if cin > cs:
+        raise cabi.I2RError("head: the weight has %d input channels, feat only %d" % (cin, cs))
+    return feat, wt, b, S, h, w, cs, J, cin
+
+
+def _pad16(wt, cin):
+    """[J, cin] -> ([J, cin16] with zero columns up to the next multiple of 16, cin16): the matrix-pipe entries take whole 16-channel
+    steps; feat's channels behind cin are the engine's zero padding, which a zero weight leaves out of every sum exactly"""
+    c16 = -(-cin // 16) * 16
+    if c16 == cin:
+        return wt, cin
+    return torch.cat([wt, wt.new_zeros(wt.shape[0], c16 - cin)], 1).contiguous(), c16
+
+
+def head_apply(feat, weight, bias):
+    """final_layer on features: feat [S, h, w, cs] NHWC, weight [J, cin(, 1, 1)], bias [J] -> heat maps [S, J, h, w] (i2r_head, the
+    kernel the forward ends in).  With it a fit loop can run val_metrics on held-out crops without the model."""
+    feat, wt, b, S, h, w, cs, J, cin = _head_inputs(feat, weight, bias)
+    if cin % 4:
+        wt, cin = _pad16(wt, cin)
+        if cin > cs:
+            raise cabi.I2RError("head_apply: cin padded to %d exceeds feat's %d channels" % (cin, cs))
+    out = torch.empty(S, J, h, w, dtype=torch.float32, device=feat.device)
+    if S == 0:
+        return out
+    with torch.cuda.device(feat.device):
+        cabi.check(cabi.lib().i2r_head(feat.data_ptr(), wt.data_ptr(), b.data_ptr(), out.data_ptr(), S, h, w, cin, cs, J,
+                                       torch.cuda.current_stream(feat.device).cuda_stream), "i2r_head")
+    return out
+
+
+def head_grad(feat, weight, bias, target=None, target_weight=None, *, joints_hm=None, joints_vis=None, sigma=2, joints_weight=None,
+              use_target_weight=True):
+    """JointsMSELoss of final_layer(feat) and its gradient with respect to final_layer, in one pass over feat (i2r_head_grad), on the
+    current stream without a host synchronisation.  feat [S, h, w, cs] fp32 NHWC (I2RModule.head_input), weight [J, cin(, 1, 1)], bias
+    [J], plus ONE target form as val_metrics takes it.  cin that is no multiple of 16 (DIM_MODEL 78) runs at the next one: feat must hold
+    that many channels, zeros behind cin (head_input's padding is that).  -> HeadGrad(loss [1] f64, dw [J, cin], db [J], sse [J] f64)."""
+    if (target is None) == (joints_hm is None):
+        raise cabi.I2RError("head_grad: give either target (+ target_weight) or joints_hm (+ joints_vis)")
+    feat, wt, b, S, h, w, cs, J, cin_true = _head_inputs(feat, weight, bias)
+    wt, cin = _pad16(wt, cin_true)
+    dev = feat.device
+    f64 = torch.zeros(1 + J, dtype=torch.float64, device=dev)                 # (a batch without crops launches nothing: all 0)
+    dw = torch.zeros(J, cin, dtype=torch.float32, device=dev)
+    db = torch.zeros(J, dtype=torch.float32, device=dev)
+    r = HeadGrad(f64[:1], dw[:, :cin_true], db, f64[1:])
+    nbytes = ctypes.c_int64(0)
+    cabi.check(cabi.lib().i2r_head_grad_ws_bytes(S, h, w, cin, J, ctypes.byref(nbytes)), "i2r_head_grad_ws_bytes")
+    ws = torch.empty((nbytes.value + 7) // 8, dtype=torch.float64, device=dev)
+    a = cabi.HeadGradArgs(feat=feat.data_ptr(), w=wt.data_ptr(), bias=b.data_ptr(), ws=ws.data_ptr(), dw=dw.data_ptr(), db=db.data_ptr(),
+                          loss=r.loss.data_ptr(), sse=r.sse.data_ptr(), sigma=float(sigma), n_crops=S, h=h, w_=w, cin=cin, in_cs=cs, w_cs=cin,
+                          joints=J, use_target_weight=int(bool(use_target_weight)))
+    if target is not None:
+        assert target.is_cuda and target.dtype == torch.float32 and tuple(target.shape) == (S, J, h, w), tuple(target.shape)
+        keep = [target.contiguous()]
+        a.target = keep[0].data_ptr()
+        if target_weight is not None:
+            keep.append(_dev(torch.as_tensor(target_weight).reshape(S, J), torch.float32, dev, (S, J)))
+            a.target_weight = keep[1].data_ptr()
+        elif use_target_weight:
+            raise cabi.I2RError("head_grad: use_target_weight without target_weight")
+    else:
+        keep = _joint_inputs(joints_hm, joints_vis, joints_weight, dev)
+        assert tuple(keep[0].shape) == (S, J, 2), (tuple(keep[0].shape), (S, J))
+        a.joints_hm, a.joints_vis = keep[0].data_ptr(), keep[1].data_ptr()
+        a.joints_weight = keep[2].data_ptr() if keep[2] is not None else None
+    if S == 0:
+        return r
+    with torch.cuda.device(dev):
+        cabi.check(cabi.lib().i2r_head_grad(ctypes.byref(a), torch.cuda.current_stream(dev).cuda_stream), "i2r_head_grad")
+    return r
+
+
+class HeadFit:
+    """final_layer re-trained on frozen features: the usual way onto another joint set or domain (a 17-joint COCO checkpoint on the 14
+    CrowdPose joints).  weight [J, cin, 1, 1] and bias [J] are nn.Parameters on the device; step() fills their .grad from head_grad and
+    lets the optimizer move them -- the update of ~1.6 k numbers is plumbing and stays in torch.  optimizer: a torch.optim optimizer over
+    (weight, bias), or a callable params -> optimizer; default what the reference's get_optimizer builds from cfg.TRAIN (Adam at
+    TRAIN.LR; TRAIN.OPTIMIZER 'sgd': SGD with TRAIN.MOMENTUM, WD, NESTEROV), Adam at 1e-4 without a cfg.
+
+        hi  = net.head_input(x, pos_mask, length)                        # frozen features, once per batch (or cached for the run)
+        fit = HeadFit.from_model(net)                                    # or HeadFit(hi.cin, 14) for a new joint set
+        loss = fit.step(hi.feat, joints_hm=jhm, joints_vis=vis)          # one train() iteration; no copy to the host
+        fit.commit(net)                                                  # same joint count: the model now predicts with the new head"""
+
+    def __init__(self, cin, joints, weight=None, bias=None, optimizer=None, cfg=None, device=None):
+        dev = torch.device(device) if device is not None else (weight.device if weight is not None and weight.is_cuda
+                                                               else torch.device("cuda", torch.cuda.current_device()))
+        self.cin, self.joints, self.cfg = int(cin), int(joints), cfg
+        if weight is None:  # nn.Conv2d's own initialisation of a 1x1 layer: kaiming_uniform(a = sqrt 5) = U(-1 / sqrt(cin), 1 / sqrt(cin)) for both
+            bound = 1.0 / np.sqrt(self.cin)
+            weight = (torch.rand(self.joints, self.cin, 1, 1) * 2 - 1) * bound
+            bias = (torch.rand(self.joints) * 2 - 1) * bound if bias is None else bias
+        elif bias is None:
+            bias = torch.zeros(self.joints)
+        self.weight = torch.nn.Parameter(weight.detach().to(dev, torch.float32).reshape(self.joints, self.cin, 1, 1).clone())
+        self.bias = torch.nn.Parameter(bias.detach().to(dev, torch.float32).reshape(self.joints).clone())
+        params = [self.weight, self.bias]
+        if optimizer is None:
+            T = cfg.TRAIN if cfg is not None else None
+            if T is not None and T.OPTIMIZER == "sgd":
+                optimizer = torch.optim.SGD(params, lr=T.LR, momentum=T.MOMENTUM, weight_decay=T.WD, nesterov=T.NESTEROV)
+            elif T is None or T.OPTIMIZER == "adam":
+                optimizer = torch.optim.Adam(params, lr=T.LR if T is not None else 1e-4)
+            else:
+                raise ValueError("HeadFit: TRAIN.OPTIMIZER %r ('adam' or 'sgd'); pass optimizer=" % (T.OPTIMIZER,))
+        elif not isinstance(optimizer, torch.optim.Optimizer):
+            optimizer = optimizer(params)
+        self.optimizer = optimizer
+
+    @classmethod
+    def from_model(cls, net, optimizer=None):
+        """start from the model's own final_layer (its config gives the default optimizer)"""
+        t = net._tensors()
+        w, b = t["final_layer.weight"], t["final_layer.bias"]
+        if w.shape[2:] != (1, 1):
+            raise ValueError("HeadFit: final_layer is %d x %d; the head re-fit is for a 1x1 layer" % tuple(w.shape[2:]))
+        return cls(w.shape[1], w.shape[0], w, b, optimizer=optimizer, cfg=net.cfg, device=w.device)
+
+    def grad(self, feat, target=None, target_weight=None, **kw):
+        """head_grad at the current parameters; with a cfg, sigma / use_target_weight / the dataset's joints_weight table default to what
+        val_metrics_cfg reads from it"""
+        cfg = self.cfg
+        if cfg is not None:
+            kw.setdefault("sigma", cfg.MODEL.SIGMA)
+            kw.setdefault("use_target_weight", cfg.LOSS.USE_TARGET_WEIGHT)
+            if target is None and cfg.LOSS.USE_DIFFERENT_JOINTS_WEIGHT and "joints_weight" not in kw and \
+                    len(JOINTS_WEIGHT.get(cfg.DATASET.DATASET, ())) == self.joints:
+                kw["joints_weight"] = JOINTS_WEIGHT[cfg.DATASET.DATASET]
+        return head_grad(feat, self.weight, self.bias, target, target_weight, **kw)
+
+    def step(self, feat, target=None, target_weight=None, **kw):
+        """one iteration of train(): the gradient into .grad, optimizer.step() -> the loss BEFORE the update (float64 [1], device)"""
+        g = self.grad(feat, target, target_weight, **kw)
+        self.weight.grad = g.dw.reshape(self.weight.shape).contiguous()
+        self.bias.grad = g.db
+        self.optimizer.step()
+        return g.loss
+
+    def state(self):
+        return {"final_layer.weight": self.weight.detach().clone(), "final_layer.bias": self.bias.detach().clone()}
+
+    def commit(self, net):
+        """write the head into the model's parameters and drop its packed engines (rebuilt at the next forward).  ValueError when the
+        joint count differs from cfg.MODEL.NUM_JOINTS: build a net with the new NUM_JOINTS and load the old state dict with state() laid
+        over it."""
+        if self.joints != net.cfg.MODEL.NUM_JOINTS:
+            raise ValueError("HeadFit.commit: %d joints, the model has NUM_JOINTS %d -- build a model with NUM_JOINTS %d and load "
+                             "dict(old_state, **fit.state())" % (self.joints, net.cfg.MODEL.NUM_JOINTS, self.joints))
+        t = net._tensors()
+        w, b = t["final_layer.weight"], t["final_layer.bias"]
+        if tuple(w.shape) != tuple(self.weight.shape):
+            raise ValueError("HeadFit.commit: weight %s, the model's final_layer is %s" % (tuple(self.weight.shape), tuple(w.shape)))
+        with torch.no_grad():
+            w.copy_(self.weight.detach())
+            b.copy_(self.bias.detach())
+        net._invalidate()
 
 
 # ---- keypoint OKS evaluation: COCOeval(gt, dt, 'keypoints') and the per-person-count table of lib/utils/KeypointEvaluator.py, on the device

@@ -8,6 +8,7 @@
 // floating-point atomics: two runs give the same bits) and applies calc_dists / dist_acc / the two AverageMeter updates.
 // Latency kernels: config 3's batch is 798 maps of 12 KB, a few microseconds of HBM time.
 #include "i2r_common.h"
+#include "i2r_targets.h"  // joint_weight, gauss: the target of a (crop, joint) map, shared with i2r_head_fit.hip
 
 // Every product and difference below is a rounding of its own (torch's four fp32 operations per loss term, numpy's float64 steps of the
 // Gaussian's argument and of calc_dists).  HIP device code contracts a * b - c to an FMA by default.  __fmul_rn / __fsub_rn do not stop
@@ -21,23 +22,6 @@ namespace {
 constexpr int MET_NT = 256;   // 4 waves per map
 constexpr int FIN_NT = 1024;  // 16 waves: wave k finishes joints k, k + 16, ...
 constexpr int CMB_NT = 256;   // i2r_val_combine: thread k totals joints k, k + 256, ...
-
-// adjust_target_weight (JointsDataset.py:438-450) + the draw decision of generate_target (:418, :429) + joints_weight (:432-433).
-// int() truncates toward zero; the comparisons are made on the truncated doubles, so a far-away mu cannot overflow an int.
-__device__ inline float joint_weight(double mx, double my, float vis, const float* jw, int j, double sigma, int h, int w, bool* draw) {
-    const double tmp = sigma * 3.0;
-    float tw = vis;
-    if (trunc(mx - tmp) >= (double)w || trunc(my - tmp) >= (double)h || trunc(mx + tmp + 1.0) < 0.0 || trunc(my + tmp + 1.0) < 0.0) tw = 0.f;
-    *draw = tw > 0.5f;  // (a weight in (0, 0.5] leaves the map zero but still reaches the loss)
-    return jw ? tw * jw[j] : tw;
-}
-
-// np.exp(-((x - mu_x) ** 2 + (y - mu_y) ** 2) / (2 * sigma ** 2)) of float32 pixel coordinates and a float64 mu: the argument in fp64
-// as the reference has it, rounded to fp32, one expf (the reference rounds a float64 exp once: within 4 fp32 ulp of it)
-__device__ inline float gauss(int x, int y, double mx, double my, double two_s2) {
-    const double dx = (double)x - mx, dy = (double)y - my;
-    return expf((float)(-(dx * dx + dy * dy) / two_s2));
-}
 
 // np.argmax order: a NaN beats every number, then the larger value, then the lower flat index
 __device__ inline bool beats(float v, int i, float bv, int bi) {

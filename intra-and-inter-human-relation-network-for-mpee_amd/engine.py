@@ -2066,8 +2066,34 @@ class Engine:
             P.release(e, t)
             e = u
         patch["multi"] = P.head(e, self.head)
+        patch["head_in"] = e  # (never released: the arena cannot hand it to another op, forward_head_input reads it behind the run)
         P.finalize()
         return P, patch
+
+    def forward_head_input(self, x, pos_mask, length):
+        """forward() plus the tensor final_layer read: -> (heatmaps [S, J, h, w], feat [S, h, w, cs]) -- feat the fp32 NHWC input of
+        P.head (channel padding kept: the model's head has the true channel count), copied out of the arena because the next forward
+        overwrites it.  One program (no part-batches), the default program of that capacity; its heat maps are forward()'s whenever
+        forward() runs one program too.  What a head re-fit trains on (caller.HeadFit).  ValueError: a class whose forward does not end
+        in the inter-human tail, the window-type block (its program belongs to one `length`), FINAL_CONV_KERNEL 3 (the head's input is
+        then a 3x3 conv's, not a per-pixel product)."""
+        if self.name not in ("interformer_pureMulti", "interformer", "interformer_2stage"):
+            raise ValueError("forward_head_input serves the inter-human models (MODEL.NAME %r has no such tail)" % self.name)
+        if self.window_attn:
+            raise ValueError("forward_head_input: not with ATTENTION_TYPE %r" % self.cfg["MODEL"]["ATTENTION_TYPE"])
+        if self.head.get("conv3") is not None:
+            raise ValueError("forward_head_input: FINAL_CONV_KERNEL 3 -- the head re-fit is for a 1x1 final_layer")
+        assert x.dim() == 4 and x.shape[1] == 3 and x.dtype == torch.float32
+        S, _, H, W = x.shape
+        assert S == sum(length), "sum(length)=%d != number of crops %d" % (sum(length), S)
+        assert all(n >= 1 for n in length), "every image needs at least one person"
+        with torch.cuda.device(self.device):
+            y = self._forward_part(x, pos_mask, list(length), None, S, H, W, max(length))
+            P = self.last_programs[0]
+            patch = next(v[1] for v in self.programs.values() if v[0] is P)
+            e = patch["head_in"]
+            assert e.dt == 0
+            return _multi(y), e.view()[:S].clone()
 
     def forward_backbone(self, x):
         """hrnet.HRNet.forward (hrnet.py:419-446): x [S,3,H,W] -> reduce(lowest branch) as an NCHW tensor [S, d, H/16, W/16]."""

@@ -3,6 +3,7 @@ whose forward() runs the HIP engine.  The module owns the parameters (load_state
 work as for the reference, tools/test.py:87-118); packed device copies (one Engine per device, shared with DataParallel
 replicas) are rebuilt lazily after any change.  After an in-place weight edit that bypasses load_state_dict / .to(),
 call _invalidate()."""
+import collections
 import math
 
 import torch
@@ -78,6 +79,9 @@ class TargetRelations:
 
     def __init__(self, members, group_len, relation, image_relation, maps):
         self.members, self.group_len, self.relation, self.image_relation, self.maps = members, group_len, relation, image_relation, maps
+
+
+HeadInput = collections.namedtuple("HeadInput", "feat heatmaps cin")  # what I2RModule.head_input returns
 
 
 def _call_forward_hooks(module, output):
@@ -580,6 +584,18 @@ class I2RModule(nn.Module):
         with torch.no_grad():
             out, (rel, views) = eng.forward(x, pos_mask, length, capture=capture, rollout=Rollout(None, maps, alpha, max(int(upsample), 1)))
         return out, PersonRelations(rel, views)
+
+    def head_input(self, x, pos_mask, length):
+        """The forward, and with it the tensor final_layer reads: what a head re-fit on frozen features trains on (caller.HeadFit,
+        caller.head_grad).  -> HeadInput(feat, heatmaps, cin): feat [S, h, w, cs] fp32 NHWC, a fresh tensor (channels cin .. cs - 1 are
+        the engine's zero padding), heatmaps [S, J, h, w] = forward's 'multi', cin = final_layer's true input channel count.
+        Served in every precision mode (the head's input is fp32 in all of them).  ValueError: FINAL_CONV_KERNEL 3, ATTENTION_TYPE
+        window, a model class without the inter-human tail.  Forward hooks are not served by this call."""
+        if torch.is_tensor(length):
+            length = length.tolist()
+        with torch.no_grad():
+            hm, feat = self.engine().forward_head_input(x, pos_mask, [int(n) for n in length])
+        return HeadInput(feat, hm, int(self._tensors()["final_layer.weight"].shape[1]))
 
     def forward(self, x, pos_mask, length):
         """model(input, pos_mask, length) -- reference lib/core/function.py:135.  With forward hooks on <stack>.layers[i].self_attn the
