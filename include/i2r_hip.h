@@ -537,6 +537,31 @@ typedef struct {
 I2R_API int i2r_person_inputs_cv2(const i2r_image_ref* images, int32_t n_images, const i2r_crop_ref* crops, int32_t n_crops, int32_t swap_rb,
                           const float* mean, const float* inv_std, float* x_out, float* mask_out, int32_t oh, int32_t ow, void* stream);
 
+/* i2r_train_inputs_cv2 -- the TRAINING samples of a batch in one launch (additive: I2R_ABI_VERSION unchanged): what
+ * JointsDataset.__getitem__ with is_train builds per person (lib/dataset/JointsDataset.py:233-334) -- the crop of the image, mirrored
+ * where the draw flips it, under a map with rotation, rescaling and possibly the half-body box; and the person's box mask after
+ * rotate_bound(mask, r) and cv2.resize -- written into the collated x_out [n_crops, 3, oh, ow] / mask_out [n_crops, 1, oh, ow] in
+ * cv2's fixed-point arithmetic, as i2r_person_inputs_cv2 does for validation (same image table, same rules for mean / inv_std, same
+ * parity note: restated from OpenCV's published algorithm, no cv2 output could be compared).
+ *   crop   cv2.warpAffine(image[:, ::-1] if flip else image, trans, (ow, oh)): tap column xi of the mirrored image reads source column
+ *          iw - 1 - xi, the border test is on xi; no second image is built.
+ *   mask   the nW x nH canvas of rotate_bound is never built: an output pixel takes the 2 x 2 taps of cv2.resize from (nW, nH) to
+ *          (ow, oh), each the fixed-point warpAffine (mask_inv_m) of the binary rectangle `box`, clipped to the image and mirrored with it.
+ * A crop whose `image` index lies outside [0, n_images), whose image entry is empty (null pointer, ih / iw <= 0) or whose canvas is empty
+ * (nw / nh <= 0) gets ZEROS in x_out / mask_out (the call still returns I2R_OK); `reserved` is ignored.  I2R_E_ARG without a launch: a
+ * null pointer, n_images / n_crops / oh / ow <= 0, more than 2^31 - 1 workgroups of 256 output pixels. */
+typedef struct {
+    double inv_m[6];               /* the INVERSE of get_affine_transform(center, scale, rot, size) in double, as cv2.warpAffine derives it */
+    double mask_inv_m[6];          /* the same inverse of rotate_bound's map: getRotationMatrix2D((iw / 2, ih / 2), rot, 1) + (nw / 2 - iw / 2, nh / 2 - ih / 2) */
+    int32_t box[4];                /* (int(x), int(y), int(x + w), int(y + h)) of the UNFLIPPED image, clipped to it or not: the kernel clips */
+    int32_t nw, nh;                /* rotate_bound's canvas: int(ih |sin| + iw |cos|), int(ih |cos| + iw |sin|) */
+    int32_t image;                 /* index into the image table */
+    int32_t flip;                  /* != 0: the sample is taken from the horizontally mirrored image */
+    int32_t reserved[4];
+} i2r_train_crop_ref;              /* 144 bytes */
+I2R_API int i2r_train_inputs_cv2(const i2r_image_ref* images, int32_t n_images, const i2r_train_crop_ref* crops, int32_t n_crops, int32_t swap_rb,
+                         const float* mean, const float* inv_std, float* x_out, float* mask_out, int32_t oh, int32_t ow, void* stream);
+
 /* ---- HRFormer-B glue (reference lib/models/hrformer.py) ---------------------------------------------------- */
 /* i2r_layernorm -- nn.LayerNorm(c, eps) over the channels of every pixel/token of an NHWC tensor
  * (GeneralTransformerBlock.norm1/norm2, hrformer.py:1198,1235-1237). w, b: [cs] zero-padded. */

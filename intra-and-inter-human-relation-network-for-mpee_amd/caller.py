@@ -195,7 +195,8 @@ JOINTS_WEIGHT = {
 def heatmap_joints(joints, center, scale, heatmap_size):
     """Image-space joints -> heat-map coordinates, the reference's joints_heatmap (JointsDataset.py:295-320 at rot 0): host, float64.
     joints [S, J, 2 or 3] (x, y first), center / scale [S, 2], heatmap_size (w, h) -> float64 numpy [S, J, 2].  cv2-unpinned like the
-    rest of the input side: the transform is input.affine_transforms, not cv2.getAffineTransform."""
+    rest of the input side: the transform is input.affine_transforms, not cv2.getAffineTransform.  The validation half only; training
+    samples (rotation, rescaling, flip, half-body box) get their joints_hm from input.train_inputs_batch."""
     from . import input as i2r_input
     j = np.asarray(joints, dtype=np.float64)
     S = j.shape[0]

@@ -8,8 +8,13 @@ The affine matrices are built on the host in float64 exactly as lib/utils/transf
 3-point solve); interpolation runs in csrc/i2r_input.hip -- by default in cv2's own fixed-point arithmetic (restated from OpenCV's
 published algorithm: 1/32-pixel coordinates, 15-bit weights, 8-bit results, the half-pixel shift rotate_bound applies to masks of
 odd-sized images), optionally in plain fp32.  cv2 itself is absent here, so this step is NOT pinned against a cv2 output; its
-geometry is pinned to float64 models of the crop and the mask (tests/_input_cases.py)."""
+geometry is pinned to float64 models of the crop and the mask (tests/_input_cases.py).
+
+The TRAINING half of __getitem__ (JointsDataset.py:233-334: random rotation and scale, flip with left / right swap, half-body crop, the
+rotated pos_mask) is here too: draw_augmentation and train_geometry restate the host arithmetic in the reference's order and number
+formats, train_inputs_batch builds the batch on the device (i2r_train_inputs_cv2) with the joints in heat-map coordinates beside it."""
 import ctypes as C
+import random
 
 import numpy as np
 import torch
@@ -123,10 +128,10 @@ def person_inputs(image, centers, scales, boxes, image_size, color_rgb=False, me
     return x, m
 
 
-def affine_transforms(centers, scales, output_size):
-    """get_affine_transform(center_i, scale_i, 0, output_size) for a whole batch of crops at once -> [S, 2, 3] float64.  Same
+def affine_transforms(centers, scales, output_size, rot=0):
+    """get_affine_transform(center_i, scale_i, rot_i, output_size) for a whole batch of crops at once -> [S, 2, 3] float64.  Same
     arithmetic as the scalar function (three float32-rounded point pairs, one 3x3 solve each -- numpy solves the stack with the same
-    LAPACK routine per matrix), so the results are bit-identical to it (tests/test_host.py)."""
+    LAPACK routine per matrix), so the results are bit-identical to it (tests/test_host.py).  rot: degrees, one value or one per crop."""
     c = np.asarray(centers, dtype=np.float64).reshape(-1, 2)
     sc = np.asarray(scales, dtype=np.float64).reshape(-1, 2) * 200.0
     S = c.shape[0]
@@ -134,8 +139,16 @@ def affine_transforms(centers, scales, output_size):
     src = np.zeros((S, 3, 2), dtype=np.float32)
     dst = np.zeros((S, 3, 2), dtype=np.float32)
     src[:, 0] = c                                            # (+ scale_tmp * shift with shift = 0)
-    src[:, 1, 0] = c[:, 0] + 0.0
-    src[:, 1, 1] = c[:, 1] + (sc[:, 0] - 1) * -0.5           # src_dir = (0, (src_w - 1) * -0.5) at rot = 0
+    rot = np.asarray(rot, dtype=np.float64)
+    if rot.ndim == 0 and rot == 0:
+        src[:, 1, 0] = c[:, 0] + 0.0
+        src[:, 1, 1] = c[:, 1] + (sc[:, 0] - 1) * -0.5       # src_dir = (0, (src_w - 1) * -0.5) at rot = 0
+    else:
+        rot_rad = np.pi * np.broadcast_to(rot, (S,)) / 180.0
+        sn, cs = np.sin(rot_rad), np.cos(rot_rad)
+        p0, p1 = np.zeros(S), (sc[:, 0] - 1) * -0.5
+        src[:, 1, 0] = c[:, 0] + (p0 * cs - p1 * sn)
+        src[:, 1, 1] = c[:, 1] + (p0 * sn + p1 * cs)
     dst[:, 0] = [(dst_w - 1) * 0.5, (dst_h - 1) * 0.5]
     dst[:, 1] = np.array([(dst_w - 1) * 0.5, (dst_h - 1) * 0.5]) + np.array([0.0, (dst_w - 1) * -0.5])
 
@@ -211,6 +224,277 @@ def person_inputs_batch(images, centers, scales, boxes, image_size, color_rgb=Fa
     center_dev = tab[off_c:off_s].view(torch.float32).view(S, 2)
     scale_dev = tab[off_s:].view(torch.float32).view(S, 2)
     return x, m, length, center_dev, scale_dev
+
+
+# ---- the TRAINING half of JointsDataset.__getitem__ (lib/dataset/JointsDataset.py:233-334 with is_train): host geometry in numpy ----
+# upper_body_ids of the dataset classes (coco.py:103, crowdpose.py:101, ochuman.py:98), keyed like caller.FLIP_PAIRS
+UPPER_BODY_IDS = {
+    "coco": (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10),
+    "crowdpose": (0, 1, 2, 3, 4, 5, 12, 13),
+    "ochuman": (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10),
+}
+# which way half_body_transform went for a person (TrainGeometry.half_body)
+HALF_BODY_OFF, HALF_BODY_INELIGIBLE, HALF_BODY_NONE, HALF_BODY_UPPER, HALF_BODY_LOWER = 0, 1, 2, 3, 4
+
+
+def draw_augmentation(scale_factor, rot_factor, flip, prob_half_body, np_random=np.random, py_random=random):
+    """The random draw __getitem__ makes once per IMAGE (JointsDataset.py:237-247; all persons of the image share it)
+    -> (rot, sf_ratio, half_flag, flip_flag).  The generators are consumed in the reference's order: py_random.random() <= 0.6 decides
+    whether there is a rotation at all and is evaluated FIRST; np_random.randn() for the rotation is consumed only then (clipped to
+    [-2 rf, 2 rf]; otherwise rot is the integer 0); randn() for the scale (clipped to [1 - sf, 1 + sf]); rand() < prob_half_body;
+    py_random.random() <= 0.5 for the flip only where `flip` is set.  np_random: the numpy.random module or a RandomState; py_random:
+    the random module or a random.Random."""
+    rf = rot_factor
+    rot = np.clip(np_random.randn() * rf, -rf * 2, rf * 2) if py_random.random() <= 0.6 else 0
+    sf = scale_factor
+    sf_ratio = np.clip(np_random.randn() * sf + 1, 1 - sf, 1 + sf)
+    half_flag = bool(np_random.rand() < prob_half_body)
+    flip_flag = bool(flip and py_random.random() <= 0.5)
+    return rot, sf_ratio, half_flag, flip_flag
+
+
+def fliplr_joints(joints, joints_vis, width, flip_pairs):
+    """lib/utils/transforms.py:33-47 on copies: x = width - x - 1, the pairs of joints and of visibilities swapped, and the joints
+    MULTIPLIED by the visibilities (an invisible joint ends at (0, 0, 0)) -> (joints, joints_vis)"""
+    j, v = np.array(joints, dtype=np.float64), np.array(joints_vis, dtype=np.float64)
+    j[:, 0] = width - j[:, 0] - 1
+    for a, b in flip_pairs:
+        j[[a, b]] = j[[b, a]]
+        v[[a, b]] = v[[b, a]]
+    return j * v, v
+
+
+def half_body_transform(joints, joints_vis, upper_body_ids, aspect_ratio, np_random=np.random, pixel_std=200):
+    """JointsDataset.half_body_transform (:71-114) -> (center, scale, branch): float32 centre and scale of the visible upper or lower
+    joints, or (None, None, HALF_BODY_NONE) when fewer than two joints are selected.  Quirks kept: the coin is np_random.randn() < 0.5
+    (sic: a normal draw, so the upper body is tried 69 % of the time), drawn on every call; the upper body needs MORE than two visible
+    joints, else the lower body where it has more than two, else the upper one after all; mean / min / max run in float32; the box is
+    widened to the aspect ratio and enlarged by 1.5."""
+    upper, lower = [], []
+    for j in range(len(joints)):
+        if joints_vis[j][0] > 0:
+            (upper if j in upper_body_ids else lower).append(joints[j])
+    if np_random.randn() < 0.5 and len(upper) > 2:
+        sel, branch = upper, HALF_BODY_UPPER
+    elif len(lower) > 2:
+        sel, branch = lower, HALF_BODY_LOWER
+    else:
+        sel, branch = upper, HALF_BODY_UPPER
+    if len(sel) < 2:
+        return None, None, HALF_BODY_NONE
+    sel = np.array(sel, dtype=np.float32)
+    center = sel.mean(axis=0)[:2]
+    lt, rb = np.amin(sel, axis=0), np.amax(sel, axis=0)
+    one, ar = np.float32(1), np.float32(aspect_ratio)
+    w, h = rb[0] - lt[0] + one, rb[1] - lt[1] + one
+    if w > ar * h:
+        h = w / ar
+    elif w < ar * h:
+        w = h * ar
+    scale = np.array([w / np.float32(pixel_std), h / np.float32(pixel_std)], dtype=np.float32) * np.float32(1.5)
+    return center, scale, branch
+
+
+def train_affine_transform(center, scale, rot, output_size):
+    """get_affine_transform(c, s, r, size) of lib/utils/transforms.py:58-96 with the reference's OWN number formats, which the train
+    branch needs to land on the reference's joints to 1e-9 px: scale * 200 and (src_w - 1) * -0.5 stay in the dtype of `scale` (float32
+    after half_body_transform, float64 after s * sf_ratio), and get_3rd_point subtracts and adds in FLOAT32 (it gets rows of the float32
+    point arrays).  get_affine_transform above does both in float64 and rounds once; the two differ by up to an ulp of a float32 point
+    coordinate, 1e-4 px in the map.  cv2.getAffineTransform is the same 3x3 solve in double as there.  -> 2x3 float64"""
+    scale = np.asarray(scale)
+    dt = scale.dtype.type if scale.dtype in (np.float32, np.float64) else np.float64
+    scale_tmp = scale.astype(dt) * dt(200.0)
+    half = (scale_tmp[0] - dt(1)) * dt(-0.5)
+    dst_w, dst_h = float(output_size[0]), float(output_size[1])
+    rot_rad = np.pi * rot / 180
+    sn, cs = np.float64(np.sin(rot_rad)), np.float64(np.cos(rot_rad))
+    src_dir = np.array([0 * cs - np.float64(half) * sn, 0 * sn + np.float64(half) * cs])
+    src = np.zeros((3, 2), dtype=np.float32)
+    dst = np.zeros((3, 2), dtype=np.float32)
+    c64 = np.asarray(center, dtype=np.float64)
+    src[0] = np.asarray(center)
+    src[1] = c64 + src_dir
+    dst[0] = [(dst_w - 1) * 0.5, (dst_h - 1) * 0.5]
+    dst[1] = [(dst_w - 1) * 0.5, (dst_h - 1) * 0.5 + (dst_w - 1) * -0.5]
+    for pts in (src, dst):
+        d = pts[0] - pts[1]                                          # float32, like get_3rd_point(src[0, :], src[1, :])
+        pts[2] = pts[1] + np.array([-d[1], d[0]], dtype=np.float32)
+    A = np.concatenate([src.astype(np.float64), np.ones((3, 1))], axis=1)
+    return np.linalg.solve(A, dst.astype(np.float64)).T
+
+
+def rotate_bound_geometry(ih, iw, rot):
+    """JointsDataset.rotate_bound (:180-202) without the pixels -> (M, nW, nH): the forward 2x3 map it hands to cv2.warpAffine and the
+    size of the canvas it asks for.  M = cv2.getRotationMatrix2D((iw // 2, ih // 2), rot, 1.0) = [[a, b, (1 - a) cx - b cy],
+    [-b, a, b cx + (1 - a) cy]] with a = cos, b = sin of the angle; nW = int(ih |b| + iw |a|), nH = int(ih |a| + iw |b|) (truncated);
+    then the translation moves by (nW / 2 - cx, nH / 2 - cy) -- half a pixel along every odd dimension already at rot = 0."""
+    cx, cy = iw // 2, ih // 2
+    ang = rot * (np.pi / 180.0)                                          # (imgwarp.cpp: angle *= CV_PI / 180)
+    a, b = float(np.cos(ang)), float(np.sin(ang))
+    M = np.array([[a, b, (1 - a) * cx - b * cy], [-b, a, b * cx + (1 - a) * cy]], dtype=np.float64)
+    cos, sin = np.abs(M[0, 0]), np.abs(M[0, 1])
+    nW, nH = int(ih * sin + iw * cos), int(ih * cos + iw * sin)
+    M[0, 2] += nW / 2 - cx
+    M[1, 2] += nH / 2 - cy
+    return M, nW, nH
+
+
+class TrainGeometry:
+    """train_geometry's result for ONE image of n persons: what __getitem__ returns beside the pixels, and what the pixels need.
+    rotation, sf_ratio, half_flag, flip: the draw; trans / trans_heatmap [n, 2, 3] float64: the forward maps of the crops;
+    center, scale [n, 2] float64 (meta['center'], meta['scale']); joints [n, J, 3] float64 (meta['joints']: x, y in the INPUT crop where
+    visible, the flipped image's coordinates -- (0, 0) after a flip -- where not); joints_hm [n, J, 3] float64 (the joints_heatmap that
+    generate_target gets); joints_vis [n, J, 3] float64; half_body int [n] (HALF_BODY_*); box int32 [n, 4]: the inclusive corners
+    cv2.rectangle fills, in the UNFLIPPED image; mask_trans 2x3, canvas (nW, nH): rotate_bound_geometry; image_shape (ih, iw)."""
+    __slots__ = ("rotation", "sf_ratio", "half_flag", "flip", "trans", "trans_heatmap", "center", "scale", "joints", "joints_hm",
+                 "joints_vis", "half_body", "box", "mask_trans", "canvas", "image_shape")
+
+
+def train_geometry(annos, draw, image_shape, image_size, heatmap_size, flip_pairs, upper_body_ids, num_joints_half_body=8,
+                   np_random=np.random):
+    """The train branch of __getitem__ for one image (JointsDataset.py:269-323), everything but the pixels, in the reference's order
+    and number formats.  annos: the image's db records, each with 'joints_3d', 'joints_3d_vis' [J, 3], 'center', 'scale' (2,) and
+    'box' (x, y, w, h); nothing is modified.  draw: draw_augmentation's tuple.  image_shape = (ih, iw); image_size / heatmap_size =
+    (W, H) / (w, h).  Per person: fliplr_joints and c[0] = iw - c[0] - 1 (in the dtype of the centre) where the image is flipped;
+    s * sf_ratio (the float64 draw promotes a float32 scale to float64, as numpy >= 2 does for the reference's own line);
+    half_body_transform where sum(vis) > num_joints_half_body and the flag is set (its own np_random.randn() is consumed then, a None
+    result keeps c, s); the two maps; the joints moved where vis > 0.  -> TrainGeometry"""
+    rot, sf_ratio, half_flag, flip = draw
+    ih, iw = int(image_shape[0]), int(image_shape[1])
+    aspect = float(image_size[0]) * 1.0 / float(image_size[1])
+    g = TrainGeometry()
+    g.rotation, g.sf_ratio, g.half_flag, g.flip, g.image_shape = rot, sf_ratio, bool(half_flag), bool(flip), (ih, iw)
+    n = len(annos)
+    assert n >= 1
+    tr, trh, cen, scl, jts, jhm, jvs, hb, box = [], [], [], [], [], [], [], [], []
+    for anno in annos:
+        joints = np.array(anno["joints_3d"], dtype=np.float64)
+        vis = np.array(anno["joints_3d_vis"], dtype=np.float64)
+        c, s = np.array(anno["center"]), np.array(anno["scale"])
+        if c.dtype not in (np.float32, np.float64):
+            c = c.astype(np.float64)
+        if flip:
+            joints, vis = fliplr_joints(joints, vis, iw, flip_pairs)
+            c[0] = iw - c[0] - 1
+        s = s.astype(np.float64) * np.float64(sf_ratio)
+        branch = HALF_BODY_OFF
+        if half_flag:
+            branch = HALF_BODY_INELIGIBLE
+            if np.sum(vis[:, 0]) > num_joints_half_body:
+                c_hb, s_hb, branch = half_body_transform(joints, vis, upper_body_ids, aspect, np_random)
+                if c_hb is not None:
+                    c, s = c_hb, s_hb
+        t = train_affine_transform(c, s, rot, image_size)
+        th = train_affine_transform(c, s, rot, heatmap_size)
+        joints_hm = joints.copy()
+        for j in range(joints.shape[0]):
+            if vis[j, 0] > 0.0:
+                pt = np.array([joints[j, 0], joints[j, 1], 1.0])
+                joints[j, 0:2] = np.dot(t, pt)
+                joints_hm[j, 0:2] = np.dot(th, pt)
+        x, y, w, h = [float(v) for v in anno["box"][:4]]
+        tr.append(t), trh.append(th), cen.append(np.asarray(c, np.float64)), scl.append(np.asarray(s, np.float64))
+        jts.append(joints), jhm.append(joints_hm), jvs.append(vis), hb.append(branch)
+        box.append([int(x), int(y), int(x + w), int(y + h)])   # cv2.rectangle's corners: int() truncates (JointsDataset.py:169-170)
+    g.trans, g.trans_heatmap, g.center, g.scale = np.stack(tr), np.stack(trh), np.stack(cen), np.stack(scl)
+    g.joints, g.joints_hm, g.joints_vis = np.stack(jts), np.stack(jhm), np.stack(jvs)
+    g.half_body = np.asarray(hb, dtype=np.int32)
+    g.box = np.clip(np.asarray(box, dtype=np.int64), -2 ** 31, 2 ** 31 - 1).astype(np.int32)
+    g.mask_trans, nW, nH = rotate_bound_geometry(ih, iw, rot)
+    g.canvas = (nW, nH)
+    return g
+
+
+_TRAIN_CROP_DT = np.dtype([("inv_m", "<f8", 6), ("mask_inv_m", "<f8", 6), ("box", "<i4", 4), ("nw", "<i4"), ("nh", "<i4"), ("image", "<i4"),
+                           ("flip", "<i4"), ("reserved", "<i4", 4)])   # i2r_train_crop_ref, 144 bytes
+assert _TRAIN_CROP_DT.itemsize == 144
+
+
+class TrainInputs:
+    """train_inputs_batch's result.  Device tensors: x [S, 3, H, W] and pos_mask [S, 1, H, W] fp32 (the collated input_list /
+    pos_mask_list after ToTensor / Normalize); joints_hm float64 [S, J, 2] and joints_vis fp32 [S, J]: the analytic target form of
+    caller.val_metrics / head_grad / HeadFit.step; joints float64 [S, J, 2] (meta['joints']); center, scale fp32 [S, 2].  Host: length
+    (persons per image), rotation and flip (one per image), geometry (the TrainGeometry of every image)."""
+    __slots__ = ("x", "pos_mask", "length", "joints_hm", "joints_vis", "joints", "center", "scale", "rotation", "flip", "geometry", "_i2r_keep")
+
+
+def train_inputs_batch(images, annos, draws, image_size, heatmap_size, dataset="coco", color_rgb=False, mean=IMAGENET_MEAN, std=IMAGENET_STD,
+                       device="cuda:0", flip_pairs=None, upper_body_ids=None, num_joints_half_body=8, np_random=np.random, geometry=None):
+    """The TRAINING samples of a batch of images on the device: what JointsDataset.__getitem__ with is_train builds per person with
+    cv2 -- crop of the (flipped) image under the rotated, rescaled, possibly half-body map, the box mask after rotate_bound(mask, r) and
+    cv2.resize -- plus the joints for the analytic targets, in ONE launch (i2r_train_inputs_cv2) and ONE pinned, stream-ordered upload.
+    images: uint8 [ih_i, iw_i, 3] tensors on `device` (unflipped: the kernel mirrors); annos: per image the list of db records
+    (train_geometry); draws: per image draw_augmentation's tuple.  dataset keys caller.FLIP_PAIRS / UPPER_BODY_IDS unless flip_pairs /
+    upper_body_ids are given.  The half-body coin of every eligible person is drawn from np_random image after image; to consume the
+    generators exactly as a loop over the reference's __getitem__ would, interleave draw_augmentation and train_geometry per image
+    yourself and hand the results in as geometry= (draws is ignored then).  cv2's fixed-point arithmetic.  -> TrainInputs"""
+    from . import caller
+    dev = torch.device(device)
+    W, H = int(image_size[0]), int(image_size[1])
+    flip_pairs = caller.FLIP_PAIRS[dataset] if flip_pairs is None else flip_pairs
+    upper_body_ids = UPPER_BODY_IDS[dataset] if upper_body_ids is None else upper_body_ids
+    n_img = len(images)
+    for im in images:
+        assert im.is_cuda and im.device == dev and im.dtype == torch.uint8 and im.dim() == 3 and im.shape[2] == 3 and im.is_contiguous()
+    if geometry is None:
+        assert len(annos) == n_img == len(draws)
+        geometry = [train_geometry(annos[i], draws[i], images[i].shape[:2], (W, H), heatmap_size, flip_pairs, upper_body_ids,
+                                   num_joints_half_body, np_random) for i in range(n_img)]
+    assert len(geometry) == n_img and all(tuple(g.image_shape) == tuple(images[i].shape[:2]) for i, g in enumerate(geometry))
+    length = [len(g.trans) for g in geometry]
+    S = sum(length)
+    J = geometry[0].joints.shape[1]
+    assert S >= 1 and all(g.joints.shape[1] == J for g in geometry)
+    # one host buffer: [crop table | image table | joints_hm f64 | joints f64 | joints_vis f32 | centres f32 | scales f32]
+    off_img = S * 144
+    off_hm = off_img + (n_img * 24 + 15) // 16 * 16
+    off_j = off_hm + S * J * 16
+    off_v = off_j + S * J * 16
+    off_c = off_v + (S * J * 4 + 15) // 16 * 16
+    off_s = off_c + S * 8
+    host = torch.empty(off_s + S * 8, dtype=torch.uint8).pin_memory()
+    hb = host.numpy()
+    hb[:] = 0
+    crops = hb[:off_img].view(_TRAIN_CROP_DT)
+    crops["inv_m"] = cv2_inverse_batch(np.concatenate([g.trans for g in geometry]))
+    crops["mask_inv_m"] = np.repeat(np.stack([cv2_inverse(g.mask_trans).reshape(6) for g in geometry]), length, axis=0)
+    boxes = np.concatenate([g.box for g in geometry]).astype(np.int64)
+    iw_p = np.repeat([g.image_shape[1] for g in geometry], length)
+    ih_p = np.repeat([g.image_shape[0] for g in geometry], length)
+    # clipped to the image: cv2.rectangle draws nothing outside it (a box wholly outside ends with x0 > x1 or y0 > y1: nothing is set)
+    crops["box"] = np.stack([np.maximum(boxes[:, 0], 0), np.maximum(boxes[:, 1], 0), np.minimum(boxes[:, 2], iw_p - 1),
+                             np.minimum(boxes[:, 3], ih_p - 1)], 1).astype(np.int32)
+    crops["nw"] = np.repeat([g.canvas[0] for g in geometry], length)
+    crops["nh"] = np.repeat([g.canvas[1] for g in geometry], length)
+    crops["image"] = np.repeat(np.arange(n_img, dtype=np.int32), length)
+    crops["flip"] = np.repeat([int(g.flip) for g in geometry], length)
+    imgs = hb[off_img:off_img + n_img * 24].view(_IMG_DT)
+    for i, im in enumerate(images):
+        imgs[i] = (im.data_ptr(), im.shape[0], im.shape[1], im.shape[1] * 3, 0)
+    hb[off_hm:off_j].view(np.float64)[:] = np.concatenate([g.joints_hm[:, :, :2] for g in geometry]).reshape(-1)
+    hb[off_j:off_j + S * J * 16].view(np.float64)[:] = np.concatenate([g.joints[:, :, :2] for g in geometry]).reshape(-1)
+    hb[off_v:off_v + S * J * 4].view(np.float32)[:] = np.concatenate([g.joints_vis[:, :, 0] for g in geometry]).astype(np.float32).reshape(-1)
+    hb[off_c:off_s].view(np.float32)[:] = np.concatenate([g.center for g in geometry]).astype(np.float32).reshape(-1)
+    hb[off_s:].view(np.float32)[:] = np.concatenate([g.scale for g in geometry]).astype(np.float32).reshape(-1)
+    tab = host.to(dev, non_blocking=True)
+    r = TrainInputs()
+    r.x = torch.empty(S, 3, H, W, dtype=torch.float32, device=dev)
+    r.pos_mask = torch.empty(S, 1, H, W, dtype=torch.float32, device=dev)
+    mean_c = (C.c_float * 3)(*mean)
+    istd_c = (C.c_float * 3)(*[1.0 / v for v in std])
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        cabi.check(cabi.lib().i2r_train_inputs_cv2(tab.data_ptr() + off_img, n_img, tab.data_ptr(), S, int(bool(color_rgb)), mean_c, istd_c,
+                                                   r.x.data_ptr(), r.pos_mask.data_ptr(), H, W, st), "i2r_train_inputs_cv2")
+    r._i2r_keep = r.x._i2r_keep = (tab, list(images), host)  # the tables / frames must outlive the stream-ordered launch that reads them
+    r.length = length
+    r.joints_hm = tab[off_hm:off_j].view(torch.float64).view(S, J, 2)
+    r.joints = tab[off_j:off_j + S * J * 16].view(torch.float64).view(S, J, 2)
+    r.joints_vis = tab[off_v:off_v + S * J * 4].view(torch.float32).view(S, J)
+    r.center = tab[off_c:off_s].view(torch.float32).view(S, 2)
+    r.scale = tab[off_s:].view(torch.float32).view(S, 2)
+    r.rotation, r.flip, r.geometry = [g.rotation for g in geometry], [g.flip for g in geometry], list(geometry)
+    return r
 
 
 def collate(batch):
