@@ -490,6 +490,48 @@ I2R_API int i2r_head_grad(const i2r_head_grad_args* a, void* stream);
  * the limits above, or a null bytes: I2R_E_ARG.  (A status return like every entry of this header; the size comes back through bytes.) */
 I2R_API int i2r_head_grad_ws_bytes(int32_t n_crops, int32_t h, int32_t w_, int32_t cin, int32_t joints, int64_t* bytes);
 
+/* i2r_head_normal -- the same fit in closed form.  With the features frozen JointsMSELoss is a quadratic in (W, b), separately per joint;
+ * this entry collects its normal equations in one pass over the features (additive: I2R_ABI_VERSION unchanged).  Write
+ * f~[s,p,:] = (feat[s,p,0..cin_out-1], 1), and take t and tw exactly as i2r_head_grad takes them (tensor or analytic form,
+ * use_target_weight == 0: tw = 1).  The state is float64, on the device, in/out:
+ *   A[j,a,b] += sum_s tw[s,j]^2 sum_p f~[s,p,a] f~[s,p,b]      [joints][cin_out + 1][cin_out + 1], symmetric, stored whole
+ *   r[j,a]   += sum_s tw[s,j]^2 sum_p f~[s,p,a] t[s,j,p]       [joints][cin_out + 1]
+ *   c[j]     += sum_s sum_p (tw[s,j] t[s,j,p])^2               [joints]   (what i2r_head_grad's sse[j] is at w = 0, bias = 0)
+ *   n        += n_crops * h * w_                               int64 [1]
+ * Over everything accumulated the loss of a head is L(W, b) = (1 / (2 n J)) sum_j (w~_j^T A_j w~_j - 2 w~_j^T r_j + c_j), w~_j =
+ * (W[j,:], b[j]): JointsMSELoss of the concatenation of all batches added; its minimiser solves A_j w~_j = r_j per joint.
+ * Rows of A and r are ld doubles apart (A[j][a][b] at (j * ld + a) * ld + b, r[j][a] at j * ld + a; ld > cin_out); what lies behind
+ * cin_out + 1 in a row, and rows behind it, are not touched.  cin is the channel count the pass runs at (a multiple of 16); cin_out <=
+ * cin is the true one: channels [cin_out, cin) are the caller's zero padding and get no state, the bias entry sits at index cin_out.
+ * Two launches.  Tile: a workgroup of four waves owns a run of 16-pixel fragments of ONE crop, reads the features once, forms the
+ * crop's Gram tiles (16-channel blocks ci <= cj only) on the fp32 matrix pipe, both operands being the read i2r_head_grad's second
+ * product makes, the product (tw tw t)^T F the way i2r_head_grad forms dw, and the column sums F^T 1; it writes fp32 partials (fp64
+ * for the sums that need no feature) to the workspace.  Finish: per crop the partials in ascending order in fp64, then weighted with
+ * tw^2 (exact in fp64) across crops in a fixed order; every state element is updated by exactly one thread as state += sum.  No
+ * floating-point atomics: equal state and inputs give equal bits, whatever the workspace held.  No fp32 accumulator ever sums more than
+ * one crop's pixels: with u = 2^-24, k = h w_, against the same sums in float64
+ *   |A - A*|[j,a,b] <= (k + 2) u sum_s tw^2 sum_p |f~_a||f~_b| + delta
+ *   |r - r*|[j,a]   <= sum_s sum_p (tw^2 e_t + (k + 4) u |tw^2 t|) |f~_a| + delta   (e_t = 2.5e-7 for a drawn analytic target, else 0)
+ *   c as i2r_head_grad's sse at o = 0; n exact; delta = (parts per crop + n_crops + 16) 2^-53 times the sum of absolute values (and
+ *   one more rounding of the state the sum is added to).
+ * ws: workspace of i2r_head_normal_ws_bytes bytes, 8-byte aligned, contents irrelevant before and after.
+ * Limits: those of i2r_head_grad (1 <= joints <= 32; cin a multiple of 16 in [16, 128], cin <= in_cs; feat 16-byte aligned, in_cs % 4
+ * == 0; h, w_ >= 1), 1 <= cin_out <= cin, ld > cin_out, state 8-byte aligned.  A violation returns I2R_E_ARG without a launch.
+ * n_crops == 0 returns I2R_OK, launches nothing and touches nothing. */
+typedef struct i2r_head_normal_args {
+    const float* feat;
+    const float* target; const float* target_weight;                                  /* tensor form */
+    const double* joints_hm; const float* joints_vis; const float* joints_weight;     /* analytic form */
+    void* ws;
+    double* A; double* r; double* c; int64_t* n;
+    double sigma;
+    int32_t n_crops, h, w_, cin, in_cs, cin_out, ld, joints, use_target_weight, reserved;
+} i2r_head_normal_args;
+I2R_API int i2r_head_normal(const i2r_head_normal_args* a, void* stream);
+/* *bytes = the workspace size i2r_head_normal needs for this shape (a function of the shape alone; 0 for n_crops == 0).  A shape outside
+ * the limits above, or a null bytes: I2R_E_ARG. */
+I2R_API int i2r_head_normal_ws_bytes(int32_t n_crops, int32_t h, int32_t w_, int32_t cin, int32_t joints, int64_t* bytes);
+
 /* ---- input side (reference lib/dataset/JointsDataset.py:296-333) ------------------------
  * i2r_crop_affine -- cv2.warpAffine(image, trans, IMAGE_SIZE, INTER_LINEAR) + ToTensor + Normalize for the n persons of ONE
  * image: out[p][c][y][x] = (bilinear(img, M_p (x, y, 1)^T) / 255 - mean[c]) * inv_std[c], taps outside the image = 0.

@@ -277,6 +277,13 @@ class HeadGradArgs(C.Structure):   # i2r_head_grad_args
                 ("use_target_weight", _i32)]
 
 
+class HeadNormalArgs(C.Structure):   # i2r_head_normal_args
+    _fields_ = [("feat", _fp), ("target", _fp), ("target_weight", _fp), ("joints_hm", _fp), ("joints_vis", _fp), ("joints_weight", _fp),
+                ("ws", _fp), ("A", _fp), ("r", _fp), ("c", _fp), ("n", _fp), ("sigma", C.c_double),
+                ("n_crops", _i32), ("h", _i32), ("w_", _i32), ("cin", _i32), ("in_cs", _i32), ("cin_out", _i32), ("ld", _i32), ("joints", _i32),
+                ("use_target_weight", _i32), ("reserved", _i32)]
+
+
 class ImageRef(C.Structure):   # i2r_image_ref (24 bytes)
     _fields_ = [("img", C.c_void_p), ("ih", _i32), ("iw", _i32), ("row_bytes", _i32), ("reserved", _i32)]
 
@@ -296,7 +303,7 @@ class Op(C.Structure):
 
 # every symbol include/i2r_hip.h declares (tests/test_host.py::test_cabi_library_exports_every_declared_symbol checks the built library exports them all)
 EXPORTS = ("i2r_conv", "i2r_conv_grouped", "i2r_conv_kernel_name", "i2r_conv_grid", "i2r_conv_wino_form", "i2r_conv_wino_forms", "i2r_conv_direct_form", "i2r_conv_direct_forms", "i2r_stem_conv", "i2r_pe_res_stem", "i2r_maxpool3x3s2", "i2r_head", "i2r_layernorm", "i2r_window_attn", "i2r_hrt_attn_block", "i2r_hrt_mlp_block", "i2r_dwconv3x3",
-           "i2r_upsample_bilinear_add", "i2r_upsample_bilinear_add_multi", "i2r_fuse_up_add", "i2r_conv1x1_pair", "i2r_conv1x1_lp", "i2r_flip_merge", "i2r_decode", "i2r_joint_tokens", "i2r_pose_nms", "i2r_group_nearest", "i2r_oks_match", "i2r_oks_accumulate", "i2r_joint_targets", "i2r_val_metrics", "i2r_val_combine", "i2r_head_grad", "i2r_head_grad_ws_bytes", "i2r_crop_affine", "i2r_box_mask", "i2r_crop_affine_cv2", "i2r_box_mask_cv2", "i2r_person_inputs_cv2", "i2r_train_inputs_cv2", "i2r_encoder_kv", "i2r_encoder_layer", "i2r_encoder_layer_form", "i2r_mh_attention", "i2r_attn_weights", "i2r_attn_query_maps", "i2r_attn_person_maps", "i2r_attn_target_maps", "i2r_attn_flip_merge", "i2r_attn_rollout_step", "i2r_token_mirror", "i2r_pe_cat_vec", "i2r_rows_gather", "i2r_rows_gather_multi", "i2r_view_scramble",
+           "i2r_upsample_bilinear_add", "i2r_upsample_bilinear_add_multi", "i2r_fuse_up_add", "i2r_conv1x1_pair", "i2r_conv1x1_lp", "i2r_flip_merge", "i2r_decode", "i2r_joint_tokens", "i2r_pose_nms", "i2r_group_nearest", "i2r_oks_match", "i2r_oks_accumulate", "i2r_joint_targets", "i2r_val_metrics", "i2r_val_combine", "i2r_head_grad", "i2r_head_grad_ws_bytes", "i2r_head_normal", "i2r_head_normal_ws_bytes", "i2r_crop_affine", "i2r_box_mask", "i2r_crop_affine_cv2", "i2r_box_mask_cv2", "i2r_person_inputs_cv2", "i2r_train_inputs_cv2", "i2r_encoder_kv", "i2r_encoder_layer", "i2r_encoder_layer_form", "i2r_mh_attention", "i2r_attn_weights", "i2r_attn_query_maps", "i2r_attn_person_maps", "i2r_attn_target_maps", "i2r_attn_flip_merge", "i2r_attn_rollout_step", "i2r_token_mirror", "i2r_pe_cat_vec", "i2r_rows_gather", "i2r_rows_gather_multi", "i2r_view_scramble",
            "i2r_run_program", "i2r_run_program_timed", "i2r_abi_version", "i2r_last_error", "i2r_device_check")
 
 _LIB = None
@@ -335,6 +342,8 @@ def load_library(path=LIB_PATH):
     L.i2r_val_combine.argtypes = [C.POINTER(ValCombineArgs), C.c_void_p]
     L.i2r_head_grad.argtypes = [C.POINTER(HeadGradArgs), C.c_void_p]
     L.i2r_head_grad_ws_bytes.argtypes = [_i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int64)]
+    L.i2r_head_normal.argtypes = [C.POINTER(HeadNormalArgs), C.c_void_p]
+    L.i2r_head_normal_ws_bytes.argtypes = [_i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int64)]
     L.i2r_crop_affine.argtypes = [_fp, _i32, _i32, _i32, _i32, _fp, _fp, _fp, _fp, _i32, _i32, _i32, C.c_void_p]
     L.i2r_box_mask.argtypes = [_fp, _i32, _i32, _fp, _i32, _i32, _i32, C.c_void_p]
     L.i2r_crop_affine_cv2.argtypes = [_fp, _i32, _i32, _i32, _i32, _fp, _fp, _fp, _fp, _i32, _i32, _i32, C.c_void_p]

@@ -28,6 +28,13 @@ function.py:30, restricted to that layer): the loss and its gradient in one fuse
     hi   = model.head_input(x, pos_mask, length)                                   # the tensor final_layer reads, copied out
     fit  = HeadFit.from_model(model)                                               # or HeadFit(hi.cin, new_joint_count, cfg=cfg)
     loss = fit.step(hi.feat, joints_hm=jhm, joints_vis=vis)                        # head_grad + optimizer.step(), no host copy
+
+and of the closed form of that re-fit: the normal equations of the loss in the layer's weight and bias, collected in one pass per batch
+and solved per joint at the end -- the exact minimiser after one epoch:
+
+    acc  = HeadSolve(hi.cin, new_joint_count, cfg=cfg)                             # float64 state on the device
+    acc.add(hi.feat, joints_hm=jhm, joints_vis=vis)                                # i2r_head_normal, once per batch, no host copy
+    fit  = acc.head_fit()                                                          # a HeadFit at the solution: commit(), state(), step()
 """
 import collections
 import ctypes
@@ -537,6 +544,161 @@ class HeadFit:
             w.copy_(self.weight.detach())
             b.copy_(self.bias.detach())
         net._invalidate()
+
+
+# ---- head re-fit in closed form: the normal equations from one pass over the features (DESIGN.md 'i2r_head_normal') -------------------
+# device tensors: A float64 [J, cin + 1, cin + 1], r float64 [J, cin + 1], c float64 [J], n int64 [1]; the bias entry is index cin
+HeadNormal = collections.namedtuple("HeadNormal", "A r c n")
+
+
+def head_normal_state(cin, joints, device):
+    """a zero state for head_normal at that (true) channel count"""
+    m = int(cin) + 1
+    return HeadNormal(torch.zeros(joints, m, m, dtype=torch.float64, device=device), torch.zeros(joints, m, dtype=torch.float64, device=device),
+                      torch.zeros(joints, dtype=torch.float64, device=device), torch.zeros(1, dtype=torch.int64, device=device))
+
+
+def head_normal(feat, target=None, target_weight=None, *, joints_hm=None, joints_vis=None, sigma=2, joints_weight=None, use_target_weight=True,
+                state=None, cin=None):
+    """The normal equations of JointsMSELoss in final_layer's (W, b) on frozen features, accumulated INTO state in one pass over feat
+    (i2r_head_normal), on the current stream without a host synchronisation.  feat [S, h, w, cs] fp32 NHWC (I2RModule.head_input) plus
+    ONE target form as head_grad takes it.  cin: the layer's input channels (default: the state's, else cs); one that is no multiple of
+    16 runs at the next one -- feat must hold that many channels, zeros behind cin (head_input's padding is that).  state: a HeadNormal
+    of dense tensors for that cin (None: a fresh zero state).  -> HeadNormal(A, r, c, n), the state itself."""
+    if (target is None) == (joints_hm is None):
+        raise cabi.I2RError("head_normal: give either target (+ target_weight) or joints_hm (+ joints_vis)")
+    assert feat.is_cuda and feat.dtype == torch.float32 and feat.dim() == 4, "feat: fp32 NHWC [S, h, w, cs] on the device"
+    feat = feat.contiguous()
+    S, h, w, cs = feat.shape
+    dev = feat.device
+    if state is not None:
+        cin = state.r.shape[1] - 1 if cin is None else int(cin)
+    elif cin is None:
+        cin = cs
+    if target is not None:
+        J = target.shape[1]
+    else:
+        J = (joints_hm if isinstance(joints_hm, torch.Tensor) else np.asarray(joints_hm)).shape[1]
+    if state is None:
+        state = head_normal_state(cin, J, dev)
+    m = cin + 1
+    for t, shape, dt in ((state.A, (J, m, m), torch.float64), (state.r, (J, m), torch.float64), (state.c, (J,), torch.float64), (state.n, (1,), torch.int64)):
+        if not (t.is_cuda and t.device == dev and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous()):
+            raise cabi.I2RError("head_normal: state tensor %s %s on %s, wanted dense %s %s on %s" % (tuple(t.shape), t.dtype, t.device, shape, dt, dev))
+    c16 = -(-cin // 16) * 16
+    if c16 > cs:
+        raise cabi.I2RError("head_normal: cin %d runs at %d channels, feat has only %d" % (cin, c16, cs))
+    nbytes = ctypes.c_int64(0)
+    cabi.check(cabi.lib().i2r_head_normal_ws_bytes(S, h, w, c16, J, ctypes.byref(nbytes)), "i2r_head_normal_ws_bytes")
+    ws = torch.empty((nbytes.value + 7) // 8, dtype=torch.float64, device=dev)
+    a = cabi.HeadNormalArgs(feat=feat.data_ptr(), ws=ws.data_ptr(), A=state.A.data_ptr(), r=state.r.data_ptr(), c=state.c.data_ptr(), n=state.n.data_ptr(),
+                            sigma=float(sigma), n_crops=S, h=h, w_=w, cin=c16, in_cs=cs, cin_out=cin, ld=m, joints=J,
+                            use_target_weight=int(bool(use_target_weight)))
+    if target is not None:
+        assert target.is_cuda and target.dtype == torch.float32 and tuple(target.shape) == (S, J, h, w), tuple(target.shape)
+        keep = [target.contiguous()]
+        a.target = keep[0].data_ptr()
+        if target_weight is not None:
+            keep.append(_dev(torch.as_tensor(target_weight).reshape(S, J), torch.float32, dev, (S, J)))
+            a.target_weight = keep[1].data_ptr()
+        elif use_target_weight:
+            raise cabi.I2RError("head_normal: use_target_weight without target_weight")
+    else:
+        keep = _joint_inputs(joints_hm, joints_vis, joints_weight, dev)
+        assert tuple(keep[0].shape) == (S, J, 2), (tuple(keep[0].shape), (S, J))
+        a.joints_hm, a.joints_vis = keep[0].data_ptr(), keep[1].data_ptr()
+        a.joints_weight = keep[2].data_ptr() if keep[2] is not None else None
+    if S == 0:
+        return state
+    with torch.cuda.device(dev):
+        cabi.check(cabi.lib().i2r_head_normal(ctypes.byref(a), torch.cuda.current_stream(dev).cuda_stream), "i2r_head_normal")
+    return state
+
+
+def solve_normal(A, r, n, ridge=0.0, rcond=None):
+    """numpy float64: per joint the minimiser of L + (ridge / 2) ||W||^2, i.e. the solution of (A_j + ridge n J diag(1 .. 1, 0)) w~ = r_j
+    (the bias is not penalised), by a symmetric eigendecomposition; directions with an eigenvalue <= rcond * lmax are dropped, which
+    gives the minimum-norm minimiser there (dead or padded channels; a joint that is never visible gets zeros).  rcond defaults to
+    (cin + 1) 2^-52, numpy's float64 convention.  -> w~ float64 [J, cin + 1]"""
+    A, r = np.asarray(A, np.float64), np.asarray(r, np.float64)
+    J, m, _ = A.shape
+    rcond = m * 2.0 ** -52 if rcond is None else float(rcond)
+    pen = np.ones(m)
+    pen[-1] = 0.0
+    out = np.zeros((J, m))
+    for j in range(J):
+        lam, V = np.linalg.eigh(A[j] + (float(ridge) * float(n) * J) * np.diag(pen))
+        keep = lam > rcond * max(float(lam[-1]), 0.0)
+        Vk = V[:, keep]
+        out[j] = Vk @ ((Vk.T @ r[j]) / lam[keep])
+    return out
+
+
+class HeadSolve:
+    """final_layer re-fitted in closed form: add() every batch of frozen features once (one pass each, i2r_head_normal), solve() for
+    the exact minimiser of JointsMSELoss over everything added.
+
+        acc = HeadSolve(hi.cin, 14, cfg=cfg)
+        for batch in loader:                                             # one epoch; several augmented ones add up the same way
+            hi = net.head_input(x, pos_mask, length)
+            acc.add(hi.feat, joints_hm=jhm, joints_vis=vis)              # no copy to the host
+        fit = acc.head_fit()                                             # a HeadFit at the solution: commit(net), state(), step()"""
+
+    def __init__(self, cin, joints, cfg=None, device=None):
+        self.cin, self.joints, self.cfg = int(cin), int(joints), cfg
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.state = head_normal_state(self.cin, self.joints, self.device)
+
+    def add(self, feat, target=None, target_weight=None, **kw):
+        """accumulate a batch; with a cfg, sigma / use_target_weight / the dataset's joints_weight table default as in HeadFit.grad"""
+        cfg = self.cfg
+        if cfg is not None:
+            kw.setdefault("sigma", cfg.MODEL.SIGMA)
+            kw.setdefault("use_target_weight", cfg.LOSS.USE_TARGET_WEIGHT)
+            if target is None and cfg.LOSS.USE_DIFFERENT_JOINTS_WEIGHT and "joints_weight" not in kw and \
+                    len(JOINTS_WEIGHT.get(cfg.DATASET.DATASET, ())) == self.joints:
+                kw["joints_weight"] = JOINTS_WEIGHT[cfg.DATASET.DATASET]
+        head_normal(feat, target, target_weight, state=self.state, cin=self.cin, **kw)
+        return self
+
+    def merge(self, other):
+        """add another accumulator's state (the state is additive: a data-parallel fit would all-reduce it)"""
+        if (other.cin, other.joints) != (self.cin, self.joints):
+            raise ValueError("HeadSolve.merge: (cin, joints) %s into %s" % ((other.cin, other.joints), (self.cin, self.joints)))
+        for mine, theirs in zip(self.state, other.state):
+            mine += theirs.to(self.device)
+        return self
+
+    def _host(self):
+        """the one copy of the state to the host -> (A, r, c, n) numpy"""
+        m = self.cin + 1
+        flat = torch.cat([self.state.A.reshape(-1), self.state.r.reshape(-1), self.state.c, self.state.n.to(torch.float64)]).cpu().numpy()
+        J = self.joints
+        A, r = flat[:J * m * m].reshape(J, m, m), flat[J * m * m:J * m * m + J * m].reshape(J, m)
+        return A, r, flat[-1 - J:-1], int(flat[-1])
+
+    def loss(self, weight, bias):
+        """L(W, b) over everything added, evaluated in float64 from the state (no feature is read) -> float"""
+        A, r, c, n = self._host()
+        J = self.joints
+        wt = np.concatenate([torch.as_tensor(weight).detach().cpu().numpy().astype(np.float64).reshape(J, self.cin),
+                             torch.as_tensor(bias).detach().cpu().numpy().astype(np.float64).reshape(J, 1)], 1)
+        if n == 0:
+            return 0.0
+        return float((np.einsum("ja,jab,jb->j", wt, A, wt) - 2.0 * (wt * r).sum(1) + c).sum() / (2.0 * n * J))
+
+    def solve(self, ridge=0.0, rcond=None):
+        """-> (weight [J, cin, 1, 1], bias [J]) fp32 on the device: solve_normal on the host (the copy of the state is the only
+        synchronisation of a fit), rounded once to fp32"""
+        A, r, _, n = self._host()
+        wt = solve_normal(A, r, n, ridge, rcond).astype(np.float32)
+        return (torch.from_numpy(np.ascontiguousarray(wt[:, :self.cin])).reshape(self.joints, self.cin, 1, 1).to(self.device),
+                torch.from_numpy(np.ascontiguousarray(wt[:, self.cin])).to(self.device))
+
+    def head_fit(self, ridge=0.0, rcond=None, optimizer=None):
+        """a HeadFit that starts at the solution"""
+        w, b = self.solve(ridge, rcond)
+        return HeadFit(self.cin, self.joints, w, b, optimizer=optimizer, cfg=self.cfg, device=self.device)
 
 
 # ---- keypoint OKS evaluation: COCOeval(gt, dt, 'keypoints') and the per-person-count table of lib/utils/KeypointEvaluator.py, on the device

@@ -344,3 +344,5 @@ extern "C" int i2r_head_grad(const i2r_head_grad_args* a, void* stream) {
     I2R_CHECK_LAUNCH("i2r_head_grad (finish)");
     return I2R_OK;
 }
+
+#include "i2r_head_normal.h"  // i2r_head_normal, i2r_head_normal_ws_bytes: the closed form of the same fit
