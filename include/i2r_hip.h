@@ -825,6 +825,13 @@ typedef struct i2r_mh_attn_args {
                                  group g; the kernel clamps to that range (a device array cannot be validated by the host entry point) */
 } i2r_mh_attn_args;
 I2R_API int i2r_mh_attention(const i2r_mh_attn_args* a, void* stream);
+/* i2r_mh_attention_form -- what i2r_mh_attention would launch for these arguments (additive: I2R_ABI_VERSION unchanged); the launcher and
+ * this query share one check and one selection.  The arguments are validated exactly as for a launch (no pointer is dereferenced).
+ * *hb = hp / 16 and *nq = 16-query tiles per wave -> enc_mh_attn_k<hb, nq>: nq = 4 (64 queries) for hb <= 2 once n_qtiles64 * heads >= 4096
+ * waves, else 2 (32 queries) for hb <= 6 once n_qtiles32 * heads >= 4096, else 1.
+ * grid (may be null) [2]: grid[0] = n_qtiles16 / 32 / 64 for nq 1 / 2 / 4, grid[1] = ceil(heads / wpb) with wpb = min(heads, 4) waves (one
+ * per head) in a workgroup; *block (may be null) = 64 wpb threads.  hb and nq are required.  No launch happens. */
+I2R_API int i2r_mh_attention_form(const i2r_mh_attn_args* a, int32_t* hb, int32_t* nq, int32_t* grid, int32_t* block);
 
 /* Attention maps: the need_weights output of nn.MultiheadAttention -- attn_output_weights averaged over the heads, [batch, L, L]
  * (torch/nn/functional.py multi_head_attention_forward; read by the reference's visualize.py:128-268,270-420 through forward hooks on

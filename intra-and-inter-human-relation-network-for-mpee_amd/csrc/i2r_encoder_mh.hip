@@ -908,38 +908,74 @@ extern "C" int i2r_view_scramble(const float* o, float* out, const int32_t* pers
     return I2R_OK;
 }
 
-extern "C" int i2r_mh_attention(const i2r_mh_attn_args* a, void* stream) {
-    I2R_CHECK_ARG(a && a->qk && a->v && a->out && a->grp_off, "i2r_mh_attention: null pointer");
-    if (const int e = mh_check_heads("i2r_mh_attention", a->heads, a->hp)) return e;
+// ---- what i2r_mh_attention launches for its arguments: ONE check and ONE rule, shared by the launcher and by the launch-nothing query
+//      i2r_mh_attention_form (include/i2r_hip.h), so that what the query reports cannot drift from what runs ----
+namespace {
+
+struct MhForm {
+    int hb, nq;      // enc_mh_attn_k<hb, nq>: hp / 16, 16-query tiles per wave
+    unsigned gx, gy;  // grid: the query tiles of 16 nq rows, the workgroups over the heads
+    unsigned block;  // threads: 64 per wave, one wave per head of the workgroup
+};
+
+int mh_select_form(const char* who, const i2r_mh_attn_args* a, MhForm& f) {
+    I2R_CHECK_ARG(a && a->qk && a->v && a->out && a->grp_off, "%s: null pointer", who);
+    if (const int e = mh_check_heads(who, a->heads, a->hp)) return e;
     const int hs = a->heads * a->hp;
     I2R_CHECK_ARG(a->k_off >= hs && a->k_off % 4 == 0 && a->qk_cs >= a->k_off + hs && a->v_cs >= hs && a->out_cs >= hs && a->qk_cs % 4 == 0 &&
                       a->v_cs % 4 == 0 && a->out_cs % 4 == 0,
-                  "i2r_mh_attention: row strides qk=%d (k at %d) v=%d out=%d for %d heads x %d", a->qk_cs, a->k_off, a->v_cs, a->out_cs, a->heads, a->hp);
+                  "%s: row strides qk=%d (k at %d) v=%d out=%d for %d heads x %d", who, a->qk_cs, a->k_off, a->v_cs, a->out_cs, a->heads, a->hp);
     I2R_CHECK_ARG(a->n_grp > 0 && a->n_qtiles64 > 0 && a->n_qtiles64 <= a->n_qtiles32 && a->n_qtiles32 <= a->n_qtiles16 && a->n_qtiles16 < (1 << 30),
-                  "i2r_mh_attention: n_grp=%d n_qtiles16/32/64=%d/%d/%d", a->n_grp, a->n_qtiles16, a->n_qtiles32, a->n_qtiles64);
-    MhK k{a->qk, a->v, a->out, a->grp_off, a->key_len, a->n_grp, a->heads, a->hp, a->k_off, a->qk_cs, a->v_cs, a->out_cs};
-    typedef void (*fn_t)(const MhK);
+                  "%s: n_grp=%d n_qtiles16/32/64=%d/%d/%d", who, a->n_grp, a->n_qtiles16, a->n_qtiles32, a->n_qtiles64);
     // query tiles per wave (they share the K / V fragments a wave loads; registers: q and o are NQ x HB fragments): up to 64 queries for
     // heads of <= 32 dims, 32 up to 96 dims, 16 beyond -- but never so few waves that the chip's 1024 SIMDs go unfilled (an inter-human
     // stack over a few hundred tokens per image keeps 16-query tiles)
+    constexpr long long kMinWaves = 4096;
+    f.hb = a->hp / 16;
+    f.nq = 1;
+    int n_tiles = a->n_qtiles16;
+    if (f.hb <= 2 && (long long)a->n_qtiles64 * a->heads >= kMinWaves) {
+        f.nq = 4;
+        n_tiles = a->n_qtiles64;
+    } else if (f.hb <= 6 && (long long)a->n_qtiles32 * a->heads >= kMinWaves) {
+        f.nq = 2;
+        n_tiles = a->n_qtiles32;
+    }
+    const int wpb = a->heads >= 4 ? 4 : a->heads;  // waves (= heads) per workgroup
+    f.gx = (unsigned)n_tiles;
+    f.gy = (unsigned)((a->heads + wpb - 1) / wpb);
+    f.block = 64u * wpb;
+    return I2R_OK;
+}
+
+}  // namespace
+
+extern "C" int i2r_mh_attention_form(const i2r_mh_attn_args* a, int32_t* hb, int32_t* nq, int32_t* grid, int32_t* block) {
+    I2R_CHECK_ARG(hb && nq, "i2r_mh_attention_form: null form pointer");
+    MhForm f;
+    if (const int e = mh_select_form("i2r_mh_attention_form", a, f)) return e;
+    *hb = f.hb;
+    *nq = f.nq;
+    if (grid) {
+        grid[0] = (int32_t)f.gx;
+        grid[1] = (int32_t)f.gy;
+    }
+    if (block) *block = (int32_t)f.block;
+    return I2R_OK;
+}
+
+extern "C" int i2r_mh_attention(const i2r_mh_attn_args* a, void* stream) {
+    MhForm f;
+    if (const int e = mh_select_form("i2r_mh_attention", a, f)) return e;
+    MhK k{a->qk, a->v, a->out, a->grp_off, a->key_len, a->n_grp, a->heads, a->hp, a->k_off, a->qk_cs, a->v_cs, a->out_cs};
+    typedef void (*fn_t)(const MhK);
     static const fn_t fn1[16] = {enc_mh_attn_k<1, 1>,  enc_mh_attn_k<2, 1>,  enc_mh_attn_k<3, 1>,  enc_mh_attn_k<4, 1>,  enc_mh_attn_k<5, 1>,  enc_mh_attn_k<6, 1>,
                                  enc_mh_attn_k<7, 1>,  enc_mh_attn_k<8, 1>,  enc_mh_attn_k<9, 1>,  enc_mh_attn_k<10, 1>, enc_mh_attn_k<11, 1>, enc_mh_attn_k<12, 1>,
                                  enc_mh_attn_k<13, 1>, enc_mh_attn_k<14, 1>, enc_mh_attn_k<15, 1>, enc_mh_attn_k<16, 1>};
     static const fn_t fn2[6] = {enc_mh_attn_k<1, 2>, enc_mh_attn_k<2, 2>, enc_mh_attn_k<3, 2>, enc_mh_attn_k<4, 2>, enc_mh_attn_k<5, 2>, enc_mh_attn_k<6, 2>};
     static const fn_t fn4[2] = {enc_mh_attn_k<1, 4>, enc_mh_attn_k<2, 4>};
-    const int hb = a->hp / 16;
-    constexpr long long kMinWaves = 4096;
-    fn_t fn = fn1[hb - 1];
-    int n_tiles = a->n_qtiles16;
-    if (hb <= 2 && (long long)a->n_qtiles64 * a->heads >= kMinWaves) {
-        fn = fn4[hb - 1];
-        n_tiles = a->n_qtiles64;
-    } else if (hb <= 6 && (long long)a->n_qtiles32 * a->heads >= kMinWaves) {
-        fn = fn2[hb - 1];
-        n_tiles = a->n_qtiles32;
-    }
-    const int wpb = a->heads >= 4 ? 4 : a->heads;  // waves (= heads) per workgroup
-    i2r_launch(fn, dim3((unsigned)n_tiles, (unsigned)((a->heads + wpb - 1) / wpb)), dim3(64 * wpb), 0, (hipStream_t)stream, k);
+    const fn_t fn = f.nq == 4 ? fn4[f.hb - 1] : f.nq == 2 ? fn2[f.hb - 1] : fn1[f.hb - 1];
+    i2r_launch(fn, dim3(f.gx, f.gy), dim3(f.block), 0, (hipStream_t)stream, k);
     I2R_CHECK_LAUNCH("i2r_mh_attention");
     return I2R_OK;
 }

@@ -734,7 +734,6 @@ def test_mh_attention_large_launches_use_wider_query_tiles(heads, hd, n_grp, nq_
         offs.append(offs[-1] + n)
     n_tok = offs[-1]
     nq16, nq32, nq64 = (sum(-(-n // t) for n in lens) for t in (16, 32, 64))
-    assert {64: nq64 * heads >= 4096, 32: nq64 * heads < 4096 <= nq32 * heads or hp > 32, 16: True}[nq_expect]
     q = torch.zeros(n_tok, heads, hp)
     k = torch.zeros(n_tok, heads, hp)
     v = torch.zeros(n_tok, heads, hp)
@@ -746,6 +745,9 @@ def test_mh_attention_large_launches_use_wider_query_tiles(heads, hd, n_grp, nq_
     out = torch.full((n_tok, hs), float("nan"), device=DEV)
     goff = torch.tensor(offs, dtype=torch.int32, device=DEV)
     a = cabi.MhAttnArgs(qk.data_ptr(), vd.data_ptr(), out.data_ptr(), goff.data_ptr(), n_grp, heads, hp, hs, 2 * hs, hs, hs, nq16, nq32, nq64)
+    hb_, nq_ = C.c_int32(-1), C.c_int32(-1)   # what the launch below runs, asked of the library
+    cabi.check(cabi.lib().i2r_mh_attention_form(C.byref(a), C.byref(hb_), C.byref(nq_), None, None), "mh_attention_form")
+    assert (hb_.value, 16 * nq_.value) == (hp // 16, nq_expect)
     cabi.check(cabi.lib().i2r_mh_attention(C.byref(a), None), "mh_attention")
     torch.cuda.synchronize()
     got = out.cpu().view(n_tok, heads, hp)
